@@ -5,7 +5,9 @@ in HBM (BASELINE.json configs[1]).  One process per GPU: under torch.distributed
 WORLD_SIZE; a bare `python bench.py --gpus N` (N > 1) re-launches itself under torch.distributed.run on 127.0.0.1.
 `--config 2` = BASELINE.json configs[2] (task-3 lung U-Net, same graph, batch 8 per GPU = global 64 on 8 GPUs).
 
-Prints ONE JSON line (rank 0).  Besides the driver contract it carries
+Prints ONE JSON line (rank 0).  A plain run does only what the headline needs: it sets up, settles the clocks, warms up, times --steps steps,
+writes what the last timed step computed if --dump-outputs DIR is given, and prints metric / value / unit / ms_per_step / dtype / config.
+With --full the line also carries
   roofline     : the dominant kernel family (conv3x3 forward + data-gradient launches: fp32 tensors, products on the fp16 matrix
                  pipe as a block-scaled two-term split): matrix FLOPs its launches EXECUTE in a step / their summed
                  hipEvent durations vs that pipe's dense peak; algorithmic bytes / FLOPs beside it
@@ -15,8 +17,12 @@ Prints ONE JSON line (rank 0).  Besides the driver contract it carries
   predict_batch1_ms : median latency of model.predict at batch 1 (T1:1137), synchronised per call
   cpu_baseline : the CPU oracle (torch-CPU restatement, kind "port") timed on the host cores on a
                  bounded sample of the same workload (rank 0, N=1 only)
+  sclk_mhz / power_w : the operating point of the timed region (amdsmi side thread)
+  comm         : N > 1 (data-parallel engines): where the gradient exchange's time goes, from extra steps behind the timed region
 Before the W warm-up steps the chip is run for SETTLE_S seconds of untimed steps: its clocks need >= 1 s of load to settle at the
-power-capped operating point (a 20-step run started cold reads ~5 % low or high depending on where in the ramp it lands).
+power-capped operating point (a 20-step run started cold reads ~5 % low or high depending on where in the ramp it lands).  After it the
+model is reset to its initial weights, a fresh optimizer and the start of its dropout stream, so the same arguments give the timed steps
+the same inputs and starting state from run to run.
 """
 import argparse
 import json
@@ -213,6 +219,24 @@ def _tap_dims(eng, n, name):
     return ptr.value, ld.value, nn.value, hh.value, ww.value, cc.value
 
 
+DUMP_BUDGET_BYTES = 60_000_000           # (under the 64 MB the dump may hold, .npy headers included)
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES):
+    """Write every array as out_dir/<name>.npy in float32 ('/' in a name becomes '.').  Where the whole would exceed `budget` bytes, every array
+    is cut to the same fraction of its elements: a fixed, seeded (np.random.default_rng(0)), sorted sample of its flattened values."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.asarray(v, np.float32) for k, v in arrays.items()}
+    frac = min(1.0, budget / max(1, sum(a.nbytes for a in arrays.values())))
+    rng = np.random.default_rng(0)
+    for name, a in arrays.items():
+        if frac < 1.0:
+            flat = a.reshape(-1)
+            a = flat[np.sort(rng.choice(flat.size, max(1, int(flat.size * frac)), replace=False))]
+        np.save(os.path.join(out_dir, name.replace("/", ".") + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -220,6 +244,11 @@ def main():
                     "self-test), run 1000 small all-reduces through either path and ten of the whole gradient buffer, print ONE JSON line with the per-call times of every rank, exit")
     ap.add_argument("--steps", type=int, default=40)     # the chip needs ~1 s of load to settle its clocks
     ap.add_argument("--warmup", type=int, default=15)
+    ap.add_argument("--full", action="store_true", help="besides the headline: the CPU baseline, the per-op roofline leg (+ live PMC traffic), the strict-fp32 leg, "
+                    "predict latency, the model.fit leg, the timed region's clock / power and, for data-parallel engines, the `comm` leg (the --no-* switches "
+                    "below turn single legs off).  Off by default: a plain run only sets up, warms up and times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32): "
+                    "loss_dice ([loss, dice_coeff] as train_batch returns it) and every weight / BatchNorm moving statistic after its optimizer update")
     ap.add_argument("--batch", type=int, default=None, help="per-GPU batch (weak scaling); default 16 (configs[1]) or 8 (--config 2)")
     ap.add_argument("--config", type=int, default=1, choices=[1, 2], help="BASELINE.json configs index: 1 = infection U-Net 512x512x1 bs16 per GPU (headline); "
                     "2 = lung U-Net (task 3, same graph T3:850-913) 512x512x1 at batch 8 per GPU = global 64 on 8 GPUs")
@@ -244,6 +273,8 @@ def main():
     ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16"], help="bf16 = activations / activation gradients stored as bf16 (U-Net graph only); "
                     "NOT the headline metric, which BASELINE.json fixes at fp32")
     args = ap.parse_args()
+    if args.steps < 1 and not args.comm_selftest:
+        ap.error("--steps must be >= 1")
     if args.batch is None:
         args.batch = 8 if args.config == 2 else 16
 
@@ -297,7 +328,8 @@ def main():
     x = torch.from_numpy(np.concatenate([xs] * reps)[:B]).cuda(); y = torch.from_numpy(np.concatenate([ys] * reps)[:B]).cuda()
     eng = HipUNet(S, S, 1, device=local, conv_algo=args.algo, process_group=pg, sync_bn=not args.no_sync_bn, dropout_rate=0.25, seed=rank,
                   arch=args.arch, dtype=args.dtype, force_dp=bool(os.environ.get("UNET_BENCH_FORCE_PG")), small_allreduce=args.small_allreduce, grad_buckets=not args.no_buckets, options=({"deterministic": 1} if args.deterministic else {}) | ({"bn_fold": 3} if args.fold16 else {}) | (json.loads(args.options) if args.options else {}) or None)
-    eng.set_weights(W.init_weights(0, 1, args.arch, (S, S)))       # identical replicas
+    w0 = W.init_weights(0, 1, args.arch, (S, S))
+    eng.set_weights(w0)                                              # identical replicas
     if args.comm_selftest:
         # a diagnosis that needs no training step: if the first minute on an 8-GPU node fails, this line still says which exchange path works and how fast it is
         mine = eng.comm_selftest()
@@ -321,32 +353,33 @@ def main():
                 eng.train_batch(x, y)
             torch.cuda.synchronize()
 
-    # ---- untimed setup 1 (rank 0, N=1): the CPU baseline first, so the GPU work of this command is one contiguous block at its end
+    # ---- untimed setup 1 (--full; rank 0, N=1): the CPU baseline first, so the GPU work of this command is one contiguous block at its end
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(S, arch=args.arch)
 
-    # ---- untimed setup 2, the roofline leg: per-op hipEvent timing (profiling mode serialises the ops and brackets each with events on the
+    # ---- untimed setup 2 (--full), the roofline leg: per-op hipEvent timing (profiling mode serialises the ops and brackets each with events on the
     # launch stream) of PROF_STEPS steps; every rank runs them (they contain the collectives), rank 0 reports.  Running it BEFORE the
     # warm-up also means the chip has seen ~0.5 s of load when the W warm-up steps start (its clocks need ~1 s to settle)
     PROF_STEPS = 8
-    roof = None
+    roof = ops = smi_prof = None
     for _ in range(2):
         eng.train_batch(x, y)                # first-touch: plans, workspace, weight images
-    settle(args.settle)                      # (a cold chip runs these launches ~40 % slower than the timed region does: the per-op times would not be the step's)
-    smi_prof = _SmiSampler(0).start() if rank == 0 else None          # (the per-op leg serialises the ops: its own operating point)
-    eng.set_profiling(True, B)
-    for _ in range(PROF_STEPS):
-        eng.train_batch(x, y)
-    torch.cuda.synchronize()
-    eng.set_profiling(False)
-    smi_prof = smi_prof.stop() if smi_prof is not None else None
-    ops = eng.op_profile(B, 0) + eng.op_profile(B, 1)
-    eng.set_weights(W.init_weights(0, 1, args.arch, (S, S))); eng.reset_optimizer()
+    if args.full:
+        settle(args.settle)                  # (a cold chip runs these launches ~40 % slower than the timed region does: the per-op times would not be the step's)
+        smi_prof = _SmiSampler(0).start() if rank == 0 else None          # (the per-op leg serialises the ops: its own operating point)
+        eng.set_profiling(True, B)
+        for _ in range(PROF_STEPS):
+            eng.train_batch(x, y)
+        torch.cuda.synchronize()
+        eng.set_profiling(False)
+        smi_prof = smi_prof.stop() if smi_prof is not None else None
+        ops = eng.op_profile(B, 0) + eng.op_profile(B, 1)
+        eng.set_weights(w0); eng.reset_optimizer()
 
-    # ---- untimed setup 3 (rank 0, N=1, the headline configuration only): the same step on the strict-fp32 kernel family (exact fp32 MFMA products)
+    # ---- untimed setup 3 (--full; rank 0, N=1, the headline configuration only): the same step on the strict-fp32 kernel family (exact fp32 MFMA products)
     strict = None
-    if rank == 0 and world == 1 and not args.no_strict_leg and args.dtype == "fp32" and args.algo == 0:
+    if args.full and rank == 0 and world == 1 and not args.no_strict_leg and args.dtype == "fp32" and args.algo == 0:
         e2 = HipUNet(S, S, 1, device=local, conv_algo=2, dropout_rate=0.25, seed=rank, arch=args.arch, dtype=args.dtype)
         e2.set_weights(W.init_weights(0, 1, args.arch, (S, S)))
         for _ in range(4):
@@ -359,9 +392,9 @@ def main():
         del e2
         torch.cuda.empty_cache()
 
-    # ---- untimed setup 4 (rank 0, N=1): latency of model.predict(x.reshape(1,H,W,1)) (T1:1137) -- inference forward at batch 1, synchronised per call
+    # ---- untimed setup 4 (--full; rank 0, N=1): latency of model.predict(x.reshape(1,H,W,1)) (T1:1137) -- inference forward at batch 1, synchronised per call
     predict_ms = predict_cold_ms = None
-    if rank == 0 and world == 1 and args.arch == "unet":
+    if args.full and rank == 0 and world == 1 and args.arch == "unet":
         x1 = x[:1].contiguous()
         for _ in range(3):
             eng.predict_batch(x1)
@@ -375,10 +408,10 @@ def main():
             ts = time.perf_counter(); eng.predict_batch(x1); torch.cuda.synchronize(); lat.append((time.perf_counter() - ts) * 1e3)
         predict_cold_ms = round(sorted(lat)[len(lat) // 2], 3)
 
-    # ---- untimed setup 5 (rank 0, N=1, U-Net): the REAL model.fit path (T1:1059-1061) -- a host-resident float64 set, as the reference's runner holds it,
+    # ---- untimed setup 5 (--full; rank 0, N=1, U-Net): the REAL model.fit path (T1:1059-1061) -- a host-resident float64 set, as the reference's runner holds it,
     # through keras_like.UNetModel.fit: upload once (pinned staging), per step a device-side gather of the shuffled batch, per epoch one host sync
     fit_stats = None
-    if rank == 0 and world == 1 and args.arch == "unet" and not args.no_fit_leg:
+    if args.full and rank == 0 and world == 1 and args.arch == "unet" and not args.no_fit_leg:
         from covidseg_amd.keras_like import UNetModel
         nfit = args.fit_steps * B
         xh = np.concatenate([xs] * ((nfit + len(xs) - 1) // len(xs)))[:nfit].astype(np.float64)
@@ -393,10 +426,13 @@ def main():
                      "fit_note": f"UNetModel.fit(x, y, batch_size={B}, epochs=3) on {nfit} host float64 slices ({args.fit_steps} steps per epoch, shuffled): fit_img_s = the whole call "
                                  f"incl. the one-time upload; fit_epoch_img_s = a steady epoch (median of epochs 2-3) -- to be read against `value`"}
         del xh, yh, model
-        eng.set_weights(W.init_weights(0, 1, args.arch, (S, S))); eng.reset_optimizer()
 
     # ---- untimed: clock settle.  The chip needs >= 1 s of this load before its clocks sit at the power-capped operating point
     settle(args.settle)
+    # ... then the state the warm-up and timed steps start from is fixed whatever ran before (the settle loop runs for a time, not a number of steps):
+    # initial weights and BatchNorm statistics, a fresh optimizer, the dropout stream from its first key
+    torch.cuda.synchronize()
+    eng.set_weights(w0); eng.reset_optimizer(); eng._drop_calls = 0
 
     # ---- the measurement the contract defines: W untimed warm-up steps, then EXACTLY K timed steps between barrier + synchronize
     for _ in range(args.warmup):
@@ -405,7 +441,7 @@ def main():
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
-    smi = _SmiSampler(int(os.environ.get("LOCAL_RANK", "0")) if not os.environ.get("UNET_BENCH_ONE_DEVICE") else 0).start() if rank == 0 else None
+    smi = _SmiSampler(int(os.environ.get("LOCAL_RANK", "0")) if not os.environ.get("UNET_BENCH_ONE_DEVICE") else 0).start() if args.full and rank == 0 else None
     t0 = time.perf_counter()
     for _ in range(args.steps):
         last = eng.train_batch(x, y)
@@ -426,12 +462,15 @@ def main():
     comm_status = eng.comm_status()
     if comm_status != 0:                       # a device-side all-reduce that timed out: the step's numbers are not a step's
         raise RuntimeError(f"rank {rank}: device-side all-reduce missed rank {comm_status - 1}")
+    # what the last timed step handed its caller: [loss, dice] and the model after its optimizer update (replicas are identical: rank 0 writes)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"loss_dice": last.cpu().numpy(), **eng.get_weights()})
 
-    # ---- untimed, behind the measurement (every rank; data-parallel engines only): where the gradient exchange's time goes -- BASELINE.md config 3 asks for "all-reduce time
-    # exposed vs hidden".  COMM_STEPS more steps with event pairs around every gradient all-reduce (on its side stream) and around the compute stream's wait in front of
-    # Adam; per-rank figures are gathered, rank 0 reports its own and the max over ranks.
+    # ---- untimed, behind the measurement (--full; every rank; data-parallel engines only): where the gradient exchange's time goes -- BASELINE.md config 3 asks for
+    # "all-reduce time exposed vs hidden".  COMM_STEPS more steps with event pairs around every gradient all-reduce (on its side stream) and around the compute stream's
+    # wait in front of Adam; per-rank figures are gathered, rank 0 reports its own and the max over ranks.
     comm = None
-    if eng._dp:
+    if args.full and eng._dp:
         COMM_STEPS = 8
         eng.set_comm_profiling(True)
         for _ in range(COMM_STEPS):
@@ -459,7 +498,7 @@ def main():
                         "optimizer; hidden = allreduce - exposed (overlapped with backward).  A/B switches: --no-buckets (one exposed all-reduce), --no-sync-bn (no small "
                         "reductions), --small-allreduce rccl"}
 
-    if rank == 0:
+    if args.full and rank == 0:
         # (conv3x3_dgrad_bn_bwd: the data gradient of a decoder block's first conv with the folded BatchNorm's backward in its epilogue -- the same
         #  kernel, same FLOPs; the op's time includes its 5 us coefficient launch)
         # (conv3x3_fwd_head: the last conv3x3 with the 1x1 sigmoid head and the loss sums in its epilogue -- the same kernel body and conv FLOPs)
@@ -587,8 +626,9 @@ def main():
                                       "classifier": "configs[4] graph at the reference's 1-channel fp32"}[args.arch],
                        "storage": args.dtype, "global_batch": B * world, "parallelism": f"dp{world}", "small_allreduce": (("device (comm.hip: IPC-mapped areas, one kernel per reduction)" if eng._comm is not None else "torch.distributed") if eng._dp else None), "conv_algo": "mfma_f32_32x32x16_bf16 direct" if args.dtype == "bf16" else {0: "auto: every conv3x3 / ConvT forward, data gradient and weight gradient as three v_mfma_f32_32x32x16_f16 products of a block-scaled two-term fp16 split (h2; fp32-class accuracy, DESIGN.md 4g); Cin=1 first layer and 1x1 head on fp32 VALU", 1: "direct fp32 VALU kernels", 2: "strict fp32: v_mfma_f32_32x32x2_f32 direct kernels"}[args.algo],
                        "deterministic": bool(args.deterministic), "bn_fold": 3 if args.fold16 else 2, "dropout": {"unet": 0.25, "unetpp": "0.2/0.4 (fused in the conv epilogue)", "classifier": 0.4}[args.arch], "last_loss_dice": [round(v, 5) for v in loss_dice]},
-            "roofline": roof,
         }
+        if args.full:
+            out["roofline"] = roof
         # the operating point of the timed region (median of ~100 Hz amdsmi samples on rank 0's GPU: mean shader clock over the 8 XCDs, socket power) -- the pool's boxes
         # differ by ~7 % on the same library; a slow BENCH line with a low clock is a slow box, not a regression
         if smi_timed is not None:

@@ -1,5 +1,7 @@
 """The module-level drop-in: the reference's menu script, unchanged, must import the ENGINE's six modules
-and reach the engine's runners when started through dropin/run_app.py -- and plain `python Scripts/app.py` must be known NOT to."""
+and reach the engine's runners when started through dropin/run_app.py -- and plain `python Scripts/app.py` must be known NOT to.
+The menu script is tests/menu_like.py (the same contract as the reference's Scripts/app.py), set up as <tmp>/Scripts/app.py beside six
+same-named decoy modules that stand for the reference's own Keras modules and fail at import: the launcher must reach past them."""
 import os
 import subprocess
 import sys
@@ -9,7 +11,19 @@ import pytest
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 DROPIN = os.path.join(ROOT, "one-stop-for-covid-19-infection-and-lung-segmentation-plus-classification_amd", "dropin")
-REF_APP = "/root/reference/Scripts/app.py"
+MODULES = ("task1_crossval_3folds_unet", "task1_crossval_4folds_unet", "task1_preprocessing_plus_unet_with_comments", "task1_unet_plus_plus",
+           "task2_covid19_classifcation", "task3_lung_segmentation_unet")
+DECOY = "decoy sibling module imported"
+
+
+def make_app(tmp_path):
+    """<tmp>/Scripts/app.py (the menu stand-in) + the six task modules next to it, each raising at import"""
+    d = tmp_path / "Scripts"
+    d.mkdir()
+    (d / "app.py").write_text(open(os.path.join(HERE, "menu_like.py")).read())
+    for m in MODULES:
+        (d / f"{m}.py").write_text(f"raise ImportError({DECOY!r} + ': {m}')\n")
+    return str(d / "app.py")
 
 
 def run_app(app, word, extra_env=None, timeout=600):
@@ -25,22 +39,21 @@ def assert_dropins_imported(out):
         assert os.path.dirname(l.split(" <- ")[1]) == DROPIN, l
 
 
-@pytest.mark.skipif(not os.path.isfile(REF_APP), reason="the reference checkout exists only in the build container")
-def test_reference_app_text_resolves_the_dropins_and_exits_cleanly_on_an_unknown_choice():
-    r = run_app(REF_APP, "seven")                         # APP:29 advertises 'seven'; no branch takes it -> the script just ends
+def test_reference_app_text_resolves_the_dropins_and_exits_cleanly_on_an_unknown_choice(tmp_path):
+    r = run_app(make_app(tmp_path), "seven")              # APP:29 advertises 'seven'; no branch takes it -> the script just ends
     assert r.returncode == 0, r.stderr[-2000:]
-    assert "Enter from one of the" in r.stdout            # the reference's own prompt text was executed (APP:29)
+    assert "Enter one of" in r.stdout                     # the menu script's own prompt was executed
+    assert DECOY not in r.stderr
     assert_dropins_imported(r.stdout)
 
 
-@pytest.mark.skipif(not os.path.isfile(REF_APP), reason="the reference checkout exists only in the build container")
-def test_reference_app_three_reaches_the_engine_and_fails_loudly_without_a_gpu():
+def test_reference_app_three_reaches_the_engine_and_fails_loudly_without_a_gpu(tmp_path):
     import torch
     if torch.cuda.is_available():
         pytest.skip("GPU present: covered by the -m gpu test below")
-    r = run_app(REF_APP, "three", {"UNET_EPOCHS": "1", "UNET_SAMPLES": "8", "UNET_SIZE": "32"})
+    r = run_app(make_app(tmp_path), "three", {"UNET_EPOCHS": "1", "UNET_SAMPLES": "8", "UNET_SIZE": "32"})
     assert r.returncode != 0 and "UNetHipError" in r.stderr, (r.returncode, r.stderr[-2000:])       # no CPU fallback: the HIP engine refuses loudly
-    assert "get_ipython" not in r.stderr                  # (what the reference's own module dies with when it is imported instead)
+    assert DECOY not in r.stderr                          # (what a sibling of the script dies with when it is imported instead)
     assert_dropins_imported(r.stdout)
 
 
@@ -54,8 +67,8 @@ def test_menu_stand_in_resolves_the_dropins():
 @pytest.mark.parametrize("word,needle", [("three", "test loss, test dice coefficient:"), ("six", "test loss, test dice coefficient:")])
 def test_menu_choice_runs_on_the_engine(word, needle, tmp_path):
     """APP:44-45 / 56-57 through the launcher on the MI355X: 'three' (infection hold-out) and 'six' (lung) complete and print the reference's
-    summary lines.  (The reference's app.py does not exist on the GPU box; tests/menu_like.py has the same contract.)"""
-    app = REF_APP if os.path.isfile(REF_APP) else os.path.join(HERE, "menu_like.py")
+    summary lines."""
+    app = make_app(tmp_path)
     env = {"UNET_EPOCHS": "1", "UNET_SAMPLES": "8", "UNET_SIZE": "32"}
     p = subprocess.run([sys.executable, os.path.join(DROPIN, "run_app.py"), app], input=word + "\n", capture_output=True, text=True,
                        env=dict(os.environ, UNET_DROPIN_TRACE="1", **env), timeout=900, cwd=str(tmp_path))

@@ -56,7 +56,7 @@ def test_bench_two_ranks_as_the_driver_launches_it():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--size", "64", "--batch", "2", "--steps", "2", "--warmup", "1", "--settle", "0"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--size", "64", "--batch", "2", "--steps", "2", "--warmup", "1", "--settle", "0", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     _check(r.stdout, 2)
@@ -69,7 +69,7 @@ def test_bench_four_and_eight_ranks_on_the_one_gpu(n):
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--size", "64", "--batch", "2", "--steps", "2", "--warmup", "1", "--settle", "0"]
+           os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--size", "64", "--batch", "2", "--steps", "2", "--warmup", "1", "--settle", "0", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _check(r.stdout, n)
@@ -93,7 +93,7 @@ def test_bench_comm_selftest_prints_a_diagnosis_without_a_training_step():
 
 
 def test_bench_bare_gpus_flag_relaunches_itself_under_torchrun():
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--size", "64", "--batch", "2", "--steps", "2", "--warmup", "1", "--settle", "0"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--size", "64", "--batch", "2", "--steps", "2", "--warmup", "1", "--settle", "0", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     _check(r.stdout, 2)
@@ -111,8 +111,8 @@ def test_bench_comm_object_at_world_one_and_the_ab_switches():
     duration is exposed, --no-sync-bn has no small reductions"""
     env = _env(); env.pop("UNET_BENCH_BACKEND"); env["UNET_BENCH_FORCE_PG"] = "1"
     for extra, kw in (([], {}), (["--no-buckets"], {"buckets": False}), (["--no-sync-bn"], {"sync_bn": False})):
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--size", "64", "--batch", "2", "--steps", "2", "--warmup", "1", "--settle", "0", "--no-cpu-baseline", "--no-strict-leg",
-               "--no-fit-leg"] + extra
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--size", "64", "--batch", "2", "--steps", "2", "--warmup", "1", "--settle", "0", "--full", "--no-cpu-baseline",
+               "--no-strict-leg", "--no-fit-leg"] + extra
         r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-3000:]
         d = json.loads([l for l in r.stdout.strip().splitlines() if l.strip()][-1])
@@ -121,3 +121,34 @@ def test_bench_comm_object_at_world_one_and_the_ab_switches():
         if extra == ["--no-buckets"]:
             c = d["comm"]
             assert abs(c["exposed_ms_per_step"]["rank0"] - c["allreduce_ms_per_step"]["rank0"]) < 1e-6 and c["hidden_ms_per_step"]["rank0"] == 0
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run (no --full) carries the headline fields and none of the extra legs; --steps sets the timed steps; --dump-outputs writes what the last
+    timed step computed (float32 .npy, within 64 MB), and the state the timed steps start from does not depend on how long the clock settle ran:
+    two --deterministic runs with different --settle write identical arrays."""
+    import numpy as np
+    env = _env()
+    for k in ("UNET_BENCH_BACKEND", "UNET_BENCH_ONE_DEVICE"):
+        env.pop(k)
+    lines, dumps = [], []
+    for run, settle in enumerate(("0", "0.5")):
+        d_out = tmp_path / f"out{run}"
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--size", "64", "--batch", "2", "--steps", "3", "--warmup", "1", "--settle", settle,
+               "--deterministic", "--dump-outputs", str(d_out)]
+        r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines.append(json.loads([l for l in r.stdout.strip().splitlines() if l.strip()][-1]))
+        files = sorted(p.name for p in d_out.iterdir())
+        dumps.append({f: np.load(d_out / f) for f in files})
+        assert sum((d_out / f).stat().st_size for f in files) <= 64e6
+    d = lines[0]
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "images/sec" and d["higher_is_better"] is True and d["dtype"].startswith("f32")
+    assert d["ms_per_step"] > 0 and abs(d["value"] - 2 * 1e3 / d["ms_per_step"]) < 1e-2 * d["value"]
+    assert not {"roofline", "cpu_baseline", "fp32_strict_img_s", "fit_img_s", "predict_batch1_ms", "comm", "sclk_mhz"} & set(d)
+    a, b = dumps
+    assert "loss_dice.npy" in a and "c1a.kernel.npy" in a and len(a) == 1 + 78 and set(a) == set(b)
+    assert all(v.dtype == np.float32 for v in a.values()) and a["c1a.kernel.npy"].shape == (3, 3, 1, 32)
+    assert np.allclose(a["loss_dice.npy"], d["config"]["last_loss_dice"], atol=1e-5)
+    for f in a:
+        assert np.array_equal(a[f], b[f]), f

@@ -11,15 +11,15 @@ set -u
 OUT=${1:-gpurun_out/prof_r03}
 mkdir -p $OUT
 export TMPDIR=/tmp
-python bench.py > $OUT/bench.json 2> $OUT/bench.err
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_driver_flags.json 2>> $OUT/bench.err
-python bench.py --config 2 --no-cpu-baseline --no-strict-leg > $OUT/bench_cfg2.json 2>> $OUT/bench.err
-python bench.py --algo 2 --no-cpu-baseline --steps 20 > $OUT/bench_strict_fp32.json 2>> $OUT/bench.err
-python bench.py --arch unetpp --size 256 --batch 32 --no-cpu-baseline --no-strict-leg > $OUT/bench_unetpp.json 2>> $OUT/bench.err
-python bench.py --arch classifier --size 224 --batch 256 --no-cpu-baseline --no-strict-leg > $OUT/bench_cls.json 2>> $OUT/bench.err
-python bench.py --arch classifier --size 224 --batch 256 --no-cpu-baseline --no-strict-leg --fold16 > $OUT/bench_cls_fold16.json 2>> $OUT/bench.err
-python bench.py --no-cpu-baseline --no-strict-leg --deterministic > $OUT/bench_deterministic.json 2>> $OUT/bench.err
-python bench.py --dtype bf16 --no-cpu-baseline > $OUT/bench_bf16.json 2>> $OUT/bench.err
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_driver_flags.json 2>> $OUT/bench.err
+python bench.py --full --config 2 --no-cpu-baseline --no-strict-leg > $OUT/bench_cfg2.json 2>> $OUT/bench.err
+python bench.py --full --algo 2 --no-cpu-baseline --steps 20 > $OUT/bench_strict_fp32.json 2>> $OUT/bench.err
+python bench.py --full --arch unetpp --size 256 --batch 32 --no-cpu-baseline --no-strict-leg > $OUT/bench_unetpp.json 2>> $OUT/bench.err
+python bench.py --full --arch classifier --size 224 --batch 256 --no-cpu-baseline --no-strict-leg > $OUT/bench_cls.json 2>> $OUT/bench.err
+python bench.py --full --arch classifier --size 224 --batch 256 --no-cpu-baseline --no-strict-leg --fold16 > $OUT/bench_cls_fold16.json 2>> $OUT/bench.err
+python bench.py --full --no-cpu-baseline --no-strict-leg --deterministic > $OUT/bench_deterministic.json 2>> $OUT/bench.err
+python bench.py --full --dtype bf16 --no-cpu-baseline > $OUT/bench_bf16.json 2>> $OUT/bench.err
 python tools/profile_ops.py > $OUT/ops.txt 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-strict-leg > $OUT/trace.log 2>&1
 for c in FETCH_SIZE WRITE_SIZE; do
