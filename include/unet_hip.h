@@ -271,6 +271,27 @@ int32_t unet_bn_maxpool_bwd_apply(unet_ctx*, const float* x, int32_t ldx, const 
 /* Replaces: Conv2D(1,(1,1),activation='sigmoid') T1:913 fused with the reductions of
  * bce_dice_loss / dice_coeff T1:784-799.  p = sigmoid(b + x.w).  If y_true != NULL,
  * loss_sums (double[4], accumulated) += (sum bce_elem, sum t*p, sum t, sum p). */
+/* The segmentation losses of the reference's scripts (T1:784-835), chosen at compile time in Keras (`compile(loss=...)`).  All of them are functions of the
+ * same four batch sums (sum l, I = sum t p, St = sum t, Sp = sum p) that the head ops accumulate, and every one has a head-logit gradient of the form
+ *   dz = cb a + q (A t + B)      (a = dBCE/dz = p_clipped - t inside the clip range, 0 outside; q = p (1 - p))
+ * with batch scalars cb, A, B of the global sums:
+ *   UNET_LOSS_BCE_DICE  0.5 sum l / N + 0.5 (1 - D), D = (2 I + 1) / S, S = St + Sp + 1   (bce_dice_loss T1:797, the default)
+ *   UNET_LOSS_BCE       sum l / N                                                         (binary_crossentropy, T1:60)
+ *   UNET_LOSS_DICE      1 - D                                                             (dice_loss T1:792)
+ *   UNET_LOSS_TVERSKY   1 - I / (I + alpha (Sp - I) + beta (St - I))                      (tversky_loss T1:801; T1 has alpha = beta = 0.5; both must be > 0)
+ *   UNET_LOSS_WEIGHTED_BCE_DICE  0.5 sum w l / sum w + 0.5 (1 - D)                         (weighted_bce_dice_loss T1:835; dz = cb w a + ...)
+ * The weighted loss takes a FIFTH sum, Sw = sum w, and weighs the first: its loss_sums are (sum w l, I, St, Sp, sum w), and its weight map w (unet_loss_weight_map)
+ * goes to every head op.  The metric stays dice_coeff = D for every loss. */
+enum { UNET_LOSS_BCE_DICE = 0, UNET_LOSS_BCE = 1, UNET_LOSS_DICE = 2, UNET_LOSS_TVERSKY = 3, UNET_LOSS_WEIGHTED_BCE_DICE = 4 };
+/* weighted_bce_dice_loss's weight map (T1:837-845): weight[n,h,wd] = 5 exp(-5 |avg - 0.5|), avg = TF's SAME average pool of y_true[n,h,wd] over a 50 x 50 window
+ * (rows r - 24 ... r + 25, columns c - 24 ... c + 25, clipped to the image; divisor = the in-image cells). */
+int32_t unet_loss_weight_map(unet_ctx*, const float* y_true, float* weight, int32_t n, int32_t h, int32_t wd, void* stream);
+/* unet_head_fwd / _bf16 with a weight map (NULL = unet_head_fwd): loss_sums[5] += (sum w bce, sum t p, sum t, sum p, sum w) */
+int32_t unet_head_fwd_ex(unet_ctx*, const float* x, const float* w, const float* bias, float* p, const float* y_true, const float* weight_map, double* loss_sums,
+                         int64_t pixels, int32_t cin, void* stream);
+int32_t unet_head_fwd_bf16_ex(unet_ctx*, const unet_bf16* x, const float* w, const float* bias, float* p, const float* y_true, const float* weight_map,
+                              double* loss_sums, int64_t pixels, int32_t cin, void* stream);
+
 int32_t unet_head_fwd(unet_ctx*, const float* x, const float* w, const float* bias, float* p,
                       const float* y_true, double* loss_sums, int64_t pixels, int32_t cin,
                       void* stream);
@@ -283,6 +304,12 @@ int32_t unet_loss_finalize(unet_ctx*, const double* loss_sums, double count, flo
 int32_t unet_head_bwd(unet_ctx*, const float* x, const float* w, const float* p, const float* y_true,
                       const double* loss_sums, double count, float* dx, float* dw, float* db,
                       int64_t pixels, int32_t cin, int32_t relu_mask, void* stream);
+/* unet_loss_finalize / unet_head_bwd with a loss selection (UNET_LOSS_*; alpha, beta: Tversky only; weight_map: the weighted loss's, NULL for the others).
+ * UNET_LOSS_BCE_DICE computes exactly what the calls without the suffix compute. */
+int32_t unet_loss_finalize_ex(unet_ctx*, const double* loss_sums, double count, int32_t loss, float alpha, float beta, float* loss_out, void* stream);
+int32_t unet_head_bwd_ex(unet_ctx*, const float* x, const float* w, const float* p, const float* y_true, const double* loss_sums, double count,
+                         int32_t loss, float alpha, float beta, const float* weight_map, float* dx, float* dw, float* db, int64_t pixels, int32_t cin, int32_t relu_mask,
+                         void* stream);
 
 /* The data gradient of the conv BEHIND `MaxPooling2D((2, 2))` + `Dropout(0.25)` (T1:862-865: c2 = Conv2D(64)(p1) ...) together with the pooled-path sums the
  * BatchNorm in front of that pool needs for its backward (what unet_maxpool2x2_dropout_bwd_sums computes in a pass of its own):
@@ -320,6 +347,16 @@ int32_t unet_head_dy(unet_ctx*, const float* p, const float* y_true, const doubl
 int32_t unet_head_bwd_stream_supported(unet_ctx*, int32_t algo, int32_t wd, int32_t cin);
 int32_t unet_head_dzm(unet_ctx*, const float* p, const float* y_true, const double* loss_sums, double count, const double* head_sums, const void* relu_bits, void* dzm,
                       float* dw_head, float* db_head, int32_t n, int32_t h, int32_t wd, void* stream);
+/* unet_conv3x3_head_fwd with a weight map (NULL = unet_conv3x3_head_fwd): loss_sums[5] as unet_head_fwd_ex, and the first per-channel head sum is sum w a y_c */
+int32_t unet_conv3x3_head_fwd_ex(unet_ctx*, const float* x, const float* w, const float* bias, float* y, const float* w_head, const float* b_head, float* p,
+                                 const float* y_true, const float* weight_map, double* loss_sums, double* head_sums, int32_t n, int32_t h, int32_t wd, int32_t cin,
+                                 float* w_ws, void* stream);
+/* unet_head_dy / unet_head_dzm with a loss selection (as unet_head_bwd_ex) */
+int32_t unet_head_dy_ex(unet_ctx*, const float* p, const float* y_true, const double* loss_sums, double count, const double* head_sums, int32_t loss, float alpha,
+                        float beta, const float* weight_map, const float* w_head, const void* relu_bits, const float* y, float* dy, float* dw_head, float* db_head, int32_t n, int32_t h,
+                        int32_t wd, void* stream);
+int32_t unet_head_dzm_ex(unet_ctx*, const float* p, const float* y_true, const double* loss_sums, double count, const double* head_sums, int32_t loss, float alpha,
+                         float beta, const float* weight_map, const void* relu_bits, void* dzm, float* dw_head, float* db_head, int32_t n, int32_t h, int32_t wd, void* stream);
 int32_t unet_conv3x3_bwd_data_dzm(unet_ctx*, const void* dzm, const float* w, const float* w_head, const void* relu_bits_in, float* dx, float* wt_ws, int32_t n, int32_t h,
                                   int32_t wd, int32_t cin, void* stream);
 int32_t unet_conv3x3_bwd_weights_dzm(unet_ctx*, const float* x, const void* dzm, const float* w_head, float* dw, float* db, void* ws, size_t ws_bytes, int32_t n, int32_t h,
@@ -405,6 +442,9 @@ int32_t unet_head_fwd_bf16(unet_ctx*, const unet_bf16* x, const float* w, const 
                            int64_t pixels, int32_t cin, void* stream);
 int32_t unet_head_bwd_bf16(unet_ctx*, const unet_bf16* x, const float* w, const float* p, const float* y_true, const double* loss_sums,
                            double count, unet_bf16* dx, float* dw, float* db, int64_t pixels, int32_t cin, int32_t relu_mask, void* stream);
+int32_t unet_head_bwd_bf16_ex(unet_ctx*, const unet_bf16* x, const float* w, const float* p, const float* y_true, const double* loss_sums, double count,
+                              int32_t loss, float alpha, float beta, const float* weight_map, unet_bf16* dx, float* dw, float* db, int64_t pixels, int32_t cin,
+                              int32_t relu_mask, void* stream);
 /* dense tail: the flattened activations x (and their gradient dx) are bf16, the 32 hidden units, dy and the weights stay fp32 */
 int32_t unet_dense_fwd_bf16(unet_ctx*, const unet_bf16* x, const float* w, const float* bias, float* y, int32_t batch, int32_t k, int32_t n, int32_t act,
                             float drop_rate, uint64_t drop_seed, void* ws, size_t ws_bytes, void* stream);
@@ -535,6 +575,12 @@ int32_t unet_model_set_loss_out(unet_model*, float* loss_out);
 int32_t unet_model_set_dropout(unet_model*, float rate, uint64_t seed);
 /* classifier only: weights of class 0 / class 1 in the loss (Keras class_weight, T2:835); default 1, 1 */
 int32_t unet_model_set_class_weights(unet_model*, float w0, float w1);
+/* U-Net / U-Net++: the training loss (UNET_LOSS_*; alpha, beta > 0: Tversky's weights, ignored by the others); default UNET_LOSS_BCE_DICE.  Valid between runs
+ * of a built model (Keras compiles after it builds the graph, and may compile again, T1:1208): the programs read it when they run.  The weighted loss adds the
+ * weight-map op to the forward programs, n h w floats to the workspace (unet_model_workspace_bytes reflects the loss that is set; a bound workspace that is too
+ * small for it: UNET_E_STATE, nothing changed) and a fifth double to the loss-sum sync point (unet_model_sync_points: re-read after this call).  The classifier
+ * keeps binary cross-entropy: any other loss is UNET_E_ARG there. */
+int32_t unet_model_set_loss(unet_model*, int32_t loss, float alpha, float beta);
 int32_t unet_model_num_ops(const unet_model*, int32_t prog);
 int32_t unet_model_sync_points(const unet_model*, int32_t prog, unet_sync_point* out, int32_t cap);
 int32_t unet_model_run(unet_model*, int32_t prog, int32_t begin, int32_t end, void* stream);

@@ -18,6 +18,8 @@ ALGO_AUTO, ALGO_NAIVE, ALGO_MFMA = 0, 1, 2          # fp16-split h2 kernels wher
 # unet_ctx_set_option (include/unet_hip.h UNET_OPT_*)
 OPTIONS = {"relu_bits": 1, "bn_fold": 2, "enc_bn_fused": 3, "bn_concat_analytic": 4, "bn_fuse_stats": 5, "deterministic": 6, "head_fused": 7, "skip_raw": 8, "pool_sums_fused": 9, "head_bwd_fused": 10, "conv_pp": 13}
 ARCH_UNET, ARCH_UNETPP, ARCH_CLASSIFIER = 0, 1, 2
+# include/unet_hip.h UNET_LOSS_*: the segmentation losses a U-Net / U-Net++ trains on (unet_model_set_loss), by their Keras names
+LOSSES = {"bce_dice_loss": 0, "binary_crossentropy": 1, "dice_loss": 2, "tversky_loss": 3, "weighted_bce_dice_loss": 4}
 DTYPE_F32, DTYPE_BF16 = 0, 1
 ACT_NONE, ACT_RELU, ACT_ELU = 0, 1, 2
 MASK_NONE, MASK_RELU, MASK_ELU, MASK_ELU_DROP = 0, 1, 2, 3
@@ -109,6 +111,13 @@ _PROTOS = {
     "unet_loss_finalize": (i32, [vp, vp, f64, vp, vp]),
     "unet_head_bwd": (i32, [vp, vp, vp, vp, vp, vp, f64, vp, vp, vp, i64, i32, i32, vp]),
     "unet_head_bwd_bf16": (i32, [vp, vp, vp, vp, vp, vp, f64, vp, vp, vp, i64, i32, i32, vp]),
+    "unet_loss_finalize_ex": (i32, [vp, vp, f64, i32, f32, f32, vp, vp]),
+    "unet_head_bwd_ex": (i32, [vp, vp, vp, vp, vp, vp, f64, i32, f32, f32, vp, vp, vp, vp, i64, i32, i32, vp]),
+    "unet_head_bwd_bf16_ex": (i32, [vp, vp, vp, vp, vp, vp, f64, i32, f32, f32, vp, vp, vp, vp, i64, i32, i32, vp]),
+    "unet_head_fwd_ex": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, vp]),
+    "unet_head_fwd_bf16_ex": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, vp]),
+    "unet_loss_weight_map": (i32, [vp, vp, vp, i32, i32, i32, vp]),
+    "unet_conv3x3_head_fwd_ex": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
     "unet_adam_keras": (i32, [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp]),
     "unet_seg_metrics_sweep": (i32, [vp, vp, vp, vp, i32, vp, i64, vp]),
     "unet_gather_samples": (i32, [vp, vp, vp, i64, i64, vp]),
@@ -119,6 +128,8 @@ _PROTOS = {
     "unet_head_dy": (i32, [vp, vp, vp, vp, f64, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "unet_head_bwd_stream_supported": (i32, [vp, i32, i32, i32]),
     "unet_head_dzm": (i32, [vp, vp, vp, vp, f64, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "unet_head_dy_ex": (i32, [vp, vp, vp, vp, f64, vp, i32, f32, f32, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "unet_head_dzm_ex": (i32, [vp, vp, vp, vp, f64, vp, i32, f32, f32, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "unet_conv3x3_bwd_data_dzm": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "unet_conv3x3_bwd_weights_dzm": (i32, [vp, vp, vp, vp, vp, vp, vp, sz, i32, i32, i32, i32, vp]),
     "unet_zero": (i32, [vp, vp, sz, vp]),
@@ -162,6 +173,7 @@ _PROTOS = {
     "unet_model_set_io": (i32, [vp, vp, vp, vp]),
     "unet_model_set_dropout": (i32, [vp, f32, u64]),
     "unet_model_set_class_weights": (i32, [vp, f32, f32]),
+    "unet_model_set_loss": (i32, [vp, i32, f32, f32]),
     "unet_model_num_ops": (i32, [vp, i32]),
     "unet_model_sync_points": (i32, [vp, i32, C.POINTER(SyncPoint), i32]),
     "unet_model_run": (i32, [vp, i32, i32, i32, vp]),

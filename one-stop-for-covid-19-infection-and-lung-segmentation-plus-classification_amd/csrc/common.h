@@ -16,6 +16,15 @@
 // Deterministic mode (UNET_OPT_DETERMINISTIC): UNET_BN_SLOTS_DET copies, every workgroup of a reduction kernel owns ONE copy (grids are capped at the copy
 // count), so each atomic lands on a zero it alone writes, and the fold kernel sums the copies in index order: bit-identical reruns.
 constexpr int UNET_BN_SLOTS = 64, UNET_BN_SLOTS_DET = 1024, UNET_BN_SLOT_DOUBLES = 2048;
+// the training loss of a U-Net / U-Net++ model (include/unet_hip.h UNET_LOSS_*): passed by value to the kernels that turn the loss sums into the loss and dz
+struct unet_loss_sel { int32_t kind = UNET_LOSS_BCE_DICE; float alpha = 0.5f, beta = 0.5f; };
+// a valid selection: a known loss; Tversky's weights both > 0 and finite (alpha = 0 or beta = 0 makes den = I + ... vanish on an all-background batch); the weighted loss
+// with its weight map where the caller consumes one per pixel (need_map)
+inline bool unet_loss_sel_ok(const unet_loss_sel& ls, const float* wm = nullptr, bool need_map = true) {
+  if (ls.kind < UNET_LOSS_BCE_DICE || ls.kind > UNET_LOSS_WEIGHTED_BCE_DICE) return false;
+  if (ls.kind == UNET_LOSS_TVERSKY && !(ls.alpha > 0.0f && ls.beta > 0.0f && ls.alpha < 1e30f && ls.beta < 1e30f)) return false;
+  return !need_map || (ls.kind == UNET_LOSS_WEIGHTED_BCE_DICE) == (wm != nullptr);
+}
 constexpr int UNET_HEAD_SUMS = 100;          // doubles behind the loss sums: the per-channel sums of a fused head's weight gradient (k_head_fold)
 struct unet_ctx {
   int device = 0;
@@ -352,19 +361,21 @@ int32_t k_conv3x3_h2_dgrad_pool_sums(unet_ctx*, const float* dy, const void* wim
 int32_t k_bn_finalize_compose(unet_ctx*, int training, const double* sums, double count, const float* gamma, const float* beta, float* mm, float* mv, float* bnp, int c,
                               const float* enc_bnp, float* comp, hipStream_t s);
 // unet_loss_finalize / unet_cls_loss_finalize with a second destination (unet_model_set_loss_out; nullptr = none)
-int32_t k_loss_finalize(unet_ctx*, const double* loss_sums, double count, float* loss_out, float* loss_out2, hipStream_t s);
+int32_t k_loss_finalize(unet_ctx*, const double* loss_sums, double count, float* loss_out, float* loss_out2, hipStream_t s, unet_loss_sel ls = {});
 int32_t k_cls_loss_finalize(unet_ctx*, const double* sums, double count, float* out, float* out2, hipStream_t s);
 int32_t k_bn_compose(unet_ctx*, const float* bnp_dec, const float* bnp_enc, float* comp, int c, hipStream_t s);
-struct h2_head_args { const float* w = nullptr; const float* b = nullptr; float* p = nullptr; const float* t = nullptr; double* slots = nullptr; float aux = 0.0f; };          // (MASK_POOL_SUMS: w = gamma, b = beta, aux = dropout rate)
+struct h2_head_args { const float* w = nullptr; const float* b = nullptr; float* p = nullptr; const float* t = nullptr; double* slots = nullptr; float aux = 0.0f; const float* wm = nullptr; };          // (MASK_POOL_SUMS: w = gamma, b = beta, aux = dropout rate)
 bool h2_conv3x3_head_selected(const unet_ctx* ctx, int algo, int wd, int K, int M);
 int32_t k_conv3x3_h2_head_fwd(unet_ctx*, const float* x, const void* wimg, const float* bias, float* y, const float* wh, const float* bh, float* p, const float* t,
-                              int n, int h, int wd, int K, hipStream_t s);
+                              int n, int h, int wd, int K, hipStream_t s, const float* wm = nullptr);          // wm: weighted_bce_dice_loss's map (EPI 4: {w l, ..| w a, ..., w}, 104 sums)
 // the sums k_conv3x3_h2_head_fwd left in the slot copies -> loss_sums[4] (+=) and head_sums[99] (+=): [32 x 3 per-channel sums][sum a, sum t q, sum q]
-int32_t k_head_fold(unet_ctx*, double* loss_sums, double* head_sums, hipStream_t s);
+int32_t k_head_fold(unet_ctx*, double* loss_sums, double* head_sums, hipStream_t s, bool weighted = false);          // weighted: [103] = sum w -> loss_sums[4]
+// weighted_bce_dice_loss's weight map w[n,h,wd] of the labels (kernels_pointwise.hip)
+int32_t k_loss_weight_map(unet_ctx*, const float* y_true, float* weight, int n, int h, int wd, hipStream_t s);
 // backward of the fused head: dy[p][c] = dz_p w_c [y_pc > 0] (mask from the sign bits `bits` or, if null, from y itself) and -- workgroup 0 -- the head's weight /
 // bias gradient out of head_sums and the batch-global loss sums (ACCUMULATED into dw[32], db[1])
 int32_t k_head_dy(unet_ctx*, const float* p, const float* t, const double* loss_sums, double count, const double* head_sums, const float* w, const unsigned long long* bits,
-                  const float* y, float* dy, float* dw, float* db, int n, int h, int wd, hipStream_t s);
+                  const float* y, float* dy, float* dw, float* db, int n, int h, int wd, hipStream_t s, unet_loss_sel ls = {}, const float* wm = nullptr);
 int32_t k_bn_maxpool_bwd_apply_k1(unet_ctx*, const float* x, int ldx, const float* bnp, const double* sums, double count, const float* g_skip, int ldg, const float* skip_k1,
                                   const float* dy_pooled, float* dx, int lddx, int n, int h, int wd, int c, float rate, uint64_t seed, hipStream_t s);
 bool h2_convT_selected(const unet_ctx* ctx, int algo, int cin, int cout);
@@ -381,7 +392,7 @@ int32_t k_conv3x3_h2_wgrad(unet_ctx*, const float* x, const float* dy, float* dw
 // the head's backward as a rank-1 stream: k_head_dzm writes dzm[n,h,wd] = {dz, 32 mask bits} (+ the head's own dw / db, accumulated), the two gradients of the
 // last conv3x3 expand it while staging
 int32_t k_head_dzm(unet_ctx*, const float* p, const float* t, const double* loss_sums, double count, const double* head_sums, const unsigned long long* bits, void* dzm, float* dw,
-                   float* db, int n, int h, int wd, hipStream_t s);
+                   float* db, int n, int h, int wd, hipStream_t s, unet_loss_sel ls = {}, const float* wm = nullptr);
 bool h2_head_bwd_selected(const unet_ctx* ctx, int algo, int wd, int cin);
 int32_t k_conv3x3_h2_dgrad_dzm(unet_ctx*, const void* dzm, const void* wimg, const float* mask, int mask_mode, float* dx, int n, int h, int wd, int M, hipStream_t s);
 int32_t k_conv3x3_h2_wgrad_dzm(unet_ctx*, const float* x, const void* dzm, const float* w_head, float* dw, float* db, void* ws, size_t ws_bytes, int n, int h, int wd, int cin,

@@ -166,7 +166,7 @@ __global__ __launch_bounds__(256, WPS) void conv_h2_kernel(const float* __restri
                                                            int mask_mode, float rate, unsigned long long seed, int tiles_x, int tiles_y, int groups,
                                                            int total_blocks, double* __restrict__ stats, int stats_c, unsigned long long* __restrict__ signs,
                                                            int mask_climit, h2_head_args hd, int img_nb, int xs, int kcps, long long y_split) {
-  constexpr bool HEAD = EPI == 1, POOLS = EPI == 2;          // EPI: 0 the general epilogue, 1 + the 1x1 sigmoid head (below), 2 + the pooled-path sums of an encoder tail (MASK_POOL_SUMS)
+  constexpr bool HEAD = EPI == 1 || EPI == 4, WHEAD = EPI == 4, POOLS = EPI == 2;          // EPI 4: HEAD for weighted_bce_dice_loss (its weight map hd.wm weighs the BCE terms)          // EPI: 0 the general epilogue, 1 + the 1x1 sigmoid head (below), 2 + the pooled-path sums of an encoder tail (MASK_POOL_SUMS)
   // EPI 3 (VDY): the general epilogue behind a VIRTUAL input -- the gradient of the last conv3x3's output, dy[p][c] = dz_p w_c [y_pc > 0] (T1:911-913 backwards), staged from
   // the 8-byte-per-pixel stream {dz_p, 32 mask bits} of head_dzm_kernel (x = that stream, ldx = 2): one value is scaled and split per staged piece, the mask bits pick
   // the channels it goes to; w_c is a per-contraction-channel factor of the weight image (h2_prep::cs).  K = 32.
@@ -471,6 +471,8 @@ __global__ __launch_bounds__(256, WPS) void conv_h2_kernel(const float* __restri
   const bool hvalid = HEAD && hpy < H && px_ < W;
   float hlabel = 0.f;
   if (HEAD && hd.t && hvalid) hlabel = hd.t[((long long)n * H + hpy) * W + px_];
+  float hwt = 0.f;
+  if (WHEAD && hd.t && hvalid) hwt = hd.wm[((long long)n * H + hpy) * W + px_];
   __builtin_amdgcn_s_setprio(2);
   mfma_chunk();
   __builtin_amdgcn_s_setprio(0);
@@ -521,8 +523,13 @@ __global__ __launch_bounds__(256, WPS) void conv_h2_kernel(const float* __restri
     {
       const bool on = hvalid && hd.t != nullptr;            // (inference: probabilities only)
       float* rec = s_rec + (hi * 32 + l31) * 8;             // {bce, t p, t, p | a, t q, q, 0}: a = dBCE/dz inside the clip range, q = p (1 - p)
-      *reinterpret_cast<float4*>(rec) = on ? make_float4(bce, tl * pr, tl, pr) : make_float4(0.f, 0.f, 0.f, 0.f);
-      *reinterpret_cast<float4*>(rec + 4) = on ? make_float4(inr ? pc - tl : 0.f, tl * qq, qq, 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
+      if constexpr (WHEAD) {                                // {w bce, t p, t, p | w a, t q, q, w}: the weighted BCE sum, sum w a y_c and, as scalar 7, sum w
+        *reinterpret_cast<float4*>(rec) = on ? make_float4(hwt * bce, tl * pr, tl, pr) : make_float4(0.f, 0.f, 0.f, 0.f);
+        *reinterpret_cast<float4*>(rec + 4) = on ? make_float4(inr ? hwt * (pc - tl) : 0.f, tl * qq, qq, hwt) : make_float4(0.f, 0.f, 0.f, 0.f);
+      } else {
+        *reinterpret_cast<float4*>(rec) = on ? make_float4(bce, tl * pr, tl, pr) : make_float4(0.f, 0.f, 0.f, 0.f);
+        *reinterpret_cast<float4*>(rec + 4) = on ? make_float4(inr ? pc - tl : 0.f, tl * qq, qq, 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
+      }
     }
     float4 g1 = make_float4(0.f, 0.f, 0.f, 0.f), g2 = g1, g3 = g1; float gs = 0.f;
 #pragma unroll
@@ -576,7 +583,7 @@ __global__ __launch_bounds__(256, WPS) void conv_h2_kernel(const float* __restri
         s_hsum[wave * 104 + 96 + lane] = sv[12];
       }
       __syncthreads();
-      if (tid < 103) {                                     // [0, 96): the three per-channel sums; 96..99: bce, t p, t, p; 100..102: sum a, sum t q, sum q
+      if (tid < (WHEAD ? 104 : 103)) {                     // [0, 96): the three per-channel sums; 96..99: bce, t p, t, p; 100..102: sum a, sum t q, sum q; (EPI 4) 103: sum w
         const float t = (s_hsum[tid] + s_hsum[104 + tid]) + (s_hsum[208 + tid] + s_hsum[312 + tid]);
         double* const row = hd.slots + (size_t)(blockIdx.x % UNET_BN_SLOTS) * UNET_BN_SLOT_DOUBLES;
         if (xs) xsum_add(row, tid, t); else atomicAdd(row + tid, (double)t);          // (xs: deterministic mode -- exact window sums, common.h)
@@ -858,7 +865,7 @@ int32_t launch_h2(unet_ctx* ctx, const float* x, int ldx, const unet_bf16* wimg,
       return UNET_OK;
     } else UNET_FAIL(ctx, UNET_E_ARG, "conv h2: K slices exist for the one-block conv3x3 launches");
   }
-  if (EPI == 1) {
+  if (EPI == 1 || EPI == 4) {
     if (gen || mask_mode != MASK_NONE || act != ACT_RELU || M != 32 || stats) UNET_FAIL(ctx, UNET_E_ARG, "conv h2 + head: a plain 32-channel ReLU forward launch only");
     r = go(conv_h2_kernel<MODE, NB, RW, false, WPS, EPI>);
   } else if (EPI == 2) {
@@ -1074,10 +1081,11 @@ bool h2_conv3x3_head_selected(const unet_ctx* ctx, int algo, int wd, int K, int 
   return ctx && ctx->opt_head_fused && ctx->bn_slots && h2_conv3x3_selected(algo, K, M) && M == 32 && (wd & 7) == 0;
 }
 int32_t k_conv3x3_h2_head_fwd(unet_ctx* ctx, const float* x, const void* wimg, const float* bias, float* y, const float* wh, const float* bh, float* p, const float* t,
-                              int n, int h, int wd, int K, hipStream_t s) {
-  if (K < 16 || (K % 16) || !wh || !bh || !p) UNET_FAIL(ctx, UNET_E_ARG, "conv3x3 h2 + head: bad args");          // (y may be null: the 32-channel tensor is then not stored)
+                              int n, int h, int wd, int K, hipStream_t s, const float* wm) {
+  if (K < 16 || (K % 16) || !wh || !bh || !p || (wm && !t)) UNET_FAIL(ctx, UNET_E_ARG, "conv3x3 h2 + head: bad args");          // (y may be null: the 32-channel tensor is then not stored)
   if ((long long)h * wd * std::max(K, 32) * 4 >= (1LL << 30)) UNET_FAIL(ctx, UNET_E_SHAPE, "conv3x3 h2: one image must stay below 1 GiB (32-bit buffer offsets)");
-  h2_head_args hd; hd.w = wh; hd.b = bh; hd.p = p; hd.t = t; hd.slots = ctx->bn_slots;
+  h2_head_args hd; hd.w = wh; hd.b = bh; hd.p = p; hd.t = t; hd.slots = ctx->bn_slots; hd.wm = wm;
+  if (wm) return launch_h2<0, 1, 2, 4, 4>(ctx, x, K, static_cast<const unet_bf16*>(wimg), bias, nullptr, MASK_NONE, y, 32, n, h, wd, K, 32, ACT_RELU, 0.0f, 0, s, 1 << 30, hd);
   return launch_h2<0, 1, 2, 4, 1>(ctx, x, K, static_cast<const unet_bf16*>(wimg), bias, nullptr, MASK_NONE, y, 32, n, h, wd, K, 32, ACT_RELU, 0.0f, 0, s, 1 << 30, hd);
 }
 

@@ -465,17 +465,79 @@ __device__ __forceinline__ float bce_elem(float p, float t, float* pc_out, bool*
   return fmaxf(z, 0.0f) - z * t + log1pf(expf(-fabsf(z)));
 }
 
+// The selectable losses (include/unet_hip.h UNET_LOSS_*): every one has dz = cb a + q (A t + B) (a = dBCE/dz inside the clip range, q = p (1 - p))
+// with batch scalars of the global sums (sum l, I, St, Sp).  The kernels below take them through a GEN = true instantiation; the default bce_dice_loss runs the
+// GEN = false one, which keeps its own expression, so its results are those of the kernels before the losses were selectable.
+struct loss_coef { double cb, A, B; };
+__device__ __forceinline__ loss_coef loss_coefs(const double* sums, double inv_count, unet_loss_sel ls) {
+  const double I = sums[1], St = sums[2], Sp = sums[3];
+  loss_coef c = {0.0, 0.0, 0.0};
+  if (ls.kind == UNET_LOSS_BCE) {
+    c.cb = inv_count;
+  } else if (ls.kind == UNET_LOSS_DICE) {                               // 1 - D:  dL/dp = -2 t / S + D / S
+    const double S = St + Sp + 1.0;
+    c.A = -2.0 / S; c.B = (2.0 * I + 1.0) / (S * S);
+  } else if (ls.kind == UNET_LOSS_TVERSKY) {                            // 1 - I / den, d den / dp = alpha + t (1 - alpha - beta)
+    const double a = ls.alpha, b = ls.beta, den = I + a * (Sp - I) + b * (St - I);
+    c.A = -(den - I * (1.0 - a - b)) / (den * den); c.B = a * I / (den * den);
+  } else {                                                              // bce_dice_loss; weighted_bce_dice_loss: the BCE half over sum w (sums[4]) instead of N
+    const double S = St + Sp + 1.0;
+    c.cb = ls.kind == UNET_LOSS_WEIGHTED_BCE_DICE ? 0.5 / sums[4] : 0.5 * inv_count; c.A = -1.0 / S; c.B = 0.5 * (2.0 * I + 1.0) / (S * S);
+  }
+  return c;
+}
+__device__ __forceinline__ float loss_dz(float pr, float t, float cb, float A, float B, float w = 1.0f) {          // w: the weight map of weighted_bce_dice_loss (1 otherwise)
+  const float lo = 1e-7f, hi = 1.0f - 1e-7f;
+  const float pc = fminf(fmaxf(pr, lo), hi);
+  const bool inr = (pr >= lo) && (pr <= hi);
+  return (inr ? cb * w * (pc - t) : 0.0f) + pr * (1.0f - pr) * (A * t + B);
+}
+
+// weighted_bce_dice_loss's weight map (T1:837-845): w = 5 exp(-5 |avg - 0.5|) with avg = K.pool2d(y, (50, 50), strides 1, padding 'same', 'avg') -- TF's SAME
+// average pool: the window of output (r, c) covers rows r - 24 ... r + 25 and columns c - 24 ... c + 25 clipped to the image, divided by the number of in-image cells.
+// (T1 scales the map by w0 / w1 before weighted_bce_loss divides by its sum: the factor cancels, so it is left out.)  A workgroup: a 64 x 64 output tile; its
+// 113 x 113 input halo in LDS, then the 50-row column sums of its 64 rows x 113 columns, then the 50-column row sums -- direct window sums, no prefix differences.
+constexpr int WM_T = 64, WM_R = 50, WM_B = 24, WM_HALO = WM_T + WM_R - 1;          // 113
+__global__ __launch_bounds__(256) void loss_weight_map_kernel(const float* __restrict__ yt, float* __restrict__ wout, int H, int W) {
+  __shared__ float s_in[WM_HALO * WM_HALO];
+  __shared__ float s_col[WM_T * WM_HALO];
+  const int tx = blockIdx.x, ty = blockIdx.y, n = blockIdx.z;
+  const int r0 = ty * WM_T - WM_B, c0 = tx * WM_T - WM_B;
+  const float* img = yt + (size_t)n * H * W;
+  for (int i = threadIdx.x; i < WM_HALO * WM_HALO; i += 256) {
+    const int r = r0 + i / WM_HALO, c = c0 + i % WM_HALO;
+    s_in[i] = (r >= 0 && r < H && c >= 0 && c < W) ? img[(size_t)r * W + c] : 0.0f;
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < WM_T * WM_HALO; i += 256) {          // column sums: output row i / 113 of the tile, halo column i % 113
+    const int orow = i / WM_HALO, col = i % WM_HALO;
+    float a = 0.0f;
+    for (int k = 0; k < WM_R; ++k) a += s_in[(orow + k) * WM_HALO + col];
+    s_col[i] = a;
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < WM_T * WM_T; i += 256) {
+    const int orow = i / WM_T, ocol = i % WM_T, r = ty * WM_T + orow, c = tx * WM_T + ocol;
+    if (r >= H || c >= W) continue;
+    float a = 0.0f;
+    for (int k = 0; k < WM_R; ++k) a += s_col[orow * WM_HALO + ocol + k];
+    const int nr = min(r + WM_R - 1 - WM_B, H - 1) - max(r - WM_B, 0) + 1, nc = min(c + WM_R - 1 - WM_B, W - 1) - max(c - WM_B, 0) + 1;
+    const float avg = a / (float)(nr * nc);
+    wout[((size_t)n * H + r) * W + c] = 5.0f * expf(-5.0f * fabsf(avg - 0.5f));
+  }
+}
+
 template <typename T>
 __global__ __launch_bounds__(TPB) void head_fwd_kernel(const T* __restrict__ x, const float* __restrict__ w,
                                                        const float* __restrict__ bias, float* __restrict__ pout,
                                                        const float* __restrict__ yt, double* sums,
-                                                       long long pixels, int cin, int nslots) {
+                                                       long long pixels, int cin, int nslots, const float* __restrict__ wm) {
   if (nslots) sums += (size_t)(blockIdx.x % nslots) * UNET_BN_SLOT_DOUBLES;          // deterministic mode: `sums` = the slot copies, one writer per copy
   const int lpp = cin >> 2;
   const int sub = threadIdx.x & (lpp - 1);
   const float4 wv = ld4(w + sub * 4);
   const float b = bias[0];
-  float sb = 0, stp = 0, st = 0, sp = 0;
+  float sb = 0, stp = 0, st = 0, sp = 0, sw = 0;          // (sw and the weighted BCE: weighted_bce_dice_loss, wm != null)
   const long long gt0 = ((long long)blockIdx.x * TPB + threadIdx.x) / lpp;
   const long long gstride = ((long long)gridDim.x * TPB) / lpp;
   const long long iters = (pixels + gstride - 1) / gstride;   // uniform trip count: shuffles stay converged
@@ -490,17 +552,20 @@ __global__ __launch_bounds__(TPB) void head_fwd_kernel(const T* __restrict__ x, 
       pout[p] = pr;
       if (yt) {
         float t = yt[p], pc; bool inr;
-        sb += bce_elem(pr, t, &pc, &inr); stp += t * pr; st += t; sp += pr;
+        const float l = bce_elem(pr, t, &pc, &inr);
+        if (wm) { const float wv = wm[p]; sb += wv * l; sw += wv; } else sb += l;
+        stp += t * pr; st += t; sp += pr;
       }
     }
   }
   if (yt) {
-    __shared__ float red[4][TPB / 64];
+    __shared__ float red[5][TPB / 64];
     sb = wave_sum(sb); stp = wave_sum(stp); st = wave_sum(st); sp = wave_sum(sp);
+    if (wm) sw = wave_sum(sw);
     int wv_ = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { red[0][wv_] = sb; red[1][wv_] = stp; red[2][wv_] = st; red[3][wv_] = sp; }
+    if ((threadIdx.x & 63) == 0) { red[0][wv_] = sb; red[1][wv_] = stp; red[2][wv_] = st; red[3][wv_] = sp; red[4][wv_] = sw; }
     __syncthreads();
-    if (threadIdx.x < 4) {
+    if (threadIdx.x < (wm ? 5 : 4)) {
       float s = 0;
       for (int k = 0; k < TPB / 64; ++k) s += red[threadIdx.x][k];
       atomicAdd(sums + threadIdx.x, (double)s);
@@ -514,13 +579,13 @@ __global__ __launch_bounds__(TPB) void head_fwd_kernel(const T* __restrict__ x, 
 template <typename T, int LPP>
 __global__ __launch_bounds__(TPB) void head_fwd_lpp_kernel(const T* __restrict__ x, const float* __restrict__ w,
                                                            const float* __restrict__ bias, float* __restrict__ pout,
-                                                           const float* __restrict__ yt, double* sums, long long pixels, int nslots) {
+                                                           const float* __restrict__ yt, double* sums, long long pixels, int nslots, const float* __restrict__ wm) {
   if (nslots) sums += (size_t)(blockIdx.x % nslots) * UNET_BN_SLOT_DOUBLES;          // deterministic mode: `sums` = the slot copies, one writer per copy
   constexpr int cin = LPP * 4;
   const int sub = threadIdx.x & (LPP - 1);
   const float4 wv = ld4(w + sub * 4);
   const float b = bias[0];
-  float sb = 0, stp = 0, st = 0, sp = 0;
+  float sb = 0, stp = 0, st = 0, sp = 0, sw = 0;          // (sw and the weighted BCE: weighted_bce_dice_loss, wm != null)
   const long long g0 = ((long long)blockIdx.x * TPB + threadIdx.x) / LPP * LPP;          // first pixel of this lane group
   const long long gstride = (long long)gridDim.x * TPB;                                  // pixels per sweep of the whole grid
   const long long iters = (pixels + gstride - 1) / gstride;                               // uniform trip count: shuffles stay converged
@@ -543,17 +608,20 @@ __global__ __launch_bounds__(TPB) void head_fwd_lpp_kernel(const T* __restrict__
       pout[p] = pr;
       if (yt) {
         float t = yt[p], pc; bool inr;
-        sb += bce_elem(pr, t, &pc, &inr); stp += t * pr; st += t; sp += pr;
+        const float l = bce_elem(pr, t, &pc, &inr);
+        if (wm) { const float wv = wm[p]; sb += wv * l; sw += wv; } else sb += l;
+        stp += t * pr; st += t; sp += pr;
       }
     }
   }
   if (yt) {
-    __shared__ float red[4][TPB / 64];
+    __shared__ float red[5][TPB / 64];
     sb = wave_sum(sb); stp = wave_sum(stp); st = wave_sum(st); sp = wave_sum(sp);
+    if (wm) sw = wave_sum(sw);
     int wv_ = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { red[0][wv_] = sb; red[1][wv_] = stp; red[2][wv_] = st; red[3][wv_] = sp; }
+    if ((threadIdx.x & 63) == 0) { red[0][wv_] = sb; red[1][wv_] = stp; red[2][wv_] = st; red[3][wv_] = sp; red[4][wv_] = sw; }
     __syncthreads();
-    if (threadIdx.x < 4) {
+    if (threadIdx.x < (wm ? 5 : 4)) {
       float s = 0;
       for (int k = 0; k < TPB / 64; ++k) s += red[threadIdx.x][k];
       atomicAdd(sums + threadIdx.x, (double)s);
@@ -561,25 +629,32 @@ __global__ __launch_bounds__(TPB) void head_fwd_lpp_kernel(const T* __restrict__
   }
 }
 
-__global__ void loss_finalize_kernel(const double* sums, double count, float* out, float* out2) {
+__global__ void loss_finalize_kernel(const double* sums, double count, float* out, float* out2, unet_loss_sel ls) {
   double dice = (2.0 * sums[1] + 1.0) / (sums[2] + sums[3] + 1.0);
-  const float l = (float)(0.5 * (sums[0] / count) + 0.5 * (1.0 - dice)), d = (float)dice;
+  double other = 1.0 - dice;                                            // UNET_LOSS_DICE
+  if (ls.kind == UNET_LOSS_BCE) other = sums[0] / count;
+  else if (ls.kind == UNET_LOSS_WEIGHTED_BCE_DICE) other = 0.5 * (sums[0] / sums[4]) + 0.5 * (1.0 - dice);
+  else if (ls.kind == UNET_LOSS_TVERSKY) other = 1.0 - sums[1] / (sums[1] + ls.alpha * (sums[3] - sums[1]) + ls.beta * (sums[2] - sums[1]));
+  const float l = ls.kind == UNET_LOSS_BCE_DICE ? (float)(0.5 * (sums[0] / count) + 0.5 * (1.0 - dice)) : (float)other, d = (float)dice;
   out[0] = l; out[1] = d;
   if (out2) { out2[0] = l; out2[1] = d; }                     // (unet_model_set_loss_out: the caller's own copy of this step's pair -- no copy kernel behind the step)
 }
 
-template <typename T>
+template <typename T, bool GEN>
 __global__ __launch_bounds__(TPB) void head_bwd_kernel(const T* __restrict__ x, const float* __restrict__ w,
                                                        const float* __restrict__ pin, const float* __restrict__ yt,
                                                        const double* __restrict__ sums, double inv_count,
                                                        T* __restrict__ dx, float* dw, float* db,
-                                                       long long pixels, int cin, int relu_mask, double* slots, int nslots) {
+                                                       long long pixels, int cin, int relu_mask, double* slots, int nslots, unet_loss_sel ls,
+                                                       const float* __restrict__ wm) {
   const int lpp = cin >> 2;
   const int sub = threadIdx.x & (lpp - 1);
   const float4 wv = ld4(w + sub * 4);
   const double S = sums[2] + sums[3] + 1.0;
   const float dice = (float)((2.0 * sums[1] + 1.0) / S), invS = (float)(1.0 / S);
   const float hb = (float)(0.5 * inv_count);
+  const loss_coef lc = GEN ? loss_coefs(sums, inv_count, ls) : loss_coef{0.0, 0.0, 0.0};
+  const float lcb = (float)lc.cb, lA = (float)lc.A, lB = (float)lc.B;
   float4 aw = make_float4(0, 0, 0, 0); float ab = 0;
   const long long gt0 = ((long long)blockIdx.x * TPB + threadIdx.x) / lpp;
   const long long gstride = ((long long)gridDim.x * TPB) / lpp;
@@ -588,7 +663,7 @@ __global__ __launch_bounds__(TPB) void head_bwd_kernel(const T* __restrict__ x, 
     (void)bce_elem(pr, t, &pc, &inr);
     // d(BCE)/dz = (p - t) inside the clip range (the p(1-p) of the sigmoid cancels the 1/(p(1-p)) of the
     // log terms analytically -- no 1-p cancellation noise near saturation); the Dice part keeps p(1-p)
-    float dz = (inr ? hb * (pc - t) : 0.0f) - 0.5f * (2.0f * t - dice) * invS * pr * (1.0f - pr);
+    float dz = GEN ? loss_dz(pr, t, lcb, lA, lB, wm ? wm[p] : 1.0f) : (inr ? hb * (pc - t) : 0.0f) - 0.5f * (2.0f * t - dice) * invS * pr * (1.0f - pr);
     float4 v = ld4(x + p * cin + sub * 4);
     st4(dx + p * cin + sub * 4, make_float4((!relu_mask || v.x > 0) ? dz * wv.x : 0.f, (!relu_mask || v.y > 0) ? dz * wv.y : 0.f,
                                             (!relu_mask || v.z > 0) ? dz * wv.z : 0.f, (!relu_mask || v.w > 0) ? dz * wv.w : 0.f));
@@ -625,9 +700,9 @@ __global__ __launch_bounds__(TPB) void head_bwd_kernel(const T* __restrict__ x, 
 
 // ---- the fused head (kernels_conv_h2.hip: conv_h2_kernel<..., HEAD>) -------------------------------------------------
 // fold of the 103 sums it left in the slot copies (cleared for the next launch): [96, 100) -> loss_sums, the rest -> head_sums[99]
-__global__ void head_fold_kernel(double* __restrict__ slots, double* __restrict__ loss_sums, double* __restrict__ head_sums, int nslots, int xs) {
+__global__ void head_fold_kernel(double* __restrict__ slots, double* __restrict__ loss_sums, double* __restrict__ head_sums, int nslots, int xs, int nsum) {
   const int i = threadIdx.x;
-  if (i >= 103) return;
+  if (i >= nsum) return;                                    // nsum 104 (weighted_bce_dice_loss): [103] = sum w -> loss_sums[4]
   double s = 0.0;
   if (xs) s = xsum_take(slots, i, nslots);
   else
@@ -638,7 +713,7 @@ __global__ void head_fold_kernel(double* __restrict__ slots, double* __restrict_
 #pragma unroll
     for (int k = 0; k < 16; ++k) s += v[k];
   }
-  if (i < 96) head_sums[i] += s; else if (i < 100) loss_sums[i - 96] += s; else head_sums[96 + (i - 100)] += s;
+  if (i < 96) head_sums[i] += s; else if (i < 100) loss_sums[i - 96] += s; else if (i < 103) head_sums[96 + (i - 100)] += s; else loss_sums[4] += s;
 }
 
 // dz of pixel p from the stored probability, the label and the batch-global sums (the same expression as head_bwd_kernel)
@@ -653,15 +728,21 @@ __device__ __forceinline__ float head_dz(float pr, float t, float hb, float dice
 // per (row, 8 pixels) four 64-bit words, bit (pixel % 8) * 8 + quad of word k = channel quad * 4 + k) or, without bits, y itself.
 // Workgroup 0 also finishes the head's own gradient: dz = hb a - invS t q + 0.5 invS dice q, so
 //   dw_c = hb S1_c - invS S2_c + 0.5 invS dice S3_c  with the three per-channel sums the forward epilogue took; db the same with the scalar sums
+template <bool GEN>
 __global__ __launch_bounds__(TPB) void head_dy_kernel(const float* __restrict__ pin, const float* __restrict__ yt, const double* __restrict__ sums, double inv_count,
                                                       const double* __restrict__ hs, const float* __restrict__ w, const unsigned long long* __restrict__ bits,
-                                                      const float* __restrict__ y, float* __restrict__ dy, float* dw, float* db, long long pixels, int wd) {
+                                                      const float* __restrict__ y, float* __restrict__ dy, float* dw, float* db, long long pixels, int wd, unet_loss_sel ls,
+                                                      const float* __restrict__ wm) {
   const double S = sums[2] + sums[3] + 1.0;
   const float dice = (float)((2.0 * sums[1] + 1.0) / S), invS = (float)(1.0 / S);
   const float hb = (float)(0.5 * inv_count);
+  const loss_coef lc = GEN ? loss_coefs(sums, inv_count, ls) : loss_coef{0.0, 0.0, 0.0};
+  const float lcb = (float)lc.cb, lA = (float)lc.A, lB = (float)lc.B;
   if (blockIdx.x == 0 && threadIdx.x < 33) {
     const int c = threadIdx.x;
-    const double g = c < 32 ? (0.5 * inv_count) * hs[c] - (1.0 / S) * hs[32 + c] + 0.5 * (1.0 / S) * ((2.0 * sums[1] + 1.0) / S) * hs[64 + c]
+    const int i0 = c < 32 ? c : 96, i1 = c < 32 ? 32 + c : 97, i2 = c < 32 ? 64 + c : 98;
+    const double g = GEN ? lc.cb * hs[i0] + lc.A * hs[i1] + lc.B * hs[i2]
+                   : c < 32 ? (0.5 * inv_count) * hs[c] - (1.0 / S) * hs[32 + c] + 0.5 * (1.0 / S) * ((2.0 * sums[1] + 1.0) / S) * hs[64 + c]
                             : (0.5 * inv_count) * hs[96] - (1.0 / S) * hs[97] + 0.5 * (1.0 / S) * ((2.0 * sums[1] + 1.0) / S) * hs[98];
     if (c < 32) dw[c] += (float)g; else db[0] += (float)g;
   }
@@ -669,7 +750,7 @@ __global__ __launch_bounds__(TPB) void head_dy_kernel(const float* __restrict__ 
   const float4 wv = ld4(w + q * 4);
   for (long long i = (long long)blockIdx.x * TPB + threadIdx.x; i < pixels * 8; i += (long long)gridDim.x * TPB) {
     const long long p = i >> 3;
-    const float dz = head_dz(pin[p], yt[p], hb, dice, invS);
+    const float dz = GEN ? loss_dz(pin[p], yt[p], lcb, lA, lB, wm ? wm[p] : 1.0f) : head_dz(pin[p], yt[p], hb, dice, invS);
     bool m0, m1, m2, m3;
     if (bits) {
       const long long row = p / wd; const int x = (int)(p - row * wd);
@@ -688,20 +769,25 @@ __global__ __launch_bounds__(TPB) void head_dy_kernel(const float* __restrict__ 
 // (bit c of mask_p = y_pc > 0; 8 bytes instead of the 128 head_dy_kernel writes): the data gradient and the weight gradient of the last conv3x3 expand it while they
 // stage it (kernels_conv_h2.hip EPI 3, kernels_wgrad_h2.hip VDY) -- w_c goes into the data gradient's weight image / the weight gradient's column scale.
 // A thread: one pixel.  The sign bits of 8 pixels x 32 channels are four 64-bit words (layout above): byte x % 8 of word k holds channels k, 4 + k, 8 + k, ...
+template <bool GEN>
 __global__ __launch_bounds__(TPB) void head_dzm_kernel(const float* __restrict__ pin, const float* __restrict__ yt, const double* __restrict__ sums, double inv_count,
                                                        const double* __restrict__ hs, const unsigned long long* __restrict__ bits, uint2* __restrict__ out, float* dw, float* db,
-                                                       long long pixels, int wd) {
+                                                       long long pixels, int wd, unet_loss_sel ls, const float* __restrict__ wm) {
   const double S = sums[2] + sums[3] + 1.0;
   const float dice = (float)((2.0 * sums[1] + 1.0) / S), invS = (float)(1.0 / S);
   const float hb = (float)(0.5 * inv_count);
+  const loss_coef lc = GEN ? loss_coefs(sums, inv_count, ls) : loss_coef{0.0, 0.0, 0.0};
+  const float lcb = (float)lc.cb, lA = (float)lc.A, lB = (float)lc.B;
   if (blockIdx.x == 0 && threadIdx.x < 33) {
     const int c = threadIdx.x;
-    const double g = c < 32 ? (0.5 * inv_count) * hs[c] - (1.0 / S) * hs[32 + c] + 0.5 * (1.0 / S) * ((2.0 * sums[1] + 1.0) / S) * hs[64 + c]
+    const int i0 = c < 32 ? c : 96, i1 = c < 32 ? 32 + c : 97, i2 = c < 32 ? 64 + c : 98;
+    const double g = GEN ? lc.cb * hs[i0] + lc.A * hs[i1] + lc.B * hs[i2]
+                   : c < 32 ? (0.5 * inv_count) * hs[c] - (1.0 / S) * hs[32 + c] + 0.5 * (1.0 / S) * ((2.0 * sums[1] + 1.0) / S) * hs[64 + c]
                             : (0.5 * inv_count) * hs[96] - (1.0 / S) * hs[97] + 0.5 * (1.0 / S) * ((2.0 * sums[1] + 1.0) / S) * hs[98];
     if (c < 32) dw[c] += (float)g; else db[0] += (float)g;
   }
   for (long long p = (long long)blockIdx.x * TPB + threadIdx.x; p < pixels; p += (long long)gridDim.x * TPB) {
-    const float dz = head_dz(pin[p], yt[p], hb, dice, invS);
+    const float dz = GEN ? loss_dz(pin[p], yt[p], lcb, lA, lB, wm ? wm[p] : 1.0f) : head_dz(pin[p], yt[p], hb, dice, invS);
     const long long row = p / wd; const int x = (int)(p - row * wd);
     const unsigned long long* bw = bits + (row * (wd >> 3) + (x >> 3)) * 4;
     const int sh = (x & 7) * 8;
@@ -1040,8 +1126,9 @@ extern "C++" template <typename T> static int32_t bn_maxpool_bwd_apply_impl(unet
 }
 
 extern "C++" template <typename T> static int32_t head_fwd_impl(unet_ctx* ctx, const T* x, const float* w, const float* bias, float* p, const float* y_true,
-                      double* loss_sums, int64_t pixels, int32_t cin, void* stream) {
+                      double* loss_sums, int64_t pixels, int32_t cin, void* stream, const float* wm = nullptr) {
   if (!x || !w || !bias || !p || (cin & 3) || !pow2(cin / 4) || cin / 4 > 64 || (y_true && !loss_sums)) UNET_FAIL(ctx, UNET_E_ARG, "head_fwd: bad args (cin/4 must be a power of two <= 64)");
+  if (!y_true) wm = nullptr;                                // (wm: weighted_bce_dice_loss's map -- the BCE sum is weighted and sum w goes to loss_sums[4])
   // deterministic mode: the four loss sums go through the context's slot copies (one workgroup per copy) and are folded in index order
   const bool det = ctx->opt_deterministic && y_true;
   const int nslots = det ? ctx->bn_nslots() : 0;
@@ -1049,30 +1136,43 @@ extern "C++" template <typename T> static int32_t head_fwd_impl(unet_ctx* ctx, c
   if (cin == 32) {            // the U-Net / U-Net++ heads
     const int lpp_blocks = det ? nslots : 2048;     // 8 loads in flight per lane: 2048 workgroups measured best (0.119 ms fp32 / 0.085 bf16; 8192: 0.141)
     const unsigned grid = (unsigned)std::max<long long>(1, std::min<long long>(cdiv64(pixels, TPB * 2), lpp_blocks));
-    hipLaunchKernelGGL((head_fwd_lpp_kernel<T, 8>), dim3(grid), dim3(TPB), 0, as_stream(stream), x, w, bias, p, y_true, target, (long long)pixels, nslots);
+    hipLaunchKernelGGL((head_fwd_lpp_kernel<T, 8>), dim3(grid), dim3(TPB), 0, as_stream(stream), x, w, bias, p, y_true, target, (long long)pixels, nslots, wm);
   } else {
-    hipLaunchKernelGGL(head_fwd_kernel<T>, dim3((unsigned)std::max<long long>(1, std::min<long long>(cdiv64(pixels * (cin / 4) / 4, TPB), det ? nslots : HEAD_BLOCKS))), dim3(TPB), 0, as_stream(stream), x, w, bias, p, y_true, target, (long long)pixels, cin, nslots);
+    hipLaunchKernelGGL(head_fwd_kernel<T>, dim3((unsigned)std::max<long long>(1, std::min<long long>(cdiv64(pixels * (cin / 4) / 4, TPB), det ? nslots : HEAD_BLOCKS))), dim3(TPB), 0, as_stream(stream), x, w, bias, p, y_true, target, (long long)pixels, cin, nslots, wm);
   }
-  if (det) hipLaunchKernelGGL(bn_slot_fold_kernel<double>, dim3(1), dim3(128), 0, as_stream(stream), ctx->bn_slots, loss_sums, 4, nslots);
+  if (det) hipLaunchKernelGGL(bn_slot_fold_kernel<double>, dim3(1), dim3(128), 0, as_stream(stream), ctx->bn_slots, loss_sums, wm ? 5 : 4, nslots);
   UNET_CHECK_LAUNCH(ctx, "head_fwd"); return UNET_OK;
 }
 
-extern "C++" int32_t k_loss_finalize(unet_ctx* ctx, const double* loss_sums, double count, float* loss_out, float* loss_out2, hipStream_t s) {
-  if (!loss_sums || !loss_out || count < 1) UNET_FAIL(ctx, UNET_E_ARG, "loss_finalize: bad args");
-  hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(1), 0, s, loss_sums, count, loss_out, loss_out2);
+extern "C++" int32_t k_loss_weight_map(unet_ctx* ctx, const float* y_true, float* weight, int n, int h, int wd, hipStream_t s) {
+  if (!y_true || !weight || n < 1 || h < 1 || wd < 1 || n > 65535 || h > 65535 * WM_T) UNET_FAIL(ctx, UNET_E_ARG, "loss_weight_map: bad args");
+  hipLaunchKernelGGL(loss_weight_map_kernel, dim3((wd + WM_T - 1) / WM_T, (h + WM_T - 1) / WM_T, n), dim3(256), 0, s, y_true, weight, h, wd);
+  UNET_CHECK_LAUNCH(ctx, "loss_weight_map"); return UNET_OK;
+}
+int32_t unet_loss_weight_map(unet_ctx* ctx, const float* y_true, float* weight, int32_t n, int32_t h, int32_t wd, void* stream) {
+  return k_loss_weight_map(ctx, y_true, weight, n, h, wd, as_stream(stream));
+}
+extern "C++" int32_t k_loss_finalize(unet_ctx* ctx, const double* loss_sums, double count, float* loss_out, float* loss_out2, hipStream_t s, unet_loss_sel ls) {
+  if (!loss_sums || !loss_out || count < 1 || !unet_loss_sel_ok(ls, nullptr, false)) UNET_FAIL(ctx, UNET_E_ARG, "loss_finalize: bad args");
+  hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(1), 0, s, loss_sums, count, loss_out, loss_out2, ls);
   UNET_CHECK_LAUNCH(ctx, "loss_finalize"); return UNET_OK;
 }
 int32_t unet_loss_finalize(unet_ctx* ctx, const double* loss_sums, double count, float* loss_out, void* stream) {
   return k_loss_finalize(ctx, loss_sums, count, loss_out, nullptr, as_stream(stream));
 }
+int32_t unet_loss_finalize_ex(unet_ctx* ctx, const double* loss_sums, double count, int32_t loss, float alpha, float beta, float* loss_out, void* stream) {          // (weighted: loss_sums[5])
+  return k_loss_finalize(ctx, loss_sums, count, loss_out, nullptr, as_stream(stream), unet_loss_sel{loss, alpha, beta});
+}
 
 extern "C++" template <typename T> static int32_t head_bwd_impl(unet_ctx* ctx, const T* x, const float* w, const float* p, const float* y_true,
                       const double* loss_sums, double count, T* dx, float* dw, float* db, int64_t pixels, int32_t cin,
-                      int32_t relu_mask, void* stream) {
-  if (!x || !w || !p || !y_true || !loss_sums || !dx || !dw || !db || (cin & 3) || !pow2(cin / 4) || cin / 4 > 64 || count < 1) UNET_FAIL(ctx, UNET_E_ARG, "head_bwd: bad args");
+                      int32_t relu_mask, void* stream, unet_loss_sel ls = {}, const float* wm = nullptr) {
+  if (!x || !w || !p || !y_true || !loss_sums || !dx || !dw || !db || (cin & 3) || !pow2(cin / 4) || cin / 4 > 64 || count < 1 || !unet_loss_sel_ok(ls, wm)) UNET_FAIL(ctx, UNET_E_ARG, "head_bwd: bad args");
   const int nslots = ctx->opt_deterministic ? ctx->bn_nslots() : 0;
-  hipLaunchKernelGGL(head_bwd_kernel<T>, dim3(std::min(grid_for(pixels * (cin / 4) / 4), 1024)), dim3(TPB), 0, as_stream(stream), x, w, p, y_true, loss_sums, 1.0 / count, dx, dw, db, (long long)pixels, cin, relu_mask,
-                     ctx->bn_slots, nslots);
+  if (ls.kind != UNET_LOSS_BCE_DICE) hipLaunchKernelGGL((head_bwd_kernel<T, true>), dim3(std::min(grid_for(pixels * (cin / 4) / 4), 1024)), dim3(TPB), 0, as_stream(stream),
+                     x, w, p, y_true, loss_sums, 1.0 / count, dx, dw, db, (long long)pixels, cin, relu_mask, ctx->bn_slots, nslots, ls, wm);
+  else hipLaunchKernelGGL((head_bwd_kernel<T, false>), dim3(std::min(grid_for(pixels * (cin / 4) / 4), 1024)), dim3(TPB), 0, as_stream(stream),
+                     x, w, p, y_true, loss_sums, 1.0 / count, dx, dw, db, (long long)pixels, cin, relu_mask, ctx->bn_slots, nslots, ls, wm);
   if (nslots) {                                            // (dw and db are adjacent in the flat gradient buffer or not: two folds)
     hipLaunchKernelGGL(bn_slot_fold_kernel<float>, dim3(1), dim3(128), 0, as_stream(stream), ctx->bn_slots, dw, cin, nslots);
     hipLaunchKernelGGL(bn_slot_fold_kernel<float>, dim3(1), dim3(128), 0, as_stream(stream), ctx->bn_slots + cin, db, 1, nslots);
@@ -1098,26 +1198,32 @@ extern "C++" int32_t k_bn_finalize_compose(unet_ctx* ctx, int training, const do
   else hipLaunchKernelGGL(bn_finalize_infer_kernel, dim3((c + 127) / 128), dim3(128), 0, s, gamma, beta, mm, mv, bnp, c, 1e-3f, enc_bnp, comp);
   UNET_CHECK_LAUNCH(ctx, "bn_finalize_compose"); return UNET_OK;
 }
-extern "C++" int32_t k_head_fold(unet_ctx* ctx, double* loss_sums, double* head_sums, hipStream_t s) {
+extern "C++" int32_t k_head_fold(unet_ctx* ctx, double* loss_sums, double* head_sums, hipStream_t s, bool weighted) {
   if (!loss_sums || !head_sums) UNET_FAIL(ctx, UNET_E_ARG, "head_fold: bad args");
-  hipLaunchKernelGGL(head_fold_kernel, dim3(1), dim3(128), 0, s, ctx->bn_slots, loss_sums, head_sums, UNET_BN_SLOTS, ctx->opt_deterministic ? 1 : 0);
+  hipLaunchKernelGGL(head_fold_kernel, dim3(1), dim3(128), 0, s, ctx->bn_slots, loss_sums, head_sums, UNET_BN_SLOTS, ctx->opt_deterministic ? 1 : 0, weighted ? 104 : 103);
   UNET_CHECK_LAUNCH(ctx, "head_fold"); return UNET_OK;
 }
 
 extern "C++" int32_t k_head_dzm(unet_ctx* ctx, const float* p, const float* t, const double* loss_sums, double count, const double* head_sums, const unsigned long long* bits,
-                               void* dzm, float* dw, float* db, int n, int h, int wd, hipStream_t s) {
-  if (!p || !t || !loss_sums || !head_sums || !bits || !dzm || !dw || !db || count < 1 || (wd & 7)) UNET_FAIL(ctx, UNET_E_ARG, "head_dzm: bad args");
+                               void* dzm, float* dw, float* db, int n, int h, int wd, hipStream_t s, unet_loss_sel ls, const float* wm) {
+  if (!p || !t || !loss_sums || !head_sums || !bits || !dzm || !dw || !db || count < 1 || (wd & 7) || !unet_loss_sel_ok(ls, wm)) UNET_FAIL(ctx, UNET_E_ARG, "head_dzm: bad args");
   const long long pixels = (long long)n * h * wd;
-  hipLaunchKernelGGL(head_dzm_kernel, dim3(std::min(grid_for(pixels), 4096)), dim3(TPB), 0, s, p, t, loss_sums, 1.0 / count, head_sums, bits, static_cast<uint2*>(dzm), dw, db, pixels, wd);
+  if (ls.kind != UNET_LOSS_BCE_DICE) hipLaunchKernelGGL((head_dzm_kernel<true>), dim3(std::min(grid_for(pixels), 4096)), dim3(TPB), 0, s, p, t, loss_sums, 1.0 / count,
+                     head_sums, bits, static_cast<uint2*>(dzm), dw, db, pixels, wd, ls, wm);
+  else hipLaunchKernelGGL((head_dzm_kernel<false>), dim3(std::min(grid_for(pixels), 4096)), dim3(TPB), 0, s, p, t, loss_sums, 1.0 / count,
+                     head_sums, bits, static_cast<uint2*>(dzm), dw, db, pixels, wd, ls, wm);
   UNET_CHECK_LAUNCH(ctx, "head_dzm"); return UNET_OK;
 }
 
 extern "C++" int32_t k_head_dy(unet_ctx* ctx, const float* p, const float* t, const double* loss_sums, double count, const double* head_sums, const float* w, const unsigned long long* bits,
-                  const float* y, float* dy, float* dw, float* db, int n, int h, int wd, hipStream_t s) {
-  if (!p || !t || !loss_sums || !head_sums || !w || (!bits && !y) || !dy || !dw || !db || count < 1 || (bits && (wd & 7))) UNET_FAIL(ctx, UNET_E_ARG, "head_dy: bad args");
+                  const float* y, float* dy, float* dw, float* db, int n, int h, int wd, hipStream_t s, unet_loss_sel ls, const float* wm) {
+  if (!p || !t || !loss_sums || !head_sums || !w || (!bits && !y) || !dy || !dw || !db || count < 1 || (bits && (wd & 7)) || !unet_loss_sel_ok(ls, wm)) UNET_FAIL(ctx, UNET_E_ARG, "head_dy: bad args");
   const long long pixels = (long long)n * h * wd;
   const int head_dy_blocks = 16384;          // (a thread: 8 iterations at 512 x 512 x 16)
-  hipLaunchKernelGGL(head_dy_kernel, dim3(std::min(grid_for(pixels * 8 / 4), head_dy_blocks)), dim3(TPB), 0, s, p, t, loss_sums, 1.0 / count, head_sums, w, bits, y, dy, dw, db, pixels, wd);
+  if (ls.kind != UNET_LOSS_BCE_DICE) hipLaunchKernelGGL((head_dy_kernel<true>), dim3(std::min(grid_for(pixels * 8 / 4), head_dy_blocks)), dim3(TPB), 0, s, p, t, loss_sums,
+                     1.0 / count, head_sums, w, bits, y, dy, dw, db, pixels, wd, ls, wm);
+  else hipLaunchKernelGGL((head_dy_kernel<false>), dim3(std::min(grid_for(pixels * 8 / 4), head_dy_blocks)), dim3(TPB), 0, s, p, t, loss_sums,
+                     1.0 / count, head_sums, w, bits, y, dy, dw, db, pixels, wd, ls, wm);
   UNET_CHECK_LAUNCH(ctx, "head_dy"); return UNET_OK;
 }
 
@@ -1213,8 +1319,20 @@ int32_t unet_maxpool2x2_dropout_bwd_bnstats(unet_ctx* ctx, const float* y, int32
 int32_t unet_maxpool2x2_dropout_bwd_bnstats_bf16(unet_ctx* ctx, const unet_bf16* y, int32_t ldy, const unet_bf16* dy, unet_bf16* dx, int32_t lddx, const float* gamma, const float* beta, double* sums, int32_t n, int32_t h, int32_t wd, int32_t c, float rate, uint64_t seed, void* stream) { return maxpool_bwd_bnstats_impl(ctx, y, ldy, dy, dx, lddx, gamma, beta, sums, n, h, wd, c, rate, seed, stream); }
 int32_t unet_head_fwd(unet_ctx* ctx, const float* x, const float* w, const float* bias, float* p, const float* y_true, double* loss_sums, int64_t pixels, int32_t cin, void* stream) { return head_fwd_impl(ctx, x, w, bias, p, y_true, loss_sums, pixels, cin, stream); }
 int32_t unet_head_fwd_bf16(unet_ctx* ctx, const unet_bf16* x, const float* w, const float* bias, float* p, const float* y_true, double* loss_sums, int64_t pixels, int32_t cin, void* stream) { return head_fwd_impl(ctx, x, w, bias, p, y_true, loss_sums, pixels, cin, stream); }
+int32_t unet_head_fwd_ex(unet_ctx* ctx, const float* x, const float* w, const float* bias, float* p, const float* y_true, const float* weight_map, double* loss_sums, int64_t pixels,
+                         int32_t cin, void* stream) { return head_fwd_impl(ctx, x, w, bias, p, y_true, loss_sums, pixels, cin, stream, weight_map); }
+int32_t unet_head_fwd_bf16_ex(unet_ctx* ctx, const unet_bf16* x, const float* w, const float* bias, float* p, const float* y_true, const float* weight_map, double* loss_sums,
+                              int64_t pixels, int32_t cin, void* stream) { return head_fwd_impl(ctx, x, w, bias, p, y_true, loss_sums, pixels, cin, stream, weight_map); }
 int32_t unet_head_bwd(unet_ctx* ctx, const float* x, const float* w, const float* p, const float* y_true, const double* loss_sums, double count, float* dx, float* dw, float* db, int64_t pixels, int32_t cin, int32_t relu_mask, void* stream) { return head_bwd_impl(ctx, x, w, p, y_true, loss_sums, count, dx, dw, db, pixels, cin, relu_mask, stream); }
 int32_t unet_head_bwd_bf16(unet_ctx* ctx, const unet_bf16* x, const float* w, const float* p, const float* y_true, const double* loss_sums, double count, unet_bf16* dx, float* dw, float* db, int64_t pixels, int32_t cin, int32_t relu_mask, void* stream) { return head_bwd_impl(ctx, x, w, p, y_true, loss_sums, count, dx, dw, db, pixels, cin, relu_mask, stream); }
+int32_t unet_head_bwd_ex(unet_ctx* ctx, const float* x, const float* w, const float* p, const float* y_true, const double* loss_sums, double count, int32_t loss, float alpha, float beta,
+                         const float* weight_map, float* dx, float* dw, float* db, int64_t pixels, int32_t cin, int32_t relu_mask, void* stream) {
+  return head_bwd_impl(ctx, x, w, p, y_true, loss_sums, count, dx, dw, db, pixels, cin, relu_mask, stream, unet_loss_sel{loss, alpha, beta}, weight_map);
+}
+int32_t unet_head_bwd_bf16_ex(unet_ctx* ctx, const unet_bf16* x, const float* w, const float* p, const float* y_true, const double* loss_sums, double count, int32_t loss, float alpha,
+                              float beta, const float* weight_map, unet_bf16* dx, float* dw, float* db, int64_t pixels, int32_t cin, int32_t relu_mask, void* stream) {
+  return head_bwd_impl(ctx, x, w, p, y_true, loss_sums, count, dx, dw, db, pixels, cin, relu_mask, stream, unet_loss_sel{loss, alpha, beta}, weight_map);
+}
 int32_t unet_copy_slice(unet_ctx* ctx, const float* src, int32_t lds, float* dst, int32_t ldd, int64_t pixels, int32_t c, void* stream) { return copy_slice_impl(ctx, src, lds, dst, ldd, pixels, c, stream); }
 int32_t unet_copy_slice_bf16(unet_ctx* ctx, const unet_bf16* src, int32_t lds, unet_bf16* dst, int32_t ldd, int64_t pixels, int32_t c, void* stream) { return copy_slice_impl(ctx, src, lds, dst, ldd, pixels, c, stream); }
 int32_t unet_accum_slices(unet_ctx* ctx, const float* const* srcs, const int32_t* lds, int32_t nsrc, float* dst, int32_t ldd, int64_t pixels, int32_t c, int32_t accumulate, void* stream) { return accum_slices_impl(ctx, srcs, lds, nsrc, dst, ldd, pixels, c, accumulate, stream); }

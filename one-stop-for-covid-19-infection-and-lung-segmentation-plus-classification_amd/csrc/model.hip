@@ -193,18 +193,23 @@ int32_t unet_conv3x3_fwd(unet_ctx* ctx, const float* x, const float* w, const fl
 
 // T1:911-913 in one launch (include/unet_hip.h): the last conv3x3 + the 1x1 sigmoid head + loss sums + the sums of the head's weight gradient
 int32_t unet_conv3x3_head_supported(unet_ctx* ctx, int32_t algo, int32_t wd, int32_t cin, int32_t cout) { return ctx && h2_conv3x3_head_selected(ctx, algo, wd, cin, cout) ? 1 : 0; }
-int32_t unet_conv3x3_head_fwd(unet_ctx* ctx, const float* x, const float* w, const float* bias, float* y, const float* w_head, const float* b_head, float* p, const float* y_true,
-                              double* loss_sums, double* head_sums, int32_t n, int32_t h, int32_t wd, int32_t cin, float* w_ws, void* stream) {
+int32_t unet_conv3x3_head_fwd_ex(unet_ctx* ctx, const float* x, const float* w, const float* bias, float* y, const float* w_head, const float* b_head, float* p,
+                                 const float* y_true, const float* weight_map, double* loss_sums, double* head_sums, int32_t n, int32_t h, int32_t wd, int32_t cin,
+                                 float* w_ws, void* stream) {
   if (!ctx || !x || !w || !bias || !w_head || !b_head || !p || !w_ws || n < 1 || h < 1 || wd < 1 || (y_true && (!loss_sums || !head_sums)))          // (y null: the 32-channel tensor is not stored)
     UNET_FAIL(ctx, UNET_E_ARG, "conv3x3_head_fwd: bad args");
   if (!h2_conv3x3_head_selected(ctx, UNET_ALGO_AUTO, wd, cin, 32)) UNET_FAIL(ctx, UNET_E_SHAPE, "conv3x3_head_fwd: not supported here (unet_conv3x3_head_supported)");
   unsigned long long* armed = ctx->signs_req;
   int32_t r = k_h2_weights(ctx, w, w_ws, cin, 32, 0, as_stream(stream));
-  if (!r) r = k_conv3x3_h2_head_fwd(ctx, x, w_ws, bias, y, w_head, b_head, p, y_true, n, h, wd, cin, as_stream(stream));
+  if (!r) r = k_conv3x3_h2_head_fwd(ctx, x, w_ws, bias, y, w_head, b_head, p, y_true, n, h, wd, cin, as_stream(stream), y_true ? weight_map : nullptr);
   ctx->signs_req = nullptr;
   if (!r && armed && ctx->signs_done != armed) UNET_FAIL(ctx, UNET_E_SHAPE, "conv3x3_head_fwd: armed with unet_request_relu_bits but the launch did not write them");
-  if (!r && y_true) r = k_head_fold(ctx, loss_sums, head_sums, as_stream(stream));
+  if (!r && y_true) r = k_head_fold(ctx, loss_sums, head_sums, as_stream(stream), weight_map != nullptr);
   return r;
+}
+int32_t unet_conv3x3_head_fwd(unet_ctx* ctx, const float* x, const float* w, const float* bias, float* y, const float* w_head, const float* b_head, float* p, const float* y_true,
+                              double* loss_sums, double* head_sums, int32_t n, int32_t h, int32_t wd, int32_t cin, float* w_ws, void* stream) {
+  return unet_conv3x3_head_fwd_ex(ctx, x, w, bias, y, w_head, b_head, p, y_true, nullptr, loss_sums, head_sums, n, h, wd, cin, w_ws, stream);
 }
 int32_t unet_head_bwd_stream_supported(unet_ctx* ctx, int32_t algo, int32_t wd, int32_t cin) {
   return ctx && cin == 32 && h2_head_bwd_selected(ctx, algo, wd, cin) && h2_wgrad_selected(algo, cin, 32) ? 1 : 0;
@@ -213,6 +218,12 @@ int32_t unet_head_dzm(unet_ctx* ctx, const float* p, const float* y_true, const 
                       float* dw_head, float* db_head, int32_t n, int32_t h, int32_t wd, void* stream) {
   if (!ctx) return UNET_E_ARG;
   return k_head_dzm(ctx, p, y_true, loss_sums, count, head_sums, static_cast<const unsigned long long*>(relu_bits), dzm, dw_head, db_head, n, h, wd, as_stream(stream));
+}
+int32_t unet_head_dzm_ex(unet_ctx* ctx, const float* p, const float* y_true, const double* loss_sums, double count, const double* head_sums, int32_t loss, float alpha,
+                         float beta, const float* weight_map, const void* relu_bits, void* dzm, float* dw_head, float* db_head, int32_t n, int32_t h, int32_t wd, void* stream) {
+  if (!ctx) return UNET_E_ARG;
+  return k_head_dzm(ctx, p, y_true, loss_sums, count, head_sums, static_cast<const unsigned long long*>(relu_bits), dzm, dw_head, db_head, n, h, wd, as_stream(stream),
+                    unet_loss_sel{loss, alpha, beta}, weight_map);
 }
 int32_t unet_conv3x3_bwd_data_dzm(unet_ctx* ctx, const void* dzm, const float* w, const float* w_head, const void* relu_bits_in, float* dx, float* wt_ws, int32_t n, int32_t h,
                                   int32_t wd, int32_t cin, void* stream) {
@@ -232,6 +243,13 @@ int32_t unet_head_dy(unet_ctx* ctx, const float* p, const float* y_true, const d
                      const float* y, float* dy, float* dw_head, float* db_head, int32_t n, int32_t h, int32_t wd, void* stream) {
   if (!ctx) return UNET_E_ARG;
   return k_head_dy(ctx, p, y_true, loss_sums, count, head_sums, w_head, static_cast<const unsigned long long*>(relu_bits), y, dy, dw_head, db_head, n, h, wd, as_stream(stream));
+}
+int32_t unet_head_dy_ex(unet_ctx* ctx, const float* p, const float* y_true, const double* loss_sums, double count, const double* head_sums, int32_t loss, float alpha,
+                        float beta, const float* weight_map, const float* w_head, const void* relu_bits, const float* y, float* dy, float* dw_head, float* db_head,
+                        int32_t n, int32_t h, int32_t wd, void* stream) {
+  if (!ctx) return UNET_E_ARG;
+  return k_head_dy(ctx, p, y_true, loss_sums, count, head_sums, w_head, static_cast<const unsigned long long*>(relu_bits), y, dy, dw_head, db_head, n, h, wd, as_stream(stream),
+                   unet_loss_sel{loss, alpha, beta}, weight_map);
 }
 
 int32_t unet_conv3x3_pick_algo(int32_t algo, int32_t wd, int32_t cin, int32_t cout) {
@@ -442,6 +460,10 @@ struct unet_model {
   const float *x = nullptr, *yt = nullptr; float* pout = nullptr; float* loss_out2 = nullptr;
   float drop_rate = 0.0f; uint64_t drop_seed = 0;
   float cw0 = 1.0f, cw1 = 1.0f;                       // classifier: class weights of the loss
+  unet_loss_sel loss;                                 // U-Net / U-Net++: the training loss (unet_model_set_loss), read by the ops when they run
+  size_t off_wmap = 0;                                // weighted_bce_dice_loss: its weight map [N, H, W] (planned only for that loss)
+  bool weighted() const { return loss.kind == UNET_LOSS_WEIGHTED_BCE_DICE; }
+  const float* wmap() const { return weighted() ? reinterpret_cast<const float*>(ws) + off_wmap : nullptr; }
   size_t off_dense_ws = 0, dense_ws_bytes = 0;
   // workspace plan (offsets in floats)
   std::map<std::string, Buf> act, grad;
@@ -545,9 +567,10 @@ void plan_scratch(unet_model* m, Carver& cv) {          // BN sums / params, los
   size_t nd = 0;
   for (auto& l : m->layers) if (l.kind == 2) { m->bn_sum_off[l.name] = nd; nd += 2 * (size_t)l.cout; }
   m->bn_sums_doubles = nd;
-  m->off_bn_sums = cv.take((nd + 4 + UNET_HEAD_SUMS) * 2);          // doubles -> 2 floats each; +4 loss sums, + the sums of a fused head (zeroed with them)
+  m->off_bn_sums = cv.take((nd + 5 + UNET_HEAD_SUMS) * 2);          // doubles -> 2 floats each; +5 loss sums (the 5th: weighted_bce_dice_loss), + the sums of a fused head (zeroed with them)
   m->off_loss_sums = m->off_bn_sums + nd * 2;
-  m->off_head_sums = m->off_loss_sums + 4 * 2;
+  m->off_head_sums = m->off_loss_sums + 5 * 2;
+  if (m->weighted()) m->off_wmap = cv.take((size_t)m->N * m->H * m->W);
   size_t nb = 0;
   for (auto& l : m->layers) if (l.kind == 2) { m->bn_bsum_off[l.name] = nb; nb += 2 * (size_t)l.cout; }
   m->off_bn_bsums = cv.take(nb * 2);
@@ -759,7 +782,7 @@ void build_programs(unet_model* m) {
   auto& FT = m->prog[UNET_PROG_FWD_TRAIN];
   auto& FI = m->prog[UNET_PROG_FWD_INFER];
   auto& BW = m->prog[UNET_PROG_BWD];
-  const size_t sums_bytes = (m->bn_sums_doubles + 4 + UNET_HEAD_SUMS) * sizeof(double);
+  const size_t sums_bytes = (m->bn_sums_doubles + 5 + UNET_HEAD_SUMS) * sizeof(double);
   // layers whose 3x3 weights are consumed as a prepared image (decided per layer exactly as the conv dispatch does)
   struct PrepItem { std::string name; int cin, cout, h, w; };
   std::vector<PrepItem> prep_items;
@@ -804,6 +827,10 @@ void build_programs(unet_model* m) {
     ADD_OP(F, "zero_sums", 0, 0, {
       if (!tr_ && !m->yt) return UNET_OK;          // (inference without labels: no statistics, no loss sums -- nothing adds into them)
       return unet_zero(ctx, m->wsf(m->off_bn_sums), sums_bytes, s);
+    });
+    if (m->weighted()) ADD_OP(F, "loss_weight_map", 0, 8.0 * m->N * m->H * m->W, {          // weighted_bce_dice_loss (T1:837-845): its map of this batch's labels
+      if (!m->yt) return UNET_OK;
+      return k_loss_weight_map(ctx, m->yt, m->wsf(m->off_wmap), m->N, m->H, m->W, s);
     });
     if (!dt) ADD_OP(F, "weight_images:fwd", 0, 0, { return prep_weights(0, s); });       // all split weight images of the program in one batch of launches
     else ADD_OP(F, "weight_images:fwd", 0, 0, { return prep_weights_bf16(0, s); });
@@ -946,7 +973,7 @@ void build_programs(unet_model* m) {
           ctx->signs_req = sg; ctx->signs_done = nullptr;
           // (c9b_virtual: nothing reads the tensor -- the backward takes p, the sums and the sign bits, inference takes p -- so it is not written: -0.5 GB per step at 512 x 512 x 16)
           int32_t r = k_conv3x3_h2_head_fwd(ctx, m->A("c9a"), m->wsf(m->wprep_f.at("c9b")), m->P("c9b/bias"), m->c9b_virtual ? nullptr : m->Aw("c9b"), m->P("out/kernel"), m->P("out/bias"),
-                                            m->pout, m->yt, ob.n, ob.h, ob.w, c, s);
+                                            m->pout, m->yt, ob.n, ob.h, ob.w, c, s, m->yt ? m->wmap() : nullptr);
           ctx->signs_req = nullptr;
           if (!r && sg && ctx->signs_done != sg) UNET_FAIL(ctx, UNET_E_STATE, "conv3x3_fwd_head: the launch did not write the ReLU sign bits its backward was planned with");
           return r;
@@ -959,18 +986,19 @@ void build_programs(unet_model* m) {
     const int64_t hp = (int64_t)hb.n * hb.h * hb.w;
     if (m->head_fused) ADD_OP(F, "head_fold", 0, 0, {
       if (!m->yt) return UNET_OK;
-      return k_head_fold(ctx, m->wsd(m->off_loss_sums), m->wsd(m->off_head_sums), s);
+      return k_head_fold(ctx, m->wsd(m->off_loss_sums), m->wsd(m->off_head_sums), s, m->weighted());
     });
     else
     ADD_OP(F, "head_fwd", 2.0 * 32 * hp, hp * (eb * 32 + 8.0), {
       if (!m->pout) UNET_FAIL(ctx, UNET_E_STATE, "head_fwd: p_out not set (unet_model_set_io)");
-      if (dt) return unet_head_fwd_bf16(ctx, CBF(m->Av("c9b")), m->P("out/kernel"), m->P("out/bias"), m->pout, m->yt, m->yt ? m->wsd(m->off_loss_sums) : nullptr, hp, hb.c, s);
-      return unet_head_fwd(ctx, m->A("c9b"), m->P("out/kernel"), m->P("out/bias"), m->pout, m->yt, m->yt ? m->wsd(m->off_loss_sums) : nullptr, hp, hb.c, s);
+      if (dt) return unet_head_fwd_bf16_ex(ctx, CBF(m->Av("c9b")), m->P("out/kernel"), m->P("out/bias"), m->pout, m->yt, m->yt ? m->wmap() : nullptr, m->yt ? m->wsd(m->off_loss_sums) : nullptr,
+                                           hp, hb.c, s);
+      return unet_head_fwd_ex(ctx, m->A("c9b"), m->P("out/kernel"), m->P("out/bias"), m->pout, m->yt, m->yt ? m->wmap() : nullptr, m->yt ? m->wsd(m->off_loss_sums) : nullptr, hp, hb.c, s);
     });
-    SY.push_back({(int)F.size() - 1, 1, true, m->off_loss_sums * 4, 4});
+    SY.push_back({(int)F.size() - 1, 1, true, m->off_loss_sums * 4, m->weighted() ? 5 : 4});
     ADD_OP(F, "loss_finalize", 0, 0, {
       if (!m->yt) return UNET_OK;
-      return k_loss_finalize(ctx, m->wsd(m->off_loss_sums), (double)hp * gcount, m->wsf(m->off_loss_out), m->loss_out2, s);
+      return k_loss_finalize(ctx, m->wsd(m->off_loss_sums), (double)hp * gcount, m->wsf(m->off_loss_out), m->loss_out2, s, m->loss);
     });
   }
 
@@ -995,7 +1023,7 @@ void build_programs(unet_model* m) {
     if (m->head_bwd_fused) ADD_OP(BW, "head_dzm", 8.0 * hp, hp * (8.0 + 4.0 + 8.0), {
       if (!m->yt || !m->pout) UNET_FAIL(ctx, UNET_E_STATE, "head_dzm: io not set");
       return k_head_dzm(ctx, m->pout, m->yt, m->wsd(m->off_loss_sums), (double)hp * gcount, m->wsd(m->off_head_sums), reinterpret_cast<const unsigned long long*>(m->wsf(m->sign_off.at("c9b"))),
-                        m->D("c9b"), m->G("out/kernel"), m->G("out/bias"), hb.n, hb.h, hb.w, s);
+                        m->D("c9b"), m->G("out/kernel"), m->G("out/bias"), hb.n, hb.h, hb.w, s, m->loss, m->wmap());
     });
     else
     if (m->head_fused) ADD_OP(BW, "head_dy", 2.0 * 32 * hp, hp * (4.0 * 32 + 8.0 + 4.0), {
@@ -1003,14 +1031,15 @@ void build_programs(unet_model* m) {
       const auto so = m->sign_off.find("c9b");
       return k_head_dy(ctx, m->pout, m->yt, m->wsd(m->off_loss_sums), (double)hp * gcount, m->wsd(m->off_head_sums), m->P("out/kernel"),
                        so == m->sign_off.end() ? nullptr : reinterpret_cast<const unsigned long long*>(m->wsf(so->second)), m->A("c9b"), m->D("c9b"),
-                       m->G("out/kernel"), m->G("out/bias"), hb.n, hb.h, hb.w, s);
+                       m->G("out/kernel"), m->G("out/bias"), hb.n, hb.h, hb.w, s, m->loss, m->wmap());
     });
     else
     ADD_OP(BW, "head_bwd", 4.0 * 32 * hp, hp * (eb * 64 + 8.0), {
       if (!m->yt || !m->pout) UNET_FAIL(ctx, UNET_E_STATE, "head_bwd: io not set");
-      if (dt) return unet_head_bwd_bf16(ctx, CBF(m->Av("c9b")), m->P("out/kernel"), m->pout, m->yt, m->wsd(m->off_loss_sums), (double)hp * gcount, WBF(m->Dv("c9b")),
+      const unet_loss_sel& L = m->loss;
+      if (dt) return unet_head_bwd_bf16_ex(ctx, CBF(m->Av("c9b")), m->P("out/kernel"), m->pout, m->yt, m->wsd(m->off_loss_sums), (double)hp * gcount, L.kind, L.alpha, L.beta, m->wmap(), WBF(m->Dv("c9b")),
                                         m->G("out/kernel"), m->G("out/bias"), hp, hb.c, 1, s);
-      return unet_head_bwd(ctx, m->A("c9b"), m->P("out/kernel"), m->pout, m->yt, m->wsd(m->off_loss_sums), (double)hp * gcount, m->D("c9b"),
+      return unet_head_bwd_ex(ctx, m->A("c9b"), m->P("out/kernel"), m->pout, m->yt, m->wsd(m->off_loss_sums), (double)hp * gcount, L.kind, L.alpha, L.beta, m->wmap(), m->D("c9b"),
                            m->G("out/kernel"), m->G("out/bias"), hp, hb.c, 1, s);
     });
     // conv backward: wgrad (x, dy) then dgrad (dy -> dx, optional relu mask = activation that produced x)
@@ -1370,7 +1399,7 @@ void build_programs_pp(unet_model* m) {
 #define CBF(p) static_cast<const unet_bf16*>(p)
 #define WBF(p) static_cast<unet_bf16*>(p)
   auto& BW = m->prog[UNET_PROG_BWD];
-  const size_t sums_bytes = (m->bn_sums_doubles + 4 + UNET_HEAD_SUMS) * sizeof(double);
+  const size_t sums_bytes = (m->bn_sums_doubles + 5 + UNET_HEAD_SUMS) * sizeof(double);
   std::map<std::string, int> lidx;
   for (size_t i = 0; i < m->layers.size(); ++i) lidx[m->layers[i].name] = (int)i;
   auto seed_of = [=](const std::string& conv) { return (uint64_t)(lidx.at(conv) + 1) * 0x9E3779B97F4A7C15ull; };
@@ -1381,6 +1410,10 @@ void build_programs_pp(unet_model* m) {
     auto& SY = m->syncref[training ? UNET_PROG_FWD_TRAIN : UNET_PROG_FWD_INFER];
     const int tr = training;
     ADD_OP(F, "zero_sums", 0, 0, { return unet_zero(ctx, m->wsf(m->off_bn_sums), sums_bytes, s); });
+    if (m->weighted()) ADD_OP(F, "loss_weight_map", 0, 8.0 * m->N * m->H * m->W, {          // weighted_bce_dice_loss (T1:837-845): its map of this batch's labels
+      if (!m->yt) return UNET_OK;
+      return k_loss_weight_map(ctx, m->yt, m->wsf(m->off_wmap), m->N, m->H, m->W, s);
+    });
     auto conv = [&](const std::string& name, const std::string& in, int cin, int cout, float rate) {
       const Buf ob = m->act.at(name);
       const uint64_t sd = seed_of(name);
@@ -1487,13 +1520,14 @@ void build_programs_pp(unet_model* m) {
     const int64_t hp = (int64_t)hb.n * hb.h * hb.w;
     ADD_OP(F, "head_fwd", 2.0 * 32 * hp, hp * (eb * 32 + 8.0), {
       if (!m->pout) UNET_FAIL(ctx, UNET_E_STATE, "head_fwd: p_out not set (unet_model_set_io)");
-      if (dt) return unet_head_fwd_bf16(ctx, CBF(m->Av("x1_4")), m->P("out/kernel"), m->P("out/bias"), m->pout, m->yt, m->yt ? m->wsd(m->off_loss_sums) : nullptr, hp, hb.c, s);
-      return unet_head_fwd(ctx, m->A("x1_4"), m->P("out/kernel"), m->P("out/bias"), m->pout, m->yt, m->yt ? m->wsd(m->off_loss_sums) : nullptr, hp, hb.c, s);
+      if (dt) return unet_head_fwd_bf16_ex(ctx, CBF(m->Av("x1_4")), m->P("out/kernel"), m->P("out/bias"), m->pout, m->yt, m->yt ? m->wmap() : nullptr, m->yt ? m->wsd(m->off_loss_sums) : nullptr,
+                                           hp, hb.c, s);
+      return unet_head_fwd_ex(ctx, m->A("x1_4"), m->P("out/kernel"), m->P("out/bias"), m->pout, m->yt, m->yt ? m->wmap() : nullptr, m->yt ? m->wsd(m->off_loss_sums) : nullptr, hp, hb.c, s);
     });
-    SY.push_back({(int)F.size() - 1, 1, true, m->off_loss_sums * 4, 4});
+    SY.push_back({(int)F.size() - 1, 1, true, m->off_loss_sums * 4, m->weighted() ? 5 : 4});
     ADD_OP(F, "loss_finalize", 0, 0, {
       if (!m->yt) return UNET_OK;
-      return k_loss_finalize(ctx, m->wsd(m->off_loss_sums), (double)hp * gcount, m->wsf(m->off_loss_out), m->loss_out2, s);
+      return k_loss_finalize(ctx, m->wsd(m->off_loss_sums), (double)hp * gcount, m->wsf(m->off_loss_out), m->loss_out2, s, m->loss);
     });
   }
 
@@ -1515,9 +1549,10 @@ void build_programs_pp(unet_model* m) {
   const int64_t hp = (int64_t)hb.n * hb.h * hb.w;
   ADD_OP(BW, "head_bwd", 4.0 * 32 * hp, hp * (eb * 64 + 8.0), {
     if (!m->yt || !m->pout) UNET_FAIL(ctx, UNET_E_STATE, "head_bwd: io not set");
-    if (dt) return unet_head_bwd_bf16(ctx, CBF(m->Av("x1_4")), m->P("out/kernel"), m->pout, m->yt, m->wsd(m->off_loss_sums), (double)hp * gcount, WBF(m->Dv("x1_4")),
+    const unet_loss_sel& L = m->loss;
+    if (dt) return unet_head_bwd_bf16_ex(ctx, CBF(m->Av("x1_4")), m->P("out/kernel"), m->pout, m->yt, m->wsd(m->off_loss_sums), (double)hp * gcount, L.kind, L.alpha, L.beta, m->wmap(), WBF(m->Dv("x1_4")),
                                       m->G("out/kernel"), m->G("out/bias"), hp, hb.c, 0, s);
-    return unet_head_bwd(ctx, m->A("x1_4"), m->P("out/kernel"), m->pout, m->yt, m->wsd(m->off_loss_sums), (double)hp * gcount, m->D("x1_4"),
+    return unet_head_bwd_ex(ctx, m->A("x1_4"), m->P("out/kernel"), m->pout, m->yt, m->wsd(m->off_loss_sums), (double)hp * gcount, L.kind, L.alpha, L.beta, m->wmap(), m->D("x1_4"),
                          m->G("out/kernel"), m->G("out/bias"), hp, hb.c, 0, s);
   });
   // BN backward: dy = grad[dyname] (dense), x = act[xname] = dropout(elu(conv)) or elu(conv); dx = grad[xname] (pre-activation gradient)
@@ -1772,7 +1807,7 @@ void build_programs_cls(unet_model* m) {
   const double eb = dt ? 2.0 : 4.0;
 #define CBF(p) static_cast<const unet_bf16*>(p)
 #define WBF(p) static_cast<unet_bf16*>(p)
-  const size_t sums_bytes = (m->bn_sums_doubles + 4 + UNET_HEAD_SUMS) * sizeof(double);
+  const size_t sums_bytes = (m->bn_sums_doubles + 5 + UNET_HEAD_SUMS) * sizeof(double);
   const Buf fb = m->act.at("p3");
   const int N = m->N, K = fb.h * fb.w * fb.c;
   const uint64_t fc_seed = 0xC2B2AE3D27D4EB4Full;
@@ -1782,6 +1817,10 @@ void build_programs_cls(unet_model* m) {
     auto& SY = m->syncref[training ? UNET_PROG_FWD_TRAIN : UNET_PROG_FWD_INFER];
     const int tr = training;
     ADD_OP(F, "zero_sums", 0, 0, { return unet_zero(ctx, m->wsf(m->off_bn_sums), sums_bytes, s); });
+    if (m->weighted()) ADD_OP(F, "loss_weight_map", 0, 8.0 * m->N * m->H * m->W, {          // weighted_bce_dice_loss (T1:837-845): its map of this batch's labels
+      if (!m->yt) return UNET_OK;
+      return k_loss_weight_map(ctx, m->yt, m->wsf(m->off_wmap), m->N, m->H, m->W, s);
+    });
     auto conv = [&](const std::string& name, const std::string& in, int cin, int cout) {
       const Buf ob = m->act.at(name);
       double px = (double)ob.n * ob.h * ob.w;
@@ -2014,6 +2053,13 @@ void resolve_sync(unet_model* m) {
 
 extern "C" {
 
+static void build_model(unet_model* m) {
+  if (m->arch == UNET_ARCH_UNET) { build_layers(m); plan_workspace(m); build_programs(m); }
+  else if (m->arch == UNET_ARCH_UNETPP) { build_layers_pp(m); plan_workspace_pp(m); build_programs_pp(m); }
+  else { build_layers_cls(m); plan_workspace_cls(m); build_programs_cls(m); }
+  arm_bn_statistics(m);
+}
+
 int32_t unet_model_create(unet_ctx* ctx, int32_t arch, int32_t in_ch, int32_t n, int32_t h, int32_t w, int32_t world_size,
                           int32_t conv_algo, int32_t dtype, unet_model** out) {
   if (!ctx || !out) return UNET_E_ARG;
@@ -2025,10 +2071,7 @@ int32_t unet_model_create(unet_ctx* ctx, int32_t arch, int32_t in_ch, int32_t n,
     UNET_FAIL(ctx, UNET_E_SHAPE, "model_create: need n>=1 and h,w multiples of %d; got n=%d h=%d w=%d", mult, n, h, w);
   unet_model* m = new unet_model();
   m->ctx = ctx; m->arch = arch; m->in_ch = in_ch; m->N = n; m->H = h; m->W = w; m->world = world_size; m->algo = conv_algo; m->dt = dtype;
-  if (arch == UNET_ARCH_UNET) { build_layers(m); plan_workspace(m); build_programs(m); }
-  else if (arch == UNET_ARCH_UNETPP) { build_layers_pp(m); plan_workspace_pp(m); build_programs_pp(m); }
-  else { build_layers_cls(m); plan_workspace_cls(m); build_programs_cls(m); }
-  arm_bn_statistics(m);
+  build_model(m);
   *out = m;
   return UNET_OK;
 }
@@ -2088,6 +2131,34 @@ int32_t unet_model_set_dropout(unet_model* m, float rate, uint64_t seed) {
 int32_t unet_model_set_class_weights(unet_model* m, float w0, float w1) {
   if (!m || m->arch != UNET_ARCH_CLASSIFIER || !(w0 >= 0) || !(w1 >= 0)) return UNET_E_ARG;
   m->cw0 = w0; m->cw1 = w1;
+  return UNET_OK;
+}
+
+int32_t unet_model_set_loss(unet_model* m, int32_t loss, float alpha, float beta) {
+  if (!m) return UNET_E_ARG;
+  const unet_loss_sel sel{loss, alpha, beta};
+  if (!unet_loss_sel_ok(sel, nullptr, false) || (m->arch == UNET_ARCH_CLASSIFIER && loss != UNET_LOSS_BCE))
+    UNET_FAIL(m->ctx, UNET_E_ARG, "model_set_loss: loss %d (alpha %g, beta %g) is not one of this graph's", loss, alpha, beta);
+  if (m->arch == UNET_ARCH_CLASSIFIER) return UNET_OK;          // (classifier: binary cross-entropy is what it computes already)
+  if ((loss == UNET_LOSS_WEIGHTED_BCE_DICE) == m->weighted()) { m->loss = sel; return UNET_OK; }
+  // to or from the weighted loss: its weight-map op, its workspace and its 5-double sync point -- the model's plan and programs are built again for it (on the
+  // same object: the ops capture it), after checking that a bound workspace still holds it
+  unet_model* t = new unet_model();
+  t->ctx = m->ctx; t->arch = m->arch; t->in_ch = m->in_ch; t->N = m->N; t->H = m->H; t->W = m->W; t->world = m->world; t->algo = m->algo; t->dt = m->dt; t->loss = sel;
+  build_model(t);
+  const size_t need = (m->grads ? t->ws_floats_train : t->ws_floats_infer) * sizeof(float);
+  delete t;
+  if (m->ws && m->ws_bytes < need)
+    UNET_FAIL(m->ctx, UNET_E_STATE, "model_set_loss: the bound workspace (%zu bytes) is too small for loss %d (%zu bytes): bind a larger one first", m->ws_bytes, loss, need);
+  unet_model keep = std::move(*m);
+  *m = unet_model();
+  m->ctx = keep.ctx; m->arch = keep.arch; m->in_ch = keep.in_ch; m->N = keep.N; m->H = keep.H; m->W = keep.W; m->world = keep.world; m->algo = keep.algo; m->dt = keep.dt;
+  m->loss = sel;
+  build_model(m);
+  m->params = keep.params; m->grads = keep.grads; m->adam_m = keep.adam_m; m->adam_v = keep.adam_v; m->state = keep.state; m->ws = keep.ws; m->ws_bytes = keep.ws_bytes;
+  m->x = keep.x; m->yt = keep.yt; m->pout = keep.pout; m->loss_out2 = keep.loss_out2; m->drop_rate = keep.drop_rate; m->drop_seed = keep.drop_seed;
+  m->cw0 = keep.cw0; m->cw1 = keep.cw1;
+  if (m->ws) resolve_sync(m);
   return UNET_OK;
 }
 

@@ -52,6 +52,7 @@ class HipUNet:
         self._arch_id = {"unet": _lib.ARCH_UNET, "unetpp": _lib.ARCH_UNETPP, "classifier": _lib.ARCH_CLASSIFIER}[arch]   # rates fixed: >0 = on
         # (classifier: task2_covid19_classifcation.py:747-776; y / p are [n] vectors, the loss tensor is (bce, f1))
         self.class_weights = (1.0, 1.0)
+        self.loss = ("bce_dice_loss", 0.5, 0.5)      # (name, alpha, beta) of the training loss: set_loss
         self.pg = process_group
         self.pg_grad = process_group
         self.world, self.rank = 1, 0
@@ -124,10 +125,12 @@ class HipUNet:
         key = (n, True) if (replicated and self._dp) else n
         if key not in self._plans:
             m = self._create_plan(n, replicated)
-            need = self.lib.unet_model_workspace_bytes(m, 1)
-            self._plans[key] = {"m": m, "bytes": need, "bound_ws": None}
             if self.arch == "classifier":
                 self.ctx.check(self.lib.unet_model_set_class_weights(m, *self.class_weights), "set_class_weights")
+            else:
+                self.ctx.check(self.lib.unet_model_set_loss(m, _lib.LOSSES[self.loss[0]], self.loss[1], self.loss[2]), "set_loss")
+            need = self.lib.unet_model_workspace_bytes(m, 1)          # (after the loss: the weighted one plans its weight map)
+            self._plans[key] = {"m": m, "bytes": need, "bound_ws": None}
         p = self._plans[key]
         if self._ws is None or self._ws.numel() < p["bytes"]:
             self._ws = torch.empty(p["bytes"], dtype=torch.uint8, device=self.dev)
@@ -177,6 +180,43 @@ class HipUNet:
         self.class_weights = (float(w0), float(w1))
         for p in self._plans.values():
             self.ctx.check(self.lib.unet_model_set_class_weights(p["m"], *self.class_weights), "set_class_weights")
+
+    def set_loss(self, name: str, alpha: float = 0.5, beta: float = 0.5):
+        """The training loss of a U-Net / U-Net++ by its Keras name (_lib.LOSSES: T1:784-801 and Keras' binary_crossentropy): applied to every existing plan
+        and to every plan created later.  alpha, beta: tversky_loss's weights (T1:801 uses 0.5, 0.5); the other losses ignore them.  The metric stays
+        dice_coeff for every loss."""
+        if self.arch == "classifier":
+            raise ValueError("set_loss: the classifier trains on binary_crossentropy (T2:829) only")
+        if name not in _lib.LOSSES:
+            raise ValueError(f"set_loss: {name!r} is not one of {sorted(_lib.LOSSES)}")
+        alpha, beta = float(alpha), float(beta)
+        if name == "tversky_loss" and not (0 < alpha < float("inf") and 0 < beta < float("inf")):
+            raise ValueError(f"set_loss: tversky_loss needs finite alpha, beta > 0 (got {alpha}, {beta})")
+        reshaped = (name == "weighted_bce_dice_loss") != (self.loss[0] == "weighted_bce_dice_loss")
+        if reshaped and self._ws is not None:
+            # to / from the weighted loss the plans grow or shrink by the weight map: make the shared workspace large enough for every plan FIRST (a set on a
+            # bound model whose workspace cannot hold the new plan is refused), then re-bind each (fresh sync points)
+            torch = _torch()
+            need = 0
+            for key, p in self._plans.items():
+                n = key[0] if isinstance(key, tuple) else key
+                t = self._create_plan(n, isinstance(key, tuple))
+                self.ctx.check(self.lib.unet_model_set_loss(t, _lib.LOSSES[name], alpha, beta), "set_loss")
+                need = max(need, self.lib.unet_model_workspace_bytes(t, 1))
+                self.lib.unet_model_destroy(t)
+            if self._ws.numel() < need:
+                torch.cuda.synchronize(self.dev)
+                self._ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
+                for p in self._plans.values():
+                    self.ctx.check(self.lib.unet_model_bind(p["m"], self.params.data_ptr(), self.grads.data_ptr(), self.adam_m.data_ptr(), self.adam_v.data_ptr(),
+                                                            self.state.data_ptr(), self._ws.data_ptr(), self._ws.numel()), "model_bind")
+        for p in self._plans.values():
+            self.ctx.check(self.lib.unet_model_set_loss(p["m"], _lib.LOSSES[name], alpha, beta), "set_loss")
+            if reshaped:
+                p["bytes"] = self.lib.unet_model_workspace_bytes(p["m"], 1)
+                p["bound_ws"] = None                                    # (re-bound at the next use: fresh sync points, inference preparation redone)
+        self._infer_ready = None
+        self.loss = (name, alpha, beta)
 
     def _out_elems(self, n):
         return n if self.arch == "classifier" else n * self.h * self.w

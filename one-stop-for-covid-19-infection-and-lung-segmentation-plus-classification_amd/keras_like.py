@@ -17,6 +17,26 @@ import numpy as np
 from . import weights as W
 
 SM_SMOOTH = 1e-5
+# the losses of the reference's segmentation scripts that compile() accepts (T1:784-835, and Keras' binary_crossentropy, T1:60); the backend's set_loss selects them
+LOSSES = ("bce_dice_loss", "binary_crossentropy", "dice_loss", "tversky_loss", "weighted_bce_dice_loss")
+TVERSKY_DEFAULT = {"alpha": 0.5, "beta": 0.5}                 # T1:801-805
+
+
+def loss_spec(loss, loss_kwargs=None):
+    """compile(loss=..., loss_kwargs=...) -> (name, {"alpha", "beta"}): a name or a Keras-style callable (its __name__) out of LOSSES; loss_kwargs only for
+    tversky_loss.  Anything else -- mean_squared_error, weighted_dice_loss (three arguments), a custom function -- is a ValueError: the hot path has no generic loss."""
+    name = loss if isinstance(loss, str) else getattr(loss, "__name__", None)
+    if name not in LOSSES:
+        raise ValueError(f"loss {loss!r} is not implemented on the hot path; compile() takes one of {list(LOSSES)}")
+    kw = dict(loss_kwargs or {})
+    if kw and name != "tversky_loss":
+        raise ValueError(f"loss_kwargs {kw} given for {name}, which takes none")
+    cfg = dict(TVERSKY_DEFAULT)
+    for k, v in kw.items():
+        if k not in cfg:
+            raise ValueError(f"tversky_loss takes alpha / beta, not {k!r}")
+        cfg[k] = float(v)
+    return name, cfg
 
 
 def sm_scores(tp, spr, sgt, smooth=SM_SMOOTH):
@@ -92,20 +112,23 @@ def load_model(path, backend=None, custom_objects=None, compile=True, **backend_
     if arch == "classifier":
         from .classifier import ClassifierModel
         model = ClassifierModel(h, in_ch, backend=backend, **backend_kw)
-        own_loss, own_metrics = "binary_crossentropy", ["f1"]
+        own_losses, own_metrics = ("binary_crossentropy",), ["f1"]
     else:
         model = UNetModel(h, in_ch, backend=backend, arch=arch, **backend_kw)
-        own_loss, own_metrics = "bce_dice_loss", ["dice_coeff"]
+        own_losses, own_metrics = LOSSES, ["dice_coeff"]
     model.load_weights(path)
     opt = W.load_optimizer(path, in_ch, arch, (h, w)) if compile else None
     if opt is not None:
-        # the compiled state names its loss / metrics: this package implements exactly one pair per graph (T1:1053, T2:829) -- a file trained on another loss must
-        # not silently continue on ours
-        if opt.get("loss") not in (None, own_loss):
-            raise ValueError(f"{path}: compiled with loss {opt['loss']!r}; this engine implements {own_loss!r} for the {arch} graph (load with compile=False for the weights only)")
+        # the compiled state names its loss / metrics: a file trained on a loss this package does not implement for the graph (T1:784-801, T2:829) must not
+        # silently continue on another one
+        if opt.get("loss") is not None and opt["loss"] not in own_losses:
+            raise ValueError(f"{path}: compiled with loss {opt['loss']!r}; this engine implements {list(own_losses)} for the {arch} graph (load with compile=False for the weights only)")
         if opt.get("metrics") and [m_ for m_ in opt["metrics"] if m_ not in own_metrics]:
             warnings.warn(f"{path}: saved metrics {opt['metrics']} -- only {own_metrics} are computed here")
-        model.compile(lr=opt["lr"])
+        if arch == "classifier":
+            model.compile(lr=opt["lr"])
+        else:
+            model.compile(lr=opt["lr"], loss=opt.get("loss") or "bce_dice_loss", loss_kwargs=opt.get("loss_config"))
         if hasattr(model.backend, "set_optimizer_state"):
             model.backend.set_optimizer_state(opt)
         else:
@@ -163,6 +186,7 @@ class UNetModel:
         self.backend = backend
         self.backend.set_weights(W.init_weights(seed, in_ch, arch))
         self.compiled = False
+        self.loss, self.loss_config = "bce_dice_loss", None
         self.verbose = 1
 
     # --- Keras-shaped surface ---------------------------------------------------------
@@ -175,11 +199,17 @@ class UNetModel:
             print_fn(f"{n:6s} {k:6s} {ci:4d} -> {co:4d}")
         print_fn(f"Total params: {total:,}\nTrainable params: {train:,}\nNon-trainable params: {total - train:,}")
 
-    def compile(self, lr: float = 0.0005, loss: str = "bce_dice_loss", metrics=("dice_coeff",)):
+    def compile(self, lr: float = 0.0005, loss="bce_dice_loss", metrics=("dice_coeff",), loss_kwargs=None):
         """model.compile(optimizer=Adam(lr), loss=bce_dice_loss, metrics=[dice_coeff]) T1:1053.
+        loss: one of LOSSES by name or as a callable named like it (dice_loss, tversky_loss, ... T1:784-801); loss_kwargs={"alpha", "beta"} for tversky_loss.
+        fit / evaluate report that loss as `loss` / `val_loss`; the metric stays dice_coeff.
         Re-compiling keeps the weights and resets the optimizer state (as Keras does, T1:1208)."""
-        if loss != "bce_dice_loss":
-            raise ValueError("only bce_dice_loss (T1:797-799) is implemented on the hot path")
+        name, cfg = loss_spec(loss, loss_kwargs)
+        if hasattr(self.backend, "set_loss"):
+            self.backend.set_loss(name, cfg["alpha"], cfg["beta"])
+        elif name != "bce_dice_loss":
+            raise ValueError(f"loss {name!r}: this backend computes bce_dice_loss only (it has no set_loss)")
+        self.loss, self.loss_config = name, (cfg if name == "tversky_loss" and cfg != TVERSKY_DEFAULT else None)
         self.backend.lr = float(lr)
         self.backend.reset_optimizer()
         self.compiled = True
@@ -198,6 +228,8 @@ class UNetModel:
         """model.save(path) -- what ModelCheckpoint(save_weights_only=False) calls (T1:1046-1047): `model_weights/` + `model_config` and, for a compiled
         model, the optimizer (`training_config`, `optimizer_weights/`: Adam's iteration count and moment slots) so that load_model resumes the fit."""
         opt = self.backend.get_optimizer_state() if self.compiled and hasattr(self.backend, "get_optimizer_state") else None
+        if opt is not None:
+            opt = dict(opt, loss=self.loss, loss_config=self.loss_config)          # training_config["loss"] (as Keras writes it) and, for a non-default Tversky, ["loss_config"]
         W.save_weights(path, self.backend.get_weights(), self.in_ch, self.arch, (self.h, self.w), full_model=True, optimizer=opt)
 
     def load_weights(self, path):

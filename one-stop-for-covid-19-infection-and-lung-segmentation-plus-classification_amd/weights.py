@@ -201,6 +201,8 @@ def _optimizer_lists(opt, in_ch, arch, hw):
     cfg = {"optimizer_config": {"class_name": "Adam", "config": dict(ADAM_DEFAULTS, learning_rate=float(opt["lr"]))},
            "loss": opt.get("loss", "bce_dice_loss"), "metrics": list(opt.get("metrics", ["dice_coeff"])), "weighted_metrics": None, "sample_weight_mode": None,
            "loss_weights": None}
+    if opt.get("loss_config"):
+        cfg["loss_config"] = dict(opt["loss_config"])          # (not a Keras field: the non-default alpha / beta of tversky_loss, read back by load_optimizer)
     return out, json.dumps(cfg)
 
 
@@ -226,7 +228,7 @@ def load_optimizer(path: str, in_ch: int = 1, arch: str = "unet", hw=None):
     cfg = json.loads(tc) if tc else {}
     oc = cfg.get("optimizer_config", {}).get("config", {})
     return {"step": int(np.asarray(vals[0]).reshape(-1)[0]), "lr": float(oc.get("learning_rate", oc.get("lr", 0.0005))), "m": m, "v": v,
-            "loss": cfg.get("loss", "bce_dice_loss"), "metrics": cfg.get("metrics", ["dice_coeff"])}
+            "loss": cfg.get("loss", "bce_dice_loss"), "metrics": cfg.get("metrics", ["dice_coeff"]), "loss_config": cfg.get("loss_config")}
 
 
 def save_weights(path: str, weights, in_ch: int = 1, arch: str = "unet", hw=None, full_model: bool = False, optimizer=None):
