@@ -378,6 +378,14 @@ int32_t unet_seg_metrics_sweep(unet_ctx*, const float* p, const float* gt, const
 int32_t unet_gather_samples(unet_ctx*, const float* src, const int64_t* idx, float* dst, int64_t n,
                             int64_t sample_floats, void* stream);
 
+/* Replaces: the reference's augmentation `seq(images=..., segmentation_maps=...)` (imgaug Fliplr / Flipud / Affine, T1:547-583) for a training batch, on the
+ * device.  dst_img[i] = src_img[idx[i]] warped through mats[6 i .. 6 i + 5] with bilinear taps (NHWC, c channels), dst_mask[i] = src_mask[idx[i]] warped with
+ * nearest-neighbour taps (floor(s + 0.5); one channel); both read 0 outside the source.  mats[i] = the INVERSE map of sample i, output pixel -> source pixel:
+ * (x, y) -> (m0 x + m1 y + m2, m3 x + m4 y + m5), pixel centres at integers (augment.py states the policy that builds it).  idx = int64 sample numbers on the
+ * device, or null for i -> i; src_mask / dst_mask both null: images only.  Any h, w; 64-bit sample offsets.  Bad arguments: UNET_E_ARG. */
+int32_t unet_augment_samples(unet_ctx*, const float* src_img, const float* src_mask, const int64_t* idx, const float* mats, float* dst_img, float* dst_mask,
+                             int64_t n, int32_t h, int32_t w, int32_t c, void* stream);
+
 int32_t unet_zero(unet_ctx*, void* ptr, size_t bytes, void* stream);
 /* concatenate([...]) of a tensor that feeds SEVERAL concats (U-Net++ nested skips, task1_unet_plus_plus.py:891-923):
  * copy a dense/sliced tensor into a channel slice of a concat buffer; and the backward: dst (+)= sum of <= 4 gradient slices */

@@ -120,7 +120,8 @@ _PROTOS = {
     "unet_conv3x3_head_fwd_ex": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
     "unet_adam_keras": (i32, [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp]),
     "unet_seg_metrics_sweep": (i32, [vp, vp, vp, vp, i32, vp, i64, vp]),
-    "unet_gather_samples": (i32, [vp, vp, vp, i64, i64, vp]),
+    "unet_gather_samples": (i32, [vp, vp, vp, vp, i64, i64, vp]),
+    "unet_augment_samples": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, vp]),
     "unet_conv3x3_head_supported": (i32, [vp, i32, i32, i32, i32]),
     "unet_conv3x3_head_fwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
     "unet_conv3x3_bwd_data_pool_sums_supported": (i32, [vp, i32, i32, i32, i32]),

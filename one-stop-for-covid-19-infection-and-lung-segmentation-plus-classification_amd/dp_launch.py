@@ -38,6 +38,8 @@ def _jsonable(v):
         return v.item()
     if isinstance(v, (int, float, str, bool)) or v is None:
         return v
+    if type(v).__name__ == "AffineAugment" and hasattr(v, "config"):
+        return v.config()                         # (augment.py: the ranks rebuild the policy from its arguments)
     return None                                   # model objects etc. do not travel
 
 

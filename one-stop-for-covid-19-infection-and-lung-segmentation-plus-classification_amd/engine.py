@@ -308,6 +308,72 @@ class HipUNet:
         self.ctx.check(self.lib.unet_gather_samples(self.ctx.handle, ds.data_ptr(), di.data_ptr(), out.data_ptr(), len(idx), sf, self._stream()), "gather_samples")
         return out
 
+    # ------------------------------------------------------------------ augmentation (augment.py: the reference's imgaug `seq`, T1:547-583)
+    def augment_table(self, mats):
+        """An epoch's float32 [n, 6] inverse-map table (AffineAugment.matrices) on the device, in ONE copy: batches then pass views of its rows."""
+        torch = _torch()
+        m = np.ascontiguousarray(mats, np.float32)
+        if m.ndim != 2 or m.shape[1] != 6:
+            raise ValueError(f"augment_table: expected a [n, 6] table, got shape {m.shape}")
+        return torch.from_numpy(m).to(self.dev, non_blocking=False)
+
+    def _mats_dev(self, mats, n):
+        torch = _torch()
+        m = mats if isinstance(mats, torch.Tensor) else self.augment_table(mats)
+        if m.device != self.dev or m.dtype != torch.float32 or tuple(m.shape) != (n, 6) or not m.is_contiguous():
+            raise ValueError(f"augment: need a contiguous float32 [{n}, 6] table on {self.dev}, got {tuple(m.shape)} {m.dtype} on {m.device}")
+        return m
+
+    def _augment(self, src_x, src_y, di, mats, n, dst_shape_x):
+        torch = _torch()
+        hh, ww = int(src_x.shape[1]), int(src_x.shape[2])
+        c = int(np.prod(src_x.shape[3:])) if src_x.dim() > 3 else 1
+        if src_y is not None and (tuple(src_y.shape[1:3]) != (hh, ww) or int(np.prod(src_y.shape[3:])) != 1):
+            raise ValueError(f"augment: masks must be [n, {hh}, {ww}(, 1)], got {tuple(src_y.shape)}")
+        out_x = torch.empty((n,) + dst_shape_x, dtype=torch.float32, device=self.dev)
+        out_y = torch.empty((n,) + tuple(src_y.shape[1:]), dtype=torch.float32, device=self.dev) if src_y is not None else None
+        self.ctx.check(self.lib.unet_augment_samples(self.ctx.handle, src_x.data_ptr(), src_y.data_ptr() if src_y is not None else None,
+                                                     di.data_ptr() if di is not None else None, mats.data_ptr(), out_x.data_ptr(),
+                                                     out_y.data_ptr() if out_y is not None else None, n, hh, ww, c, self._stream()), "augment_samples")
+        return out_x, out_y
+
+    def take_augmented(self, ds_x, ds_y, idx, mats):
+        """(augment(ds_x[idx]), augment(ds_y[idx])) on the device (unet_augment_samples) out of resident datasets: bilinear images, nearest-neighbour masks, each
+        sample through its row of `mats` (a device [len(idx), 6] view of the epoch's table, or a host array).  The indices go up through the pinned ring `take`
+        uses; a contiguous range needs none.  ds_y may be None (images only)."""
+        torch = _torch()
+        idx = np.ascontiguousarray(idx, np.int64)
+        n = len(idx)
+        if n == 0:
+            return (torch.empty((0,) + tuple(ds_x.shape[1:]), dtype=torch.float32, device=self.dev),
+                    None if ds_y is None else torch.empty((0,) + tuple(ds_y.shape[1:]), dtype=torch.float32, device=self.dev))
+        if idx.min() < 0 or idx.max() >= ds_x.shape[0] or (ds_y is not None and ds_y.shape[0] != ds_x.shape[0]):
+            raise IndexError(f"take_augmented: indices outside [0, {ds_x.shape[0]}) or image / mask sets of different length")
+        m = self._mats_dev(mats, n)
+        if np.all(np.diff(idx) == 1):                                        # a contiguous range: the sample offset goes into the base pointers
+            i0 = int(idx[0])
+            return self._augment(ds_x[i0:i0 + n], None if ds_y is None else ds_y[i0:i0 + n], None, m, n, tuple(ds_x.shape[1:]))
+        k = self._idx_i % 8; self._idx_i += 1
+        if self._idx_ev[k] is not None:
+            self._idx_ev[k].synchronize()
+        if self._idx_pin[k] is None or self._idx_pin[k].numel() < n:
+            self._idx_pin[k] = torch.empty(max(n, 256), dtype=torch.int64).pin_memory()
+        self._idx_pin[k][:n].copy_(torch.from_numpy(idx))
+        di = self._idx_pin[k][:n].to(self.dev, non_blocking=True)
+        ev = torch.cuda.Event(); ev.record(torch.cuda.current_stream(self.dev)); self._idx_ev[k] = ev
+        return self._augment(ds_x, ds_y, di, m, n, tuple(ds_x.shape[1:]))
+
+    def augment_batch(self, xb, yb, mats):
+        """(augment(xb), augment(yb)) for a batch that is not resident (host arrays go through the pinned staging of _to_dev); yb may be None."""
+        xd = self._to_dev(xb)
+        yd = self._to_dev(yb) if yb is not None else None
+        n = int(xd.shape[0])
+        if n == 0:
+            return xd, yd
+        if xd.dim() < 3 or (yd is not None and yd.shape[0] != n):
+            raise ValueError(f"augment_batch: images must be [n, h, w(, c)], masks [n, h, w(, 1)]; got {tuple(xd.shape)}, {None if yd is None else tuple(yd.shape)}")
+        return self._augment(xd.contiguous(), None if yd is None else yd.contiguous(), None, self._mats_dev(mats, n), n, tuple(xd.shape[1:]))
+
     def _make_comm(self):
         """unet_comm_* communicator over the ranks of self.pg (one node, <= 8 ranks), verified by one all-reduce of known values; None (= RCCL) unless
         EVERY rank got through."""

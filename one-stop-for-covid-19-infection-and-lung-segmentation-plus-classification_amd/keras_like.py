@@ -14,6 +14,7 @@ import warnings
 
 import numpy as np
 
+from . import augment as AUG
 from . import weights as W
 
 SM_SMOOTH = 1e-5
@@ -168,6 +169,21 @@ class BatchSource:
                 out.append(a[int(idx[0]):int(idx[0]) + len(idx)] if len(idx) and np.all(np.diff(idx) == 1) else a[idx])
         return out
 
+    def augmented(self, idx, mats):
+        """The batch x[idx], y[idx] warped through `mats` (its rows of the epoch's augmentation table, augment.py): resident sets go straight through
+        take_augmented (one kernel reads the resident samples); anything else is cut as __call__ does and goes through augment_batch."""
+        (dx, ax), (dy, ay) = self.dev
+        if dx is not None and (ay is None or dy is not None):
+            return list(self.backend.take_augmented(dx, dy, idx, mats))
+        xb, yb = self(idx)
+        return list(self.backend.augment_batch(xb, yb, mats))
+
+
+def has_augment(backend):
+    """fit(augment=...) / UNetModel.augment need a backend that uploads a table and warps a batch (engine.HipUNet: augment_table, augment_batch,
+    take_augmented for resident sets)."""
+    return hasattr(backend, "augment_table") and hasattr(backend, "augment_batch")
+
 
 class History:
     def __init__(self):
@@ -239,12 +255,19 @@ class UNetModel:
         return W.to_json(self.h, self.w, self.in_ch, self.arch)
 
     def fit(self, x, y, batch_size=32, epochs=1, validation_data=None, checkpoint_dice=None, checkpoint_loss=None,
-            shuffle=True, shuffle_seed=0, dropout=True, device_resident="auto"):
+            shuffle=True, shuffle_seed=0, dropout=True, device_resident="auto", augment=None, augment_seed=None):
         """model.fit(...) T1:1059-1061.  Per epoch: shuffle, bs-`batch_size` steps with a short
         last batch, loss = sample-weighted mean of batch losses, dice_coeff = mean of per-batch
         values; then a full validation pass; ModelCheckpoint(save_best_only) on val_dice_coeff
-        (max) and val_loss (min) T1:1046-1047."""
+        (max) and val_loss (min) T1:1046-1047.
+        augment: None (no augmentation), True (the reference's imgaug `seq`, T1:547-583) or an augment.AffineAugment.  The training batches (never the
+        validation pass) are warped on the device: position j of epoch e's shuffled order goes through row j of policy.matrices(n, augment_seed, e), and
+        augment_seed defaults to shuffle_seed.  The shuffle order and the dropout stream do not depend on it."""
         assert self.compiled, "call compile() first"
+        policy = AUG.resolve(augment)
+        if policy is not None and not has_augment(self.backend):
+            raise ValueError(f"fit(augment=...): backend {type(self.backend).__name__} has no augmentation hook (augment_table / augment_batch)")
+        aug_seed = shuffle_seed if augment_seed is None else int(augment_seed)
         hist = History()
         n = len(x)
         best_dice, best_loss = -np.inf, np.inf
@@ -255,11 +278,17 @@ class UNetModel:
         for ep in range(epochs):
             t_ep = time.perf_counter()
             order = rng.permutation(n) if shuffle else np.arange(n)
+            # the epoch's augmentation table goes to the device in one copy; a batch passes a view of its rows (a rank's shard: a contiguous run of them)
+            table = self.backend.augment_table(policy.matrices(n, aug_seed, ep, x.shape[1], x.shape[2])) if policy is not None else None
             outs, sizes = [], []
             for i in range(0, n, batch_size):
                 idx = order[i:i + batch_size]
                 sel, kw = dp_shard(idx, world, rank)
-                xb, yb = src(sel)
+                if table is None:
+                    xb, yb = src(sel)
+                else:
+                    pos, _ = dp_shard(np.arange(i, i + len(idx)), world, rank)
+                    xb, yb = src.augmented(sel, table[int(pos[0]):int(pos[0]) + len(pos)])
                 outs.append(self.backend.train_batch(xb, yb, dropout, **kw))                  # [loss, dice_coeff] of the WHOLE batch on every rank
                 sizes.append(len(idx))
             vals = np.stack([_host(o) for o in outs])                     # one host sync per epoch
@@ -289,6 +318,30 @@ class UNetModel:
         if world > 1:
             self.backend.barrier()                                    # the checkpoint files exist before any rank goes on to load_weights (T1:1073)
         return hist
+
+    def augment(self, x, y=None, seed=0, policy=None, batch_size=256):
+        """seq(images=x, segmentation_maps=y) (T1:583) on the device, for users who augment offline as the reference does: sample k goes through row k of
+        policy.matrices(len(x), seed, 0) -- the table fit(augment=policy, augment_seed=seed) uses in its first epoch.  policy: None / True (the reference's
+        `seq`) or an AffineAugment.  Returns float32 host arrays shaped like the inputs: (x_aug, y_aug), or x_aug alone without y."""
+        pol = AUG.resolve(True if policy is None else policy)
+        if not has_augment(self.backend):
+            raise ValueError(f"augment: backend {type(self.backend).__name__} has no augmentation hook (augment_table / augment_batch)")
+        n = len(x)
+        if y is not None and len(y) != n:
+            raise ValueError(f"augment: {n} images but {len(y)} masks")
+        host = lambda v: v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v, np.float32)
+        xs, ys = [], []
+        if n:
+            table = self.backend.augment_table(pol.matrices(n, seed, 0, x.shape[1], x.shape[2]))
+            for i in range(0, n, batch_size):
+                xb, yb = self.backend.augment_batch(x[i:i + batch_size], None if y is None else y[i:i + batch_size], table[i:i + batch_size])
+                xs.append(host(xb))
+                if y is not None:
+                    ys.append(host(yb))
+        xa = np.concatenate(xs, 0) if xs else np.zeros(np.shape(x), np.float32)
+        if y is None:
+            return xa
+        return xa, (np.concatenate(ys, 0) if ys else np.zeros(np.shape(y), np.float32))
 
     def evaluate(self, x, y, batch_size=32, thresholds=None, verbose=0, device_resident="auto", _source=None):
         """model.evaluate T1:1101: loss = sample-weighted mean over batches; every metric = mean of

@@ -43,7 +43,7 @@ def _get_data(data, size, n_samples, seed):
 
 def _segmentation_runner(tag, ckpt_dice, ckpt_loss, fine_range, data=None, input_size=None, epochs=None, batch_size=None,
                          n_samples=None, seed=0, backend=None, dropout=True, init_weights=None, workdir=".", verbose=1, arch="unet",
-                         **backend_kw):
+                         augment=None, **backend_kw):
     size = input_size or _env_int("UNET_SIZE", 224)
     epochs = epochs if epochs is not None else _env_int("UNET_EPOCHS", 80)
     batch_size = batch_size or _env_int("UNET_BATCH", 32)
@@ -59,7 +59,7 @@ def _segmentation_runner(tag, ckpt_dice, ckpt_loss, fine_range, data=None, input
     model.compile(lr=0.0005)                                                                                # T1:1053
     fd, fl = os.path.join(workdir, ckpt_dice), os.path.join(workdir, ckpt_loss)
     results = model.fit(x_train, y_train, batch_size=batch_size, epochs=epochs, validation_data=(x_valid, y_valid),
-                        checkpoint_dice=fd, checkpoint_loss=fl, dropout=dropout, shuffle_seed=seed)         # T1:1059-1061
+                        checkpoint_dice=fd, checkpoint_loss=fl, dropout=dropout, shuffle_seed=seed, augment=augment)   # T1:1059-1061
     if os.path.exists(fd):
         model.load_weights(fd)                                                                              # T1:1073
     out = {"history": results.history, "model": model, "tag": tag}
@@ -120,7 +120,7 @@ def runner_lung_segmentation(**kw):
 
 
 def _kfold_runner(k, data=None, input_size=None, epochs=None, batch_size=None, n_samples=None, seed=0, backend=None, dropout=True,
-                  init_weights=None, workdir=".", verbose=1, reinit_each_fold=False, overwrite_fold_files=True, **backend_kw):
+                  init_weights=None, workdir=".", verbose=1, reinit_each_fold=False, overwrite_fold_files=True, augment=None, **backend_kw):
     """K-fold driver of task1_crossval_{3,4}folds_unet.py (CV4:1045-1108, 1183-1330; CV3:1005-1052, 1136-1300): same U-Net,
     same recipe, KFold(n_splits=k, random_state=42, shuffle=True).  Faithful to the reference by default, including its two
     quirks: ONE model object is trained through all folds without re-initialisation (CV4:1019, 1051-1090 -> fold leakage,
@@ -151,7 +151,7 @@ def _kfold_runner(k, data=None, input_size=None, epochs=None, batch_size=None, n
             model.set_weights(w0)
         model.compile(lr=0.0005)                                                                             # CV4:1062
         histories.append(model.fit(x_train, y_train, batch_size=batch_size, epochs=epochs, validation_data=(x_valid, y_valid),
-                                   checkpoint_dice=paths[fold_number - 1], dropout=dropout, shuffle_seed=seed + fold_number).history)
+                                   checkpoint_dice=paths[fold_number - 1], dropout=dropout, shuffle_seed=seed + fold_number, augment=augment).history)
     print(f"Time of {k}-fold cross validation: ", time.perf_counter() - start)                               # CV4:1099
     from .keras_like import dp_info
     world, rank = dp_info(model.backend)
