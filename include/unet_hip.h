@@ -386,6 +386,35 @@ int32_t unet_gather_samples(unet_ctx*, const float* src, const int64_t* idx, flo
 int32_t unet_augment_samples(unet_ctx*, const float* src_img, const float* src_mask, const int64_t* idx, const float* mats, float* dst_img, float* dst_mask,
                              int64_t n, int32_t h, int32_t w, int32_t c, void* stream);
 
+/* Replaces: the reference's feature-tap clustering (T1:1386-1496): sklearn PCA(n_components=1000) + KMeans(n_clusters=2) over the flattened conv2d_9
+ * activations, on the device (cluster.py builds PCA / KMeans on these entries).  Every input is fp32, row-major, with a leading dimension in elements;
+ * every offset is 64-bit (matrices beyond 2^31 bytes are fine); every reduction runs in a fixed order (no floating-point atomics): reruns are bit-identical.
+ * Bad arguments: UNET_E_ARG. */
+enum { UNET_FEAT_OUT_F32 = 0, UNET_FEAT_OUT_F64 = 1 };
+/* mu[j] = (1/n) sum_i x[i * ldx + j], j < d, accumulated in fp64 in row order.  mu: d doubles. */
+int32_t unet_feat_col_mean(unet_ctx*, const float* x, int64_t ldx, int64_t n, int64_t d, double* mu, void* stream);
+/* Bytes of workspace unet_feat_gemm_nt needs for this shape (0: none). */
+size_t unet_feat_gemm_nt_workspace(int64_t m, int64_t p, int64_t d, int32_t sym);
+/* Centred NT product C[m x p] = (A - 1 mu_a^T)(B - 1 mu_b^T)^T: C[i][j] = sum_{t<d} (a[i * lda + t] - mu_a[t]) (b[j * ldb + t] - mu_b[t]).  mu_a / mu_b:
+ * d doubles each, or null for no mean; each is rounded to fp32 and subtracted as the operand is staged.  v_mfma_f32_32x32x2_f32 products, fp32 within a
+ * K block of 32, fp64 across blocks and across the K slabs of a split (added in slab order).  sym = 1 (the Gram matrix: a == b, lda == ldb,
+ * mu_a == mu_b, m == p): only the upper-triangle tiles are computed and mirrored, C is exactly symmetric.  c: fp32 or fp64 (c_dtype UNET_FEAT_OUT_*),
+ * leading dimension ldc.  ws: device scratch of unet_feat_gemm_nt_workspace(m, p, d, sym) bytes. */
+int32_t unet_feat_gemm_nt(unet_ctx*, const float* a, int64_t lda, const double* mu_a, const float* b, int64_t ldb, const double* mu_b, int64_t m,
+                          int64_t p, int64_t d, int32_t sym, void* c, int64_t ldc, int32_t c_dtype, void* ws, size_t ws_bytes, void* stream);
+/* Bytes of workspace unet_feat_gemm_tn needs for this shape (0: none). */
+size_t unet_feat_gemm_tn_workspace(int64_t k, int64_t d, int64_t n);
+/* Combine (TN) product out[k x d] = W^T (X - 1 mu^T): out[r][j] = sum_{i<n} w[i * ldw + r] (x[i * ldx + j] - mu[j]).  W: n x k, X: n x d, mu: d doubles
+ * or null.  The tile core of unet_feat_gemm_nt with the reduction over the sample axis.  out: fp32 or fp64 (out_dtype), leading dimension ldo; ws: device
+ * scratch of unet_feat_gemm_tn_workspace(k, d, n) bytes. */
+int32_t unet_feat_gemm_tn(unet_ctx*, const float* w, int64_t ldw, const float* x, int64_t ldx, const double* mu, int64_t n, int64_t k, int64_t d,
+                          void* out, int64_t ldo, int32_t out_dtype, void* ws, size_t ws_bytes, void* stream);
+/* One Lloyd step (and KMeans.predict): points P (n x p fp32, leading dimension ldp), centres (k x p fp64, dense).  labels[i] = argmin_c ||P_i - centre_c||^2
+ * (fp64 distances from direct differences; the lower index wins a tie), dist[i] = that squared distance, sums[c][j] = sum over the points of cluster c
+ * of P[i][j] in fp64 (point order; k x p dense), counts[c] = their number, *inertia = sum_i dist[i].  One launch. */
+int32_t unet_kmeans_step(unet_ctx*, const float* pts, int64_t ldp, int64_t n, int64_t p, const double* centres, int32_t k, int32_t* labels,
+                         double* dist, double* sums, int64_t* counts, double* inertia, void* stream);
+
 int32_t unet_zero(unet_ctx*, void* ptr, size_t bytes, void* stream);
 /* concatenate([...]) of a tensor that feeds SEVERAL concats (U-Net++ nested skips, task1_unet_plus_plus.py:891-923):
  * copy a dense/sliced tensor into a channel slice of a concat buffer; and the backward: dst (+)= sum of <= 4 gradient slices */

@@ -122,6 +122,13 @@ _PROTOS = {
     "unet_seg_metrics_sweep": (i32, [vp, vp, vp, vp, i32, vp, i64, vp]),
     "unet_gather_samples": (i32, [vp, vp, vp, vp, i64, i64, vp]),
     "unet_augment_samples": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, vp]),
+    # feature-tap PCA / KMeans (cluster.py)
+    "unet_feat_col_mean": (i32, [vp, vp, i64, i64, i64, vp, vp]),
+    "unet_feat_gemm_nt_workspace": (sz, [i64, i64, i64, i32]),
+    "unet_feat_gemm_nt": (i32, [vp, vp, i64, vp, vp, i64, vp, i64, i64, i64, i32, vp, i64, i32, vp, sz, vp]),
+    "unet_feat_gemm_tn_workspace": (sz, [i64, i64, i64]),
+    "unet_feat_gemm_tn": (i32, [vp, vp, i64, vp, i64, vp, i64, i64, i64, vp, i64, i32, vp, sz, vp]),
+    "unet_kmeans_step": (i32, [vp, vp, i64, i64, i64, vp, i32, vp, vp, vp, vp, vp, vp]),
     "unet_conv3x3_head_supported": (i32, [vp, i32, i32, i32, i32]),
     "unet_conv3x3_head_fwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
     "unet_conv3x3_bwd_data_pool_sums_supported": (i32, [vp, i32, i32, i32, i32]),

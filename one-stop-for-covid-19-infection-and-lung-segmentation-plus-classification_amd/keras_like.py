@@ -417,6 +417,34 @@ class UNetModel:
             outs.append(self.backend.tap(len(xb), name, **kw))
         return np.concatenate(outs, 0)
 
+    def feature_matrix(self, layer_name, x, batch_size=32):
+        """The reference's PCA input (T1:1386-1404): the activation of `layer_name` for every slice of x, each flattened in (C, H, W) order
+        (np.rollaxis(curr_img, 2).flatten()), as an fp32 torch tensor [n, C*H*W] on the backend's device.  Built from tap_device views (a device
+        permute + copy per batch; bf16 taps widened to fp32); backends without tap_device go through tap.  ValueError when the matrix does not
+        fit in free device memory (there is no host fallback)."""
+        import torch
+        rev = {v.split("/")[0]: k.split("/")[0] for k, v in W.keras_names(self.in_ch, self.arch).items()}
+        name = rev.get(layer_name, layer_name)
+        kw = {"replicated": True} if dp_info(self.backend)[0] > 1 else {}
+        dev_tap = hasattr(self.backend, "tap_device")
+        out = None
+        for i in range(0, len(x), batch_size):
+            xb = x[i:i + batch_size]
+            self.backend.predict_batch(xb, **kw)
+            t = self.backend.tap_device(len(xb), name, **kw) if dev_tap else torch.from_numpy(np.asarray(self.backend.tap(len(xb), name, **kw)))
+            t = t.permute(0, 3, 1, 2).reshape(t.shape[0], -1)
+            if out is None:
+                d = t.shape[1]
+                nbytes = len(x) * d * 4
+                if t.is_cuda:
+                    free = torch.cuda.mem_get_info(t.device)[0]
+                    if nbytes > free:
+                        raise ValueError(f"feature_matrix({layer_name}): {len(x)} x {d} fp32 features need {nbytes / 2**30:.2f} GiB, "
+                                         f"{free / 2**30:.2f} GiB of device memory is free")
+                out = torch.empty((len(x), d), dtype=torch.float32, device=t.device)
+            out[i:i + len(xb)].copy_(t)
+        return out
+
     def predict(self, x, batch_size=32):
         """model.predict T1:1137."""
         outs = []

@@ -43,7 +43,7 @@ def _get_data(data, size, n_samples, seed):
 
 def _segmentation_runner(tag, ckpt_dice, ckpt_loss, fine_range, data=None, input_size=None, epochs=None, batch_size=None,
                          n_samples=None, seed=0, backend=None, dropout=True, init_weights=None, workdir=".", verbose=1, arch="unet",
-                         augment=None, **backend_kw):
+                         augment=None, cluster=False, cluster_layer="conv2d_9", cluster_components=1000, **backend_kw):
     size = input_size or _env_int("UNET_SIZE", 224)
     epochs = epochs if epochs is not None else _env_int("UNET_EPOCHS", 80)
     batch_size = batch_size or _env_int("UNET_BATCH", 32)
@@ -94,7 +94,55 @@ def _segmentation_runner(tag, ckpt_dice, ckpt_loss, fine_range, data=None, input
     print("Best Threshold for Recall:", the_prec_rec_range[np.argmax(recalls)])
     print("Best precision score:", precisions[np.argmax(precisions)]); print("Best recall score:", recalls[np.argmax(recalls)])
     out.update(prec_rec_range=the_prec_rec_range, precisions=precisions, recalls=recalls)
+    if cluster:
+        out["cluster"] = _cluster_eval(model, cts, x_valid, y_valid, cluster_layer, cluster_components)
     return out
+
+
+def _cluster_eval(model, cts, x_valid, y_valid, layer, n_components, thr=0.547):
+    """T1:1386-1496 on the engine: features of every slice of cts -> PCA -> KMeans(2, random_state=0); the hold-out features -> transform ->
+    predict; evaluate on the whole hold-out set and on each cluster.  Scores are [loss, FScore@thr, IOUScore@thr] (Keras' accuracy slot is left
+    out).  n_components is clipped to min(n_components, n - 1, d); an empty hold-out cluster is not evaluated (its score is None)."""
+    from .cluster import PCA, KMeans
+    hwc = model.intermediate_output(layer, cts[:1]).shape[1:]                                               # (H, W, C) of the tap
+    data = model.feature_matrix(layer, cts)
+    print("Extracted feature shape:", (len(cts),) + hwc)                                                   # T1:1406
+    print("Flattened features for the input of PCA:", tuple(data.shape))                                    # T1:1413
+    k = min(int(n_components), data.shape[0] - 1, data.shape[1])
+    if k != n_components:
+        print(f"Note: n_components clipped from {n_components} to {k} (n_samples - 1 = {data.shape[0] - 1}, n_features = {data.shape[1]})")
+    pca = PCA(n_components=k).fit(data)
+    total = float(np.sum(pca.explained_variance_ratio_))
+    print("Total variance explained:", total)                                                               # T1:1417
+    new_data = pca.transform(data)
+    print("Input data shape for Clustering:", tuple(new_data.shape))                                        # T1:1419
+    kmeans = KMeans(n_clusters=2, random_state=0).fit(new_data)
+    u, cnt = np.unique(kmeans.labels_, return_counts=True)
+    print("Label count for Kmeans on cts:", dict(zip(u.tolist(), cnt.tolist())))                            # T1:1424
+    vdata = model.feature_matrix(layer, x_valid)
+    print("Extracted feature shape:", (len(x_valid),) + hwc)                                                # T1:1437
+    print("Flattened features for the input of PCA:", tuple(vdata.shape))                                   # T1:1444
+    vlab = kmeans.predict(pca.transform(vdata))
+    vu, vcnt = np.unique(vlab, return_counts=True)
+    print("Label count for Kmeans on valid:", dict(zip(vu.tolist(), vcnt.tolist())))                        # T1:1450
+    subsets = [np.where(vlab == j)[0] for j in (0, 1)]
+    print(x_valid[subsets[0]].shape, x_valid[subsets[1]].shape)                                             # T1:1469
+
+    def score(xs, ys):
+        ev = model.evaluate(xs, ys, batch_size=32, thresholds=[thr])
+        return [float(ev["loss"]), float(ev["dice"][0]), float(ev["iou"][0])]
+
+    scores = [score(x_valid, y_valid)]
+    print("test loss, test dice coefficient, test iou:", scores[0])                                         # T1:1488-1489
+    for j, sel in enumerate(subsets):
+        if len(sel) == 0:
+            print(f"cluster {j} of the hold-out set is empty: no evaluate")
+            scores.append(None)
+            continue
+        scores.append(score(x_valid[sel], y_valid[sel]))
+        print("test loss, test dice coefficient:", scores[-1])                                              # T1:1490-1493
+    return {"label_counts": np.bincount(kmeans.labels_, minlength=2).tolist(), "valid_label_counts": np.bincount(vlab, minlength=2).tolist(),
+            "explained_variance": total, "n_components": k, "valid_labels": vlab, "scores": scores}
 
 
 def holdout_runner_unet_infection_segmentation(**kw):
