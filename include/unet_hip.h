@@ -414,6 +414,19 @@ int32_t unet_feat_gemm_tn(unet_ctx*, const float* w, int64_t ldw, const float* x
  * of P[i][j] in fp64 (point order; k x p dense), counts[c] = their number, *inertia = sum_i dist[i].  One launch. */
 int32_t unet_kmeans_step(unet_ctx*, const float* pts, int64_t ldp, int64_t n, int64_t p, const double* centres, int32_t k, int32_t* labels,
                          double* dist, double* sums, int64_t* counts, double* inertia, void* stream);
+/* Routing (routed.py: a new slice goes to its cluster's expert, the plan the reference states above T1:1386): the PCA projection of a batch of taps and its
+ * nearest centre, fused.  tap: the engine's NHWC view [n][h][w] with pixel stride ld >= c (fp32, or bf16 widened to fp32 when tap_bf16), read in place.
+ * comps_hwc: k x d fp32 (d = h * w * c), the PCA components permuted into tap order (h, w, c); mu_hwc: d fp32 (the PCA mean rounded to fp32, subtracted
+ * term by term as operands are staged), or null.  proj[i][r] = sum_t (x_i[t] - mu[t]) comps[r][t] with the precision of unet_feat_gemm_nt (fp32 within K
+ * blocks of 32, fp64 across blocks and across K slabs, added in slab order), rounded to fp32 (n x k, or null: not stored).  labels[i] / dist[i] as
+ * unet_kmeans_step against centres (nc x k fp64, dense): fp64 squared distances by direct differences from the fp32 projections, the lowest index wins a
+ * tie.  The reduction order depends on (d, k) only -- never on n or on a row's position -- so a row's outputs are bit-identical alone or in any batch, and
+ * reruns are bit-identical (no floating-point atomics).  64-bit addressing.  Two launches.  ws: device scratch of unet_cluster_route_workspace(n, d, k)
+ * bytes.  Bad arguments (nc outside 1..16, k < 1, ld < c, a short workspace): UNET_E_ARG. */
+size_t unet_cluster_route_workspace(int64_t n, int64_t d, int32_t k);
+int32_t unet_cluster_route(unet_ctx*, const void* tap, int32_t tap_bf16, int64_t n, int32_t h, int32_t w, int32_t c, int64_t ld,
+                           const float* comps_hwc, const float* mu_hwc, int32_t k, const double* centres, int32_t nc,
+                           float* proj, int32_t* labels, double* dist, void* ws, size_t ws_bytes, void* stream);
 
 int32_t unet_zero(unet_ctx*, void* ptr, size_t bytes, void* stream);
 /* concatenate([...]) of a tensor that feeds SEVERAL concats (U-Net++ nested skips, task1_unet_plus_plus.py:891-923):

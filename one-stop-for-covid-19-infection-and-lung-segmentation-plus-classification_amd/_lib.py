@@ -129,6 +129,9 @@ _PROTOS = {
     "unet_feat_gemm_tn_workspace": (sz, [i64, i64, i64]),
     "unet_feat_gemm_tn": (i32, [vp, vp, i64, vp, i64, vp, i64, i64, i64, vp, i64, i32, vp, sz, vp]),
     "unet_kmeans_step": (i32, [vp, vp, i64, i64, i64, vp, i32, vp, vp, vp, vp, vp, vp]),
+    # routing to per-cluster experts (cluster.Router)
+    "unet_cluster_route_workspace": (sz, [i64, i64, i32]),
+    "unet_cluster_route": (i32, [vp, vp, i32, i64, i32, i32, i32, i64, vp, vp, i32, vp, i32, vp, vp, vp, vp, sz, vp]),
     "unet_conv3x3_head_supported": (i32, [vp, i32, i32, i32, i32]),
     "unet_conv3x3_head_fwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
     "unet_conv3x3_bwd_data_pool_sums_supported": (i32, [vp, i32, i32, i32, i32]),

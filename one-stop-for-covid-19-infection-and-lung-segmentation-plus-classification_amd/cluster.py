@@ -308,3 +308,107 @@ class KMeans:
 
     def fit_predict(self, X, y=None):
         return self.fit(X).labels_
+
+
+ROUTER_FORMAT = 1
+
+
+def chw_to_hwc(a, tap_shape):
+    """Rows flattened in the reference's (C, H, W) order (np.rollaxis(curr_img, 2).flatten(), T1:1403-1411) -> the same rows in tap order (H, W, C).
+    a: [k, C*H*W] (or [C*H*W]) torch tensor or array; tap_shape (h, w, c)."""
+    h, w, c = (int(v) for v in tap_shape)
+    lead = tuple(a.shape[:-1])
+    if hasattr(a, "permute"):
+        return a.reshape(lead + (c, h, w)).movedim(-3, -1).reshape(lead + (h * w * c,))
+    return np.moveaxis(np.asarray(a).reshape(lead + (c, h, w)), -3, -1).reshape(lead + (h * w * c,))
+
+
+def hwc_to_chw(a, tap_shape):
+    """The inverse of chw_to_hwc."""
+    h, w, c = (int(v) for v in tap_shape)
+    lead = tuple(a.shape[:-1])
+    if hasattr(a, "permute"):
+        return a.reshape(lead + (h, w, c)).movedim(-1, -3).reshape(lead + (c * h * w,))
+    return np.moveaxis(np.asarray(a).reshape(lead + (h, w, c)), -1, -3).reshape(lead + (c * h * w,))
+
+
+class Router:
+    """The assignment step of the routed two-model system (routed.py): a tap of `layer` -> PCA projection -> nearest KMeans centre, for one batch
+    at a time, through unet_cluster_route.  Built once from a fitted PCA and KMeans: the components and the mean are permuted into tap order
+    (h, w, c) so that the kernel reads the engine's NHWC tap in place; the mean is rounded to fp32 (as PCA.transform stages it) and the centres
+    stay fp64.
+
+    Attributes: comps_hwc [k, d] fp32, mu_hwc [d] fp32, centres [nc, k] fp64 (torch, on `device`), mean64 [d] fp64 in (C, H, W) order (host),
+    explained_variance_ratio (host), tap_shape (h, w, c), layer."""
+
+    def __init__(self, pca, kmeans, tap_shape, layer="conv2d_9", device="cuda"):
+        comps = getattr(pca, "_comps_dev", None)
+        if comps is None or str(device) == "cpu":
+            comps = np.asarray(pca.components_, np.float32)
+        centres = getattr(kmeans, "_centres64", None)
+        if centres is None:
+            centres = np.asarray(kmeans.cluster_centers_, np.float64)
+        self._build(comps, np.asarray(pca.mean_, np.float64), centres, tap_shape, layer, np.asarray(pca.explained_variance_ratio_), device)
+
+    @classmethod
+    def from_arrays(cls, components, mean, centres, tap_shape, layer="conv2d_9", explained_variance_ratio=None, device="cuda"):
+        """components [k, d] and mean [d] in the reference's (C, H, W) flatten order, centres [nc, k]."""
+        r = cls.__new__(cls)
+        r._build(components, np.asarray(mean, np.float64), centres, tap_shape, layer, explained_variance_ratio, device)
+        return r
+
+    def _build(self, comps, mean, centres, tap_shape, layer, evr, device):
+        torch = _torch()
+        self.tap_shape = tuple(int(v) for v in tap_shape)
+        self.layer = layer
+        h, w, c = self.tap_shape
+        d = h * w * c
+        k = int(comps.shape[0])
+        if tuple(comps.shape) != (k, d) or mean.shape != (d,):
+            raise ValueError(f"Router: components {tuple(comps.shape)} / mean {mean.shape} do not match the tap shape {self.tap_shape} (d = {d})")
+        centres = torch.as_tensor(np.asarray(centres.cpu() if hasattr(centres, "cpu") else centres, np.float64))
+        if centres.ndim != 2 or centres.shape[1] != k or not 1 <= centres.shape[0] <= 16:
+            raise ValueError(f"Router: centres {tuple(centres.shape)} must be [nc, {k}] with 1 <= nc <= 16")
+        if not isinstance(comps, torch.Tensor):
+            comps = torch.from_numpy(np.ascontiguousarray(comps, np.float32))
+        self.comps_hwc = chw_to_hwc(comps.to(device=device, dtype=torch.float32), self.tap_shape).contiguous()
+        self.mean64 = mean
+        self.mu_hwc = torch.from_numpy(np.ascontiguousarray(chw_to_hwc(mean, self.tap_shape), np.float32)).to(device)
+        self.centres = centres.to(device).contiguous()
+        self.explained_variance_ratio = None if evr is None else np.asarray(evr)
+        self.n_components, self.n_clusters, self.n_features = k, int(centres.shape[0]), d
+
+    def components_chw(self):
+        """The components in the reference's (C, H, W) order, fp32 numpy [k, d]."""
+        return hwc_to_chw(self.comps_hwc, self.tap_shape).cpu().numpy()
+
+    def assign(self, tap, want_proj=False):
+        """One batch of taps [n, h, w, c] -- the engine's tap_device view (pixel stride >= c, fp32 or bf16), or any fp32 / bf16 tensor of that shape
+        on the device -> (labels int32 [n], squared distances fp64 [n], projections fp32 [n, k] or None), device tensors."""
+        torch = _torch(); lib, ctx = _ctx()
+        if tuple(tap.shape[1:]) != self.tap_shape:
+            raise ValueError(f"Router.assign: tap shape {tuple(tap.shape[1:])}, the router was built for {self.tap_shape}")
+        if tap.dtype not in (torch.float32, torch.bfloat16):
+            tap = tap.to(torch.float32)
+        n, h, w, c = tap.shape
+        ld = tap.stride(2)
+        if not (tap.stride(3) == 1 and ld >= c and tap.stride(1) == w * ld and tap.stride(0) == h * w * ld) or not tap.is_cuda:
+            tap = tap.to(device=self.comps_hwc.device).contiguous()
+            ld = c
+        k = self.n_components
+        labels = torch.empty(n, dtype=torch.int32, device=tap.device)
+        dist = torch.empty(n, dtype=torch.float64, device=tap.device)
+        proj = torch.empty((n, k), dtype=torch.float32, device=tap.device) if want_proj else None
+        ws = _workspace(lib.unet_cluster_route_workspace(n, h * w * c, k))
+        ctx.check(lib.unet_cluster_route(ctx.handle, tap.data_ptr(), int(tap.dtype == torch.bfloat16), n, h, w, c, ld, self.comps_hwc.data_ptr(),
+                                         self.mu_hwc.data_ptr(), k, self.centres.data_ptr(), self.n_clusters,
+                                         proj.data_ptr() if proj is not None else None, labels.data_ptr(), dist.data_ptr(), ws.data_ptr(), ws.numel(),
+                                         _stream()), "cluster_route")
+        return labels, dist, proj
+
+    def arrays(self):
+        """What router.npz holds (routed.ClusterRoutedModel.save)."""
+        return {"format": np.int64(ROUTER_FORMAT), "components": self.components_chw(), "mean": self.mean64,
+                "centres": self.centres.cpu().numpy(), "tap_shape": np.asarray(self.tap_shape, np.int64), "layer": np.asarray(self.layer),
+                "explained_variance_ratio": (np.asarray([], np.float64) if self.explained_variance_ratio is None
+                                             else np.asarray(self.explained_variance_ratio))}

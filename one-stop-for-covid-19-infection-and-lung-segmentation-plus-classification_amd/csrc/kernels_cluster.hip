@@ -258,6 +258,214 @@ __global__ __launch_bounds__(KM_THREADS) void kmeans_step_kernel(const float* __
 
 bool aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 
+// ---- routing (routed.py: a new slice's cluster, T1:1386-1496 applied to one batch) -----------------------------------------------------------------
+// proj[i][r] = sum_t (x_i[t] - mu[t]) comps[r][t] over the tap in (h, w, c) order, then labels[i] = argmin_c ||proj_i - centre_c||^2.  n is small (one
+// predict batch), k <= ~1000, d up to 512 * 32 * 32: the product streams comps once per 64 rows.  Launch 1 (route_partial_kernel): a workgroup owns 32
+// components x (up to) 64 rows x one K slab; its four waves take the slab's K blocks of 32 round-robin, each block one 16-step run of
+// v_mfma_f32_32x32x2_f32 (lane (l31, hi) loads 16 contiguous terms t = kb + 16 hi + 0..15 of component r0 + l31 and of row i0 + l31: step s pairs them,
+// so a block covers its 32 terms once) whose fp32 result is added into fp64; the waves fold in a fixed tree ((w0 + w1) + (w2 + w3)) and the workgroup
+// writes one fp64 partial per (slab, row, component).  Launch 2 (route_assign_kernel): one workgroup per row adds the slabs in slab order, rounds to
+// fp32 (the points unet_kmeans_step sees), and takes fp64 squared distances by direct differences: thread-strided over components, then a fixed LDS
+// tree; the lowest index wins a tie.  The slab plan depends on (d, k) alone and a row's arithmetic never on its neighbours, so route(x)[i] is
+// bit-identical to route(x[i:i+1]).
+constexpr int RT_CT = 32, RT_WAVES = 4, RT_NC_MAX = 16;
+constexpr long long RT_TARGET_WG = 2048;
+
+struct RoutePlan {
+  long long tiles_k, slabs, kslab;
+};
+RoutePlan route_plan(long long d, long long k) {
+  RoutePlan p;
+  p.tiles_k = (k + RT_CT - 1) / RT_CT;
+  const long long blocks = (d + KB - 1) / KB;
+  long long want = (RT_TARGET_WG + p.tiles_k - 1) / p.tiles_k;
+  const long long by_len = (blocks + 4 * RT_WAVES - 1) / (4 * RT_WAVES);       // >= 4 K blocks per wave
+  if (want > by_len) want = by_len;
+  if (want < 1) want = 1;
+  p.kslab = (blocks + want - 1) / want * KB;
+  p.slabs = (d + p.kslab - 1) / p.kslab;
+  return p;
+}
+
+// 16 terms t0..t0+15 of tap row `row` (NHWC view, pixel stride ld, row stride hw * ld), the fp32 mean subtracted; zero past n or d
+template <typename T>
+__device__ __forceinline__ void route_load_x(const T* __restrict__ x, long long rs, int c, long long ld, const float* __restrict__ mu, long long n,
+                                             long long d, long long row, long long t0, bool vec, float v[16]) {
+  if (vec && row < n && t0 + 16 <= d) {                        // c % 16 == 0: the 16 terms are 16 channels of one pixel
+    const long long pix = t0 / c;
+    const T* p = x + row * rs + pix * ld + (t0 - pix * c);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const float4 a = ld4(p + 4 * q);
+      v[4 * q + 0] = a.x; v[4 * q + 1] = a.y; v[4 * q + 2] = a.z; v[4 * q + 3] = a.w;
+    }
+    if (mu) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const float4 m = *reinterpret_cast<const float4*>(mu + t0 + 4 * q);
+        v[4 * q + 0] -= m.x; v[4 * q + 1] -= m.y; v[4 * q + 2] -= m.z; v[4 * q + 3] -= m.w;
+      }
+    }
+  } else {
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      const long long t = t0 + e;
+      if (row < n && t < d) {
+        const long long pix = t / c;
+        v[e] = ld1(x + row * rs + pix * ld + (t - pix * c)) - (mu ? mu[t] : 0.f);
+      } else {
+        v[e] = 0.f;
+      }
+    }
+  }
+}
+
+// 16 terms t0..t0+15 of component r (dense k x d); zero past k or d
+__device__ __forceinline__ void route_load_w(const float* __restrict__ w, long long k, long long d, long long r, long long t0, bool vec, float v[16]) {
+  if (vec && r < k && t0 + 16 <= d) {
+    const float* p = w + r * d + t0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const float4 a = *reinterpret_cast<const float4*>(p + 4 * q);
+      v[4 * q + 0] = a.x; v[4 * q + 1] = a.y; v[4 * q + 2] = a.z; v[4 * q + 3] = a.w;
+    }
+  } else {
+#pragma unroll
+    for (int e = 0; e < 16; ++e) v[e] = (r < k && t0 + e < d) ? w[r * d + t0 + e] : 0.f;
+  }
+}
+
+// part[(slab * n + i) * k + r]: the fp64 partial of row i, component r over K slab `slab`.  NT row tiles of 32 (NT * 32 rows per workgroup).
+template <typename T, int NT>
+__global__ __launch_bounds__(RT_WAVES * 64) void route_partial_kernel(const T* __restrict__ x, long long rs, int c, long long ld, int vec_x,
+                                                                       const float* __restrict__ w, const float* __restrict__ mu, int vec_w, long long n,
+                                                                       long long d, long long k, long long kslab, double* __restrict__ part) {
+  __shared__ double red[2 * NT * 16 * 64];                   // two waves' fp64 accumulators [wave pair][j][lane]; reused as the [row][component] tile
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l31 = lane & 31, hi = lane >> 5;
+  const long long r0 = (long long)blockIdx.x * RT_CT, slab = blockIdx.y, i0 = (long long)blockIdx.z * (32 * NT);
+  const long long kbeg = slab * kslab, kend = kbeg + kslab < d ? kbeg + kslab : d;
+  f32x16 acc[NT];
+  double acc64[NT][16];
+#pragma unroll
+  for (int y = 0; y < NT; ++y)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { acc[y][r] = 0.f; acc64[y][r] = 0.0; }
+
+  float va[16], vb[NT][16];
+  long long kb = kbeg + (long long)wave * KB;
+  if (kb < kend) {
+    route_load_w(w, k, d, r0 + l31, kb + 16 * hi, vec_w, va);
+#pragma unroll
+    for (int y = 0; y < NT; ++y) route_load_x(x, rs, c, ld, mu, n, d, i0 + 32 * y + l31, kb + 16 * hi, vec_x, vb[y]);
+  }
+  for (; kb < kend; kb += RT_WAVES * KB) {
+    float ca[16], cb[NT][16];
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      ca[e] = va[e];
+#pragma unroll
+      for (int y = 0; y < NT; ++y) cb[y][e] = vb[y][e];
+    }
+    const long long kn = kb + RT_WAVES * KB;
+    if (kn < kend) {                                           // the wave's next block loads under this block's MFMAs
+      route_load_w(w, k, d, r0 + l31, kn + 16 * hi, vec_w, va);
+#pragma unroll
+      for (int y = 0; y < NT; ++y) route_load_x(x, rs, c, ld, mu, n, d, i0 + 32 * y + l31, kn + 16 * hi, vec_x, vb[y]);
+    }
+#pragma unroll
+    for (int s = 0; s < 16; ++s)
+#pragma unroll
+      for (int y = 0; y < NT; ++y) acc[y] = __builtin_amdgcn_mfma_f32_32x32x2f32(ca[s], cb[y][s], acc[y], 0, 0, 0);
+#pragma unroll
+    for (int y = 0; y < NT; ++y)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) { acc64[y][r] += (double)acc[y][r]; acc[y][r] = 0.f; }
+  }
+
+  // fixed fold: w0 += w1, w2 += w3, then w0 += w2
+  if (wave & 1) {
+#pragma unroll
+    for (int y = 0; y < NT; ++y)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) red[((wave >> 1) * NT * 16 + y * 16 + r) * 64 + lane] = acc64[y][r];
+  }
+  __syncthreads();
+  if (!(wave & 1)) {
+#pragma unroll
+    for (int y = 0; y < NT; ++y)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc64[y][r] += red[((wave >> 1) * NT * 16 + y * 16 + r) * 64 + lane];
+  }
+  __syncthreads();
+  if (wave == 2) {
+#pragma unroll
+    for (int y = 0; y < NT; ++y)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) red[(y * 16 + r) * 64 + lane] = acc64[y][r];
+  }
+  __syncthreads();
+  if (wave == 0) {
+#pragma unroll
+    for (int y = 0; y < NT; ++y)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc64[y][r] += red[(y * 16 + r) * 64 + lane];
+  }
+  __syncthreads();
+  if (wave == 0) {                                             // D row (r&3) + 8(r>>2) + 4hi = component, column l31 = row: stage as [row][component]
+#pragma unroll
+    for (int y = 0; y < NT; ++y)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) red[(32 * y + l31) * RT_CT + (r & 3) + 8 * (r >> 2) + 4 * hi] = acc64[y][r];
+  }
+  __syncthreads();
+  for (int e = threadIdx.x; e < 32 * NT * RT_CT; e += RT_WAVES * 64) {
+    const long long i = i0 + e / RT_CT, r = r0 + e % RT_CT;
+    if (i < n && r < k) part[(slab * n + i) * k + r] = red[e];
+  }
+}
+
+// one workgroup per row: proj (fp32) = the slabs added in slab order; fp64 squared distances to every centre; lowest-index argmin
+constexpr int RA_THREADS = 256;
+__global__ __launch_bounds__(RA_THREADS) void route_assign_kernel(const double* __restrict__ part, long long slabs, long long n, long long k,
+                                                                  const double* __restrict__ cen, int nc, float* __restrict__ proj,
+                                                                  int* __restrict__ labels, double* __restrict__ dist) {
+  __shared__ double red[RT_NC_MAX * RA_THREADS];
+  const long long i = blockIdx.x;
+  double s[RT_NC_MAX];
+#pragma unroll
+  for (int cc = 0; cc < RT_NC_MAX; ++cc) s[cc] = 0.0;
+  for (long long r = threadIdx.x; r < k; r += RA_THREADS) {
+    double v = 0.0;
+    for (long long sl = 0; sl < slabs; ++sl) v += part[(sl * n + i) * k + r];
+    const float pf = (float)v;
+    if (proj) proj[i * k + r] = pf;
+#pragma unroll
+    for (int cc = 0; cc < RT_NC_MAX; ++cc)
+      if (cc < nc) {
+        const double df = (double)pf - cen[(long long)cc * k + r];
+        s[cc] = fma(df, df, s[cc]);
+      }
+  }
+#pragma unroll
+  for (int cc = 0; cc < RT_NC_MAX; ++cc)
+    if (cc < nc) red[cc * RA_THREADS + threadIdx.x] = s[cc];
+  __syncthreads();
+  for (int wdt = RA_THREADS / 2; wdt >= 1; wdt >>= 1) {
+    if ((int)threadIdx.x < wdt)
+      for (int cc = 0; cc < nc; ++cc) red[cc * RA_THREADS + threadIdx.x] += red[cc * RA_THREADS + threadIdx.x + wdt];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    double best = red[0];
+    int bl = 0;
+    for (int cc = 1; cc < nc; ++cc)
+      if (red[cc * RA_THREADS] < best) { best = red[cc * RA_THREADS]; bl = cc; }
+    labels[i] = bl;
+    dist[i] = best;
+  }
+}
+
+
 template <bool TN>
 int32_t run_gemm(unet_ctx* ctx, const char* what, const float* a, long long lda, const double* mu_a, const float* b, long long ldb, const double* mu_b,
                  long long m, long long p, long long K, bool sym, void* c, long long ldc, int32_t c_dtype, void* ws, size_t ws_bytes, void* stream) {
@@ -326,6 +534,46 @@ int32_t unet_kmeans_step(unet_ctx* ctx, const float* pts, int64_t ldp, int64_t n
   hipLaunchKernelGGL(kmeans_step_kernel, dim3(1), dim3(KM_THREADS), 0, as_stream(stream), pts, (long long)ldp, (long long)n, (long long)p, centres, (int)k,
                      labels, dist, sums, reinterpret_cast<long long*>(counts), inertia);
   UNET_CHECK_LAUNCH(ctx, "kmeans_step");
+  return UNET_OK;
+}
+
+size_t unet_cluster_route_workspace(int64_t n, int64_t d, int32_t k) {
+  if (n < 1 || d < 1 || k < 1) return 0;
+  const RoutePlan p = route_plan(d, k);
+  return (size_t)(p.slabs * n * (long long)k * 8);
+}
+
+int32_t unet_cluster_route(unet_ctx* ctx, const void* tap, int32_t tap_bf16, int64_t n, int32_t h, int32_t w, int32_t c, int64_t ld,
+                           const float* comps_hwc, const float* mu_hwc, int32_t k, const double* centres, int32_t nc, float* proj, int32_t* labels,
+                           double* dist, void* ws, size_t ws_bytes, void* stream) {
+  if (!tap || !comps_hwc || !centres || !labels || !dist || n < 1 || h < 1 || w < 1 || c < 1 || ld < c || k < 1 || nc < 1 || nc > RT_NC_MAX)
+    UNET_FAIL(ctx, UNET_E_ARG, "cluster_route: bad args (tap, comps, centres, labels, dist non-null; n, h, w, c, k >= 1; ld >= c; 1 <= nc <= %d)", RT_NC_MAX);
+  const long long d = (long long)h * w * c, rs = (long long)h * w * ld;
+  const RoutePlan p = route_plan(d, k);
+  const size_t need = (size_t)(p.slabs * n * (long long)k * 8);
+  if (!ws || ws_bytes < need) UNET_FAIL(ctx, UNET_E_ARG, "cluster_route: workspace of %zu bytes is smaller than the %zu the shape needs", ws_bytes, need);
+  const long long tiles_n = (n + 63) / 64;
+  if (p.tiles_k > 0x7fffffffLL || p.slabs > 65535 || tiles_n > 65535 || n > 0x7fffffffLL)
+    UNET_FAIL(ctx, UNET_E_SHAPE, "cluster_route: n = %lld, d = %lld, k = %d is too large", (long long)n, d, k);
+  const int vec_x = c % 16 == 0 && ld % 4 == 0 && aligned16(tap) && (!mu_hwc || aligned16(mu_hwc));
+  const int vec_w = d % 4 == 0 && aligned16(comps_hwc);
+  double* part = static_cast<double*>(ws);
+  const bool two = n > 32;
+  const dim3 grid((unsigned)p.tiles_k, (unsigned)p.slabs, (unsigned)(two ? tiles_n : n > 0 ? (n + 31) / 32 : 1));
+  const dim3 block(RT_WAVES * 64);
+  if (tap_bf16) {
+    const unet_bf16* x = static_cast<const unet_bf16*>(tap);
+    if (two) hipLaunchKernelGGL((route_partial_kernel<unet_bf16, 2>), grid, block, 0, as_stream(stream), x, rs, (int)c, (long long)ld, vec_x, comps_hwc, mu_hwc, vec_w, (long long)n, d, (long long)k, p.kslab, part);
+    else hipLaunchKernelGGL((route_partial_kernel<unet_bf16, 1>), grid, block, 0, as_stream(stream), x, rs, (int)c, (long long)ld, vec_x, comps_hwc, mu_hwc, vec_w, (long long)n, d, (long long)k, p.kslab, part);
+  } else {
+    const float* x = static_cast<const float*>(tap);
+    if (two) hipLaunchKernelGGL((route_partial_kernel<float, 2>), grid, block, 0, as_stream(stream), x, rs, (int)c, (long long)ld, vec_x, comps_hwc, mu_hwc, vec_w, (long long)n, d, (long long)k, p.kslab, part);
+    else hipLaunchKernelGGL((route_partial_kernel<float, 1>), grid, block, 0, as_stream(stream), x, rs, (int)c, (long long)ld, vec_x, comps_hwc, mu_hwc, vec_w, (long long)n, d, (long long)k, p.kslab, part);
+  }
+  UNET_CHECK_LAUNCH(ctx, "cluster_route");
+  hipLaunchKernelGGL(route_assign_kernel, dim3((unsigned)n), dim3(RA_THREADS), 0, as_stream(stream), part, p.slabs, (long long)n, (long long)k, centres, (int)nc,
+                     proj, labels, dist);
+  UNET_CHECK_LAUNCH(ctx, "cluster_route");
   return UNET_OK;
 }
 

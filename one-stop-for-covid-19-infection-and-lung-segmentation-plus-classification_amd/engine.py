@@ -47,6 +47,7 @@ class HipUNet:
         # options: {"deterministic": 1, "bn_fold": 0, ...} (_lib.OPTIONS; include/unet_hip.h UNET_OPT_*) -> a private context carrying them
         # (engines with equal options share one context -- single thread, single stream; private_context=True: a context of this engine's own, _lib.Context)
         self.ctx = _lib.Context.get(self.device_index, options, private=private_context).retain()
+        self.options = dict(options) if options else None
         self.h, self.w, self.in_ch, self.algo = h, w, in_ch, conv_algo
         self.arch = arch                       # "unet" (T1:853-916) or "unetpp" (task1_unet_plus_plus.py:858-950; its dropout
         self._arch_id = {"unet": _lib.ARCH_UNET, "unetpp": _lib.ARCH_UNETPP, "classifier": _lib.ARCH_CLASSIFIER}[arch]   # rates fixed: >0 = on
@@ -110,6 +111,12 @@ class HipUNet:
         # nothing overlaps it, so its whole duration is exposed (what the 5 overlapped buckets are measured against)
         self.grad_buckets = bool(grad_buckets)
         self._comm_prof = None                 # set_comm_profiling: event pairs of the gradient all-reduces and of the compute stream's wait in front of Adam
+
+    def spawn(self, seed: int = 0):
+        """A new single-process engine with this one's shape, graph, dtype, options and dropout rate (its own weights, optimizer and workspace):
+        the experts of routed.ClusterRoutedModel."""
+        return HipUNet(self.h, self.w, self.in_ch, device=self.device_index, conv_algo=self.algo, sync_bn=self.sync_bn, dropout_rate=self.dropout_rate,
+                       seed=seed, lr=self.lr, arch=self.arch, dtype=self.dtype, options=self.options)
 
     # ------------------------------------------------------------------ plans / buffers
     def _create_plan(self, n, replicated=False):

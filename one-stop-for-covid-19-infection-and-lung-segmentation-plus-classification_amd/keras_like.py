@@ -56,6 +56,18 @@ def _host(v):
     return np.asarray(v, np.float64)
 
 
+def binary_matches(p, y):
+    """Keras' binary_accuracy numerator for one batch: the number of pixels where y == (p > 0.5), with y compared as fp32 (a fractional y never
+    matches).  An exact integer: an int64 device tensor for device p, a Python int for host p."""
+    if hasattr(p, "detach"):
+        import torch
+        yd = y if isinstance(y, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(y, np.float32))
+        yd = yd.to(device=p.device, dtype=torch.float32).reshape(p.shape)
+        return torch.count_nonzero(yd == (p > 0.5).to(torch.float32))
+    p = np.asarray(p)
+    return int(np.count_nonzero(np.asarray(y, np.float32).reshape(p.shape) == (p > np.float32(0.5)).astype(np.float32)))
+
+
 def dp_info(backend):
     """(world, rank) of a data-parallel backend (engine.HipUNet built with a process group), else (1, 0)."""
     return (int(backend.world), int(backend.rank)) if getattr(backend, "_dp", False) else (1, 0)
@@ -200,6 +212,7 @@ class UNetModel:
             from .engine import HipUNet                      # raises loudly without GPU / library
             backend = HipUNet(self.h, self.w, in_ch, seed=seed, arch=arch, **backend_kw)
         self.backend = backend
+        self.seed = seed
         self.backend.set_weights(W.init_weights(seed, in_ch, arch))
         self.compiled = False
         self.loss, self.loss_config = "bce_dice_loss", None
@@ -343,12 +356,17 @@ class UNetModel:
             return xa
         return xa, (np.concatenate(ys, 0) if ys else np.zeros(np.shape(y), np.float32))
 
-    def evaluate(self, x, y, batch_size=32, thresholds=None, verbose=0, device_resident="auto", _source=None):
+    def evaluate(self, x, y, batch_size=32, thresholds=None, verbose=0, device_resident="auto", _source=None, accuracy=False):
         """model.evaluate T1:1101: loss = sample-weighted mean over batches; every metric = mean of
         the per-batch values.  With `thresholds`, ONE forward pass per batch feeds all thresholds
-        (the reference re-compiles and re-runs evaluate per threshold, T1:1205-1211)."""
+        (the reference re-compiles and re-runs evaluate per threshold, T1:1205-1211).
+        accuracy=True adds "accuracy": Keras' 'accuracy' metric (binary_accuracy, T1:1482) as evaluate reports it -- the fraction of ALL pixels of
+        the set where y == (p > 0.5), counted exactly (binary_matches), not a mean of per-batch values."""
         losses, dices, sizes, per_batch = [], [], [], []
         world, rank = dp_info(self.backend)
+        if accuracy and world > 1:
+            raise ValueError("evaluate(accuracy=True) is not available under data parallelism")
+        matches, pixels = [], 0
         src = _source if _source is not None else self._eval_source(x, y, device_resident)
         for i in range(0, len(x), batch_size):
             sel, kw = dp_shard(np.arange(i, min(i + batch_size, len(x))), world, rank)
@@ -357,6 +375,8 @@ class UNetModel:
             losses.append(ld); sizes.append(min(i + batch_size, len(x)) - i)
             if thresholds is not None and len(thresholds):
                 per_batch.append(self.backend.threshold_sums(p, yb, thresholds, **kw))
+            if accuracy:
+                matches.append(binary_matches(p, yb)); pixels += int(np.prod(p.shape))
         vals = np.stack([_host(v) for v in losses])
         check_comm(self.backend, "evaluate")
         out = {"loss": float(np.average(vals[:, 0], weights=sizes)), "dice_coeff": float(vals[:, 1].mean())}
@@ -364,6 +384,8 @@ class UNetModel:
             sc = [sm_scores(s[:, 0], s[:, 1], s[:, 2]) for s in (_host(b) for b in per_batch)]
             for k in ("dice", "iou", "precision", "recall"):
                 out[k] = np.mean([b[k] for b in sc], axis=0)
+        if accuracy:
+            out["accuracy"] = sum(int(m) for m in matches) / pixels if pixels else float("nan")
         return out
 
     def _eval_source(self, x, y, device_resident):

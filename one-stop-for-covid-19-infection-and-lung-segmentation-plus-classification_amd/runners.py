@@ -43,7 +43,9 @@ def _get_data(data, size, n_samples, seed):
 
 def _segmentation_runner(tag, ckpt_dice, ckpt_loss, fine_range, data=None, input_size=None, epochs=None, batch_size=None,
                          n_samples=None, seed=0, backend=None, dropout=True, init_weights=None, workdir=".", verbose=1, arch="unet",
-                         augment=None, cluster=False, cluster_layer="conv2d_9", cluster_components=1000, **backend_kw):
+                         augment=None, cluster=False, cluster_layer="conv2d_9", cluster_components=1000, route=False, route_init="base",
+                         route_epochs=None, **backend_kw):
+    cluster = cluster or route
     size = input_size or _env_int("UNET_SIZE", 224)
     epochs = epochs if epochs is not None else _env_int("UNET_EPOCHS", 80)
     batch_size = batch_size or _env_int("UNET_BATCH", 32)
@@ -95,14 +97,45 @@ def _segmentation_runner(tag, ckpt_dice, ckpt_loss, fine_range, data=None, input
     print("Best precision score:", precisions[np.argmax(precisions)]); print("Best recall score:", recalls[np.argmax(recalls)])
     out.update(prec_rec_range=the_prec_rec_range, precisions=precisions, recalls=recalls)
     if cluster:
-        out["cluster"] = _cluster_eval(model, cts, x_valid, y_valid, cluster_layer, cluster_components)
+        fitted = {}
+        out["cluster"] = _cluster_eval(model, cts, x_valid, y_valid, cluster_layer, cluster_components, _fitted=fitted)
+    if route:
+        out["routed"] = _routed_eval(model, fitted, x_train, y_train, x_valid, y_valid, route_init, epochs if route_epochs is None else route_epochs,
+                                     batch_size, fd, fl, dropout, seed, augment)
     return out
 
 
-def _cluster_eval(model, cts, x_valid, y_valid, layer, n_components, thr=0.547):
+def _routed_eval(model, fitted, x_train, y_train, x_valid, y_valid, init, epochs, batch_size, fd, fl, dropout, seed, augment, thr=0.547):
+    """The routed two-model system (routed.py) on the cluster step's PCA and KMeans: route x_train, train one expert per cluster (checkpoints
+    cluster{j}_<name>, the best-dice one reloaded as T1:1073 does for the base), and evaluate the routed hold-out set as a whole and per cluster
+    with Keras' accuracy: [loss, FScore@thr, IOUScore@thr, accuracy] per cluster."""
+    from .routed import ClusterRoutedModel, _prefixed
+    rm = ClusterRoutedModel(model, layer=fitted["layer"], n_components=fitted["pca"].n_components_, n_clusters=2, random_state=0)
+    rm.set_router(fitted["pca"], fitted["kmeans"], fitted["hwc"])
+    rm.fit(x_train, y_train, init=init, batch_size=batch_size, epochs=epochs, validation_data=(x_valid, y_valid), checkpoint_dice=fd,
+           checkpoint_loss=fl, dropout=dropout, shuffle_seed=seed, augment=augment)
+    for j, e in enumerate(rm.experts):
+        if e is not model and os.path.exists(_prefixed(fd, j)):
+            e.load_weights(_prefixed(fd, j))
+    tr = np.bincount(rm.route(x_train), minlength=2).tolist()
+    print("Routed training rows per cluster:", tr, "experts:", rm.expert_source)
+    ev = rm.evaluate(x_valid, y_valid, batch_size=32, thresholds=(thr,), accuracy=True)
+    whole = [float(ev["whole"]["dice"][0]), float(ev["whole"]["iou"][0]), float(ev["whole"]["accuracy"])]
+    print("routed test dice coefficient, test iou, test accuracy:", whole)
+    for j, sc in enumerate(ev["per_cluster"]):
+        if sc is None:
+            print(f"routed cluster {j} of the hold-out set is empty: no evaluate")
+        else:
+            print(f"routed cluster {j} test loss, test dice coefficient, test iou, test accuracy:", sc)
+    return {"label_counts": tr, "valid_label_counts": ev["counts"], "valid_labels": ev["labels"], "whole": whole, "scores": ev["per_cluster"],
+            "expert_source": list(rm.expert_source), "model": rm}
+
+
+def _cluster_eval(model, cts, x_valid, y_valid, layer, n_components, thr=0.547, _fitted=None):
     """T1:1386-1496 on the engine: features of every slice of cts -> PCA -> KMeans(2, random_state=0); the hold-out features -> transform ->
     predict; evaluate on the whole hold-out set and on each cluster.  Scores are [loss, FScore@thr, IOUScore@thr] (Keras' accuracy slot is left
-    out).  n_components is clipped to min(n_components, n - 1, d); an empty hold-out cluster is not evaluated (its score is None)."""
+    out here; the routed step reports it).  n_components is clipped to min(n_components, n - 1, d); an empty hold-out cluster is not evaluated (its
+    score is None).  _fitted: a dict that receives the fitted pca, kmeans, tap shape and layer."""
     from .cluster import PCA, KMeans
     hwc = model.intermediate_output(layer, cts[:1]).shape[1:]                                               # (H, W, C) of the tap
     data = model.feature_matrix(layer, cts)
@@ -117,6 +150,8 @@ def _cluster_eval(model, cts, x_valid, y_valid, layer, n_components, thr=0.547):
     new_data = pca.transform(data)
     print("Input data shape for Clustering:", tuple(new_data.shape))                                        # T1:1419
     kmeans = KMeans(n_clusters=2, random_state=0).fit(new_data)
+    if _fitted is not None:                                                                                 # (the routed step reuses them)
+        _fitted.update(pca=pca, kmeans=kmeans, hwc=hwc, layer=layer)
     u, cnt = np.unique(kmeans.labels_, return_counts=True)
     print("Label count for Kmeans on cts:", dict(zip(u.tolist(), cnt.tolist())))                            # T1:1424
     vdata = model.feature_matrix(layer, x_valid)
