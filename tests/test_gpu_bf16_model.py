@@ -11,8 +11,10 @@ Tolerances (measured values in brackets, tools/debug_bf16.py):
     that close to zero; a flipped element is a 100 % error of that gradient element, i.e. sqrt(0.002/0.5) = 6e-2 relative L2
     at the first masked tensor, growing upstream [6e-2 at c9b -> 0.17 at c3a].  This is a property of comparing ANY two bf16
     evaluations of a ReLU network (the fp32 test counts the same flips, there they are 0..8 elements), not a kernel error:
-    on the elements whose mask agrees the head gradient is checked to 1e-2, and each kernel is pinned to 4e-3 on identical
-    inputs in test_gpu_bf16_ops.py.  Bound here: 0.25 relative L2 and cosine >= 0.97 (a wiring error -- wrong slice, a missing
+    on the elements whose mask agrees the head gradient is checked to 1e-2, and each kernel is pinned on identical inputs at the
+    op level: the conv / ConvT / dense kernels to 4e-3 relative L2 in test_gpu_bf16_ops.py; the BatchNorm, pooling / dropout, head
+    and slice kernels per element (every stored value the nearest-even bf16 of the float64 result, keep masks exact) in
+    test_gpu_storage_ops.py.  Bound here: 0.25 relative L2 and cosine >= 0.97 (a wiring error -- wrong slice, a missing
     skip / pool contribution -- is an O(1) error).
 """
 import numpy as np
