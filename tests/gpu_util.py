@@ -67,6 +67,75 @@ def elem_ratio(got, want, a1, a2=None, floor=0.0):
     return float(r.max())
 
 
+# ---- bf16 rounding of float64 values and the per-element check of a stored output (bounds: the docstring of test_gpu_storage_ops.py) ---------------------
+U = 2.0 ** -24                                # the fp32 unit round-off
+
+
+def rne_bf16(a):
+    m, e = np.frexp(np.asarray(a, np.float64))
+    return np.ldexp(np.rint(m * 256.0), e - 8)                      # 8 significant bits, ties to even (np.rint)
+
+
+def trunc_bf16(a):
+    m, e = np.frexp(np.asarray(a, np.float64))
+    return np.ldexp(np.trunc(m * 256.0), e - 8)
+
+
+def check_store(got, ref, A, k, dt, what, tol=None):
+    """per-element check of an output stored in dtype dt; returns the largest error / bound ratio.  The allowance is k u A, or the array `tol` where the caller
+    derives it itself (the matrix-core ops: EPS_SPLIT * A1 + the epilogue's roundings)"""
+    got = np.asarray(got, np.float64); ref = np.asarray(ref, np.float64)
+    if tol is None:
+        tol = k * U * np.broadcast_to(np.asarray(A, np.float64), ref.shape)
+    else:
+        tol = np.broadcast_to(np.asarray(tol, np.float64), ref.shape); k = "tol"
+    err = np.abs(got - ref)
+    if dt == "fp32":
+        bad = err > tol
+        r = float(np.max(np.where(err == 0, 0.0, err / (tol + 1e-300)))) if err.size else 0.0
+        assert not bad.any(), f"{what}: {np.count_nonzero(bad)} / {bad.size} elements beyond {k} u A; worst ratio {r:.3g} at {np.unravel_index(np.argmax(err / (tol + 1e-300)), err.shape)}"
+    else:
+        lo, hi = rne_bf16(ref - tol), rne_bf16(ref + tol)
+        bad = (got < lo) | (got > hi)
+        assert not bad.any(), (f"{what}: {np.count_nonzero(bad)} / {bad.size} elements are not RNE_bf16 of the float64 reference; first at {np.argwhere(bad)[0]}: "
+                               f"got {got[bad][0]!r} ref {ref[bad][0]!r}")
+        tr = trunc_bf16(ref)
+        rounded = rne_bf16(ref) != ref                                   # (where the store has nothing to round, truncation is rounding)
+        caught = ((tr < lo) | (tr > hi))[rounded]
+        assert rounded.sum() == 0 or caught.mean() > 0.2, f"{what}: the check is too weak here: a truncating store would fail on only {caught.mean():.1%} of the rounded elements"
+        slack = got != rne_bf16(ref)                                     # the elements that needed the midpoint allowance: |ref - midpoint| / (k u A)
+        mid = 0.5 * (got[slack] + rne_bf16(ref[slack]))
+        r = float((np.abs(ref[slack] - mid) / tol[slack]).max()) if slack.any() else 0.0
+        print(f"bound-ratio {what} {dt} k={k} {r:.3g} (midpoint allowance used by {np.count_nonzero(slack)} of {slack.size})")
+        return r
+    print(f"bound-ratio {what} {dt} k={k} {r:.3g}")
+    return r
+
+
+def check_sum(got, ref, bound, what, dt=""):
+    got = np.asarray(got, np.float64); ref = np.asarray(ref, np.float64); bound = np.broadcast_to(np.asarray(bound, np.float64), ref.shape)
+    err = np.abs(got - ref)
+    r = float(np.max(np.where(err == 0, 0.0, err / (bound + 1e-300))))
+    print(f"bound-ratio {what} {dt} {r:.3g}")
+    assert (err <= bound).all(), f"{what}: worst error / bound {r:.3g} (channel {np.argmax(err / (bound + 1e-300))})"
+    return r
+
+
+def convT_abs_sums(x, k, dy):
+    """A1 arrays (float64 numpy) of convT2x2s2 forward (y_a1 = sum_c |x| |w|), data gradient (dx_a1 = sum_{ab,o} |dU| |w|), weight gradient (dw_a1 = sum_p |dU| |x|)
+    and bias gradient (db_a1 = sum |dU|): x [n,h,w,ci], k [2,2,co,ci], dy [n,2h,2w,co]"""
+    xa, ka, da = np.abs(np.asarray(x, np.float64)), np.abs(np.asarray(k, np.float64)), np.abs(np.asarray(dy, np.float64))
+    n, h, w, ci = xa.shape
+    co = ka.shape[2]
+    out = {"y_a1": np.zeros((n, 2 * h, 2 * w, co)), "dx_a1": np.zeros((n, h, w, ci)), "dw_a1": np.zeros((2, 2, co, ci)), "db_a1": da.sum((0, 1, 2))}
+    for a in range(2):
+        for b in range(2):
+            out["y_a1"][:, a::2, b::2] = xa @ ka[a, b].T
+            out["dx_a1"] += da[:, a::2, b::2] @ ka[a, b]
+            out["dw_a1"][a, b] = da[:, a::2, b::2].reshape(-1, co).T @ xa.reshape(-1, ci)
+    return out
+
+
 def conv_abs_sums(x, k, dy, with_floor=True):
     """A1 / A2 arrays (float64 numpy) of conv3x3 forward (y), data gradient (dx) and weight gradient (dw) for the bound above, from |x|, |k|, |dy|."""
     import torch

@@ -33,10 +33,10 @@ import torch
 import loss_family_oracle as LF
 import philox_ref as PX
 from covidseg_amd import _lib
+from gpu_util import U, check_store, check_sum, rne_bf16, trunc_bf16          # (the bf16 matrix-core op tests use the same checks)
 from oracle import unet_oracle as O
 
 pytestmark = pytest.mark.gpu
-U = 2.0 ** -24
 DTYPES = ["fp32", "bf16"]
 SENT = 7.0                                   # sentinel around an output slice (bf16-exact): must survive every launch unchanged
 BAD_IN = 30720.0                              # sentinel around an input slice: a kernel that reads it leaves every bound far behind
@@ -183,53 +183,6 @@ def unwindows(v):
     out = np.zeros((n, 2 * ho, 2 * wo, c), v.dtype)
     out[:, 0::2, 0::2], out[:, 0::2, 1::2], out[:, 1::2, 0::2], out[:, 1::2, 1::2] = v[0], v[1], v[2], v[3]
     return out
-
-
-# ---- bf16 rounding of float64 values and the per-element check ------------------------------------------------------------------------------
-def rne_bf16(a):
-    m, e = np.frexp(np.asarray(a, np.float64))
-    return np.ldexp(np.rint(m * 256.0), e - 8)                      # 8 significant bits, ties to even (np.rint)
-
-
-def trunc_bf16(a):
-    m, e = np.frexp(np.asarray(a, np.float64))
-    return np.ldexp(np.trunc(m * 256.0), e - 8)
-
-
-def check_store(got, ref, A, k, dt, what):
-    """per-element check of an output stored in dtype dt (module docstring); returns the largest error / bound ratio"""
-    got = np.asarray(got, np.float64); ref = np.asarray(ref, np.float64)
-    tol = k * U * np.broadcast_to(np.asarray(A, np.float64), ref.shape)
-    err = np.abs(got - ref)
-    if dt == "fp32":
-        bad = err > tol
-        r = float(np.max(np.where(err == 0, 0.0, err / (tol + 1e-300)))) if err.size else 0.0
-        assert not bad.any(), f"{what}: {np.count_nonzero(bad)} / {bad.size} elements beyond {k} u A; worst ratio {r:.3g} at {np.unravel_index(np.argmax(err / (tol + 1e-300)), err.shape)}"
-    else:
-        lo, hi = rne_bf16(ref - tol), rne_bf16(ref + tol)
-        bad = (got < lo) | (got > hi)
-        assert not bad.any(), (f"{what}: {np.count_nonzero(bad)} / {bad.size} elements are not RNE_bf16 of the float64 reference; first at {np.argwhere(bad)[0]}: "
-                               f"got {got[bad][0]!r} ref {ref[bad][0]!r}")
-        tr = trunc_bf16(ref)
-        rounded = rne_bf16(ref) != ref                                   # (where the store has nothing to round, truncation is rounding)
-        caught = ((tr < lo) | (tr > hi))[rounded]
-        assert rounded.sum() == 0 or caught.mean() > 0.2, f"{what}: the check is too weak here: a truncating store would fail on only {caught.mean():.1%} of the rounded elements"
-        slack = got != rne_bf16(ref)                                     # the elements that needed the midpoint allowance: |ref - midpoint| / (k u A)
-        mid = 0.5 * (got[slack] + rne_bf16(ref[slack]))
-        r = float((np.abs(ref[slack] - mid) / tol[slack]).max()) if slack.any() else 0.0
-        print(f"bound-ratio {what} {dt} k={k} {r:.3g} (midpoint allowance used by {np.count_nonzero(slack)} of {slack.size})")
-        return r
-    print(f"bound-ratio {what} {dt} k={k} {r:.3g}")
-    return r
-
-
-def check_sum(got, ref, bound, what, dt=""):
-    got = np.asarray(got, np.float64); ref = np.asarray(ref, np.float64); bound = np.broadcast_to(np.asarray(bound, np.float64), ref.shape)
-    err = np.abs(got - ref)
-    r = float(np.max(np.where(err == 0, 0.0, err / (bound + 1e-300))))
-    print(f"bound-ratio {what} {dt} {r:.3g}")
-    assert (err <= bound).all(), f"{what}: worst error / bound {r:.3g} (channel {np.argmax(err / (bound + 1e-300))})"
-    return r
 
 
 # ---- BatchNorm -------------------------------------------------------------------------------------------------------------------------------
