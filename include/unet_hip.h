@@ -557,6 +557,36 @@ int32_t unet_pre_resize_u8(unet_ctx*, const uint8_t* src, int32_t n, int32_t sh,
 int32_t unet_pre_contours_u8(unet_ctx*, const uint8_t* host_imgs, int32_t n, int32_t h, int32_t w, int32_t max_contours, double* areas, int32_t* rects,
                              int32_t* counts, int32_t threads);
 
+/* ---- a CT volume on the device: raw NIfTI voxels -> slice batch -> mask volume (csrc/kernels_volume.hip; bit-exact against tests/volume_oracle.py) ----
+ * Replaces the first half of read_nii / read_nii_demo (T1:285-297, 317-337; the same text T3:284-300): `ct_scan.get_fdata()` (float64; `scaled` != 0:
+ * (float64(v) * slope) + inter, two rounded operations -- the caller applies nibabel's rules for a zero / non-finite slope and a non-finite inter),
+ * `np.rot90`, `array[:, :, z0:z1]`, `cv2.resize(slice, (S, S), INTER_AREA)` on the FLOAT64 slice (OpenCV resize.cpp, 64-bit float path, restated: parity
+ * unpinned) and the per-slice min-max.  vox: the whole volume on the device, Fortran order [X, Y, Z], `dtype` a NIfTI-1 datatype code
+ * (2 uint8, 256 int8, 4 int16, 512 uint16, 8 int32, 768 uint32, 16 float32, 64 float64), native byte order.  Outputs for the n = z1 - z0 kept slices, each
+ * optional (null = not wanted), dense [n][S][S]:
+ *   img_f32  float32((img - min)/(max - min)), the division in float64 as numpy does           T1:296, 337
+ *   img_u8   np.uint8(img * 255) of that float64 image (truncation; NaN -> 0)                   T1:165, 363
+ *   lung_u8  img[img > 0] = 1 -> np.uint8(img * 255)                                            T1:341 + 213
+ *   uniform  int32 [n]: 1 where np.unique(slice).size == 1 on the slice BEFORE the resize       T1:333
+ *   minmax   double [n][2]: the resized image's min and max
+ * A slice whose resized image has max == min gives what numpy gives: NaN in img_f32, 0 in both uint8 forms.
+ * ws: unet_vol_slices_ws_bytes(n, S) bytes, 16-byte aligned; it starts with the resized float64 images [n][S][S] (tests read this stage). */
+size_t unet_vol_slices_ws_bytes(int32_t n, int32_t S);
+int32_t unet_vol_slices_f64(unet_ctx*, const void* vox, int32_t dtype, int32_t X, int32_t Y, int32_t Z, int32_t scaled, double slope, double inter, int32_t z0,
+                            int32_t z1, int32_t S, float* img_f32, uint8_t* img_u8, uint8_t* lung_u8, int32_t* uniform, double* minmax, void* ws, size_t ws_bytes,
+                            void* stream);
+/* The inverse of crop -> INTER_AREA resize to 125 x 250 -> fuse -> INTER_LINEAR resize to d x d (T1:352-358, 486): prob [n][d][d] (the model's output) -> canvas
+ * [n][S][S].  rects: HOST array [n][2][4] = (x, y, w, h) of the two lung rectangles per slice (w <= 0 or h <= 0: absent), or NULL.  A canvas pixel (r, c) inside
+ * rectangle k takes the bilinear sample (half-pixel centres, clamped to the edge, coordinates in float64, blend in float32 as top = p00 + (p01 - p00) fx, bot likewise,
+ * value = top + (bot - top) fy, every operation rounded on its own) of prob at u' = (u + 0.5) d / 250 - 0.5, v' = (v + 0.5) d / 250 - 0.5 with u = (c - x + 0.5) 125 / w - 0.5 + 125 k,
+ * v = (r - y + 0.5) 250 / h - 0.5; both rectangles: the larger value; neither: 0.  A slice without rectangles (it fell through uncropped, T1:347) is sampled
+ * over the whole canvas: u' = (c + 0.5) d / S - 0.5. */
+int32_t unet_vol_paste_back(unet_ctx*, const float* prob, int32_t n, int32_t d, const int32_t* rects, float* canvas, int32_t S, void* stream);
+/* canvas [z1 - z0][S][S] -> patient space: resampled to [Y, X] with the same sampler, np.rot90 undone, mask[x + X (y + Y z)] = p > threshold (uint8, Fortran
+ * order [X, Y, Z]; the slices outside [z0, z1) are set to 0) and counts[z - z0] = set voxels of slice z (int64 [z1 - z0]; integer sums: exact, the same on every run). */
+int32_t unet_vol_unslice(unet_ctx*, const float* canvas, int32_t S, float threshold, int32_t X, int32_t Y, int32_t Z, int32_t z0, int32_t z1, uint8_t* mask,
+                         int64_t* counts, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Model level.  Replaces the Keras Model built at T1:853-916 and driven by
  * compile/fit/evaluate/predict (T1:1053-1061, 1101, 1137).  A model is a fixed-shape plan:

@@ -171,6 +171,11 @@ _PROTOS = {
     "unet_pre_clahe_u8": (i32, [vp, vp, vp, i32, i32, i32, f32, i32, i32, vp, sz, vp]),
     "unet_pre_resize_u8": (i32, [vp, vp, i32, i32, i32, vp, vp, i32, i32, i32, i32, i32, vp]),
     "unet_pre_contours_u8": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp, i32]),        # host buffers (ABI v7)
+    # a CT volume on the device: raw voxels -> slice batch -> mask volume (kernels_volume.hip, volume.py)
+    "unet_vol_slices_ws_bytes": (sz, [i32, i32]),
+    "unet_vol_slices_f64": (i32, [vp, vp, i32, i32, i32, i32, i32, f64, f64, i32, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "unet_vol_paste_back": (i32, [vp, vp, i32, i32, vp, vp, i32, vp]),
+    "unet_vol_unslice": (i32, [vp, vp, i32, f32, i32, i32, i32, i32, i32, vp, vp, vp]),
     "unet_model_create": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(vp)]),
     "unet_model_dtype": (i32, [vp]),
     "unet_model_tap_elem_bytes": (i32, [vp, C.c_char_p, i32]),

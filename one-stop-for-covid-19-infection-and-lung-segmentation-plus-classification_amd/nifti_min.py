@@ -1,0 +1,179 @@
+"""A minimal NIfTI-1 reader and writer: what `nib.load(path)` + `get_fdata()` need for the CT scans and masks of the reference (T1:285-286,
+317-318), written against the published NIfTI-1 specification (nifti1.h) with the standard library and numpy only -- nibabel is not installed
+here, so like hdf5_min.py this restates documented semantics ("parity unpinned": tests/test_nifti_min.py builds its files with struct.pack at
+the specification's byte offsets, independently of this writer; the day nibabel is at hand the same files pin it).
+
+Read:  single-file NIfTI-1 (`.nii`, magic `n+1\\0`), or `.nii.gz` through gzip; both byte orders (found from sizeof_hdr == 348); vox_offset honoured;
+       uint8, int8, int16, uint16, int32, uint32, float32, float64; 3-D data, or more dimensions when every trailing one is 1; Fortran order
+       (dim[1] fastest).
+Write: a uint8 or float32 volume with the geometry of a source header (dim, pixdim, qform / sform, xyzt_units), scl_slope = 1, scl_inter = 0.
+Everything else is refused with a NiftiFormatError that names the case.
+"""
+from __future__ import annotations
+
+import gzip
+import struct
+
+import numpy as np
+
+HEADER_BYTES = 348
+# NIfTI-1 datatype code -> numpy type (without byte order)
+DTYPES = {2: "u1", 256: "i1", 4: "i2", 512: "u2", 8: "i4", 768: "u4", 16: "f4", 64: "f8"}
+_REFUSED_TYPES = {1: "binary (1 bit)", 32: "complex64", 1792: "complex128", 2048: "complex256", 128: "RGB24", 2304: "RGBA32", 1536: "float128", 1024: "int64",
+                  1280: "uint64", 0: "unknown (0)"}
+_CODE_OF = {np.dtype(v).newbyteorder("=").str[1:]: k for k, v in DTYPES.items()}
+
+
+class NiftiFormatError(ValueError):
+    pass
+
+
+class NiftiVolume:
+    """What a read returns: `raw` (the voxels as stored, numpy [X, Y, Z] in Fortran order, native byte order), `slope` / `inter` (scl_slope, scl_inter as
+    stored), `pixdim` (pixdim[1:4]), `header` (the 348 header bytes, for a mask written with the same geometry), `byteorder` ('<' or '>')."""
+
+    def __init__(self, raw, slope, inter, pixdim, header, byteorder):
+        self.raw, self.slope, self.inter, self.pixdim, self.header, self.byteorder = raw, slope, inter, pixdim, header, byteorder
+
+    @property
+    def shape(self):
+        return self.raw.shape
+
+    @property
+    def scaling(self):
+        return scaling(self.slope, self.inter)
+
+    def get_fdata(self):
+        return apply_scaling(self.raw, self.slope, self.inter)
+
+    def __iter__(self):                                        # raw, (slope, inter), pixdim, header = read(path)
+        return iter((self.raw, (self.slope, self.inter), self.pixdim, self.header))
+
+
+def scaling(slope, inter):
+    """nibabel's reading of (scl_slope, scl_inter): None when the data are not scaled (slope 0 or not finite), else (slope, inter) as float64 with a
+    non-finite inter counted as 0."""
+    slope, inter = float(slope), float(inter)
+    if slope == 0.0 or not np.isfinite(slope):
+        return None
+    return slope, (inter if np.isfinite(inter) else 0.0)
+
+
+def apply_scaling(raw, slope, inter):
+    """get_fdata(): float64; (float64(v) * slope) + inter -- two rounded operations -- when the header scales, else the cast alone."""
+    a = np.asarray(raw).astype(np.float64)
+    sc = scaling(slope, inter)
+    if sc is None:
+        return a
+    a *= sc[0]
+    a += sc[1]
+    return a
+
+
+def _read_all(path):
+    path = str(path)
+    if path.endswith(".hdr") or path.endswith(".img"):
+        raise NiftiFormatError(f"{path}: a .hdr / .img pair is not supported (single-file .nii / .nii.gz only)")
+    with open(path, "rb") as f:
+        head = f.read(2)
+        f.seek(0)
+        if head == b"\x1f\x8b":
+            with gzip.GzipFile(fileobj=f) as g:
+                return g.read()
+        return f.read()
+
+
+def parse_header(buf):
+    """(byteorder, fields) of the 348 header bytes; raises NiftiFormatError for what this reader refuses."""
+    if len(buf) < 4:
+        raise NiftiFormatError("file too short for a NIfTI header")
+    (le,), (be,) = struct.unpack("<i", buf[:4]), struct.unpack(">i", buf[:4])
+    if le == 540 or be == 540:
+        raise NiftiFormatError("NIfTI-2 file (sizeof_hdr == 540) is not supported")
+    if le == HEADER_BYTES:
+        bo = "<"
+    elif be == HEADER_BYTES:
+        bo = ">"
+    else:
+        raise NiftiFormatError(f"not a NIfTI-1 file: sizeof_hdr is {le}, not 348, in either byte order")
+    if len(buf) < HEADER_BYTES:
+        raise NiftiFormatError("file too short for a NIfTI header: fewer than 348 bytes")
+    magic = bytes(buf[344:348])
+    if magic == b"ni1\x00":
+        raise NiftiFormatError("NIfTI-1 .hdr / .img pair (magic 'ni1') is not supported (single-file 'n+1' only)")
+    if magic != b"n+1\x00":
+        raise NiftiFormatError(f"not a single-file NIfTI-1 file: magic {magic!r}")
+    dim = struct.unpack(bo + "8h", buf[40:56])
+    datatype, bitpix = struct.unpack(bo + "2h", buf[70:74])
+    pixdim = struct.unpack(bo + "8f", buf[76:108])
+    vox_offset, slope, inter = struct.unpack(bo + "3f", buf[108:120])
+    return bo, {"dim": dim, "datatype": datatype, "bitpix": bitpix, "pixdim": pixdim, "vox_offset": vox_offset, "scl_slope": slope, "scl_inter": inter,
+                "xyzt_units": buf[123]}
+
+
+def read(path):
+    """-> NiftiVolume (unpacks as raw, (slope, inter), pixdim[1:4], header bytes)."""
+    buf = _read_all(path)
+    bo, h = parse_header(buf)
+    code = h["datatype"]
+    if code not in DTYPES:
+        raise NiftiFormatError(f"datatype {code} ({_REFUSED_TYPES.get(code, 'not a NIfTI-1 code')}) is not supported: only uint8, int8, int16, uint16, int32, uint32, "
+                               "float32, float64")
+    dim = h["dim"]
+    nd = dim[0]
+    if not 3 <= nd <= 7:
+        raise NiftiFormatError(f"dim[0] = {nd}: only 3-D data (or more dimensions with every trailing one equal to 1)")
+    if any(d != 1 for d in dim[4:nd + 1]):
+        raise NiftiFormatError(f"truly {nd}-D data (dim = {list(dim[1:nd + 1])}): only volumes whose dimensions past the third are 1")
+    shape = tuple(int(d) for d in dim[1:4])
+    if any(d < 1 for d in shape):
+        raise NiftiFormatError(f"dim = {list(dim[1:4])}: every dimension must be positive")
+    dt = np.dtype(DTYPES[code]).newbyteorder(bo)
+    nvox = shape[0] * shape[1] * shape[2]
+    off = int(h["vox_offset"])
+    if off < HEADER_BYTES + 4:
+        off = HEADER_BYTES + 4                                  # (a single file's data cannot start before byte 352)
+    if len(buf) < off + nvox * dt.itemsize:
+        raise NiftiFormatError(f"file too short: {len(buf)} bytes, but vox_offset {off} + {nvox} voxels x {dt.itemsize} bytes = {off + nvox * dt.itemsize}")
+    raw = np.frombuffer(buf, dt, nvox, off).reshape(shape, order="F")
+    raw = raw.astype(dt.newbyteorder("="), order="F")           # native byte order, own memory (Fortran order kept)
+    return NiftiVolume(raw, float(np.float32(h["scl_slope"])), float(np.float32(h["scl_inter"])), tuple(float(p) for p in h["pixdim"][1:4]), bytes(buf[:HEADER_BYTES]), bo)
+
+
+def default_header(shape, pixdim=(1.0, 1.0, 1.0)):
+    """The 348 bytes of a little-endian NIfTI-1 header for a bare [X, Y, Z] volume (no qform / sform), for volumes that did not come from a file."""
+    h = bytearray(HEADER_BYTES)
+    struct.pack_into("<i", h, 0, HEADER_BYTES)
+    struct.pack_into("<8h", h, 40, 3, int(shape[0]), int(shape[1]), int(shape[2]), 1, 1, 1, 1)
+    struct.pack_into("<8f", h, 76, 1.0, float(pixdim[0]), float(pixdim[1]), float(pixdim[2]), 0.0, 0.0, 0.0, 0.0)
+    h[123] = 2                                                   # NIFTI_UNITS_MM
+    h[344:348] = b"n+1\x00"
+    return bytes(h)
+
+
+def write(path, volume, header=None, pixdim=(1.0, 1.0, 1.0)):
+    """Write a uint8 or float32 [X, Y, Z] volume as `.nii`, or gzip-compressed when the path ends in `.gz`.  `header`: the 348 bytes of the source
+    (NiftiVolume.header) -- its dim, pixdim, qform / sform fields, xyzt_units and byte order are kept byte for byte; datatype, bitpix, vox_offset = 352,
+    scl_slope = 1, scl_inter = 0 and the calibration range are set for the new data."""
+    vol = np.asarray(volume)
+    if vol.ndim != 3 or vol.dtype not in (np.dtype(np.uint8), np.dtype(np.float32)):
+        raise NiftiFormatError(f"write: a 3-D uint8 or float32 volume is expected, not {vol.dtype} with {vol.ndim} dimensions")
+    if header is None:
+        header = default_header(vol.shape, pixdim)
+    bo, h = parse_header(header)
+    if tuple(h["dim"][1:4]) != tuple(vol.shape):
+        raise NiftiFormatError(f"write: the volume is {tuple(vol.shape)} but the source header says {tuple(h['dim'][1:4])}")
+    out = bytearray(header[:HEADER_BYTES])
+    code = _CODE_OF[vol.dtype.str[1:]]
+    struct.pack_into(bo + "2h", out, 70, code, vol.dtype.itemsize * 8)
+    struct.pack_into(bo + "3f", out, 108, 352.0, 1.0, 0.0)
+    struct.pack_into(bo + "2f", out, 124, 0.0, 0.0)              # cal_max, cal_min: no display range
+    out[344:348] = b"n+1\x00"
+    data = np.asarray(vol, vol.dtype.newbyteorder(bo)).tobytes(order="F")
+    blob = bytes(out) + b"\x00\x00\x00\x00" + data                # (four extension bytes: no extensions)
+    if str(path).endswith(".gz"):
+        with open(path, "wb") as f, gzip.GzipFile(fileobj=f, mode="wb", compresslevel=1, mtime=0, filename="") as g:
+            g.write(blob)
+    else:
+        with open(path, "wb") as f:
+            f.write(blob)

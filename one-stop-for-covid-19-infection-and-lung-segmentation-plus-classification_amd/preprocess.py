@@ -57,20 +57,26 @@ def min_max_to_u8(img):
 
 def clahe_u8(img_u8, clip_limit=3.0, tile_grid_size=(8, 8)):
     """cv2.createCLAHE(clipLimit, tileGridSize).apply(img) for uint8 slice(s)."""
-    torch = _torch(); lib, ctx = _ctx()
+    torch = _torch()
     if isinstance(img_u8, torch.Tensor):                          # already on the device (clahe_enhancer): [n, h, w] uint8
         x, single = img_u8, False
     else:
         a, single = _as_batch(img_u8)
         x = torch.from_numpy(np.ascontiguousarray(a, np.uint8)).cuda()
+    r = _clahe_device(x, clip_limit, tile_grid_size).cpu().numpy()
+    return r[0] if single else r
+
+
+def _clahe_device(x, clip_limit=3.0, tile_grid_size=(8, 8)):
+    """clahe_u8 on a contiguous uint8 device tensor [n, h, w]; the result stays on the device (volume.py chains it with the crops)."""
+    torch = _torch(); lib, ctx = _ctx()
     n, h, w = x.shape
     tx, ty = int(tile_grid_size[0]), int(tile_grid_size[1])
     out = torch.empty_like(x)
     ws = torch.empty(max(lib.unet_pre_clahe_ws_bytes(n, tx, ty), 16), dtype=torch.uint8, device="cuda")
     ctx.check(lib.unet_pre_clahe_u8(ctx.handle, x.data_ptr(), out.data_ptr(), n, h, w, float(clip_limit), tx, ty, ws.data_ptr(), ws.numel(),
                                     torch.cuda.current_stream().cuda_stream), "pre_clahe_u8")
-    r = out.cpu().numpy()
-    return r[0] if single else r
+    return out
 
 
 def clahe_enhancer(test_img, demo=0):

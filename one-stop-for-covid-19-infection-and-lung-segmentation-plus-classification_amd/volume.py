@@ -1,0 +1,354 @@
+"""A CT scan in, a mask volume out: the first half of the reference's read_nii / read_nii_demo (T1:281-297, 310-337; the same text in T3:284-300),
+the dataset loop around it (T1:390-393, 421-429) and the way back from a predicted 224 x 224 map of the two fused lung crops to the patient's volume.
+
+    load_volume(path_or_array, kind)      kind = "demo" | "lungs" | "cts" | "infections": the four uses of read_nii / read_nii_demo
+    build_dataset(rows)                   rows of (ct, lung_mask, infection_mask) -> cts, infections for the runners' data= argument
+    segment_volume(ct, model, ...)        -> VolumeSegmentation: mask volume in the CT's geometry, infected volume in ml, optional .nii(.gz) file
+
+The voxels are uploaded once as stored (nifti_min reads the file); decode, np.rot90, the slice trim, cv2.resize(float64, INTER_AREA) and the min-max run
+in unet_vol_slices_f64, CLAHE / crop / fuse / resize in the uint8 kernels of preprocess.py on device pointers: between the upload and the returned batch
+only the lung rectangles live on the host.  Like the rest of the product there is no CPU fallback.
+
+Two ways to pair a CT slice with its lung rectangles (`box_indexing`):
+  "reference"  T1:347-353 as written: the rectangle list was shortened by every skipped (uniform) lung slice but is indexed by raw slice number, so every
+               slice after a skipped one takes its neighbour's boxes and the last slices find none and fall through uncropped
+  "slice"      rectangles keyed by slice number; only the slices whose lung mask was uniform fall through
+A slice that falls through is not cropped: here its whole frame goes through the same uint8 resize to new_dim (no CLAHE: T1:348 sits inside the `if`).
+The reference instead carries the float [0, 1] frame to T1:520's np.uint8 cast, which leaves a near-black image; such slices are listed in the
+returned info so that a caller can drop them.
+"""
+from __future__ import annotations
+
+import os
+import time
+import warnings
+
+import numpy as np
+
+from . import _lib, nifti_min
+from . import preprocess as PRE
+
+KINDS = ("demo", "lungs", "cts", "infections")
+BOX_INDEXING = ("reference", "slice")
+
+
+def _torch():
+    import torch
+    return torch
+
+
+def trim_range(n_slices, trim=(0.2, 0.8)):
+    """array[:, :, round(slices*0.2):round(slices*0.8)] (T1:288-289): Python's round of the float product."""
+    z0, z1 = round(n_slices * trim[0]), round(n_slices * trim[1])
+    if not 0 <= z0 < z1 <= n_slices:
+        raise ValueError(f"trim {trim} keeps no slice of {n_slices}")
+    return z0, z1
+
+
+def box_plan(n_slices, kept, box_indexing="reference"):
+    """For kept-range slices 0..n_slices-1: the index into the rectangle list each one uses, or -1 where it falls through.  `kept`: the slice numbers
+    the rectangle list was built from (the non-uniform lung slices, in order)."""
+    if box_indexing not in BOX_INDEXING:
+        raise ValueError(f"box_indexing must be one of {BOX_INDEXING}, not {box_indexing!r}")
+    kept = [int(k) for k in kept]
+    plan = np.full(n_slices, -1, np.int64)
+    if box_indexing == "reference":                                 # T1:347 `img_no < len(all_points1)`, T1:352 `all_points1[img_no]`
+        m = min(n_slices, len(kept))
+        plan[:m] = np.arange(m)
+    else:
+        for k, s in enumerate(kept):
+            if 0 <= s < n_slices:
+                plan[s] = k
+    return plan
+
+
+def whole_frame_rects(n, size):
+    """The boxes used when there is no lung mask: the left and the right half of the frame."""
+    half = size // 2
+    r1 = np.tile(np.array([0, 0, half, size], np.int32), (n, 1))
+    r2 = np.tile(np.array([half, 0, size - half, size], np.int32), (n, 1))
+    return r1, r2
+
+
+def drop_constant(cts, infections):
+    """T1:421-429: the slices whose infection mask holds a single value are deleted from both lists.  -> (cts, infections, dropped indices)"""
+    keep, dropped = [], []
+    for i in range(len(infections)):
+        (dropped if np.unique(np.asarray(infections[i])).size == 1 else keep).append(i)
+    return [cts[i] for i in keep], [infections[i] for i in keep], dropped
+
+
+def _source(path_or_array):
+    """-> nifti_min.NiftiVolume for a path, a NiftiVolume, or a bare [X, Y, Z] array (taken as get_fdata's result: not scaled, 1 mm voxels)."""
+    if isinstance(path_or_array, nifti_min.NiftiVolume):
+        return path_or_array
+    if isinstance(path_or_array, (str, os.PathLike)):
+        return nifti_min.read(path_or_array)
+    a = np.asarray(path_or_array)
+    if a.ndim != 3:
+        raise ValueError(f"a volume is [X, Y, Z]; got {a.ndim} dimensions")
+    if a.dtype.str[1:] not in ("u1", "i1", "i2", "u2", "i4", "u4", "f4", "f8"):
+        a = a.astype(np.float64)
+    a = np.asfortranarray(a.astype(a.dtype.newbyteorder("="), copy=False))
+    return nifti_min.NiftiVolume(a, 0.0, 0.0, (1.0, 1.0, 1.0), nifti_min.default_header(a.shape), "<")
+
+
+def _ctx():
+    torch = _torch()
+    if not torch.cuda.is_available():
+        raise _lib.UNetHipError("volume: no GPU visible to torch; the kernels have no CPU fallback")
+    return _lib.load(), _lib.Context.get(torch.cuda.current_device())
+
+
+def _stream():
+    return _torch().cuda.current_stream().cuda_stream
+
+
+def upload(vol):
+    """The raw voxels of a NiftiVolume as one device byte buffer in Fortran order."""
+    torch = _torch()
+    raw = np.asfortranarray(vol.raw)
+    flat = raw.reshape(-1, order="F").view(np.uint8)
+    return torch.from_numpy(flat).cuda()
+
+
+def slices_f64(vol, dev, z0, z1, size, want=("f32",)):
+    """unet_vol_slices_f64 on an uploaded volume: dict of device tensors for the wanted outputs ("f32", "u8", "lung") + "uniform" [n] int32 and "minmax" [n, 2]."""
+    torch = _torch(); lib, ctx = _ctx()
+    X, Y, Z = vol.raw.shape
+    n = z1 - z0
+    code = {v: k for k, v in nifti_min.DTYPES.items()}[vol.raw.dtype.str[1:]]
+    sc = vol.scaling
+    out = {"uniform": torch.empty(n, dtype=torch.int32, device="cuda"), "minmax": torch.empty((n, 2), dtype=torch.float64, device="cuda")}
+    if "f32" in want:
+        out["f32"] = torch.empty((n, size, size), dtype=torch.float32, device="cuda")
+    if "u8" in want:
+        out["u8"] = torch.empty((n, size, size), dtype=torch.uint8, device="cuda")
+    if "lung" in want:
+        out["lung"] = torch.empty((n, size, size), dtype=torch.uint8, device="cuda")
+    ws = torch.empty(max(lib.unet_vol_slices_ws_bytes(n, size), 16), dtype=torch.uint8, device="cuda")
+    ptr = lambda k: out[k].data_ptr() if k in out else None
+    ctx.check(lib.unet_vol_slices_f64(ctx.handle, dev.data_ptr(), code, X, Y, Z, 1 if sc else 0, sc[0] if sc else 1.0, sc[1] if sc else 0.0, z0, z1, size,
+                                      ptr("f32"), ptr("u8"), ptr("lung"), out["uniform"].data_ptr(), out["minmax"].data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+              "vol_slices_f64")
+    out["_ws"] = ws                                                 # (the float64 stage, for the tests; freed with the dict)
+    return out
+
+
+def _flat_slices(mm):
+    """slice indices whose resized image has max == min (numpy's 0/0: NaN image, 0 in uint8) -- reported, not repaired"""
+    return [int(i) for i in np.nonzero(mm[:, 0] == mm[:, 1])[0]]
+
+
+def _resize_dev(x, rects, out, x0, dw, interp):
+    lib, ctx = _ctx()
+    PRE._resize_into(lib, ctx, x, rects, out, x0, dw, interp)
+
+
+def _chain_u8(u8, boxed_u8, rects1, rects2, plan, new_dim):
+    """crop + INTER_AREA to 125 x 250 + fuse for the slices with boxes (from boxed_u8), the whole frame of u8 for those that fall through, INTER_LINEAR to
+    new_dim, / 255: [n, new_dim, new_dim, 1] float32 on the device (+ per-slice "the uint8 image before the last resize holds one value")."""
+    torch = _torch(); lib, ctx = _ctx()
+    n = u8.shape[0]
+    boxed = np.nonzero(plan >= 0)[0]; fell = np.nonzero(plan < 0)[0]
+    if new_dim is None and len(fell) and len(boxed):
+        raise ValueError("new_dim=None: slices that fall through stay at the frame size and cannot share an array with the 250 x 250 fused ones; pass new_dim")
+    constant = torch.zeros(n, dtype=torch.bool, device="cuda")
+    side = int(new_dim) if new_dim is not None else (250 if len(boxed) else u8.shape[1])
+    out_u8 = torch.empty((n, side, side), dtype=torch.uint8, device="cuda")
+    if len(boxed):
+        idx = torch.from_numpy(boxed).cuda()
+        x = boxed_u8 if len(boxed) == n else boxed_u8.index_select(0, idx).contiguous()
+        r1 = np.asarray(rects1, np.int32).reshape(-1, 4)[plan[boxed]]; r2 = np.asarray(rects2, np.int32).reshape(-1, 4)[plan[boxed]]
+        fused = torch.empty((len(boxed), 250, 250), dtype=torch.uint8, device="cuda")
+        _resize_dev(x, r1, fused, 0, 125, PRE.INTER_AREA)
+        _resize_dev(x, r2, fused, 125, 125, PRE.INTER_AREA)
+        constant[idx] = fused.flatten(1).amax(1) == fused.flatten(1).amin(1)
+        if new_dim is None:
+            res = fused
+        else:
+            res = torch.empty((len(boxed), side, side), dtype=torch.uint8, device="cuda")
+            _resize_dev(fused, None, res, 0, side, PRE.INTER_LINEAR)
+        if len(boxed) == n:
+            out_u8 = res
+        else:
+            out_u8[idx] = res
+    if len(fell):
+        idx = torch.from_numpy(fell).cuda()
+        x = u8 if len(fell) == n else u8.index_select(0, idx).contiguous()
+        constant[idx] = x.flatten(1).amax(1) == x.flatten(1).amin(1)
+        if new_dim is None:
+            res = x
+        else:
+            res = torch.empty((len(fell), side, side), dtype=torch.uint8, device="cuda")
+            _resize_dev(x, None, res, 0, side, PRE.INTER_LINEAR)
+        if len(fell) == n:
+            out_u8 = res
+        else:
+            out_u8[idx] = res
+    out = torch.empty(out_u8.shape, dtype=torch.float32, device="cuda")
+    ctx.check(lib.unet_pre_u8_to_unit(ctx.handle, out_u8.data_ptr(), out.data_ptr(), out_u8.numel(), _stream()), "pre_u8_to_unit")
+    return out[..., None], constant
+
+
+def load_volume(path_or_array, kind, img_size=512, trim=(0.2, 0.8), rects=None, box_indexing="reference", new_dim=None, return_info=False):
+    """read_nii_demo(filepath, data) / read_nii(filepath, data, string) for one file (T1:281-297, 310-376); everything stays on the device.
+
+    kind "demo"        -> float32 [n, img_size, img_size] tensor: the min-max normalised slices
+         "lungs"       -> (rects1, rects2, kept_slice_numbers): `all_points1`, `all_points2` (int32 [k, 4] (x, y, w, h)) of the non-uniform slices (T1:333, 339-345);
+                          the contour search is the library's host code (unet_pre_contours_u8), so the uint8 lung images make the one trip to the host
+         "cts"         -> float32 [n, d, d, 1] tensor: min-max -> CLAHE -> crop / fuse with `rects` -> INTER_LINEAR to new_dim -> / 255
+         "infections"  -> the same chain without CLAHE
+    rects: what a "lungs" call returned (None: no cropping at all, every slice's whole frame).  Slice numbers count from the first kept slice.
+    return_info=True adds a dict: z0, z1, shape, pixdim, fell_through, flat (slices with max == min: NaN / 0, as numpy gives), constant (cts / infections:
+    slices whose uint8 image before the last resize holds a single value -- the T1:423 test), seconds (decode / upload / device)."""
+    if kind not in KINDS:
+        raise ValueError(f"kind must be one of {KINDS}, not {kind!r}")
+    torch = _torch()
+    t0 = time.perf_counter()
+    vol = _source(path_or_array)
+    t1 = time.perf_counter()
+    X, Y, Z = vol.raw.shape
+    z0, z1 = trim_range(Z, trim)
+    n = z1 - z0
+    S = int(img_size)
+    dev = upload(vol)
+    info = {"z0": z0, "z1": z1, "shape": (X, Y, Z), "pixdim": vol.pixdim, "header": vol.header, "fell_through": [], "flat": [], "constant": []}
+    info["seconds"] = {"decode": t1 - t0}
+    want = {"demo": ("f32",), "lungs": ("lung",), "cts": ("u8",), "infections": ("u8",)}[kind]
+    st = slices_f64(vol, dev, z0, z1, S, want)
+    if kind == "demo":
+        result = st["f32"]
+        info["flat"] = _flat_slices(st["minmax"].cpu().numpy())
+    elif kind == "lungs":
+        uniform = st["uniform"].cpu().numpy()
+        kept = [int(i) for i in np.nonzero(uniform == 0)[0]]
+        if kept:
+            lung = (st["lung"] if len(kept) == n else st["lung"][torch.from_numpy(np.asarray(kept)).cuda()]).cpu().numpy()
+            r1, r2 = PRE.lung_rects(lung)
+        else:
+            r1, r2 = np.zeros((0, 4), np.int32), np.zeros((0, 4), np.int32)
+        info["uniform"] = [int(i) for i in np.nonzero(uniform)[0]]
+        result = (r1, r2, kept)
+    else:
+        if rects is None:
+            plan = np.full(n, -1, np.int64); r1 = r2 = None
+        else:
+            r1, r2, kept = rects
+            plan = box_plan(n, kept, box_indexing)
+        u8 = st["u8"]
+        boxed_u8 = PRE._clahe_device(u8, 3.0, (8, 8)) if (kind == "cts" and (plan >= 0).any()) else u8
+        result, constant = _chain_u8(u8, boxed_u8, r1, r2, plan, new_dim)
+        mm = st["minmax"].cpu().numpy()                             # (16 bytes per slice: the report, not image data)
+        info["flat"] = _flat_slices(mm)
+        info["fell_through"] = [int(i) for i in np.nonzero(plan < 0)[0]] if rects is not None else []
+        info["constant"] = [int(i) for i in np.nonzero(constant.cpu().numpy())[0]]
+    if info["flat"]:
+        warnings.warn(f"load_volume({kind!r}): slices {info['flat']} (of the kept range) are constant after the resize: (img - min)/(max - min) is 0/0 there "
+                      "(NaN in the float image, 0 in uint8, as numpy gives)", RuntimeWarning, stacklevel=2)
+    return (result, info) if return_info else result
+
+
+def build_dataset(rows, img_size=512, new_dim=224, trim=(0.2, 0.8), box_indexing="reference", return_info=False):
+    """The T1:390-393 loop over (ct_scan, lung_mask, infection_mask) rows (paths or [X, Y, Z] arrays) -- lungs first, for the rectangles, then cts and
+    infections with them -- and the empty-mask filter of T1:421-429.  -> (cts, infections) float32 [N, new_dim, new_dim, 1] numpy arrays, the `data=` argument
+    of the runners (holdout_runner_unet_infection_segmentation(data=build_dataset(rows)))."""
+    torch = _torch()
+    cts, infs, report = [], [], []
+    for ct, lung, inf in rows:
+        rects = load_volume(lung, "lungs", img_size, trim)
+        c, ci = load_volume(ct, "cts", img_size, trim, rects, box_indexing, new_dim, return_info=True)
+        with warnings.catch_warnings():                              # an empty infection mask is expected here: T1:421-429 drops it below
+            warnings.simplefilter("ignore", RuntimeWarning)
+            m, mi = load_volume(inf, "infections", img_size, trim, rects, box_indexing, new_dim, return_info=True)
+        if c.shape != m.shape:
+            raise ValueError(f"the CT gives {tuple(c.shape)} slices but its infection mask {tuple(m.shape)}")
+        keep = np.ones(c.shape[0], bool); keep[mi["constant"]] = False          # T1:423: np.unique(infections[i]).size == 1
+        k = torch.from_numpy(np.nonzero(keep)[0]).cuda()
+        cts.append(c.index_select(0, k)); infs.append(m.index_select(0, k))
+        report.append({"kept": int(keep.sum()), "dropped": mi["constant"], "fell_through": ci["fell_through"], "flat": sorted(set(ci["flat"]) | set(mi["flat"]))})
+    x, y = torch.cat(cts).cpu().numpy(), torch.cat(infs).cpu().numpy()
+    return (x, y, report) if return_info else (x, y)
+
+
+class VolumeSegmentation:
+    """mask: uint8 [X, Y, Z] in the CT's own geometry (numpy, Fortran order); voxel_ml; counts / ml_per_slice [Z] (0 on the trimmed slices); total_ml;
+    lung_ml and infected_share when a lung mask was given; fell_through / flat: kept-range slice numbers; z0, z1; seconds: where the time went."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def paste_back(prob, rects1, rects2, size):
+    """unet_vol_paste_back: prob [n, d, d(, 1)] float32 device tensor -> canvas [n, size, size]; rects*: int [n, 4] with w <= 0 for "none"."""
+    torch = _torch(); lib, ctx = _ctx()
+    p = prob.reshape(prob.shape[0], prob.shape[1], prob.shape[2]).contiguous()
+    n, d = p.shape[0], p.shape[1]
+    r = None
+    if rects1 is not None:
+        r = np.ascontiguousarray(np.concatenate([np.asarray(rects1, np.int32).reshape(n, 4), np.asarray(rects2, np.int32).reshape(n, 4)], 1))
+    canvas = torch.empty((n, size, size), dtype=torch.float32, device="cuda")
+    ctx.check(lib.unet_vol_paste_back(ctx.handle, p.data_ptr(), n, d, r.ctypes.data if r is not None else None, canvas.data_ptr(), size, _stream()), "vol_paste_back")
+    return canvas
+
+
+def unslice(canvas, threshold, shape, z0, z1):
+    """unet_vol_unslice: canvas [z1 - z0, S, S] -> (mask uint8 device tensor of X*Y*Z bytes in Fortran order, counts int64 [z1 - z0])."""
+    torch = _torch(); lib, ctx = _ctx()
+    X, Y, Z = (int(v) for v in shape)
+    canvas = canvas.contiguous()
+    mask = torch.empty(X * Y * Z, dtype=torch.uint8, device="cuda")
+    counts = torch.empty(z1 - z0, dtype=torch.int64, device="cuda")
+    ctx.check(lib.unet_vol_unslice(ctx.handle, canvas.data_ptr(), canvas.shape[1], float(threshold), X, Y, Z, z0, z1, mask.data_ptr(), counts.data_ptr(), _stream()),
+              "vol_unslice")
+    return mask, counts
+
+
+def segment_volume(ct, model, lung_mask=None, threshold=0.547, batch_size=32, out_path=None, img_size=512, trim=(0.2, 0.8)):
+    """CT file (or array) -> VolumeSegmentation.  `model`: a UNetModel or a routed.ClusterRoutedModel (only `predict` is used); lung_mask=None: whole-frame
+    boxes (the two halves of the frame); boxes are keyed by slice number (box_indexing="slice"); out_path: the mask as .nii / .nii.gz with the CT's geometry."""
+    torch = _torch()
+    sec = {}
+    t0 = time.perf_counter()
+    vol = _source(ct)
+    sec["decode"] = time.perf_counter() - t0
+    X, Y, Z = vol.raw.shape
+    z0, z1 = trim_range(Z, trim)
+    n, S = z1 - z0, int(img_size)
+    d = int(getattr(model, "h", None) or model.base.h)
+    if lung_mask is not None:
+        lv = _source(lung_mask)
+        if lv.raw.shape != vol.raw.shape:
+            raise ValueError(f"the lung mask is {lv.raw.shape}, the CT {vol.raw.shape}")
+        r1, r2, kept = load_volume(lv, "lungs", S, trim)
+    else:
+        lv = None
+        r1, r2 = whole_frame_rects(n, S); kept = list(range(n))
+    plan = box_plan(n, kept, "slice")
+    t0 = time.perf_counter()
+    x, info = load_volume(vol, "cts", S, trim, (r1, r2, kept), "slice", d, return_info=True)
+    torch.cuda.synchronize(); sec["load_volume"] = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    prob = torch.from_numpy(np.ascontiguousarray(model.predict(x, batch_size=batch_size), np.float32)).cuda()
+    torch.cuda.synchronize(); sec["predict"] = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    R1, R2 = np.zeros((n, 4), np.int32), np.zeros((n, 4), np.int32)
+    has = plan >= 0
+    R1[has], R2[has] = np.asarray(r1, np.int32).reshape(-1, 4)[plan[has]], np.asarray(r2, np.int32).reshape(-1, 4)[plan[has]]
+    canvas = paste_back(prob, R1, R2, S)
+    mask_dev, counts_dev = unslice(canvas, threshold, (X, Y, Z), z0, z1)
+    mask = mask_dev.cpu().numpy().reshape((X, Y, Z), order="F")
+    counts = np.zeros(Z, np.int64); counts[z0:z1] = counts_dev.cpu().numpy()
+    sec["paste_unslice"] = time.perf_counter() - t0
+    voxel_mm3 = float(np.prod(np.asarray(vol.pixdim, np.float64)))          # count * prod(pixdim) / 1000 = millilitres
+    res = VolumeSegmentation(mask=mask, counts=counts, voxel_ml=voxel_mm3 / 1000.0, ml_per_slice=counts * voxel_mm3 / 1000.0,
+                             total_ml=float(counts.sum()) * voxel_mm3 / 1000.0, lung_ml=None,
+                             infected_share=None, fell_through=[int(i) for i in np.nonzero(~has)[0]], flat=info["flat"], z0=z0, z1=z1, pixdim=vol.pixdim,
+                             threshold=float(threshold), seconds=sec)
+    if lv is not None:
+        lung_vox = int(np.count_nonzero(lv.get_fdata()[:, :, z0:z1]))
+        res.lung_ml = lung_vox * voxel_mm3 / 1000.0
+        res.infected_share = (res.total_ml / res.lung_ml) if lung_vox else float("nan")
+    if out_path is not None:
+        nifti_min.write(out_path, mask, vol.header)
+    return res
