@@ -587,6 +587,26 @@ int32_t unet_vol_paste_back(unet_ctx*, const float* prob, int32_t n, int32_t d, 
 int32_t unet_vol_unslice(unet_ctx*, const float* canvas, int32_t S, float threshold, int32_t X, int32_t Y, int32_t Z, int32_t z0, int32_t z1, uint8_t* mask,
                          int64_t* counts, void* stream);
 
+/* ---- connected components of a mask volume (csrc/kernels_components.hip; exact against tests/components_oracle.py and scikit-image's label) ----
+ * mask: uint8 [X, Y, Z] in Fortran order (x fastest: what unet_vol_unslice writes), foreground = non-zero.  connectivity 1, 2, 3 = 6, 18, 26 neighbours
+ * (scikit-image's `connectivity=` of a 3-D array); anything else: UNET_E_ARG.  labels: int32, same layout, 16-byte aligned; 0 on the background, the components
+ * numbered 1..n in ascending order of the C-order index (x Y + y) Z + z of their first voxel -- element for element `skimage.measure.label(mask != 0,
+ * connectivity=c)` and `scipy.ndimage.label(mask, generate_binary_structure(3, c))`.  n_out: device int32, the number of components.  X Y Z < 2^31 (otherwise
+ * UNET_E_ARG, nothing launched); a volume with a zero dimension gives n = 0 and touches nothing else.  ws: unet_vol_label_ws_bytes(X, Y, Z) bytes, 16-byte
+ * aligned (one flag byte per voxel + the prefix sum's chunk totals).  Seven launches, each a phase of a union-find on C-order keys (brick-local in LDS, merge
+ * across brick faces, flatten, count / scan / number the roots, final labels); integer arithmetic only: the same result on every run. */
+size_t unet_vol_label_ws_bytes(int32_t X, int32_t Y, int32_t Z);
+int32_t unet_vol_label(unet_ctx*, const uint8_t* mask, int32_t X, int32_t Y, int32_t Z, int32_t connectivity, int32_t* labels, int32_t* n_out, void* ws, size_t ws_bytes,
+                       void* stream);
+/* Per component, one pass with integer atomics (summed per lane and per wave first): stats = n records of 64 bytes, record i for label i + 1:
+ *   int64 count, sum_x, sum_y, sum_z;  int32 x0, x1, y0, y1, z0, z1 (inclusive bounding box), 2 x int32 padding.
+ * The centroid is the caller's sum / count.  labels 16-byte aligned, stats 8-byte aligned; a label outside 1..n is ignored. */
+int32_t unet_vol_component_stats(unet_ctx*, const int32_t* labels, int32_t X, int32_t Y, int32_t Z, int32_t n, void* stats, void* stream);
+/* mask[v] = keep[labels[v]] ? 1 : 0 over the whole volume (keep: device uint8 [n + 1], keep[0] = 0 for the background; a label outside 0..n is dropped) and
+ * counts[z - z0] = set voxels of slice z for z in [z0, z1) (int64, as unet_vol_unslice reports them). */
+int32_t unet_vol_filter_components(unet_ctx*, const int32_t* labels, const uint8_t* keep, int32_t n, int32_t X, int32_t Y, int32_t Z, int32_t z0, int32_t z1, uint8_t* mask,
+                                   int64_t* counts, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Model level.  Replaces the Keras Model built at T1:853-916 and driven by
  * compile/fit/evaluate/predict (T1:1053-1061, 1101, 1137).  A model is a fixed-shape plan:

@@ -176,6 +176,11 @@ _PROTOS = {
     "unet_vol_slices_f64": (i32, [vp, vp, i32, i32, i32, i32, i32, f64, f64, i32, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
     "unet_vol_paste_back": (i32, [vp, vp, i32, i32, vp, vp, i32, vp]),
     "unet_vol_unslice": (i32, [vp, vp, i32, f32, i32, i32, i32, i32, i32, vp, vp, vp]),
+    # connected components of a mask volume (kernels_components.hip, volume.label_volume)
+    "unet_vol_label_ws_bytes": (sz, [i32, i32, i32]),
+    "unet_vol_label": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
+    "unet_vol_component_stats": (i32, [vp, vp, i32, i32, i32, i32, vp, vp]),
+    "unet_vol_filter_components": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
     "unet_model_create": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(vp)]),
     "unet_model_dtype": (i32, [vp]),
     "unet_model_tap_elem_bytes": (i32, [vp, C.c_char_p, i32]),

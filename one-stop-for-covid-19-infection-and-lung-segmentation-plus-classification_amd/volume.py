@@ -4,6 +4,9 @@ the dataset loop around it (T1:390-393, 421-429) and the way back from a predict
     load_volume(path_or_array, kind)      kind = "demo" | "lungs" | "cts" | "infections": the four uses of read_nii / read_nii_demo
     build_dataset(rows)                   rows of (ct, lung_mask, infection_mask) -> cts, infections for the runners' data= argument
     segment_volume(ct, model, ...)        -> VolumeSegmentation: mask volume in the CT's geometry, infected volume in ml, optional .nii(.gz) file
+    label_volume(mask, connectivity)      -> (labels, n): connected components on the device, numbered as skimage.measure.label numbers them
+    component_table(labels, n, pixdim)    -> one row per component: voxels, ml, bounding box, centroid
+    remove_small / keep_largest(mask)     -> the mask without its small components / with its k largest only
 
 The voxels are uploaded once as stored (nifti_min reads the file); decode, np.rot90, the slice trim, cv2.resize(float64, INTER_AREA) and the min-max run
 in unet_vol_slices_f64, CLAHE / crop / fuse / resize in the uint8 kernels of preprocess.py on device pointers: between the upload and the returned batch
@@ -273,7 +276,8 @@ def build_dataset(rows, img_size=512, new_dim=224, trim=(0.2, 0.8), box_indexing
 
 class VolumeSegmentation:
     """mask: uint8 [X, Y, Z] in the CT's own geometry (numpy, Fortran order); voxel_ml; counts / ml_per_slice [Z] (0 on the trimmed slices); total_ml;
-    lung_ml and infected_share when a lung mask was given; fell_through / flat: kept-range slice numbers; z0, z1; seconds: where the time went."""
+    lung_ml and infected_share when a lung mask was given; fell_through / flat: kept-range slice numbers; z0, z1; seconds: where the time went;
+    lesions / n_lesions / removed_ml: the component table of the mask, its length and the volume a min_lesion_ml filter removed (None when not asked for)."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -304,9 +308,174 @@ def unslice(canvas, threshold, shape, z0, z1):
     return mask, counts
 
 
-def segment_volume(ct, model, lung_mask=None, threshold=0.547, batch_size=32, out_path=None, img_size=512, trim=(0.2, 0.8)):
+# ---- connected components of a mask volume (csrc/kernels_components.hip) ------------------------------------------------------------------------
+# one record of unet_vol_component_stats (include/unet_hip.h): 64 bytes
+_STAT_DTYPE = np.dtype([("voxels", "<i8"), ("sx", "<i8"), ("sy", "<i8"), ("sz", "<i8"), ("x0", "<i4"), ("x1", "<i4"), ("y0", "<i4"), ("y1", "<i4"),
+                        ("z0", "<i4"), ("z1", "<i4"), ("pad", "<i4", (2,))])
+LESION_DTYPE = np.dtype([("label", np.int32), ("voxels", np.int64), ("ml", np.float64), ("x0", np.int32), ("x1", np.int32), ("y0", np.int32), ("y1", np.int32),
+                         ("z0", np.int32), ("z1", np.int32), ("cx", np.float64), ("cy", np.float64), ("cz", np.float64)])
+
+
+def _check_connectivity(connectivity):
+    if connectivity not in (1, 2, 3):
+        raise ValueError(f"connectivity must be 1 (6 neighbours), 2 (18) or 3 (26), not {connectivity!r}")
+    return int(connectivity)
+
+
+def _mask_to_device(mask, shape=None):
+    """-> (device uint8 tensor of X*Y*Z bytes in Fortran order, (X, Y, Z)).  A numpy [X, Y, Z] array of any integer / bool dtype and order (foreground = non-zero),
+    or the device byte tensor `unslice` returns together with shape=."""
+    torch = _torch()
+    if isinstance(mask, torch.Tensor):
+        if shape is None:
+            raise ValueError("a device mask is a flat Fortran-order byte buffer: pass shape=(X, Y, Z)")
+        shape = tuple(int(v) for v in shape)
+        if mask.dtype != torch.uint8 or not mask.is_cuda or mask.numel() != int(np.prod(shape)):
+            raise ValueError(f"a device mask is a uint8 cuda tensor of prod(shape) = {int(np.prod(shape))} elements")
+        return mask.contiguous().reshape(-1), shape
+    a = np.asarray(mask)
+    if a.ndim != 3:
+        raise ValueError(f"a volume is [X, Y, Z]; got {a.ndim} dimensions")
+    if a.dtype.kind not in "biu":
+        raise ValueError(f"a mask has a bool or integer dtype, not {a.dtype}")
+    flat = np.asfortranarray((a != 0).astype(np.uint8)).reshape(-1, order="F")
+    return torch.from_numpy(flat).cuda(), tuple(int(v) for v in a.shape)
+
+
+def label_device(mask_dev, shape, connectivity=1):
+    """unet_vol_label on a device mask -> (labels: int32 device tensor of X*Y*Z elements in Fortran order, n)."""
+    torch = _torch(); lib, ctx = _ctx()
+    X, Y, Z = shape
+    if X * Y * Z >= 2 ** 31:
+        raise ValueError(f"a volume of {X} x {Y} x {Z} has 2^31 voxels or more")
+    labels = torch.empty(X * Y * Z, dtype=torch.int32, device="cuda")
+    n_dev = torch.zeros(1, dtype=torch.int32, device="cuda")
+    ws = torch.empty(max(int(lib.unet_vol_label_ws_bytes(X, Y, Z)), 16), dtype=torch.uint8, device="cuda")
+    ctx.check(lib.unet_vol_label(ctx.handle, mask_dev.data_ptr(), X, Y, Z, _check_connectivity(connectivity), labels.data_ptr(), n_dev.data_ptr(), ws.data_ptr(), ws.numel(),
+                                 _stream()), "vol_label")
+    return labels, int(n_dev.item())
+
+
+def label_volume(mask, connectivity=1, return_device=False, shape=None):
+    """Connected components of mask != 0 -> (labels, n): int32 [X, Y, Z] (numpy, Fortran order; return_device=True: the flat device tensor), 0 on the background,
+    components 1..n in the order of their first voxel in C order -- skimage.measure.label(mask != 0, connectivity=connectivity) element for element."""
+    dev, shape = _mask_to_device(mask, shape)
+    labels, n = label_device(dev, shape, connectivity)
+    return (labels if return_device else labels.cpu().numpy().reshape(shape, order="F")), n
+
+
+def component_stats_device(labels_dev, shape, n):
+    """unet_vol_component_stats -> numpy records [n] (voxels, sx, sy, sz, x0, x1, y0, y1, z0, z1): 64 bytes per component come back, the labels stay."""
+    torch = _torch(); lib, ctx = _ctx()
+    X, Y, Z = shape
+    st = torch.empty(max(n, 1) * _STAT_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+    ctx.check(lib.unet_vol_component_stats(ctx.handle, labels_dev.data_ptr(), X, Y, Z, n, st.data_ptr(), _stream()), "vol_component_stats")
+    return st[:n * _STAT_DTYPE.itemsize].cpu().numpy().view(_STAT_DTYPE)
+
+
+def table_from_stats(stats, pixdim=(1, 1, 1)):
+    """records of component_stats_device (or any arrays voxels, sx.., x0..) -> the LESION_DTYPE table: ml = voxels * prod(pixdim) / 1000, centroid = sum / count"""
+    n = len(stats["voxels"])
+    voxel_mm3 = float(np.prod(np.asarray(pixdim, np.float64)))
+    t = np.zeros(n, LESION_DTYPE)
+    t["label"] = np.arange(1, n + 1)
+    t["voxels"] = stats["voxels"]
+    t["ml"] = np.asarray(stats["voxels"], np.int64) * voxel_mm3 / 1000.0
+    for k in ("x0", "x1", "y0", "y1", "z0", "z1"):
+        t[k] = stats[k]
+    cnt = np.asarray(stats["voxels"], np.float64)
+    for k in "xyz":
+        t["c" + k] = np.asarray(stats["s" + k], np.float64) / cnt
+    return t
+
+
+def component_table(labels, n, pixdim=(1, 1, 1), shape=None):
+    """One row per component, sorted by label: label, voxels, ml, x0, x1, y0, y1, z0, z1 (inclusive bounds), cx, cy, cz (float64 voxel coordinates).
+    labels: what label_volume returned (numpy [X, Y, Z], or the device tensor together with shape=)."""
+    torch = _torch()
+    if isinstance(labels, torch.Tensor):
+        if shape is None:
+            raise ValueError("device labels are a flat Fortran-order buffer: pass shape=(X, Y, Z)")
+        dev, shape = labels.contiguous().reshape(-1), tuple(int(v) for v in shape)
+    else:
+        a = np.asarray(labels)
+        if a.ndim != 3:
+            raise ValueError(f"a volume is [X, Y, Z]; got {a.ndim} dimensions")
+        shape = tuple(int(v) for v in a.shape)
+        dev = torch.from_numpy(np.asfortranarray(a.astype(np.int32, copy=False)).reshape(-1, order="F")).cuda()
+    return table_from_stats(component_stats_device(dev, shape, int(n)), pixdim)
+
+
+def filter_components(labels_dev, keep, n, shape, z0=0, z1=None):
+    """unet_vol_filter_components: keep [n + 1] (bool; entry 0 is the background's and is forced to 0) -> (mask device bytes, counts int64 [z1 - z0] device)."""
+    torch = _torch(); lib, ctx = _ctx()
+    X, Y, Z = shape
+    z1 = Z if z1 is None else z1
+    k = np.ascontiguousarray(np.asarray(keep).astype(bool).astype(np.uint8))
+    if k.shape != (n + 1,):
+        raise ValueError(f"keep has one entry per label 0..{n}, not {k.shape}")
+    k[0] = 0
+    kd = torch.from_numpy(k).cuda()
+    mask = torch.empty(X * Y * Z, dtype=torch.uint8, device="cuda")
+    counts = torch.empty(max(z1 - z0, 0), dtype=torch.int64, device="cuda")
+    ctx.check(lib.unet_vol_filter_components(ctx.handle, labels_dev.data_ptr(), kd.data_ptr(), n, X, Y, Z, z0, z1, mask.data_ptr(), counts.data_ptr(), _stream()),
+              "vol_filter_components")
+    return mask, counts
+
+
+def min_voxels_from_ml(min_ml, pixdim):
+    """the smallest voxel count whose volume reaches min_ml millilitres: ceil(min_ml * 1000 / prod(pixdim))"""
+    return int(np.ceil(float(min_ml) * 1000.0 / float(np.prod(np.asarray(pixdim, np.float64)))))
+
+
+def largest_labels(voxels, k):
+    """labels (1-based, ascending) of the k components with the most voxels, ties to the lower label"""
+    voxels = np.asarray(voxels, np.int64)
+    order = np.lexsort((np.arange(voxels.size), -voxels))
+    return np.sort(order[:max(0, int(k))] + 1)
+
+
+def _filtered(mask, connectivity, choose, return_device, shape):
+    dev, shape = _mask_to_device(mask, shape)
+    labels, n = label_device(dev, shape, connectivity)
+    st = component_stats_device(labels, shape, n)
+    keep = np.zeros(n + 1, bool)
+    keep[1:] = choose(st["voxels"])
+    out, _ = filter_components(labels, keep, n, shape, 0, 0)
+    return out if return_device else out.cpu().numpy().reshape(shape, order="F")
+
+
+def remove_small(mask, min_voxels=None, min_ml=None, pixdim=None, connectivity=1, return_device=False, shape=None):
+    """The mask (uint8 0 / 1) without the components of fewer than min_voxels voxels: skimage.morphology.remove_small_objects(mask != 0, min_size=min_voxels,
+    connectivity=connectivity).  min_ml (with pixdim in mm) instead: min_voxels = ceil(min_ml * 1000 / prod(pixdim))."""
+    if (min_voxels is None) == (min_ml is None):
+        raise ValueError("pass exactly one of min_voxels, min_ml")
+    if min_ml is not None:
+        if pixdim is None:
+            raise ValueError("min_ml needs pixdim (the voxel's edge lengths in mm)")
+        min_voxels = min_voxels_from_ml(min_ml, pixdim)
+    mv = int(min_voxels)
+    return _filtered(mask, connectivity, lambda v: v >= mv, return_device, shape)
+
+
+def keep_largest(mask, k=2, connectivity=1, return_device=False, shape=None):
+    """The mask (uint8 0 / 1) with only its k components of the most voxels, ties to the lower label (the 3-D form of the reference's "two largest regions")."""
+    def choose(v):
+        sel = np.zeros(v.size, bool)
+        sel[largest_labels(v, k) - 1] = True
+        return sel
+    return _filtered(mask, connectivity, choose, return_device, shape)
+
+
+
+def segment_volume(ct, model, lung_mask=None, threshold=0.547, batch_size=32, out_path=None, img_size=512, trim=(0.2, 0.8), min_lesion_ml=None, connectivity=1,
+                   lesions=False):
     """CT file (or array) -> VolumeSegmentation.  `model`: a UNetModel or a routed.ClusterRoutedModel (only `predict` is used); lung_mask=None: whole-frame
-    boxes (the two halves of the frame); boxes are keyed by slice number (box_indexing="slice"); out_path: the mask as .nii / .nii.gz with the CT's geometry."""
+    boxes (the two halves of the frame); boxes are keyed by slice number (box_indexing="slice"); out_path: the mask as .nii / .nii.gz with the CT's geometry.
+    min_lesion_ml: connected components (`connectivity` 1, 2, 3 = 6, 18, 26 neighbours) smaller than that are removed on the device before the mask comes to the
+    host or reaches out_path; counts, ml_per_slice, total_ml, infected_share then describe the filtered mask and removed_ml what went.  lesions=True (or a
+    filter): res.lesions = the component_table of the final mask, res.n_lesions its length.  The labels never leave the device."""
+    _check_connectivity(connectivity)
     torch = _torch()
     sec = {}
     t0 = time.perf_counter()
@@ -337,14 +506,29 @@ def segment_volume(ct, model, lung_mask=None, threshold=0.547, batch_size=32, ou
     R1[has], R2[has] = np.asarray(r1, np.int32).reshape(-1, 4)[plan[has]], np.asarray(r2, np.int32).reshape(-1, 4)[plan[has]]
     canvas = paste_back(prob, R1, R2, S)
     mask_dev, counts_dev = unslice(canvas, threshold, (X, Y, Z), z0, z1)
+    voxel_mm3 = float(np.prod(np.asarray(vol.pixdim, np.float64)))          # count * prod(pixdim) / 1000 = millilitres
+    table, removed_ml = None, None
+    if min_lesion_ml is not None or lesions:
+        torch.cuda.synchronize(); tc = time.perf_counter()
+        labels_dev, n_comp = label_device(mask_dev, (X, Y, Z), connectivity)
+        table = table_from_stats(component_stats_device(labels_dev, (X, Y, Z), n_comp), vol.pixdim)
+        if min_lesion_ml is not None:
+            before = int(counts_dev.sum().item())
+            keep = np.zeros(n_comp + 1, bool)
+            keep[1:] = table["voxels"] >= min_voxels_from_ml(min_lesion_ml, vol.pixdim)
+            mask_dev, counts_dev = filter_components(labels_dev, keep, n_comp, (X, Y, Z), z0, z1)
+            table = table[keep[1:]]                                  # the kept components keep their order: renumbered, this is the table of the filtered mask
+            table["label"] = np.arange(1, len(table) + 1)
+            removed_ml = float(before) * voxel_mm3 / 1000.0 - float(counts_dev.sum().item()) * voxel_mm3 / 1000.0
+        del labels_dev
+        torch.cuda.synchronize(); sec["components"] = time.perf_counter() - tc
     mask = mask_dev.cpu().numpy().reshape((X, Y, Z), order="F")
     counts = np.zeros(Z, np.int64); counts[z0:z1] = counts_dev.cpu().numpy()
     sec["paste_unslice"] = time.perf_counter() - t0
-    voxel_mm3 = float(np.prod(np.asarray(vol.pixdim, np.float64)))          # count * prod(pixdim) / 1000 = millilitres
     res = VolumeSegmentation(mask=mask, counts=counts, voxel_ml=voxel_mm3 / 1000.0, ml_per_slice=counts * voxel_mm3 / 1000.0,
                              total_ml=float(counts.sum()) * voxel_mm3 / 1000.0, lung_ml=None,
                              infected_share=None, fell_through=[int(i) for i in np.nonzero(~has)[0]], flat=info["flat"], z0=z0, z1=z1, pixdim=vol.pixdim,
-                             threshold=float(threshold), seconds=sec)
+                             threshold=float(threshold), seconds=sec, lesions=table, n_lesions=None if table is None else len(table), removed_ml=removed_ml)
     if lv is not None:
         lung_vox = int(np.count_nonzero(lv.get_fdata()[:, :, z0:z1]))
         res.lung_ml = lung_vox * voxel_mm3 / 1000.0
