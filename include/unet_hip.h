@@ -607,8 +607,45 @@ int32_t unet_vol_component_stats(unet_ctx*, const int32_t* labels, int32_t X, in
 int32_t unet_vol_filter_components(unet_ctx*, const int32_t* labels, const uint8_t* keep, int32_t n, int32_t X, int32_t Y, int32_t Z, int32_t z0, int32_t z1, uint8_t* mask,
                                    int64_t* counts, void* stream);
 
+/* ---- a mask volume against its ground truth (csrc/kernels_volscore.hip; exact against tests/volscore_oracle.py) ----
+ * All volumes: [X, Y, Z] in Fortran order, X Y Z < 2^31 (otherwise UNET_E_ARG, nothing launched); a mask's foreground = non-zero.
+ * counts[z][3] = int64 {tp, fp, fn} of slice z (pred & truth, pred & ~truth, truth & ~pred): integer sums per lane, per wave, then one atomic per workgroup and
+ * slice; exact and the same on every run. */
+int32_t unet_vol_confusion(unet_ctx*, const uint8_t* pred, const uint8_t* truth, int32_t X, int32_t Y, int32_t Z, int64_t* counts, void* stream);
+/* surface[v] = mask[v] != 0 and some neighbour of v within the structuring element (connectivity 1, 2, 3 = 6, 18, 26 neighbours; anything else UNET_E_ARG) is
+ * background; voxels outside the volume are background.  Element for element m ^ scipy.ndimage.binary_erosion(m, generate_binary_structure(3, c)) (border_value 0),
+ * as uint8 0 / 1; surface must not be the mask's own buffer.  count: device int64, the number of surface voxels. */
+int32_t unet_vol_surface(unet_ctx*, const uint8_t* mask, int32_t X, int32_t Y, int32_t Z, int32_t connectivity, uint8_t* surface, int64_t* count, void* stream);
+/* Exact squared Euclidean distance transform.  The features are the non-zero voxels of vol (features_nonzero != 0) or its zero voxels (== 0); w = HOST pointer to
+ * (sx^2, sy^2, sz^2), positive and finite, squared by the caller in float64.  For every voxel
+ *     d2[v] = min over features f of fl( fl( fl(wx i^2) + fl(wy j^2) ) + fl(wz k^2) ),    (i, j, k) = v - f,
+ * every fl one IEEE double operation (i^2 is an exact integer; no fused multiply-add); +inf everywhere when there is no feature.  fl(a + c) is monotone in a, so
+ * the minimum commutes with the rounding and three passes (x, y, z) that each take the TRUE minimum along their line give this value bit for bit; the passes scan
+ * the whole line.  No dimension may exceed UNET_VOL_EDT_MAX_DIM (UNET_E_ARG, nothing launched); a volume with a zero dimension touches nothing.  The passes run
+ * in place in d2 (8-byte aligned): unet_vol_edt_ws_bytes is 0 today and ws may be null. */
+#define UNET_VOL_EDT_MAX_DIM 4096
+size_t unet_vol_edt_ws_bytes(int32_t X, int32_t Y, int32_t Z);
+int32_t unet_vol_edt_sq(unet_ctx*, const uint8_t* vol, int32_t X, int32_t Y, int32_t Z, int32_t features_nonzero, const double* w, double* d2, void* ws, size_t ws_bytes,
+                        void* stream);
+/* x[i] = sqrt(x[i]) in place, n doubles. */
+int32_t unet_vol_sqrt_f64(unet_ctx*, double* x, int64_t n, void* stream);
+/* Over the voxels of the byte volume `surface` that are non-zero: result (device, 24 bytes, 8-byte aligned) = { int64 count, double max d2 (exact; 0 when count = 0),
+ * double sum of sqrt(d2) }, and the d2 values themselves in gathered[0 .. min(count, capacity)) in no particular order (they are sorted afterwards).
+ * ws: UNET_VOL_SURFDIST_WS_BYTES bytes, 8-byte aligned.  The sum has a fixed shape and uses no floating-point atomics, so it is the same on every run:
+ *   items = ceil(N / 16), G = min(ceil(items / 256), UNET_VOL_SURFDIST_WS_BYTES / 8) workgroups of 256 lanes;
+ *   a lane adds its voxels one by one: a chain of at most 16 ceil(items / (256 G)) additions; a 6-level butterfly over the 64 lanes of a wave; the 4 wave sums left to
+ *   right (3 additions); a second launch of ONE workgroup: a chain of ceil(G / 256) partial sums per lane, the same butterfly, the same 3 additions.
+ * The longest chain of additions behind the sum is therefore 16 ceil(items / (256 G)) + ceil(G / 256) + 18. */
+#define UNET_VOL_SURFDIST_WS_BYTES 32768
+int32_t unet_vol_surface_distances(unet_ctx*, const uint8_t* surface, const double* d2, int32_t X, int32_t Y, int32_t Z, void* result, double* gathered, int64_t capacity,
+                                   void* ws, size_t ws_bytes, void* stream);
+/* Two label volumes of unet_vol_label with n_t and n_p components: cover_t[i] = voxels of truth component i + 1 where labels_p is non-zero, cover_p[j] = voxels of
+ * predicted component j + 1 where labels_t is non-zero (device int64; integer atomics, summed per lane and per wave first).  A label outside 1..n is ignored. */
+int32_t unet_vol_lesion_overlap(unet_ctx*, const int32_t* labels_t, int32_t n_t, const int32_t* labels_p, int32_t n_p, int32_t X, int32_t Y, int32_t Z, int64_t* cover_t,
+                                int64_t* cover_p, void* stream);
+
 /* ------------------------------------------------------------------------------------
- * Model level.  Replaces the Keras Model built at T1:853-916 and driven by
+ * Model level. Replaces the Keras Model built at T1:853-916 and driven by
  * compile/fit/evaluate/predict (T1:1053-1061, 1101, 1137).  A model is a fixed-shape plan:
  * three op programs (training forward, backward, inference forward) over caller-owned
  * flat buffers.  Programs can be run in [begin,end) slices so a data-parallel host can put

@@ -181,6 +181,14 @@ _PROTOS = {
     "unet_vol_label": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
     "unet_vol_component_stats": (i32, [vp, vp, i32, i32, i32, i32, vp, vp]),
     "unet_vol_filter_components": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
+    # a mask volume against its ground truth (csrc/kernels_volscore.hip)
+    "unet_vol_confusion": (i32, [vp, vp, vp, i32, i32, i32, vp, vp]),
+    "unet_vol_surface": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp]),
+    "unet_vol_edt_ws_bytes": (sz, [i32, i32, i32]),
+    "unet_vol_edt_sq": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
+    "unet_vol_sqrt_f64": (i32, [vp, vp, i64, vp]),
+    "unet_vol_surface_distances": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, i64, vp, sz, vp]),
+    "unet_vol_lesion_overlap": (i32, [vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp]),
     "unet_model_create": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(vp)]),
     "unet_model_dtype": (i32, [vp]),
     "unet_model_tap_elem_bytes": (i32, [vp, C.c_char_p, i32]),

@@ -7,6 +7,9 @@ the dataset loop around it (T1:390-393, 421-429) and the way back from a predict
     label_volume(mask, connectivity)      -> (labels, n): connected components on the device, numbered as skimage.measure.label numbers them
     component_table(labels, n, pixdim)    -> one row per component: voxels, ml, bounding box, centroid
     remove_small / keep_largest(mask)     -> the mask without its small components / with its k largest only
+    surface(mask, connectivity)           -> the mask's surface voxels (mask ^ binary_erosion)
+    distance_transform(mask, pixdim)      -> float64 distance of every foreground voxel to the background, in mm (scipy's distance_transform_edt with sampling=)
+    score_volume(pred, truth, pixdim)     -> VolumeScore: Dice / IoU / volume error, Hausdorff / HD95 / surface distances in mm, lesion-wise detection
 
 The voxels are uploaded once as stored (nifti_min reads the file); decode, np.rot90, the slice trim, cv2.resize(float64, INTER_AREA) and the min-max run
 in unet_vol_slices_f64, CLAHE / crop / fuse / resize in the uint8 kernels of preprocess.py on device pointers: between the upload and the returned batch
@@ -277,7 +280,8 @@ def build_dataset(rows, img_size=512, new_dim=224, trim=(0.2, 0.8), box_indexing
 class VolumeSegmentation:
     """mask: uint8 [X, Y, Z] in the CT's own geometry (numpy, Fortran order); voxel_ml; counts / ml_per_slice [Z] (0 on the trimmed slices); total_ml;
     lung_ml and infected_share when a lung mask was given; fell_through / flat: kept-range slice numbers; z0, z1; seconds: where the time went;
-    lesions / n_lesions / removed_ml: the component table of the mask, its length and the volume a min_lesion_ml filter removed (None when not asked for)."""
+    lesions / n_lesions / removed_ml: the component table of the mask, its length and the volume a min_lesion_ml filter removed (None when not asked for);
+    score: the VolumeScore of the final mask against the `truth` given to segment_volume (None without one)."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -466,15 +470,264 @@ def keep_largest(mask, k=2, connectivity=1, return_device=False, shape=None):
         return sel
     return _filtered(mask, connectivity, choose, return_device, shape)
 
+# ---- a mask volume against its ground truth (csrc/kernels_volscore.hip) ------------------------------------------------------
+EDT_MAX_DIM = 4096                                                  # UNET_VOL_EDT_MAX_DIM
+_SURFDIST_WS_BYTES = 32768                                          # UNET_VOL_SURFDIST_WS_BYTES
+SCORED_LESION_DTYPE = {"truth": np.dtype(LESION_DTYPE.descr + [("covered_voxels", "<i8"), ("covered_share", "<f8"), ("detected", "?")]),
+                       "pred": np.dtype(LESION_DTYPE.descr + [("covered_voxels", "<i8"), ("covered_share", "<f8"), ("matched", "?")])}
+
+
+def _check_pixdim(pixdim):
+    try:
+        p = np.asarray(pixdim, np.float64).reshape(-1)
+    except (TypeError, ValueError):
+        raise ValueError(f"pixdim is three positive finite numbers, not {pixdim!r}") from None
+    if p.shape != (3,) or not np.isfinite(p).all() or not (p > 0).all() or not np.isfinite(p * p).all() or not (p * p > 0).all():
+        raise ValueError(f"pixdim is three positive finite numbers (with finite, non-zero squares), not {pixdim!r}")
+    return p
+
+
+def _check_volume_dims(shape):
+    X, Y, Z = shape
+    if X * Y * Z >= 2 ** 31:
+        raise ValueError(f"a volume of {X} x {Y} x {Z} has 2^31 voxels or more")
+
+
+def confusion_device(pred_dev, truth_dev, shape):
+    """unet_vol_confusion -> int64 [Z, 3] numpy: tp, fp, fn of every slice"""
+    torch = _torch(); lib, ctx = _ctx()
+    X, Y, Z = shape
+    _check_volume_dims(shape)
+    counts = torch.empty((max(Z, 1), 3), dtype=torch.int64, device="cuda")
+    ctx.check(lib.unet_vol_confusion(ctx.handle, pred_dev.data_ptr(), truth_dev.data_ptr(), X, Y, Z, counts.data_ptr(), _stream()), "vol_confusion")
+    return counts[:Z].cpu().numpy()
+
+
+def surface_device(mask_dev, shape, connectivity=1):
+    """unet_vol_surface -> (surface: uint8 device tensor of X*Y*Z bytes in Fortran order, the number of surface voxels)"""
+    torch = _torch(); lib, ctx = _ctx()
+    X, Y, Z = shape
+    _check_volume_dims(shape)
+    surf = torch.empty(X * Y * Z, dtype=torch.uint8, device="cuda")
+    count = torch.zeros(1, dtype=torch.int64, device="cuda")
+    ctx.check(lib.unet_vol_surface(ctx.handle, mask_dev.data_ptr(), X, Y, Z, _check_connectivity(connectivity), surf.data_ptr(), count.data_ptr(), _stream()), "vol_surface")
+    return surf, int(count.item())
+
+
+def edt_sq_device(vol_dev, shape, pixdim=(1, 1, 1), features_nonzero=True):
+    """unet_vol_edt_sq -> float64 device tensor of X*Y*Z elements: the exact squared distance (mm^2) of every voxel to the nearest feature -- the non-zero voxels of
+    vol_dev, or its zero voxels; +inf everywhere when there is none."""
+    torch = _torch(); lib, ctx = _ctx()
+    X, Y, Z = shape
+    p = _check_pixdim(pixdim)
+    _check_volume_dims(shape)
+    if max(shape) > EDT_MAX_DIM:
+        raise ValueError(f"the distance transform takes at most {EDT_MAX_DIM} voxels per axis, not {X} x {Y} x {Z}")
+    w = np.ascontiguousarray(p * p)
+    d2 = torch.empty(X * Y * Z, dtype=torch.float64, device="cuda")
+    ws = torch.empty(max(int(lib.unet_vol_edt_ws_bytes(X, Y, Z)), 16), dtype=torch.uint8, device="cuda")
+    ctx.check(lib.unet_vol_edt_sq(ctx.handle, vol_dev.data_ptr(), X, Y, Z, 1 if features_nonzero else 0, w.ctypes.data, d2.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+              "vol_edt_sq")
+    return d2
+
+
+def sqrt_device(x):
+    """unet_vol_sqrt_f64: in place on a contiguous float64 device tensor"""
+    lib, ctx = _ctx()
+    ctx.check(lib.unet_vol_sqrt_f64(ctx.handle, x.data_ptr(), x.numel(), _stream()), "vol_sqrt_f64")
+    return x
+
+
+def surface_distances_device(surf_dev, d2_dev, shape, capacity):
+    """unet_vol_surface_distances -> (count, max d2, sum of sqrt(d2), the d2 values of the surface voxels as a device tensor of min(count, capacity) doubles)"""
+    torch = _torch(); lib, ctx = _ctx()
+    X, Y, Z = shape
+    res = torch.zeros(3, dtype=torch.int64, device="cuda")
+    gathered = torch.empty(max(int(capacity), 1), dtype=torch.float64, device="cuda")
+    ws = torch.empty(_SURFDIST_WS_BYTES, dtype=torch.uint8, device="cuda")
+    ctx.check(lib.unet_vol_surface_distances(ctx.handle, surf_dev.data_ptr(), d2_dev.data_ptr(), X, Y, Z, res.data_ptr(), gathered.data_ptr(), int(capacity), ws.data_ptr(),
+                                             ws.numel(), _stream()), "vol_surface_distances")
+    r = res.cpu().numpy()
+    count = int(r[0])
+    return count, float(r[1:2].view(np.float64)[0]), float(r[2:3].view(np.float64)[0]), gathered[:min(count, int(capacity))]
+
+
+def lesion_overlap_device(labels_t, n_t, labels_p, n_p, shape):
+    """unet_vol_lesion_overlap -> (cover_t int64 [n_t], cover_p int64 [n_p]) numpy"""
+    torch = _torch(); lib, ctx = _ctx()
+    X, Y, Z = shape
+    ct = torch.zeros(max(n_t, 1), dtype=torch.int64, device="cuda"); cp = torch.zeros(max(n_p, 1), dtype=torch.int64, device="cuda")
+    ctx.check(lib.unet_vol_lesion_overlap(ctx.handle, labels_t.data_ptr(), n_t, labels_p.data_ptr(), n_p, X, Y, Z, ct.data_ptr(), cp.data_ptr(), _stream()), "vol_lesion_overlap")
+    return ct[:n_t].cpu().numpy(), cp[:n_p].cpu().numpy()
+
+
+def surface(mask, connectivity=1, return_device=False, shape=None):
+    """The surface voxels of mask != 0 as uint8 0 / 1: the foreground voxels with a background neighbour among the 6 / 18 / 26 of `connectivity` 1 / 2 / 3, voxels
+    outside the volume counting as background -- m ^ scipy.ndimage.binary_erosion(m, generate_binary_structure(3, connectivity))."""
+    _check_connectivity(connectivity)
+    dev, shape = _mask_to_device(mask, shape)
+    surf, _ = surface_device(dev, shape, connectivity)
+    return surf if return_device else surf.cpu().numpy().reshape(shape, order="F")
+
+
+def distance_transform(mask, pixdim=(1, 1, 1), squared=False, return_device=False, shape=None):
+    """float64 distance (pixdim's unit) of every foreground voxel to the nearest background voxel, 0 on the background:
+    scipy.ndimage.distance_transform_edt(mask != 0, sampling=pixdim).  squared=True: the exact squared distance of unet_vol_edt_sq (include/unet_hip.h states it
+    operation by operation); otherwise its square root, taken on the device.  A mask without background gives +inf everywhere."""
+    _check_pixdim(pixdim)
+    dev, shape = _mask_to_device(mask, shape)
+    d = edt_sq_device(dev, shape, pixdim, features_nonzero=False)
+    if not squared:
+        sqrt_device(d)
+    return d if return_device else d.cpu().numpy().reshape(shape, order="F")
+
+
+def _same(a, b):
+    if isinstance(a, np.ndarray) or isinstance(b, np.ndarray):
+        if not (isinstance(a, np.ndarray) and isinstance(b, np.ndarray)) or a.dtype != b.dtype or a.shape != b.shape:
+            return False
+        if a.dtype.names:
+            return all(_same(a[k], b[k]) for k in a.dtype.names)
+        return bool(np.array_equal(a, b, equal_nan=a.dtype.kind == "f"))
+    if isinstance(a, float) and isinstance(b, float) and a != a and b != b:
+        return True
+    return type(a) is type(b) and a == b
+
+
+class VolumeScore:
+    """What score_volume returns.  Overlap: tp, fp, fn, dice, iou, precision, recall, pred_ml, truth_ml, volume_error_ml, and per slice tp_per_slice, fp_per_slice,
+    fn_per_slice, per_slice_dice [Z].  Surface (in pixdim's unit): hd_pred_to_truth, hd_truth_to_pred, hd, asd_pred_to_truth, asd_truth_to_pred, assd, hd95 (at
+    `percentile`), n_surface_pred, n_surface_truth.  Lesions (None when not asked for): truth_lesions (the component table + covered_voxels, covered_share, detected),
+    pred_lesions (+ covered_voxels, covered_share, matched), n_truth_lesions, n_pred_lesions, lesion_recall, lesion_precision, missed_lesions, false_positive_lesions.
+    Two scores compare equal when every field holds the same values (nan equal to nan)."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def __eq__(self, other):
+        return isinstance(other, VolumeScore) and self.__dict__.keys() == other.__dict__.keys() and all(_same(v, other.__dict__[k]) for k, v in self.__dict__.items())
+
+    __hash__ = None
+
+    def __repr__(self):
+        return f"VolumeScore(dice={self.dice:.4f}, hd95={self.hd95:.3f}, assd={self.assd:.3f}, lesion_recall={self.lesion_recall})"
+
+
+def _ratio(a, b):
+    return float(a) / float(b) if b else float("nan")
+
+
+def _percentile_of_sorted(sorted_dev, q):
+    """np.percentile(values, q) (linear interpolation) of sqrt(values) from an ascending device tensor of squared values: the two order statistics come to the host,
+    sqrt is monotone, so they are the order statistics of the square roots"""
+    n = sorted_dev.numel()
+    pos = (float(q) / 100.0) * (n - 1)
+    lo = min(int(np.floor(pos)), n - 1); hi = min(lo + 1, n - 1)
+    a, b = (float(v) for v in np.sqrt(sorted_dev[[lo, hi]].cpu().numpy()))
+    t = pos - lo
+    r = a + (b - a) * t                                             # numpy's _lerp
+    if t >= 0.5:
+        r = b - (b - a) * (1.0 - t)
+    return float(r)
+
+
+def score_volume(pred, truth, pixdim=(1, 1, 1), connectivity=1, lesion_connectivity=1, percentile=95.0, min_overlap_voxels=1, lesions=True, shape=None):
+    """A predicted mask against the ground truth of the same geometry -> VolumeScore.  pred, truth: numpy [X, Y, Z] arrays (bool / integer, foreground = non-zero) or
+    flat device byte tensors with shape=; pixdim: the voxel's edge lengths in mm.  `connectivity` (1, 2, 3) is the structuring element of the surfaces,
+    `lesion_connectivity` that of the lesions; a truth lesion is detected (a predicted one matched) when at least min_overlap_voxels of its voxels are marked by the
+    other mask.  Both masks empty: every distance 0.0, dice = iou = 1.0; exactly one empty: every distance inf.  Everything is computed on the device; the Hausdorff
+    distance is the host's sqrt of the device's exact maximum, hd95 the host's interpolation between two order statistics of the device's sort."""
+    torch = _torch()
+    p = _check_pixdim(pixdim)
+    _check_connectivity(connectivity); _check_connectivity(lesion_connectivity)
+    if not 0.0 <= float(percentile) <= 100.0:
+        raise ValueError(f"percentile must lie in [0, 100], not {percentile!r}")
+    for m in (pred, truth):                                         # refused before anything is uploaded or launched
+        if not isinstance(m, torch.Tensor):
+            a = np.asarray(m)
+            if a.ndim != 3:
+                raise ValueError(f"a volume is [X, Y, Z]; got {a.ndim} dimensions")
+            if a.dtype.kind not in "biu":
+                raise ValueError(f"a mask has a bool or integer dtype, not {a.dtype}")
+    said = [(None if shape is None else tuple(int(v) for v in shape)) if isinstance(m, torch.Tensor) else tuple(np.shape(m)) for m in (pred, truth)]
+    if None not in said and said[0] != said[1]:
+        raise ValueError(f"the prediction is {said[0]}, the truth {said[1]}")
+    pd, ps = _mask_to_device(pred, shape)
+    td, ts = _mask_to_device(truth, shape)
+    if ps != ts:
+        raise ValueError(f"the prediction is {ps}, the truth {ts}")
+    shape = ps
+    _check_volume_dims(shape)
+    if max(shape) > EDT_MAX_DIM:
+        raise ValueError(f"the distance transform takes at most {EDT_MAX_DIM} voxels per axis, not {shape}")
+    X, Y, Z = shape
+    f = {}
+    counts = confusion_device(pd, td, shape)
+    tp, fp, fn = (int(v) for v in counts.sum(axis=0)) if Z else (0, 0, 0)
+    voxel_mm3 = float(np.prod(p))
+    empty = tp + fp + fn == 0
+    den = (2 * counts[:, 0] + counts[:, 1] + counts[:, 2]).astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        per_slice = np.where(den > 0, 2.0 * counts[:, 0] / den, np.nan)
+    f.update(tp=tp, fp=fp, fn=fn, dice=1.0 if empty else 2.0 * tp / (2 * tp + fp + fn), iou=1.0 if empty else tp / (tp + fp + fn),
+             precision=_ratio(tp, tp + fp), recall=_ratio(tp, tp + fn), pred_ml=float(tp + fp) * voxel_mm3 / 1000.0, truth_ml=float(tp + fn) * voxel_mm3 / 1000.0,
+             tp_per_slice=counts[:, 0].copy(), fp_per_slice=counts[:, 1].copy(), fn_per_slice=counts[:, 2].copy(), per_slice_dice=per_slice, percentile=float(percentile))
+    f["volume_error_ml"] = f["pred_ml"] - f["truth_ml"]
+    # surfaces and their distances: A = surface(pred), B = surface(truth); d(a, B) from the transform whose features are B's voxels
+    sa, na = surface_device(pd, shape, connectivity) if X * Y * Z else (pd, 0)
+    sb, nb = surface_device(td, shape, connectivity) if X * Y * Z else (td, 0)
+    f.update(n_surface_pred=na, n_surface_truth=nb)
+    names = ("hd_pred_to_truth", "hd_truth_to_pred", "hd", "asd_pred_to_truth", "asd_truth_to_pred", "assd", "hd95")
+    if na == 0 or nb == 0:
+        f.update({k: 0.0 if na == nb else float("inf") for k in names})
+    else:
+        d2 = edt_sq_device(sb, shape, p, True)
+        ca, max_a, sum_a, ga = surface_distances_device(sa, d2, shape, na)
+        d2 = edt_sq_device(sa, shape, p, True)
+        cb, max_b, sum_b, gb = surface_distances_device(sb, d2, shape, nb)
+        del d2
+        if (ca, cb) != (na, nb):
+            raise _lib.UNetHipError(f"score_volume: the surfaces hold {na} and {nb} voxels but {ca} and {cb} distances were gathered")
+        f["hd_pred_to_truth"], f["hd_truth_to_pred"] = float(np.sqrt(max_a)), float(np.sqrt(max_b))
+        f["hd"] = max(f["hd_pred_to_truth"], f["hd_truth_to_pred"])
+        f["asd_pred_to_truth"], f["asd_truth_to_pred"] = sum_a / na, sum_b / nb
+        f["assd"] = (f["asd_pred_to_truth"] + f["asd_truth_to_pred"]) / 2.0
+        pooled, _ = torch.sort(torch.cat([ga, gb]))                 # ~10^6 values: plumbing
+        f["hd95"] = _percentile_of_sorted(pooled, percentile)
+    del sa, sb
+    f.update(truth_lesions=None, pred_lesions=None, n_truth_lesions=None, n_pred_lesions=None, lesion_recall=None, lesion_precision=None, missed_lesions=None,
+             false_positive_lesions=None)
+    if lesions:
+        mov = int(min_overlap_voxels)
+        lt, nt = label_device(td, shape, lesion_connectivity)
+        lp, npred = label_device(pd, shape, lesion_connectivity)
+        cover_t, cover_p = lesion_overlap_device(lt, nt, lp, npred, shape)
+        tables = {}
+        for who, lab, n, cover, flag in (("truth", lt, nt, cover_t, "detected"), ("pred", lp, npred, cover_p, "matched")):
+            base = table_from_stats(component_stats_device(lab, shape, n), p)
+            t = np.zeros(n, SCORED_LESION_DTYPE[who])
+            for k in LESION_DTYPE.names:
+                t[k] = base[k]
+            t["covered_voxels"] = cover
+            t["covered_share"] = cover.astype(np.float64) / base["voxels"].astype(np.float64)
+            t[flag] = cover >= mov
+            tables[who] = t
+        det, mat = int(tables["truth"]["detected"].sum()), int(tables["pred"]["matched"].sum())
+        f.update(truth_lesions=tables["truth"], pred_lesions=tables["pred"], n_truth_lesions=nt, n_pred_lesions=npred, lesion_recall=_ratio(det, nt),
+                 lesion_precision=_ratio(mat, npred), missed_lesions=nt - det, false_positive_lesions=npred - mat)
+    return VolumeScore(**f)
+
 
 
 def segment_volume(ct, model, lung_mask=None, threshold=0.547, batch_size=32, out_path=None, img_size=512, trim=(0.2, 0.8), min_lesion_ml=None, connectivity=1,
-                   lesions=False):
+                   lesions=False, truth=None):
     """CT file (or array) -> VolumeSegmentation.  `model`: a UNetModel or a routed.ClusterRoutedModel (only `predict` is used); lung_mask=None: whole-frame
     boxes (the two halves of the frame); boxes are keyed by slice number (box_indexing="slice"); out_path: the mask as .nii / .nii.gz with the CT's geometry.
     min_lesion_ml: connected components (`connectivity` 1, 2, 3 = 6, 18, 26 neighbours) smaller than that are removed on the device before the mask comes to the
     host or reaches out_path; counts, ml_per_slice, total_ml, infected_share then describe the filtered mask and removed_ml what went.  lesions=True (or a
-    filter): res.lesions = the component_table of the final mask, res.n_lesions its length.  The labels never leave the device."""
+    filter): res.lesions = the component_table of the final mask, res.n_lesions its length.  The labels never leave the device.
+    truth: the ground-truth mask in the CT's geometry (path or [X, Y, Z] array, foreground = non-zero): the final mask is scored against it before it leaves the
+    device, res.score = score_volume(mask, truth, pixdim, lesion_connectivity=connectivity); None without a truth."""
     _check_connectivity(connectivity)
     torch = _torch()
     sec = {}
@@ -482,6 +735,12 @@ def segment_volume(ct, model, lung_mask=None, threshold=0.547, batch_size=32, ou
     vol = _source(ct)
     sec["decode"] = time.perf_counter() - t0
     X, Y, Z = vol.raw.shape
+    truth_mask = None
+    if truth is not None:
+        tv = _source(truth)
+        if tv.raw.shape != vol.raw.shape:
+            raise ValueError(f"the truth mask is {tv.raw.shape}, the CT {vol.raw.shape}")
+        truth_mask = tv.get_fdata() != 0
     z0, z1 = trim_range(Z, trim)
     n, S = z1 - z0, int(img_size)
     d = int(getattr(model, "h", None) or model.base.h)
@@ -522,13 +781,18 @@ def segment_volume(ct, model, lung_mask=None, threshold=0.547, batch_size=32, ou
             removed_ml = float(before) * voxel_mm3 / 1000.0 - float(counts_dev.sum().item()) * voxel_mm3 / 1000.0
         del labels_dev
         torch.cuda.synchronize(); sec["components"] = time.perf_counter() - tc
+    score = None
+    if truth_mask is not None:
+        torch.cuda.synchronize(); ts = time.perf_counter()
+        score = score_volume(mask_dev, truth_mask, vol.pixdim, lesion_connectivity=connectivity, shape=(X, Y, Z))
+        torch.cuda.synchronize(); sec["score"] = time.perf_counter() - ts
     mask = mask_dev.cpu().numpy().reshape((X, Y, Z), order="F")
     counts = np.zeros(Z, np.int64); counts[z0:z1] = counts_dev.cpu().numpy()
     sec["paste_unslice"] = time.perf_counter() - t0
     res = VolumeSegmentation(mask=mask, counts=counts, voxel_ml=voxel_mm3 / 1000.0, ml_per_slice=counts * voxel_mm3 / 1000.0,
                              total_ml=float(counts.sum()) * voxel_mm3 / 1000.0, lung_ml=None,
                              infected_share=None, fell_through=[int(i) for i in np.nonzero(~has)[0]], flat=info["flat"], z0=z0, z1=z1, pixdim=vol.pixdim,
-                             threshold=float(threshold), seconds=sec, lesions=table, n_lesions=None if table is None else len(table), removed_ml=removed_ml)
+                             threshold=float(threshold), seconds=sec, lesions=table, n_lesions=None if table is None else len(table), removed_ml=removed_ml, score=score)
     if lv is not None:
         lung_vox = int(np.count_nonzero(lv.get_fdata()[:, :, z0:z1]))
         res.lung_ml = lung_vox * voxel_mm3 / 1000.0
