@@ -598,6 +598,11 @@ int32_t unet_vol_unslice(unet_ctx*, const float* canvas, int32_t S, float thresh
 size_t unet_vol_label_ws_bytes(int32_t X, int32_t Y, int32_t Z);
 int32_t unet_vol_label(unet_ctx*, const uint8_t* mask, int32_t X, int32_t Y, int32_t Z, int32_t connectivity, int32_t* labels, int32_t* n_out, void* ws, size_t ws_bytes,
                        void* stream);
+/* The same inside every axial slice: two voxels are neighbours only when dz = 0; connectivity 1, 2 = 4, 8 neighbours (anything else: UNET_E_ARG).  Contract, workspace
+ * (unet_vol_label_ws_bytes) and numbering rule are unet_vol_label's: element for element scipy.ndimage.label(mask, s) with s = generate_binary_structure(3, c) whose
+ * z = -1 and z = +1 planes are cleared. */
+int32_t unet_vol_label_planar(unet_ctx*, const uint8_t* mask, int32_t X, int32_t Y, int32_t Z, int32_t connectivity, int32_t* labels, int32_t* n_out, void* ws,
+                              size_t ws_bytes, void* stream);
 /* Per component, one pass with integer atomics (summed per lane and per wave first): stats = n records of 64 bytes, record i for label i + 1:
  *   int64 count, sum_x, sum_y, sum_z;  int32 x0, x1, y0, y1, z0, z1 (inclusive bounding box), 2 x int32 padding.
  * The centroid is the caller's sum / count.  labels 16-byte aligned, stats 8-byte aligned; a label outside 1..n is ignored. */
@@ -643,6 +648,39 @@ int32_t unet_vol_surface_distances(unet_ctx*, const uint8_t* surface, const doub
  * predicted component j + 1 where labels_t is non-zero (device int64; integer atomics, summed per lane and per wave first).  A label outside 1..n is ignored. */
 int32_t unet_vol_lesion_overlap(unet_ctx*, const int32_t* labels_t, int32_t n_t, const int32_t* labels_p, int32_t n_p, int32_t X, int32_t Y, int32_t Z, int64_t* cover_t,
                                 int64_t* cover_p, void* stream);
+
+/* ---- binary morphology of a mask volume (csrc/kernels_morph.hip; exact against tests/morph_oracle.py and scipy.ndimage) ----
+ * All volumes: [X, Y, Z] in Fortran order, X Y Z < 2^31; a mask's foreground = non-zero; results are uint8 0 / 1.  Every refusal is UNET_E_ARG with nothing launched; a
+ * volume with a zero dimension touches nothing.  counts (nullable): device int64 [Z], 8-byte aligned, the set voxels of every slice of the result, as unet_vol_unslice
+ * reports them (integer sums: exact, the same on every run).
+ *
+ * unet_vol_morph: op on the structuring element s = generate_binary_structure(3, connectivity) (connectivity 1, 2, 3 = 6, 18, 26 neighbours + the centre), or, with
+ * planar != 0, s with its z = -1 and z = +1 planes cleared (connectivity 1, 2 only: every axial slice is processed on its own).  One step:
+ *     dilate:  out[v] = OR over o in s of m[v + o]          erode:  out[v] = AND over o in s of m[v + o]
+ * where m outside the volume is border_value (0 or 1) at EVERY step -- scipy.ndimage.binary_dilation / binary_erosion(mask, s, iterations, border_value=b).
+ *     UNET_MORPH_DILATE / _ERODE: `iterations` steps;  _OPEN: `iterations` erosions then as many dilations;  _CLOSE: dilations then erosions, all with the same
+ * border_value -- scipy.ndimage.binary_opening / binary_closing(mask, s, iterations, border_value=b).  iterations outside 1..UNET_VOL_MORPH_MAX_ITERATIONS, another op,
+ * connectivity or border_value: UNET_E_ARG.  out (X Y Z bytes) must not overlap the mask.  ws: unet_vol_morph_ws_bytes(X, Y, Z) bytes, 16-byte aligned: two volumes of
+ * one bit per voxel (rows padded to 64 voxels).  The byte volume is read once (pack) and written once (unpack, with the counts); each step is one launch over the packed
+ * words: 2 + steps launches.  X need not be a multiple of anything (a multiple of 16 with 16-byte aligned buffers takes the 16-byte path). */
+enum { UNET_MORPH_DILATE = 0, UNET_MORPH_ERODE = 1, UNET_MORPH_OPEN = 2, UNET_MORPH_CLOSE = 3 };
+#define UNET_VOL_MORPH_MAX_ITERATIONS 64
+size_t unet_vol_morph_ws_bytes(int32_t X, int32_t Y, int32_t Z);
+int32_t unet_vol_morph(unet_ctx*, const uint8_t* mask, int32_t X, int32_t Y, int32_t Z, int32_t op, int32_t connectivity, int32_t planar, int32_t iterations,
+                       int32_t border_value, uint8_t* out, int64_t* counts, void* ws, size_t ws_bytes, void* stream);
+/* out[v] = d2[v] <= r2 (keep_le != 0) or d2[v] > r2 (keep_le == 0), d2 the result of unet_vol_edt_sq (X Y Z doubles), r2 = fl(r r) squared by the caller in float64,
+ * finite and >= 0.  With d2 = the distance to the mask's foreground, `<=` is the dilation of the mask by the closed ball of radius r in the unit of the transform's
+ * weights; with d2 = the distance to the mask's background, `>` is its erosion by that ball; both exact by the definition of d2.  The transform has no feature outside
+ * the volume: the erosion treats the outside as FOREGROUND (a mask without background is kept whole), the dilation as background.  out must not overlap d2. */
+int32_t unet_vol_ball(unet_ctx*, const double* d2, int32_t X, int32_t Y, int32_t Z, double r2, int32_t keep_le, uint8_t* out, int64_t* counts, void* stream);
+/* scipy.ndimage.binary_fill_holes(mask, s), s as for unet_vol_morph (connectivity 1..3, or planar with 1..2): out = mask | every component of the mask's ZERO voxels
+ * under s's connectivity that holds no voxel of the border -- the six faces of the volume, or, planar, the four edges of each slice.  The components are unet_vol_label's
+ * (unet_vol_label_planar's) of the complement; one pass over the faces marks the labels found there (same-value byte stores); a last pass writes out and the counts.
+ * Nothing iterates until stable: 7 + 2 launches whatever the mask.  out must not overlap the mask.  ws: unet_vol_fill_holes_ws_bytes(X, Y, Z) bytes, 16-byte aligned
+ * (the labels, one byte per possible label, the label workspace: about 7 bytes per voxel). */
+size_t unet_vol_fill_holes_ws_bytes(int32_t X, int32_t Y, int32_t Z);
+int32_t unet_vol_fill_holes(unet_ctx*, const uint8_t* mask, int32_t X, int32_t Y, int32_t Z, int32_t connectivity, int32_t planar, uint8_t* out, int64_t* counts, void* ws,
+                            size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Model level. Replaces the Keras Model built at T1:853-916 and driven by

@@ -22,6 +22,8 @@ ARCH_UNET, ARCH_UNETPP, ARCH_CLASSIFIER = 0, 1, 2
 LOSSES = {"bce_dice_loss": 0, "binary_crossentropy": 1, "dice_loss": 2, "tversky_loss": 3, "weighted_bce_dice_loss": 4}
 DTYPE_F32, DTYPE_BF16 = 0, 1
 ACT_NONE, ACT_RELU, ACT_ELU = 0, 1, 2
+MORPH_OPS = {"dilate": 0, "erode": 1, "open": 2, "close": 3}          # include/unet_hip.h UNET_MORPH_*
+MORPH_MAX_ITERATIONS = 64
 MASK_NONE, MASK_RELU, MASK_ELU, MASK_ELU_DROP = 0, 1, 2, 3
 PROG_FWD_TRAIN, PROG_BWD, PROG_FWD_INFER = 0, 1, 2
 SYNC_BN_FWD, SYNC_LOSS, SYNC_BN_BWD, SYNC_GRAD_BUCKET = 0, 1, 2, 3
@@ -189,6 +191,13 @@ _PROTOS = {
     "unet_vol_sqrt_f64": (i32, [vp, vp, i64, vp]),
     "unet_vol_surface_distances": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, i64, vp, sz, vp]),
     "unet_vol_lesion_overlap": (i32, [vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp]),
+    # binary morphology of a mask volume (csrc/kernels_morph.hip, volume.binary_closing / fill_holes / postprocess)
+    "unet_vol_label_planar": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
+    "unet_vol_morph_ws_bytes": (sz, [i32, i32, i32]),
+    "unet_vol_morph": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
+    "unet_vol_ball": (i32, [vp, vp, i32, i32, i32, f64, i32, vp, vp, vp]),
+    "unet_vol_fill_holes_ws_bytes": (sz, [i32, i32, i32]),
+    "unet_vol_fill_holes": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
     "unet_model_create": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(vp)]),
     "unet_model_dtype": (i32, [vp]),
     "unet_model_tap_elem_bytes": (i32, [vp, C.c_char_p, i32]),

@@ -457,6 +457,9 @@ int32_t k_convT_bf16_wgrad(unet_ctx*, const unet_bf16* x, const unet_bf16* dy, i
                            int wd, int cin, int cout, hipStream_t s);
 size_t wgrad_reduce_scratch_floats(int taps, int ca, int cb, int cbias, int nslabs);
 int32_t k_wgrad_reduce(unet_ctx*, float* part, int nslabs, int taps, int ca, int cb, int cbias, float* dw, float* db, hipStream_t s);
+// connected components (kernels_components.hip): the launches of unet_vol_label with the planar predicate and the complement as options (kernels_morph.hip labels the background)
+int32_t k_vol_label(unet_ctx*, const uint8_t* mask, int X, int Y, int Z, int connectivity, int planar, int invert, int32_t* labels, int32_t* n_out, void* ws, size_t ws_bytes,
+                    hipStream_t s);
 // first layer (cin = 1): fp32 image in, bf16 activations out / bf16 gradient in (kernels_conv_naive.hip)
 int32_t k_conv3x3_c1_fwd_bf16(unet_ctx*, const float* x, const float* w, const float* bias, unet_bf16* y, int n, int h, int wd, int cout, int act,
                               float rate, uint64_t seed, hipStream_t s);

@@ -1,5 +1,6 @@
 // Connected components of a mask volume on the device: labels, per-component statistics, filtering by a keep table.
 //   skimage.measure.label(mask != 0, connectivity=c) / scipy.ndimage.label(mask, generate_binary_structure(3, c))          unet_vol_label
+//   scipy.ndimage.label with that structure's z = -1, +1 planes cleared: components inside every axial slice                                          unet_vol_label_planar
 //   skimage.measure.regionprops' area / bbox / centroid sums, as exact integers                                              unet_vol_component_stats
 //   skimage.morphology.remove_small_objects, "keep the k largest" (the keep table is the caller's)                          unet_vol_filter_components
 // The volume is [X, Y, Z] in Fortran order (f = x + X (y + Y z), what unet_vol_unslice writes); a component's number is the rank of the smallest C-order
@@ -36,6 +37,9 @@ __device__ __forceinline__ void cc_f_to_xyz(const cc_dims& d, long long f, int* 
 }
 // neighbour offset (dx, dy, dz) belongs to connectivity c when it moves along at most c axes
 __device__ __forceinline__ bool cc_conn(int dx, int dy, int dz, int c) { return (dx != 0) + (dy != 0) + (dz != 0) <= c; }
+// the planar predicate (unet_vol_label_planar): the same rule inside one axial slice -- c = 1, 2: 4, 8 neighbours; nothing joins two slices
+__device__ __forceinline__ bool cc_conn_planar(int dx, int dy, int dz, int c) { return dz == 0 && (dx != 0) + (dy != 0) <= c; }
+__device__ __forceinline__ bool cc_joined(int dx, int dy, int dz, int c, int planar) { return planar ? cc_conn_planar(dx, dy, dz, c) : cc_conn(dx, dy, dz, c); }
 
 // ---- (a) brick-local union-find in LDS -------------------------------------------------------------------------------------------------------
 // local index l = (lx * 8 + ly) * 8 + lz: the same order as the global key inside a brick, so the smallest l of a set is its smallest key.
@@ -63,7 +67,7 @@ __device__ __forceinline__ void lds_union(int* P, int a, int b) {
 }
 
 template <bool VEC>
-__global__ __launch_bounds__(TPB) void cc_local_kernel(const uint8_t* __restrict__ mask, cc_dims d, int conn, int nbx, int nby, int32_t* __restrict__ labels) {
+__global__ __launch_bounds__(TPB) void cc_local_kernel(const uint8_t* __restrict__ mask, cc_dims d, int conn, int planar, int invert, int nbx, int nby, int32_t* __restrict__ labels) {
   __shared__ int P[BRICK + 4];
   const int tid = threadIdx.x;
   const int b = blockIdx.x;
@@ -83,6 +87,10 @@ __global__ __launch_bounds__(TPB) void cc_local_kernel(const uint8_t* __restrict
 #pragma unroll
     for (int i = 0; i < 16; ++i) fg |= (row_in && gx0 + i < d.X && mask[f0 + i]) ? (1u << i) : 0u;
   }
+  if (invert) {                                                       // the complement (unet_vol_fill_holes): only the voxels inside the volume turn
+    const int in = row_in ? min(max(d.X - gx0, 0), 16) : 0;
+    fg = ~fg & ((1u << in) - 1u);
+  }
   const int l0 = ((seg * 16) * BY + ly) * BZ + lz;                    // lx = seg * 16 + i -> l = l0 + 64 i
 #pragma unroll
   for (int i = 0; i < 16; ++i) P[sidx(l0 + 64 * i)] = ((fg >> i) & 1u) ? l0 + 64 * i : -1;
@@ -92,7 +100,7 @@ __global__ __launch_bounds__(TPB) void cc_local_kernel(const uint8_t* __restrict
     const int lx = seg * 16 + i, l = l0 + 64 * i;
     for (int o = 14; o < 27; ++o) {                                  // the 13 offsets after (0, 0, 0) in (dx, dy, dz) order: each pair once
       const int dx = o / 9 - 1, dy = (o / 3) % 3 - 1, dz = o % 3 - 1;
-      if (!cc_conn(dx, dy, dz, conn)) continue;
+      if (!cc_joined(dx, dy, dz, conn, planar)) continue;
       const int nx = lx + dx, ny = ly + dy, nz = lz + dz;
       if (nx >= BX || ny < 0 || ny >= BY || nz < 0 || nz >= BZ) continue;
       const int nl = (nx * BY + ny) * BZ + nz;
@@ -144,7 +152,7 @@ __device__ __forceinline__ void g_union(int32_t* labels, const cc_dims& d, int a
 }
 // one thread per voxel of the planes x = 64 i, y = 8 j, z = 8 k (i, j, k >= 1): its nine neighbours one step DOWN that axis.  Two adjacent voxels of
 // different bricks differ in the brick coordinate of at least one axis; there the higher one lies on such a plane and the lower one is among its nine.
-__global__ __launch_bounds__(TPB) void cc_merge_kernel(int32_t* labels, cc_dims d, int conn, long long PX, long long PY, long long PZ) {
+__global__ __launch_bounds__(TPB) void cc_merge_kernel(int32_t* labels, cc_dims d, int conn, int planar, long long PX, long long PY, long long PZ) {
   const long long total = PX + PY + PZ;
   for (long long i = (long long)blockIdx.x * TPB + threadIdx.x; i < total; i += (long long)gridDim.x * TPB) {
     int axis, x, y, z;
@@ -156,7 +164,7 @@ __global__ __launch_bounds__(TPB) void cc_merge_kernel(int32_t* labels, cc_dims 
     for (int u = -1; u <= 1; ++u)
       for (int v = -1; v <= 1; ++v) {
         const int dx = axis == 0 ? -1 : u, dy = axis == 1 ? -1 : (axis == 0 ? u : v), dz = axis == 2 ? -1 : v;
-        if (!cc_conn(dx, dy, dz, conn)) continue;
+        if (!cc_joined(dx, dy, dz, conn, planar)) continue;
         const int nx = x + dx, ny = y + dy, nz = z + dz;
         if (nx < 0 || nx >= d.X || ny < 0 || ny >= d.Y || nz < 0 || nz >= d.Z) continue;
         const int bk = g_load(labels + cc_f(d, nx, ny, nz));
@@ -399,21 +407,10 @@ inline long long cc_chunks(long long N) { return (N + CHUNK - 1) / CHUNK; }
 constexpr long long GRID_CAP = 256 * 32;                             // grid-stride launches: 32 workgroups per CU
 }  // namespace
 
-extern "C" {
-
-size_t unet_vol_label_ws_bytes(int32_t X, int32_t Y, int32_t Z) {
-  if (!cc_dims_ok(X, Y, Z)) return 0;
-  const long long N = (long long)X * Y * Z;
-  if (N == 0) return 0;
-  return cc_flag_bytes(N) + (size_t)((cc_chunks(N) * sizeof(int32_t) + 15) / 16 * 16);
-}
-
-int32_t unet_vol_label(unet_ctx* ctx, const uint8_t* mask, int32_t X, int32_t Y, int32_t Z, int32_t connectivity, int32_t* labels, int32_t* n_out, void* ws, size_t ws_bytes,
-                       void* stream) {
-  if (!ctx || !n_out) UNET_FAIL(ctx, UNET_E_ARG, "vol_label: bad args");
-  if (connectivity < 1 || connectivity > 3) UNET_FAIL(ctx, UNET_E_ARG, "vol_label: connectivity %d is not 1 (6 neighbours), 2 (18) or 3 (26)", connectivity);
+// the launches behind unet_vol_label / unet_vol_label_planar / unet_vol_fill_holes (invert: the components of the mask's ZERO voxels); connectivity is the caller's to check
+int32_t k_vol_label(unet_ctx* ctx, const uint8_t* mask, int X, int Y, int Z, int connectivity, int planar, int invert, int32_t* labels, int32_t* n_out, void* ws, size_t ws_bytes,
+                    hipStream_t s) {
   if (!cc_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_label: %d x %d x %d is negative or has 2^31 voxels or more", X, Y, Z);
-  hipStream_t s = as_stream(stream);
   const cc_dims d = cc_make(X, Y, Z);
   if (d.N == 0) { UNET_HIP(ctx, hipMemsetAsync(n_out, 0, sizeof(int32_t), s)); return UNET_OK; }
   if (!mask || !labels || !ws) UNET_FAIL(ctx, UNET_E_ARG, "vol_label: bad args");
@@ -428,11 +425,11 @@ int32_t unet_vol_label(unet_ctx* ctx, const uint8_t* mask, int32_t X, int32_t Y,
   const long long bricks = (long long)nbx * nby * nbz;
   if (bricks > 0x7FFFFFFFLL) UNET_FAIL(ctx, UNET_E_ARG, "vol_label: too many bricks");
   if ((X % 16) == 0 && (reinterpret_cast<uintptr_t>(mask) % 16) == 0)
-    hipLaunchKernelGGL(cc_local_kernel<true>, dim3((unsigned)bricks), dim3(TPB), 0, s, mask, d, connectivity, nbx, nby, labels);
+    hipLaunchKernelGGL(cc_local_kernel<true>, dim3((unsigned)bricks), dim3(TPB), 0, s, mask, d, connectivity, planar, invert, nbx, nby, labels);
   else
-    hipLaunchKernelGGL(cc_local_kernel<false>, dim3((unsigned)bricks), dim3(TPB), 0, s, mask, d, connectivity, nbx, nby, labels);
+    hipLaunchKernelGGL(cc_local_kernel<false>, dim3((unsigned)bricks), dim3(TPB), 0, s, mask, d, connectivity, planar, invert, nbx, nby, labels);
   const long long PX = (long long)(nbx - 1) * Y * Z, PY = (long long)(nby - 1) * X * Z, PZ = (long long)(nbz - 1) * X * Y;
-  if (PX + PY + PZ > 0) hipLaunchKernelGGL(cc_merge_kernel, dim3(cc_blocks(PX + PY + PZ, GRID_CAP)), dim3(TPB), 0, s, labels, d, connectivity, PX, PY, PZ);
+  if (PX + PY + PZ > 0) hipLaunchKernelGGL(cc_merge_kernel, dim3(cc_blocks(PX + PY + PZ, GRID_CAP)), dim3(TPB), 0, s, labels, d, connectivity, planar, PX, PY, PZ);
   const long long quads = (d.N + 3) / 4;
   hipLaunchKernelGGL(cc_flatten_kernel, dim3(cc_blocks(quads, GRID_CAP)), dim3(TPB), 0, s, labels, d, flags);
   hipLaunchKernelGGL(cc_count_kernel, dim3((unsigned)nb), dim3(TPB), 0, s, flags, (long long)npad, bsum);
@@ -440,6 +437,29 @@ int32_t unet_vol_label(unet_ctx* ctx, const uint8_t* mask, int32_t X, int32_t Y,
   hipLaunchKernelGGL(cc_number_kernel, dim3((unsigned)nb), dim3(TPB), 0, s, flags, (long long)npad, bsum, d, labels);
   hipLaunchKernelGGL(cc_final_kernel, dim3(cc_blocks(quads, GRID_CAP)), dim3(TPB), 0, s, labels, d);
   UNET_CHECK_LAUNCH(ctx, "vol_label"); return UNET_OK;
+}
+
+extern "C" {
+
+size_t unet_vol_label_ws_bytes(int32_t X, int32_t Y, int32_t Z) {
+  if (!cc_dims_ok(X, Y, Z)) return 0;
+  const long long N = (long long)X * Y * Z;
+  if (N == 0) return 0;
+  return cc_flag_bytes(N) + (size_t)((cc_chunks(N) * sizeof(int32_t) + 15) / 16 * 16);
+}
+
+int32_t unet_vol_label(unet_ctx* ctx, const uint8_t* mask, int32_t X, int32_t Y, int32_t Z, int32_t connectivity, int32_t* labels, int32_t* n_out, void* ws, size_t ws_bytes,
+                       void* stream) {
+  if (!ctx || !n_out) UNET_FAIL(ctx, UNET_E_ARG, "vol_label: bad args");
+  if (connectivity < 1 || connectivity > 3) UNET_FAIL(ctx, UNET_E_ARG, "vol_label: connectivity %d is not 1 (6 neighbours), 2 (18) or 3 (26)", connectivity);
+  return k_vol_label(ctx, mask, X, Y, Z, connectivity, 0, 0, labels, n_out, ws, ws_bytes, as_stream(stream));
+}
+
+int32_t unet_vol_label_planar(unet_ctx* ctx, const uint8_t* mask, int32_t X, int32_t Y, int32_t Z, int32_t connectivity, int32_t* labels, int32_t* n_out, void* ws, size_t ws_bytes,
+                              void* stream) {
+  if (!ctx || !n_out) UNET_FAIL(ctx, UNET_E_ARG, "vol_label_planar: bad args");
+  if (connectivity < 1 || connectivity > 2) UNET_FAIL(ctx, UNET_E_ARG, "vol_label_planar: connectivity %d is not 1 (4 neighbours in the slice) or 2 (8)", connectivity);
+  return k_vol_label(ctx, mask, X, Y, Z, connectivity, 1, 0, labels, n_out, ws, ws_bytes, as_stream(stream));
 }
 
 int32_t unet_vol_component_stats(unet_ctx* ctx, const int32_t* labels, int32_t X, int32_t Y, int32_t Z, int32_t n, void* stats, void* stream) {

@@ -10,6 +10,10 @@ the dataset loop around it (T1:390-393, 421-429) and the way back from a predict
     surface(mask, connectivity)           -> the mask's surface voxels (mask ^ binary_erosion)
     distance_transform(mask, pixdim)      -> float64 distance of every foreground voxel to the background, in mm (scipy's distance_transform_edt with sampling=)
     score_volume(pred, truth, pixdim)     -> VolumeScore: Dice / IoU / volume error, Hausdorff / HD95 / surface distances in mm, lesion-wise detection
+    binary_dilation / _erosion / _opening / _closing(mask, connectivity, iterations, border_value, per_slice)     scipy.ndimage's, on the device
+    dilate_mm / erode_mm / open_mm / close_mm(mask, radius_mm, pixdim)     the same by a ball of radius_mm millimetres, from the exact distance transform
+    fill_holes(mask, connectivity, per_slice)     scipy.ndimage.binary_fill_holes
+    postprocess(mask, steps, pixdim)      a list of (name, kwargs) cleaning steps applied in order on the device; segment_volume(postprocess=steps) runs it
 
 The voxels are uploaded once as stored (nifti_min reads the file); decode, np.rot90, the slice trim, cv2.resize(float64, INTER_AREA) and the min-max run
 in unet_vol_slices_f64, CLAHE / crop / fuse / resize in the uint8 kernels of preprocess.py on device pointers: between the upload and the returned batch
@@ -281,7 +285,8 @@ class VolumeSegmentation:
     """mask: uint8 [X, Y, Z] in the CT's own geometry (numpy, Fortran order); voxel_ml; counts / ml_per_slice [Z] (0 on the trimmed slices); total_ml;
     lung_ml and infected_share when a lung mask was given; fell_through / flat: kept-range slice numbers; z0, z1; seconds: where the time went;
     lesions / n_lesions / removed_ml: the component table of the mask, its length and the volume a min_lesion_ml filter removed (None when not asked for);
-    score: the VolumeScore of the final mask against the `truth` given to segment_volume (None without one)."""
+    score: the VolumeScore of the final mask against the `truth` given to segment_volume (None without one);
+    postprocess_ml: the volume the `postprocess` steps added to the mask (negative: removed; None without steps)."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -346,8 +351,18 @@ def _mask_to_device(mask, shape=None):
     return torch.from_numpy(flat).cuda(), tuple(int(v) for v in a.shape)
 
 
-def label_device(mask_dev, shape, connectivity=1):
-    """unet_vol_label on a device mask -> (labels: int32 device tensor of X*Y*Z elements in Fortran order, n)."""
+def _check_structure(connectivity, per_slice):
+    """the structuring element of the morphology / per-slice labelling: generate_binary_structure(3, connectivity), per_slice: without its z = -1, +1 planes"""
+    if per_slice:
+        if connectivity not in (1, 2):
+            raise ValueError(f"per_slice: connectivity must be 1 (4 neighbours in the slice) or 2 (8), not {connectivity!r}")
+        return int(connectivity)
+    return _check_connectivity(connectivity)
+
+
+def label_device(mask_dev, shape, connectivity=1, per_slice=False):
+    """unet_vol_label (per_slice: unet_vol_label_planar) on a device mask -> (labels: int32 device tensor of X*Y*Z elements in Fortran order, n)."""
+    connectivity = _check_structure(connectivity, per_slice)
     torch = _torch(); lib, ctx = _ctx()
     X, Y, Z = shape
     if X * Y * Z >= 2 ** 31:
@@ -355,16 +370,20 @@ def label_device(mask_dev, shape, connectivity=1):
     labels = torch.empty(X * Y * Z, dtype=torch.int32, device="cuda")
     n_dev = torch.zeros(1, dtype=torch.int32, device="cuda")
     ws = torch.empty(max(int(lib.unet_vol_label_ws_bytes(X, Y, Z)), 16), dtype=torch.uint8, device="cuda")
-    ctx.check(lib.unet_vol_label(ctx.handle, mask_dev.data_ptr(), X, Y, Z, _check_connectivity(connectivity), labels.data_ptr(), n_dev.data_ptr(), ws.data_ptr(), ws.numel(),
-                                 _stream()), "vol_label")
+    entry = lib.unet_vol_label_planar if per_slice else lib.unet_vol_label
+    ctx.check(entry(ctx.handle, mask_dev.data_ptr(), X, Y, Z, connectivity, labels.data_ptr(), n_dev.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+              "vol_label_planar" if per_slice else "vol_label")
     return labels, int(n_dev.item())
 
 
-def label_volume(mask, connectivity=1, return_device=False, shape=None):
+def label_volume(mask, connectivity=1, return_device=False, shape=None, per_slice=False):
     """Connected components of mask != 0 -> (labels, n): int32 [X, Y, Z] (numpy, Fortran order; return_device=True: the flat device tensor), 0 on the background,
-    components 1..n in the order of their first voxel in C order -- skimage.measure.label(mask != 0, connectivity=connectivity) element for element."""
+    components 1..n in the order of their first voxel in C order -- skimage.measure.label(mask != 0, connectivity=connectivity) element for element.
+    per_slice=True: components never cross from one axial slice to the next (connectivity 1, 2 = 4, 8 neighbours in the slice): scipy.ndimage.label(mask, s) with
+    s = generate_binary_structure(3, connectivity) and s[:, :, 0] = s[:, :, 2] = False; the numbering rule is the same."""
+    _check_structure(connectivity, per_slice)
     dev, shape = _mask_to_device(mask, shape)
-    labels, n = label_device(dev, shape, connectivity)
+    labels, n = label_device(dev, shape, connectivity, per_slice)
     return (labels if return_device else labels.cpu().numpy().reshape(shape, order="F")), n
 
 
@@ -717,18 +736,280 @@ def score_volume(pred, truth, pixdim=(1, 1, 1), connectivity=1, lesion_connectiv
                  lesion_precision=_ratio(mat, npred), missed_lesions=nt - det, false_positive_lesions=npred - mat)
     return VolumeScore(**f)
 
+# ---- binary morphology of a mask volume (csrc/kernels_morph.hip) ----------------------------------------------------------------
+MORPH_MAX_ITERATIONS = _lib.MORPH_MAX_ITERATIONS                     # UNET_VOL_MORPH_MAX_ITERATIONS
+
+
+def _check_mask_host(mask, shape=None):
+    """what _mask_to_device refuses, before anything is uploaded or launched"""
+    torch = _torch()
+    if isinstance(mask, torch.Tensor):
+        if shape is None:
+            raise ValueError("a device mask is a flat Fortran-order byte buffer: pass shape=(X, Y, Z)")
+        return
+    a = np.asarray(mask)
+    if a.ndim != 3:
+        raise ValueError(f"a volume is [X, Y, Z]; got {a.ndim} dimensions")
+    if a.dtype.kind not in "biu":
+        raise ValueError(f"a mask has a bool or integer dtype, not {a.dtype}")
+
+
+def _check_morph(op, connectivity, iterations, border_value, per_slice):
+    if op not in _lib.MORPH_OPS:
+        raise ValueError(f"op must be one of {tuple(_lib.MORPH_OPS)}, not {op!r}")
+    connectivity = _check_structure(connectivity, per_slice)
+    if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or not 1 <= iterations <= MORPH_MAX_ITERATIONS:
+        raise ValueError(f"iterations must be an integer in 1..{MORPH_MAX_ITERATIONS} (scipy's iterations < 1, \"until stable\", is not offered), not {iterations!r}")
+    if border_value not in (0, 1):
+        raise ValueError(f"border_value must be 0 or 1, not {border_value!r}")
+    return connectivity, int(iterations), int(border_value)
+
+
+def _check_radius(radius_mm):
+    try:
+        r = float(radius_mm)
+    except (TypeError, ValueError):
+        raise ValueError(f"radius_mm is a finite number >= 0, not {radius_mm!r}") from None
+    if not (np.isfinite(r) and r >= 0.0 and np.isfinite(r * r)):
+        raise ValueError(f"radius_mm is a finite number >= 0 (with a finite square), not {radius_mm!r}")
+    return r
+
+
+def morph_device(mask_dev, shape, op, connectivity=1, iterations=1, border_value=0, per_slice=False):
+    """unet_vol_morph on a device mask -> (result: uint8 device tensor of X*Y*Z bytes in Fortran order, counts: int64 [Z] device tensor, the set voxels per slice)"""
+    connectivity, iterations, border_value = _check_morph(op, connectivity, iterations, border_value, per_slice)
+    torch = _torch(); lib, ctx = _ctx()
+    X, Y, Z = shape
+    _check_volume_dims(shape)
+    out = torch.empty(X * Y * Z, dtype=torch.uint8, device="cuda")
+    counts = torch.zeros(Z, dtype=torch.int64, device="cuda")
+    ws = torch.empty(max(int(lib.unet_vol_morph_ws_bytes(X, Y, Z)), 16), dtype=torch.uint8, device="cuda")
+    ctx.check(lib.unet_vol_morph(ctx.handle, mask_dev.data_ptr(), X, Y, Z, _lib.MORPH_OPS[op], connectivity, 1 if per_slice else 0, iterations, border_value, out.data_ptr(),
+                                 counts.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "vol_morph")
+    return out, counts
+
+
+def ball_device(mask_dev, shape, radius_mm, pixdim, dilate):
+    """The mask dilated (dilate=True) or eroded by the closed ball of radius_mm: unet_vol_edt_sq to the foreground / to the background, then unet_vol_ball with
+    r2 = fl(r r) -> (result device bytes, counts int64 [Z] device)"""
+    r = _check_radius(radius_mm)
+    torch = _torch(); lib, ctx = _ctx()
+    X, Y, Z = shape
+    d2 = edt_sq_device(mask_dev, shape, pixdim, features_nonzero=bool(dilate))
+    out = torch.empty(X * Y * Z, dtype=torch.uint8, device="cuda")
+    counts = torch.zeros(Z, dtype=torch.int64, device="cuda")
+    ctx.check(lib.unet_vol_ball(ctx.handle, d2.data_ptr(), X, Y, Z, r * r, 1 if dilate else 0, out.data_ptr(), counts.data_ptr(), _stream()), "vol_ball")
+    return out, counts
+
+
+def fill_holes_device(mask_dev, shape, connectivity=1, per_slice=False):
+    """unet_vol_fill_holes on a device mask -> (result device bytes, counts int64 [Z] device)"""
+    connectivity = _check_structure(connectivity, per_slice)
+    torch = _torch(); lib, ctx = _ctx()
+    X, Y, Z = shape
+    _check_volume_dims(shape)
+    out = torch.empty(X * Y * Z, dtype=torch.uint8, device="cuda")
+    counts = torch.zeros(Z, dtype=torch.int64, device="cuda")
+    ws = torch.empty(max(int(lib.unet_vol_fill_holes_ws_bytes(X, Y, Z)), 16), dtype=torch.uint8, device="cuda")
+    ctx.check(lib.unet_vol_fill_holes(ctx.handle, mask_dev.data_ptr(), X, Y, Z, connectivity, 1 if per_slice else 0, out.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel(),
+                                      _stream()), "vol_fill_holes")
+    return out, counts
+
+
+def _result(dev, shape, return_device):
+    return dev if return_device else dev.cpu().numpy().reshape(shape, order="F")
+
+
+def _binary(op, mask, connectivity, iterations, border_value, per_slice, return_device, shape):
+    _check_morph(op, connectivity, iterations, border_value, per_slice)
+    _check_mask_host(mask, shape)
+    dev, shape = _mask_to_device(mask, shape)
+    return _result(morph_device(dev, shape, op, connectivity, iterations, border_value, per_slice)[0], shape, return_device)
+
+
+def binary_dilation(mask, connectivity=1, iterations=1, border_value=0, per_slice=False, return_device=False, shape=None):
+    """scipy.ndimage.binary_dilation(mask != 0, generate_binary_structure(3, connectivity), iterations=iterations, border_value=border_value) as uint8 0 / 1, element for
+    element.  connectivity 1, 2, 3 = 6, 18, 26 neighbours; iterations 1..64; border_value 0 / 1: what the voxels outside the volume hold at every step.  per_slice=True:
+    the structure without its z = -1 and z = +1 planes (connectivity 1 or 2): every axial slice on its own."""
+    return _binary("dilate", mask, connectivity, iterations, border_value, per_slice, return_device, shape)
+
+
+def binary_erosion(mask, connectivity=1, iterations=1, border_value=0, per_slice=False, return_device=False, shape=None):
+    """scipy.ndimage.binary_erosion with the structure and parameters of binary_dilation.  border_value=0 erodes from the volume's faces, 1 does not."""
+    return _binary("erode", mask, connectivity, iterations, border_value, per_slice, return_device, shape)
+
+
+def binary_opening(mask, connectivity=1, iterations=1, border_value=0, per_slice=False, return_device=False, shape=None):
+    """scipy.ndimage.binary_opening: `iterations` erosions, then as many dilations, all with the same border_value."""
+    return _binary("open", mask, connectivity, iterations, border_value, per_slice, return_device, shape)
+
+
+def binary_closing(mask, connectivity=1, iterations=1, border_value=0, per_slice=False, return_device=False, shape=None):
+    """scipy.ndimage.binary_closing: `iterations` dilations, then as many erosions, all with the same border_value (with 0, the erosions eat into what touches a face)."""
+    return _binary("close", mask, connectivity, iterations, border_value, per_slice, return_device, shape)
+
+
+def _ball(ops, mask, radius_mm, pixdim, return_device, shape):
+    _check_radius(radius_mm); _check_pixdim(pixdim)
+    _check_mask_host(mask, shape)
+    dev, shape = _mask_to_device(mask, shape)
+    for dilate in ops:
+        dev, _ = ball_device(dev, shape, radius_mm, pixdim, dilate)
+    return _result(dev, shape, return_device)
+
+
+def dilate_mm(mask, radius_mm, pixdim=(1, 1, 1), return_device=False, shape=None):
+    """The mask dilated by the closed ball of radius_mm millimetres under the voxel spacing pixdim: every voxel whose exact squared distance to the foreground
+    (unet_vol_edt_sq, include/unet_hip.h) is <= fl(radius_mm^2).  Nothing outside the volume is foreground."""
+    return _ball((True,), mask, radius_mm, pixdim, return_device, shape)
+
+
+def erode_mm(mask, radius_mm, pixdim=(1, 1, 1), return_device=False, shape=None):
+    """The mask eroded by that ball: every voxel whose squared distance to the background is > fl(radius_mm^2).  The distance transform has no feature outside the
+    volume, so the outside counts as FOREGROUND here: a lesion that touches a face is not eroded from that face, and a mask without background stays whole."""
+    return _ball((False,), mask, radius_mm, pixdim, return_device, shape)
+
+
+def open_mm(mask, radius_mm, pixdim=(1, 1, 1), return_device=False, shape=None):
+    """erode_mm, then dilate_mm: removes what the ball does not fit into"""
+    return _ball((False, True), mask, radius_mm, pixdim, return_device, shape)
+
+
+def close_mm(mask, radius_mm, pixdim=(1, 1, 1), return_device=False, shape=None):
+    """dilate_mm, then erode_mm: closes gaps narrower than the ball (the erosion's outside is foreground, so nothing is lost at the faces)"""
+    return _ball((True, False), mask, radius_mm, pixdim, return_device, shape)
+
+
+def fill_holes(mask, connectivity=1, per_slice=False, return_device=False, shape=None):
+    """scipy.ndimage.binary_fill_holes(mask != 0, generate_binary_structure(3, connectivity)) as uint8 0 / 1: the mask plus every background component (under that
+    connectivity) that does not reach a face of the volume.  per_slice=True: the structure without its z = -1, +1 planes -- every slice's holes are filled in 2-D, the
+    border being the slice's four edges."""
+    _check_structure(connectivity, per_slice)
+    _check_mask_host(mask, shape)
+    dev, shape = _mask_to_device(mask, shape)
+    return _result(fill_holes_device(dev, shape, connectivity, per_slice)[0], shape, return_device)
+
+
+_MORPH_STEPS = {"dilate": "dilate", "erode": "erode", "open": "open", "close": "close",
+                "binary_dilation": "dilate", "binary_erosion": "erode", "binary_opening": "open", "binary_closing": "close"}
+_BALL_STEPS = {"dilate_mm": (True,), "erode_mm": (False,), "open_mm": (False, True), "close_mm": (True, False)}
+POSTPROCESS_STEPS = tuple(_MORPH_STEPS) + tuple(_BALL_STEPS) + ("fill_holes", "remove_small", "keep_largest")
+_STEP_KEYS = {"morph": {"connectivity", "iterations", "border_value", "per_slice"}, "ball": {"radius_mm", "pixdim"}, "fill_holes": {"connectivity", "per_slice"},
+              "remove_small": {"min_voxels", "min_ml", "pixdim", "connectivity"}, "keep_largest": {"k", "connectivity"}}
+
+
+def _check_steps(steps, pixdim):
+    """-> [(kind, name, kwargs)] with every argument checked on the host: a bad step is refused before the first one runs"""
+    if pixdim is not None:
+        _check_pixdim(pixdim)
+    out = []
+    try:
+        steps = list(steps)
+    except TypeError:
+        raise ValueError(f"steps is a list of (name, kwargs) pairs, not {steps!r}") from None
+    for st in steps:
+        if isinstance(st, str):
+            st = (st, {})
+        if not isinstance(st, (tuple, list)) or len(st) != 2 or not isinstance(st[0], str) or not isinstance(st[1], (dict, type(None))):
+            raise ValueError(f"a step is a (name, kwargs) pair, not {st!r}")
+        name, kw = st[0], dict(st[1] or {})
+        if name not in POSTPROCESS_STEPS:
+            raise ValueError(f"unknown step {name!r}: one of {POSTPROCESS_STEPS}")
+        kind = "morph" if name in _MORPH_STEPS else "ball" if name in _BALL_STEPS else name
+        extra = set(kw) - _STEP_KEYS[kind]
+        if extra:
+            raise ValueError(f"step {name!r} takes {sorted(_STEP_KEYS[kind])}, not {sorted(extra)}")
+        if kind == "morph":
+            _check_morph(_MORPH_STEPS[name], kw.get("connectivity", 1), kw.get("iterations", 1), kw.get("border_value", 0), kw.get("per_slice", False))
+        elif kind == "ball":
+            if "radius_mm" not in kw:
+                raise ValueError(f"step {name!r} needs radius_mm")
+            kw.setdefault("pixdim", pixdim)
+            if kw["pixdim"] is None:
+                raise ValueError(f"step {name!r} needs pixdim (the voxel's edge lengths in mm)")
+            _check_radius(kw["radius_mm"]); _check_pixdim(kw["pixdim"])
+        elif kind == "fill_holes":
+            _check_structure(kw.get("connectivity", 1), kw.get("per_slice", False))
+        elif kind == "remove_small":
+            _check_connectivity(kw.get("connectivity", 1))
+            if (kw.get("min_voxels") is None) == (kw.get("min_ml") is None):
+                raise ValueError("remove_small: pass exactly one of min_voxels, min_ml")
+            if kw.get("min_ml") is not None:
+                kw.setdefault("pixdim", pixdim)
+                if kw["pixdim"] is None:
+                    raise ValueError("remove_small: min_ml needs pixdim (the voxel's edge lengths in mm)")
+                kw["min_voxels"] = min_voxels_from_ml(kw["min_ml"], _check_pixdim(kw["pixdim"]))
+            kw["min_voxels"] = int(kw["min_voxels"])
+        else:
+            _check_connectivity(kw.get("connectivity", 1))
+            kw["k"] = int(kw.get("k", 2))
+        out.append((kind, name, kw))
+    return out
+
+
+def _components_step(dev, shape, connectivity, choose):
+    labels, n = label_device(dev, shape, connectivity)
+    st = component_stats_device(labels, shape, n)
+    keep = np.zeros(n + 1, bool)
+    keep[1:] = choose(st["voxels"])
+    return filter_components(labels, keep, n, shape, 0, shape[2])
+
+
+def postprocess_device(mask_dev, shape, steps, pixdim=None):
+    """the checked steps on a device mask -> (result device bytes, counts int64 [Z] device or None when there was no step)"""
+    counts = None
+    for kind, name, kw in _check_steps(steps, pixdim):
+        if kind == "morph":
+            mask_dev, counts = morph_device(mask_dev, shape, _MORPH_STEPS[name], kw.get("connectivity", 1), kw.get("iterations", 1), kw.get("border_value", 0),
+                                            kw.get("per_slice", False))
+        elif kind == "ball":
+            for dilate in _BALL_STEPS[name]:
+                mask_dev, counts = ball_device(mask_dev, shape, kw["radius_mm"], kw["pixdim"], dilate)
+        elif kind == "fill_holes":
+            mask_dev, counts = fill_holes_device(mask_dev, shape, kw.get("connectivity", 1), kw.get("per_slice", False))
+        elif kind == "remove_small":
+            mv = kw["min_voxels"]
+            mask_dev, counts = _components_step(mask_dev, shape, kw.get("connectivity", 1), lambda v: v >= mv)
+        else:
+            def choose(v, k=kw["k"]):
+                sel = np.zeros(v.size, bool)
+                sel[largest_labels(v, k) - 1] = True
+                return sel
+            mask_dev, counts = _components_step(mask_dev, shape, kw.get("connectivity", 1), choose)
+    return mask_dev, counts
+
+
+def postprocess(mask, steps, pixdim=None, return_device=False, shape=None):
+    """The cleaning steps, in order, on the device; the mask goes up once and comes back once.  steps: a list of (name, kwargs) pairs (a bare name: no arguments):
+        "dilate" / "erode" / "open" / "close"              connectivity, iterations, border_value, per_slice          (binary_dilation ... binary_closing)
+        "dilate_mm" / "erode_mm" / "open_mm" / "close_mm"  radius_mm, pixdim (default: this call's pixdim)
+        "fill_holes"                                       connectivity, per_slice
+        "remove_small"                                     min_voxels or min_ml (+ pixdim, default this call's), connectivity
+        "keep_largest"                                     k, connectivity
+    The usual clinical cleaning: [("close", {"iterations": 2}), ("fill_holes", {}), ("remove_small", {"min_ml": 0.05})].  Every step's arguments are checked before the
+    first one runs."""
+    _check_steps(steps, pixdim)
+    _check_mask_host(mask, shape)
+    dev, shape = _mask_to_device(mask, shape)
+    return _result(postprocess_device(dev, shape, steps, pixdim)[0], shape, return_device)
 
 
 def segment_volume(ct, model, lung_mask=None, threshold=0.547, batch_size=32, out_path=None, img_size=512, trim=(0.2, 0.8), min_lesion_ml=None, connectivity=1,
-                   lesions=False, truth=None):
+                   lesions=False, truth=None, postprocess=None):
     """CT file (or array) -> VolumeSegmentation.  `model`: a UNetModel or a routed.ClusterRoutedModel (only `predict` is used); lung_mask=None: whole-frame
     boxes (the two halves of the frame); boxes are keyed by slice number (box_indexing="slice"); out_path: the mask as .nii / .nii.gz with the CT's geometry.
     min_lesion_ml: connected components (`connectivity` 1, 2, 3 = 6, 18, 26 neighbours) smaller than that are removed on the device before the mask comes to the
     host or reaches out_path; counts, ml_per_slice, total_ml, infected_share then describe the filtered mask and removed_ml what went.  lesions=True (or a
     filter): res.lesions = the component_table of the final mask, res.n_lesions its length.  The labels never leave the device.
     truth: the ground-truth mask in the CT's geometry (path or [X, Y, Z] array, foreground = non-zero): the final mask is scored against it before it leaves the
-    device, res.score = score_volume(mask, truth, pixdim, lesion_connectivity=connectivity); None without a truth."""
+    device, res.score = score_volume(mask, truth, pixdim, lesion_connectivity=connectivity); None without a truth.
+    postprocess: a list of steps as volume.postprocess takes them (pixdim: the CT's), run on the device right after the mask volume is formed and before min_lesion_ml,
+    lesions and truth: counts, ml_per_slice, total_ml, infected_share, the lesion table and the score then describe the cleaned mask (counts over all Z slices: a
+    dilation may reach a trimmed slice), res.postprocess_ml is the volume the steps added (negative: removed) and seconds["postprocess"] their time; None: nothing
+    runs and res.postprocess_ml is None."""
     _check_connectivity(connectivity)
+    if postprocess is not None:
+        _check_steps(postprocess, (1.0, 1.0, 1.0))                   # the steps' own arguments, before any work (the CT's pixdim takes this one's place below)
     torch = _torch()
     sec = {}
     t0 = time.perf_counter()
@@ -766,6 +1047,16 @@ def segment_volume(ct, model, lung_mask=None, threshold=0.547, batch_size=32, ou
     canvas = paste_back(prob, R1, R2, S)
     mask_dev, counts_dev = unslice(canvas, threshold, (X, Y, Z), z0, z1)
     voxel_mm3 = float(np.prod(np.asarray(vol.pixdim, np.float64)))          # count * prod(pixdim) / 1000 = millilitres
+    cz0, cz1 = z0, z1                                               # the slices counts_dev speaks about
+    postprocess_ml = None
+    if postprocess is not None:
+        torch.cuda.synchronize(); tp = time.perf_counter()
+        before = int(counts_dev.sum().item())
+        mask_dev, cleaned = postprocess_device(mask_dev, (X, Y, Z), postprocess, vol.pixdim)
+        if cleaned is not None:
+            counts_dev, cz0, cz1 = cleaned, 0, Z
+        postprocess_ml = float(int(counts_dev.sum().item()) - before) * voxel_mm3 / 1000.0
+        torch.cuda.synchronize(); sec["postprocess"] = time.perf_counter() - tp
     table, removed_ml = None, None
     if min_lesion_ml is not None or lesions:
         torch.cuda.synchronize(); tc = time.perf_counter()
@@ -775,7 +1066,7 @@ def segment_volume(ct, model, lung_mask=None, threshold=0.547, batch_size=32, ou
             before = int(counts_dev.sum().item())
             keep = np.zeros(n_comp + 1, bool)
             keep[1:] = table["voxels"] >= min_voxels_from_ml(min_lesion_ml, vol.pixdim)
-            mask_dev, counts_dev = filter_components(labels_dev, keep, n_comp, (X, Y, Z), z0, z1)
+            mask_dev, counts_dev = filter_components(labels_dev, keep, n_comp, (X, Y, Z), cz0, cz1)
             table = table[keep[1:]]                                  # the kept components keep their order: renumbered, this is the table of the filtered mask
             table["label"] = np.arange(1, len(table) + 1)
             removed_ml = float(before) * voxel_mm3 / 1000.0 - float(counts_dev.sum().item()) * voxel_mm3 / 1000.0
@@ -787,12 +1078,13 @@ def segment_volume(ct, model, lung_mask=None, threshold=0.547, batch_size=32, ou
         score = score_volume(mask_dev, truth_mask, vol.pixdim, lesion_connectivity=connectivity, shape=(X, Y, Z))
         torch.cuda.synchronize(); sec["score"] = time.perf_counter() - ts
     mask = mask_dev.cpu().numpy().reshape((X, Y, Z), order="F")
-    counts = np.zeros(Z, np.int64); counts[z0:z1] = counts_dev.cpu().numpy()
+    counts = np.zeros(Z, np.int64); counts[cz0:cz1] = counts_dev.cpu().numpy()
     sec["paste_unslice"] = time.perf_counter() - t0
     res = VolumeSegmentation(mask=mask, counts=counts, voxel_ml=voxel_mm3 / 1000.0, ml_per_slice=counts * voxel_mm3 / 1000.0,
                              total_ml=float(counts.sum()) * voxel_mm3 / 1000.0, lung_ml=None,
                              infected_share=None, fell_through=[int(i) for i in np.nonzero(~has)[0]], flat=info["flat"], z0=z0, z1=z1, pixdim=vol.pixdim,
-                             threshold=float(threshold), seconds=sec, lesions=table, n_lesions=None if table is None else len(table), removed_ml=removed_ml, score=score)
+                             threshold=float(threshold), seconds=sec, lesions=table, n_lesions=None if table is None else len(table), removed_ml=removed_ml, score=score,
+                             postprocess_ml=postprocess_ml)
     if lv is not None:
         lung_vox = int(np.count_nonzero(lv.get_fdata()[:, :, z0:z1]))
         res.lung_ml = lung_vox * voxel_mm3 / 1000.0
