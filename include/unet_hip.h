@@ -682,6 +682,40 @@ size_t unet_vol_fill_holes_ws_bytes(int32_t X, int32_t Y, int32_t Z);
 int32_t unet_vol_fill_holes(unet_ctx*, const uint8_t* mask, int32_t X, int32_t Y, int32_t Z, int32_t connectivity, int32_t planar, uint8_t* out, int64_t* counts, void* ws,
                             size_t ws_bytes, void* stream);
 
+/* ---- several models and test-time symmetries on one volume (csrc/kernels_ensemble.hip; bit-exact against tests/ensemble_oracle.py) ----
+ * Every entry point checks its arguments first and refuses a bad one with UNET_E_ARG and nothing launched; a zero-sized input (n d d = 0, count = 0, nvox = 0,
+ * X Y Z = 0) is a no-op that returns UNET_OK.  Volumes: [X, Y, Z] in Fortran order, X Y Z < 2^31.  All launches go to the caller's stream.
+ *
+ * unet_vol_dihedral: src, dst float32 [n][d][d] (dst must not overlap src); `code` is one of the eight symmetries of the square, by their numpy meaning on axes (1, 2):
+ *     0 id   1 rot90 = np.rot90(a, 1, (1, 2))   2 rot180   3 rot270   4 hflip = a[:, :, ::-1]   5 vflip = a[:, ::-1, :]   6 transpose = a.swapaxes(1, 2)
+ *     7 antitranspose = rot180 of the transpose.
+ * A copy of 32-bit words: bit-exact, NaN payloads and signed zeros included.  Codes 1, 3, 6, 7 go through a 32 x 33 LDS tile, so both the reads and the writes run along
+ * rows.  The inverse is the same call with the inverse code (1 <-> 3, every other code is its own inverse): the caller owns that table (volume.DIHEDRAL_INVERSE). */
+int32_t unet_vol_dihedral(unet_ctx*, const float* src, int32_t n, int32_t d, int32_t code, float* dst, void* stream);
+/* acc[i] = first ? fl(w c[i]) : fl(acc[i] + fl(w c[i])) for i < count: the product and the sum are rounded on their own (no fused multiply-add), so a numpy float32 loop
+ * that adds the members in the same order gives the same bits.  acc must not overlap the canvas. */
+int32_t unet_vol_canvas_axpy(unet_ctx*, const float* canvas, float w, float* acc, int64_t count, int32_t first, void* stream);
+/* acc[i] = fl(acc[i] / denom) in place: the correctly rounded float32 quotient (x / 1 = x). */
+int32_t unet_vol_canvas_div(unet_ctx*, float* acc, float denom, int64_t count, void* stream);
+/* canvas [z1 - z0][S][S] -> prob float32 [X, Y, Z] (Fortran order), 0 outside [z0, z1): geometry and sampler of unet_vol_unslice without the comparison.  Both kernels
+ * call one device function (csrc/vol_sample.h), so prob[v] > t is unet_vol_unslice's mask[v] for every t, element for element. */
+int32_t unet_vol_unslice_prob(unet_ctx*, const float* canvas, int32_t S, int32_t X, int32_t Y, int32_t Z, int32_t z0, int32_t z1, float* prob, void* stream);
+/* words: uint32 per voxel.  Bit `member` (0..31) of words[v] = mask[v] != 0; first != 0 overwrites the word (the other bits become 0), otherwise the bit is OR-ed in. */
+int32_t unet_vol_vote_pack(unet_ctx*, const uint8_t* mask, int32_t member, int32_t first, uint32_t* words, int64_t nvox, void* stream);
+/* The vote words of M members (1..32; bits at or above M are a caller error and take no part) -> with v = popcount(words[.]):
+ *   mask           uint8, unet_vol_unslice's layout: v >= min_votes (1 <= min_votes <= M)
+ *   votes          uint8: v; may be NULL
+ *   counts         int64 [Z]: the set voxels of mask per slice
+ *   member_voxels  int64 [M]: the voxels member m marked
+ *   pair           int64 [M][M]: the voxels members a and b both marked; symmetric, its diagonal is member_voxels
+ *   hist           int64 [M + 1]: the voxels with k votes
+ * Integer sums only: exact and the same on every run.  One lane per voxel; a wave adds from ballots: the consensus bit for counts, one ballot per vote count present for
+ * hist, and for pair, for every bit a with a non-empty ballot and every b >= a, the popcount of the ballot of (w >> a) & (w >> b) & 1.  A wave whose words are all zero
+ * writes its zeros and is otherwise skipped.  Sums are int32 in LDS per workgroup (a workgroup sees fewer than 2^31 voxels) and leave it as one 64-bit atomic per non-zero
+ * entry; the grid is bounded (at most 2048 workgroups) and strides over the slices and inside them.  A second launch of one workgroup mirrors pair and copies its diagonal. */
+int32_t unet_vol_vote_reduce(unet_ctx*, const uint32_t* words, int32_t M, int32_t X, int32_t Y, int32_t Z, int32_t min_votes, uint8_t* mask, uint8_t* votes,
+                             int64_t* counts, int64_t* member_voxels, int64_t* pair, int64_t* hist, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Model level. Replaces the Keras Model built at T1:853-916 and driven by
  * compile/fit/evaluate/predict (T1:1053-1061, 1101, 1137).  A model is a fixed-shape plan:

@@ -198,6 +198,13 @@ _PROTOS = {
     "unet_vol_ball": (i32, [vp, vp, i32, i32, i32, f64, i32, vp, vp, vp]),
     "unet_vol_fill_holes_ws_bytes": (sz, [i32, i32, i32]),
     "unet_vol_fill_holes": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
+    # several models and test-time symmetries on one volume (csrc/kernels_ensemble.hip, volume.segment_volume_ensemble / vote_volume)
+    "unet_vol_dihedral": (i32, [vp, vp, i32, i32, i32, vp, vp]),
+    "unet_vol_canvas_axpy": (i32, [vp, vp, f32, vp, i64, i32, vp]),
+    "unet_vol_canvas_div": (i32, [vp, vp, f32, i64, vp]),
+    "unet_vol_unslice_prob": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
+    "unet_vol_vote_pack": (i32, [vp, vp, i32, i32, vp, i64, vp]),
+    "unet_vol_vote_reduce": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
     "unet_model_create": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(vp)]),
     "unet_model_dtype": (i32, [vp]),
     "unet_model_tap_elem_bytes": (i32, [vp, C.c_char_p, i32]),

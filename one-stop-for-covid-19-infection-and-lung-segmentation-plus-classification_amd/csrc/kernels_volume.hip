@@ -6,6 +6,7 @@
 // Bit-exact against tests/volume_oracle.py, which restates OpenCV's resize.cpp for 64-bit float images (cv2 is not in this image: parity unpinned, like CLAHE).
 // Compiled with -ffp-contract=off (csrc/Makefile): every product and sum below is rounded on its own, as the C++ / numpy expressions it restates are.
 #include "common.h"
+#include "vol_sample.h"
 
 namespace {
 constexpr int TPB = 256;
@@ -194,18 +195,6 @@ __global__ __launch_bounds__(TPB) void vol_outputs_kernel(const double* __restri
   }
 }
 
-// ---- bilinear sample with half-pixel centres, clamped to the edge: coordinates in float64, the blend in float32 in this fixed order -----------------
-//   fx = float32(u - floor(u));  top = p00 + (p01 - p00) * fx;  bot = p10 + (p11 - p10) * fx;  value = top + (bot - top) * fy      (a constant map stays that constant exactly)
-__device__ __forceinline__ float vol_bilerp(const float* __restrict__ p, int w, int h, double u, double v) {
-  const double fu = floor(u), fv = floor(v);
-  const float fx = (float)(u - fu), fy = (float)(v - fv);
-  const int xi = (int)fu, yi = (int)fv;
-  const int x0 = max(0, min(xi, w - 1)), x1 = max(0, min(xi + 1, w - 1)), y0 = max(0, min(yi, h - 1)), y1 = max(0, min(yi + 1, h - 1));
-  const float p00 = p[(long long)y0 * w + x0], p01 = p[(long long)y0 * w + x1], p10 = p[(long long)y1 * w + x0], p11 = p[(long long)y1 * w + x1];
-  const float top = __fadd_rn(p00, __fmul_rn(__fsub_rn(p01, p00), fx)), bot = __fadd_rn(p10, __fmul_rn(__fsub_rn(p11, p10), fx));
-  return __fadd_rn(top, __fmul_rn(__fsub_rn(bot, top), fy));
-}
-
 constexpr int PASTE_SLICES = 64;                                    // slices per launch: their rectangles travel as a kernel argument (2 KiB)
 struct paste_rects { int r[PASTE_SLICES][8]; };
 __global__ __launch_bounds__(TPB) void vol_paste_kernel(const float* __restrict__ prob, int d, paste_rects rc, int img0, float* __restrict__ canvas, int S) {
@@ -244,13 +233,10 @@ __global__ __launch_bounds__(TPB) void vol_unslice_kernel(const float* __restric
   int cnt = 0;
   for (int q = blockIdx.x * TPB + threadIdx.x; q < XV * Y; q += gridDim.x * TPB) {
     const int y = q / XV, x0 = (q - y * XV) * V;
-    const int i = Y - 1 - y;
-    const double v = (i + 0.5) * S / Y - 0.5;
     uint8_t b[V];
 #pragma unroll
     for (int k = 0; k < V; ++k) {
-      const double u = (x0 + k + 0.5) * S / X - 0.5;
-      b[k] = vol_bilerp(p, S, S, u, v) > t ? 1 : 0;
+      b[k] = vol_unslice_px(p, S, X, Y, x0 + k, y) > t ? 1 : 0;
       cnt += b[k];
     }
     uint8_t* dst = mask + ((long long)(z0 + li) * Y + y) * X + x0;

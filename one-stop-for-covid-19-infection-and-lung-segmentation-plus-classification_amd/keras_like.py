@@ -475,3 +475,13 @@ class UNetModel:
             p, _ = self.backend.predict_batch(x[i:i + batch_size], **kw)
             outs.append(p)
         return np.concatenate([(_o.detach().cpu().numpy() if hasattr(_o, "detach") else np.asarray(_o)) for _o in outs], 0)
+
+    def predict_device(self, x, batch_size=32):
+        """predict's loop with the batches concatenated on the device: [n, h, w, 1] float32 torch tensor, never through the host (volume.segment_volume_ensemble)."""
+        import torch
+        outs = []
+        kw = {"replicated": True} if dp_info(self.backend)[0] > 1 else {}          # every rank predicts everything (no gather needed)
+        for i in range(0, len(x), batch_size):
+            p, _ = self.backend.predict_batch(x[i:i + batch_size], **kw)
+            outs.append(p if hasattr(p, "detach") else torch.from_numpy(np.ascontiguousarray(p, np.float32)))
+        return torch.cat(outs, 0)

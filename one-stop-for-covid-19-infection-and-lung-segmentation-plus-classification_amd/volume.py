@@ -14,6 +14,8 @@ the dataset loop around it (T1:390-393, 421-429) and the way back from a predict
     dilate_mm / erode_mm / open_mm / close_mm(mask, radius_mm, pixdim)     the same by a ball of radius_mm millimetres, from the exact distance transform
     fill_holes(mask, connectivity, per_slice)     scipy.ndimage.binary_fill_holes
     postprocess(mask, steps, pixdim)      a list of (name, kwargs) cleaning steps applied in order on the device; segment_volume(postprocess=steps) runs it
+    segment_volume_ensemble(ct, models, tta, combine, weights)     several models x the square's symmetries (TTA) on one CT: mean / voted mask, agreement map and statistics
+    vote_volume(masks, rule) / dihedral(x, code) / models_from_weights(paths, input_size)     the pieces: up to 32 masks voted on the device, one symmetry, fold files -> models
 
 The voxels are uploaded once as stored (nifti_min reads the file); decode, np.rot90, the slice trim, cv2.resize(float64, INTER_AREA) and the min-max run
 in unet_vol_slices_f64, CLAHE / crop / fuse / resize in the uint8 kernels of preprocess.py on device pointers: between the upload and the returned batch
@@ -994,6 +996,42 @@ def postprocess(mask, steps, pixdim=None, return_device=False, shape=None):
     return _result(postprocess_device(dev, shape, steps, pixdim)[0], shape, return_device)
 
 
+def _prepare_segmentation(ct, lung_mask, truth, img_size, trim, input_size):
+    """The front of segment_volume / segment_volume_ensemble: decode the CT (and the truth and lung masks), the lung rectangles keyed by slice number, the prepared
+    batch x [n, d, d, 1] on the device (d = input_size(), asked for once the truth mask has been checked) -> (vol, lv, truth_mask, z0, z1, S, x, info, R1, R2, has, seconds); R1, R2: int32 [n, 4] per kept slice, zeros where has is False."""
+    torch = _torch()
+    sec = {}
+    t0 = time.perf_counter()
+    vol = _source(ct)
+    sec["decode"] = time.perf_counter() - t0
+    X, Y, Z = vol.raw.shape
+    truth_mask = None
+    if truth is not None:
+        tv = _source(truth)
+        if tv.raw.shape != vol.raw.shape:
+            raise ValueError(f"the truth mask is {tv.raw.shape}, the CT {vol.raw.shape}")
+        truth_mask = tv.get_fdata() != 0
+    z0, z1 = trim_range(Z, trim)
+    n, S = z1 - z0, int(img_size)
+    d = input_size()
+    if lung_mask is not None:
+        lv = _source(lung_mask)
+        if lv.raw.shape != vol.raw.shape:
+            raise ValueError(f"the lung mask is {lv.raw.shape}, the CT {vol.raw.shape}")
+        r1, r2, kept = load_volume(lv, "lungs", S, trim)
+    else:
+        lv = None
+        r1, r2 = whole_frame_rects(n, S); kept = list(range(n))
+    plan = box_plan(n, kept, "slice")
+    t0 = time.perf_counter()
+    x, info = load_volume(vol, "cts", S, trim, (r1, r2, kept), "slice", d, return_info=True)
+    torch.cuda.synchronize(); sec["load_volume"] = time.perf_counter() - t0
+    R1, R2 = np.zeros((n, 4), np.int32), np.zeros((n, 4), np.int32)
+    has = plan >= 0
+    R1[has], R2[has] = np.asarray(r1, np.int32).reshape(-1, 4)[plan[has]], np.asarray(r2, np.int32).reshape(-1, 4)[plan[has]]
+    return vol, lv, truth_mask, z0, z1, S, x, info, R1, R2, has, sec
+
+
 def segment_volume(ct, model, lung_mask=None, threshold=0.547, batch_size=32, out_path=None, img_size=512, trim=(0.2, 0.8), min_lesion_ml=None, connectivity=1,
                    lesions=False, truth=None, postprocess=None):
     """CT file (or array) -> VolumeSegmentation.  `model`: a UNetModel or a routed.ClusterRoutedModel (only `predict` is used); lung_mask=None: whole-frame
@@ -1011,41 +1049,23 @@ def segment_volume(ct, model, lung_mask=None, threshold=0.547, batch_size=32, ou
     if postprocess is not None:
         _check_steps(postprocess, (1.0, 1.0, 1.0))                   # the steps' own arguments, before any work (the CT's pixdim takes this one's place below)
     torch = _torch()
-    sec = {}
-    t0 = time.perf_counter()
-    vol = _source(ct)
-    sec["decode"] = time.perf_counter() - t0
+    vol, lv, truth_mask, z0, z1, S, x, info, R1, R2, has, sec = _prepare_segmentation(ct, lung_mask, truth, img_size, trim, lambda: int(getattr(model, "h", None) or model.base.h))
     X, Y, Z = vol.raw.shape
-    truth_mask = None
-    if truth is not None:
-        tv = _source(truth)
-        if tv.raw.shape != vol.raw.shape:
-            raise ValueError(f"the truth mask is {tv.raw.shape}, the CT {vol.raw.shape}")
-        truth_mask = tv.get_fdata() != 0
-    z0, z1 = trim_range(Z, trim)
-    n, S = z1 - z0, int(img_size)
-    d = int(getattr(model, "h", None) or model.base.h)
-    if lung_mask is not None:
-        lv = _source(lung_mask)
-        if lv.raw.shape != vol.raw.shape:
-            raise ValueError(f"the lung mask is {lv.raw.shape}, the CT {vol.raw.shape}")
-        r1, r2, kept = load_volume(lv, "lungs", S, trim)
-    else:
-        lv = None
-        r1, r2 = whole_frame_rects(n, S); kept = list(range(n))
-    plan = box_plan(n, kept, "slice")
-    t0 = time.perf_counter()
-    x, info = load_volume(vol, "cts", S, trim, (r1, r2, kept), "slice", d, return_info=True)
-    torch.cuda.synchronize(); sec["load_volume"] = time.perf_counter() - t0
     t0 = time.perf_counter()
     prob = torch.from_numpy(np.ascontiguousarray(model.predict(x, batch_size=batch_size), np.float32)).cuda()
     torch.cuda.synchronize(); sec["predict"] = time.perf_counter() - t0
     t0 = time.perf_counter()
-    R1, R2 = np.zeros((n, 4), np.int32), np.zeros((n, 4), np.int32)
-    has = plan >= 0
-    R1[has], R2[has] = np.asarray(r1, np.int32).reshape(-1, 4)[plan[has]], np.asarray(r2, np.int32).reshape(-1, 4)[plan[has]]
     canvas = paste_back(prob, R1, R2, S)
     mask_dev, counts_dev = unslice(canvas, threshold, (X, Y, Z), z0, z1)
+    return _finish_segmentation(vol, lv, truth_mask, mask_dev, counts_dev, z0, z1, has, info, threshold, sec, t0, postprocess, min_lesion_ml, lesions, connectivity, out_path)
+
+
+def _finish_segmentation(vol, lv, truth_mask, mask_dev, counts_dev, z0, z1, has, info, threshold, sec, t0, postprocess, min_lesion_ml, lesions, connectivity, out_path,
+                         **extra):
+    """What segment_volume and segment_volume_ensemble do with the mask volume once it is formed (mask_dev, counts_dev [z1 - z0], both on the device): postprocess,
+    min_lesion_ml / lesions, truth, the download, the lung share and out_path -> VolumeSegmentation (+ `extra` fields).  t0: when the paste-back began."""
+    torch = _torch()
+    X, Y, Z = vol.raw.shape
     voxel_mm3 = float(np.prod(np.asarray(vol.pixdim, np.float64)))          # count * prod(pixdim) / 1000 = millilitres
     cz0, cz1 = z0, z1                                               # the slices counts_dev speaks about
     postprocess_ml = None
@@ -1084,11 +1104,328 @@ def segment_volume(ct, model, lung_mask=None, threshold=0.547, batch_size=32, ou
                              total_ml=float(counts.sum()) * voxel_mm3 / 1000.0, lung_ml=None,
                              infected_share=None, fell_through=[int(i) for i in np.nonzero(~has)[0]], flat=info["flat"], z0=z0, z1=z1, pixdim=vol.pixdim,
                              threshold=float(threshold), seconds=sec, lesions=table, n_lesions=None if table is None else len(table), removed_ml=removed_ml, score=score,
-                             postprocess_ml=postprocess_ml)
+                             postprocess_ml=postprocess_ml, **extra)
     if lv is not None:
         lung_vox = int(np.count_nonzero(lv.get_fdata()[:, :, z0:z1]))
         res.lung_ml = lung_vox * voxel_mm3 / 1000.0
         res.infected_share = (res.total_ml / res.lung_ml) if lung_vox else float("nan")
     if out_path is not None:
         nifti_min.write(out_path, mask, vol.header)
+    return res
+
+
+# ---- several models and test-time symmetries on one volume (csrc/kernels_ensemble.hip) ---------------------------------------
+TTA = ("id", "rot90", "rot180", "rot270", "hflip", "vflip", "transpose", "antitranspose")          # unet_vol_dihedral's codes, by their numpy meaning on axes (1, 2)
+DIHEDRAL_INVERSE = (0, 3, 2, 1, 4, 5, 6, 7)                         # rot90 <-> rot270; the others are their own inverses
+MAX_MEMBERS = 32                                                    # one bit per member in a uint32 vote word
+
+
+def _dihedral_code(code):
+    if isinstance(code, str):
+        if code not in TTA:
+            raise ValueError(f"unknown symmetry {code!r}: one of {TTA}")
+        return TTA.index(code)
+    if isinstance(code, bool) or not isinstance(code, (int, np.integer)) or not 0 <= code < len(TTA):
+        raise ValueError(f"a symmetry is one of {TTA} or its index 0..7, not {code!r}")
+    return int(code)
+
+
+def dihedral_device(x, code):
+    """unet_vol_dihedral on a float32 device tensor [n, d, d(, 1)] -> a new tensor of the same shape"""
+    torch = _torch(); lib, ctx = _ctx()
+    x = x.contiguous()
+    out = torch.empty_like(x)
+    ctx.check(lib.unet_vol_dihedral(ctx.handle, x.data_ptr(), x.shape[0], x.shape[1], int(code), out.data_ptr(), _stream()), "vol_dihedral")
+    return out
+
+
+def dihedral(x, code, inverse=False, return_device=False):
+    """One of the eight symmetries of the square (TTA, by name or index) applied to every slice of x: [n, d, d] or [n, d, d, 1] float32, a numpy array or a device tensor.
+    The result has x's shape and is a bit-exact copy: np.rot90(x, k, (1, 2)) for rot90 / rot180 / rot270, x[:, :, ::-1] for hflip, x[:, ::-1] for vflip, the swap of
+    axes 1 and 2 for transpose and its rot180 for antitranspose.  inverse=True applies the symmetry that undoes `code`."""
+    code = _dihedral_code(code)
+    if inverse:
+        code = DIHEDRAL_INVERSE[code]
+    torch = _torch()
+    shape = tuple(x.shape)
+    if len(shape) not in (3, 4) or shape[1] != shape[2] or (len(shape) == 4 and shape[3] != 1):
+        raise ValueError(f"dihedral takes [n, d, d] or [n, d, d, 1], not {shape}")
+    if isinstance(x, torch.Tensor):
+        if x.dtype != torch.float32:
+            raise ValueError(f"dihedral takes float32, not {x.dtype}")
+        dev = x.cuda()
+    else:
+        a = np.asarray(x)
+        if a.dtype != np.float32:
+            raise ValueError(f"dihedral takes float32, not {a.dtype}")
+        dev = torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    out = dihedral_device(dev, code)
+    return out if return_device else out.cpu().numpy()
+
+
+def min_votes_of(rule, M):
+    """The smallest number of votes that makes a voxel foreground: "majority" M // 2 + 1 (strict: a tie is background), "any" 1, "all" M, an int k with 1 <= k <= M."""
+    if isinstance(rule, str):
+        if rule not in ("majority", "any", "all"):
+            raise ValueError(f"rule must be \"majority\", \"any\", \"all\" or an int in 1..{M}, not {rule!r}")
+        return {"majority": M // 2 + 1, "any": 1, "all": M}[rule]
+    if isinstance(rule, bool) or not isinstance(rule, (int, np.integer)) or not 1 <= rule <= M:
+        raise ValueError(f"rule must be \"majority\", \"any\", \"all\" or an int in 1..{M}, not {rule!r}")
+    return int(rule)
+
+
+def vote_pack_device(mask_dev, member, words, first):
+    """unet_vol_vote_pack: bit `member` of the uint32 vote words (an int32 device tensor of one element per voxel) = mask_dev != 0"""
+    lib, ctx = _ctx()
+    ctx.check(lib.unet_vol_vote_pack(ctx.handle, mask_dev.data_ptr(), int(member), 1 if first else 0, words.data_ptr(), mask_dev.numel(), _stream()), "vol_vote_pack")
+
+
+def vote_reduce_device(words, M, shape, min_votes):
+    """unet_vol_vote_reduce -> dict of device tensors: mask, votes (uint8, X*Y*Z in Fortran order), counts int64 [Z], member_voxels [M], pair [M, M], hist [M + 1]"""
+    torch = _torch(); lib, ctx = _ctx()
+    X, Y, Z = shape
+    N = X * Y * Z
+    out = {"mask": torch.empty(N, dtype=torch.uint8, device="cuda"), "votes": torch.empty(N, dtype=torch.uint8, device="cuda"),
+           "counts": torch.zeros(Z, dtype=torch.int64, device="cuda"), "member_voxels": torch.zeros(M, dtype=torch.int64, device="cuda"),
+           "pair": torch.zeros((M, M), dtype=torch.int64, device="cuda"), "hist": torch.zeros(M + 1, dtype=torch.int64, device="cuda")}
+    ctx.check(lib.unet_vol_vote_reduce(ctx.handle, words.data_ptr(), M, X, Y, Z, int(min_votes), out["mask"].data_ptr(), out["votes"].data_ptr(), out["counts"].data_ptr(),
+                                       out["member_voxels"].data_ptr(), out["pair"].data_ptr(), out["hist"].data_ptr(), _stream()), "vol_vote_reduce")
+    return out
+
+
+def pairwise_dice(pair):
+    """2 pair[a, b] / (v_a + v_b) with v = diag(pair): float64 [M, M], NaN where both members are empty"""
+    pair = np.asarray(pair, np.int64)
+    v = np.diag(pair).astype(np.float64)
+    den = v[:, None] + v[None, :]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(den > 0, 2.0 * pair.astype(np.float64) / den, np.nan)
+
+
+class VoteResult:
+    """What vote_volume returns.  mask: uint8 [X, Y, Z], votes >= min_votes; votes: uint8 [X, Y, Z], the members that marked each voxel (both numpy in Fortran order, or
+    flat device tensors with return_device=True); counts int64 [Z]: the mask's voxels per slice; member_voxels int64 [M]; pair int64 [M, M]: the voxels two members
+    share (its diagonal is member_voxels); pairwise_dice float64 [M, M]; hist int64 [M + 1]: the voxels with k votes; unanimous_voxels = hist[M];
+    uncertain_voxels = sum(hist[1:M]): marked by some member but not by all; min_votes."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def _vote_stats(r, M, min_votes):
+    pair, hist = r["pair"].cpu().numpy(), r["hist"].cpu().numpy()
+    return dict(counts=r["counts"].cpu().numpy(), member_voxels=r["member_voxels"].cpu().numpy(), pair=pair, pairwise_dice=pairwise_dice(pair), hist=hist,
+                unanimous_voxels=int(hist[M]), uncertain_voxels=int(hist[1:M].sum()), min_votes=int(min_votes))
+
+
+def vote_volume(masks, rule="majority", return_device=False, shape=None):
+    """Up to 32 mask volumes of one geometry (several models' or several raters' masks of one CT) -> VoteResult: the consensus mask under `rule` ("majority": more than
+    half, a tie is background; "any"; "all"; an int k: at least k votes), the per-voxel vote count and how far the members agree.  masks: a list of numpy [X, Y, Z]
+    arrays (bool / integer, foreground = non-zero) or flat device byte tensors with shape=, as the other functions of this module take them.  Each mask is packed into
+    one bit of a 32-bit word per voxel (unet_vol_vote_pack); one pass over the words (unet_vol_vote_reduce) gives everything else in integer arithmetic."""
+    torch = _torch()
+    try:
+        masks = list(masks)
+    except TypeError:
+        raise ValueError(f"masks is a list of mask volumes, not {masks!r}") from None
+    M = len(masks)
+    if M == 0:
+        raise ValueError("vote_volume needs at least one mask")
+    if M > MAX_MEMBERS:
+        raise ValueError(f"vote_volume takes at most {MAX_MEMBERS} masks (one bit each in a 32-bit word), not {M}")
+    min_votes = min_votes_of(rule, M)
+    said = None
+    for m in masks:                                                 # refused before anything is uploaded or launched
+        _check_mask_host(m, shape)
+        sh = tuple(int(v) for v in shape) if isinstance(m, torch.Tensor) else tuple(np.shape(m))
+        if said is not None and sh != said:
+            raise ValueError(f"the masks have different shapes: {said} and {sh}")
+        said = sh
+    _check_volume_dims(said)
+    N = int(np.prod(said))
+    words = torch.empty(N, dtype=torch.int32, device="cuda")
+    for k, m in enumerate(masks):
+        dev, _ = _mask_to_device(m, shape)
+        vote_pack_device(dev, k, words, k == 0)
+        del dev
+    r = vote_reduce_device(words, M, said, min_votes)
+    conv = (lambda t: t) if return_device else (lambda t: t.cpu().numpy().reshape(said, order="F"))
+    return VoteResult(mask=conv(r["mask"]), votes=conv(r["votes"]), shape=said, **_vote_stats(r, M, min_votes))
+
+
+def canvas_axpy_device(canvas, w, acc, first):
+    """unet_vol_canvas_axpy: acc = first ? w canvas : acc + w canvas, the product and the sum rounded to float32 on their own"""
+    lib, ctx = _ctx()
+    ctx.check(lib.unet_vol_canvas_axpy(ctx.handle, canvas.data_ptr(), float(np.float32(w)), acc.data_ptr(), canvas.numel(), 1 if first else 0, _stream()), "vol_canvas_axpy")
+
+
+def canvas_div_device(acc, denom):
+    """unet_vol_canvas_div: acc /= denom in place, the correctly rounded float32 quotient"""
+    lib, ctx = _ctx()
+    ctx.check(lib.unet_vol_canvas_div(ctx.handle, acc.data_ptr(), float(np.float32(denom)), acc.numel(), _stream()), "vol_canvas_div")
+
+
+def unslice_prob(canvas, shape, z0, z1):
+    """unet_vol_unslice_prob: canvas [z1 - z0, S, S] -> float32 device tensor of X*Y*Z elements in Fortran order: the value unslice compares with its threshold"""
+    torch = _torch(); lib, ctx = _ctx()
+    X, Y, Z = (int(v) for v in shape)
+    canvas = canvas.contiguous()
+    prob = torch.empty(X * Y * Z, dtype=torch.float32, device="cuda")
+    ctx.check(lib.unet_vol_unslice_prob(ctx.handle, canvas.data_ptr(), canvas.shape[1], X, Y, Z, z0, z1, prob.data_ptr(), _stream()), "vol_unslice_prob")
+    return prob
+
+
+def models_from_weights(paths, input_size, **kw):
+    """One UNetModel(input_size, **kw) per weight file (.hdf5 / .h5 / .npz, what model.save_weights and the k-fold runners write: unet_covid_fold1.hdf5 ...), each
+    with its file loaded: the `models` argument of segment_volume_ensemble."""
+    from .keras_like import UNetModel
+    paths = [os.fspath(p) for p in paths]
+    if not paths:
+        raise ValueError("models_from_weights needs at least one weight file")
+    for p in paths:
+        if not p.lower().endswith((".hdf5", ".h5", ".npz")):
+            raise ValueError(f"{p!r} is not a .hdf5, .h5 or .npz weight file")
+        if not os.path.exists(p):
+            raise ValueError(f"weight file {p!r} does not exist")
+    models = []
+    for p in paths:
+        m = UNetModel(int(input_size), **kw)
+        m.load_weights(p)
+        m.verbose = 0
+        models.append(m)
+    return models
+
+
+def _check_ensemble(models, tta, combine, weights):
+    """-> (models, members [(model index, tta name)], member weights float32 [M], wsum float32, min_votes or None for combine="mean", the models' input size); every
+    refusal is a ValueError raised before any device work"""
+    try:
+        models = list(models)
+    except TypeError:
+        raise ValueError(f"models is a list of models, not {models!r}") from None
+    if not models:
+        raise ValueError("segment_volume_ensemble needs at least one model")
+    if isinstance(tta, str):
+        tta = (tta,)
+    tta = tuple(tta)
+    if not tta:
+        raise ValueError("tta needs at least one symmetry (\"id\")")
+    for name in tta:
+        if not isinstance(name, str) or name not in TTA:
+            raise ValueError(f"unknown tta symmetry {name!r}: one of {TTA}")
+    if len(set(tta)) != len(tta):
+        raise ValueError(f"tta repeats a symmetry: {tta}")
+    M = len(models) * len(tta)
+    if M > MAX_MEMBERS:
+        raise ValueError(f"{len(models)} models x {len(tta)} symmetries = {M} members; at most {MAX_MEMBERS} (one bit each in a 32-bit vote word)")
+    if weights is None:
+        w = np.ones(len(models), np.float32)
+    else:
+        try:
+            w = np.asarray(list(weights), np.float32)
+        except (TypeError, ValueError):
+            raise ValueError(f"weights is one number per model, not {weights!r}") from None
+        if w.shape != (len(models),):
+            raise ValueError(f"weights has one entry per model ({len(models)}), not {w.shape}")
+        if not np.isfinite(w).all() or (w < 0).any():
+            raise ValueError(f"weights are finite and not negative, not {weights!r}")
+    sizes = []
+    for m in models:
+        h = getattr(m, "h", None) or getattr(getattr(m, "base", None), "h", None)
+        if h is None:
+            raise ValueError(f"{m!r} has no input size (h): not a model segment_volume accepts")
+        sizes.append(int(h))
+    if len(set(sizes)) != 1:
+        raise ValueError(f"the models have different input sizes: {sizes}")
+    members = [(i, name) for i in range(len(models)) for name in tta]
+    mw = np.asarray([w[i] for i, _ in members], np.float32)
+    wsum = np.float32(0.0)
+    for v in mw:                                                    # the float32 sum in member order
+        wsum = np.float32(wsum + v)
+    if not wsum > 0:
+        raise ValueError("the weights sum to 0")
+    min_votes = None
+    if not (isinstance(combine, str) and combine == "mean"):
+        try:
+            min_votes = min_votes_of(combine, M)
+        except ValueError:
+            raise ValueError(f"combine must be \"mean\", \"majority\", \"any\", \"all\" or an int in 1..{M}, not {combine!r}") from None
+    return models, members, mw, wsum, min_votes, sizes[0]
+
+
+def _predict_device(model, x, batch_size):
+    """the model's probabilities for the device batch x as a float32 device tensor: predict_device where the model has one, else predict and an upload"""
+    torch = _torch()
+    if hasattr(model, "predict_device"):
+        return model.predict_device(x, batch_size=batch_size).to(device="cuda", dtype=torch.float32)
+    return torch.from_numpy(np.ascontiguousarray(model.predict(x, batch_size=batch_size), np.float32)).cuda()
+
+
+def segment_volume_ensemble(ct, models, tta=("id",), combine="mean", weights=None, lung_mask=None, threshold=0.547, batch_size=32, out_path=None, img_size=512,
+                            trim=(0.2, 0.8), min_lesion_ml=None, connectivity=1, lesions=False, truth=None, postprocess=None, return_prob=False, prob_path=None,
+                            votes_path=None):
+    """segment_volume with several members: every (model, symmetry) pair of `models` (each anything segment_volume accepts, all of one input size) and `tta` (names of
+    TTA, no repeats), in model-major order, at most 32.  A member sees the prepared batch under its symmetry (transformed once, on the device), its probabilities are
+    transformed back, pasted onto the canvas and (a) thresholded into the member's mask, which becomes one bit of a vote word per voxel, (b) added into the weighted
+    mean canvas: acc = w_0 c_0, acc = acc + w_m c_m in member order, then acc / wsum, every float32 operation rounded on its own (weights: one per model, None: all 1;
+    wsum: the float32 sum of the member weights in order).  combine="mean": the final mask is the thresholded mean probability; "majority" / "any" / "all" / int k: the
+    members' masks voted (vote_volume's rules).  Everything after the mask is formed -- postprocess, min_lesion_ml, lesions, truth, out_path, the lung share -- is
+    segment_volume's, and so are the result's fields.  Added: members [(model index, tta name)], votes (uint8 [X, Y, Z]: how many members marked the voxel),
+    member_ml, pairwise_dice, vote_hist (voxels with k votes), unanimous_ml (all members), uncertain_ml (some but not all), combine, seconds["members"] (predict time per
+    member), and prob (float32 [X, Y, Z], the mean probability in patient space) with return_prob=True or prob_path (None otherwise).  prob_path / votes_path: those two
+    volumes as .nii / .nii.gz with the CT's header.  The vote statistics describe the members' masks at `threshold` in both modes (combine="mean" counts them under the
+    majority rule).  One member ("id",) with combine="mean" and weight 1 is segment_volume bit for bit.  Under data parallelism every rank runs every member."""
+    _check_connectivity(connectivity)
+    models, members, mw, wsum, min_votes, d = _check_ensemble(models, tta, combine, weights)
+    if postprocess is not None:
+        _check_steps(postprocess, (1.0, 1.0, 1.0))
+    torch = _torch()
+    M = len(members)
+    vol, lv, truth_mask, z0, z1, S, x, info, R1, R2, has, sec = _prepare_segmentation(ct, lung_mask, truth, img_size, trim, lambda: d)
+    X, Y, Z = vol.raw.shape
+    _check_volume_dims((X, Y, Z))
+    sec["members"] = []
+    t0 = time.perf_counter()
+    words = torch.empty(X * Y * Z, dtype=torch.int32, device="cuda")
+    acc = torch.empty((z1 - z0, S, S), dtype=torch.float32, device="cuda")
+    batches = {"id": x}
+    for k, (mi, name) in enumerate(members):
+        if name not in batches:                                     # each symmetry of the batch is made once and serves every model
+            batches[name] = dihedral_device(x, TTA.index(name))
+        torch.cuda.synchronize(); tm = time.perf_counter()
+        prob = _predict_device(models[mi], batches[name], batch_size)
+        torch.cuda.synchronize(); sec["members"].append(time.perf_counter() - tm)
+        if name != "id":
+            prob = dihedral_device(prob, DIHEDRAL_INVERSE[TTA.index(name)])
+        canvas = paste_back(prob, R1, R2, S)
+        member_mask, _ = unslice(canvas, threshold, (X, Y, Z), z0, z1)
+        vote_pack_device(member_mask, k, words, k == 0)
+        canvas_axpy_device(canvas, mw[k], acc, k == 0)
+        del prob, canvas, member_mask
+    del batches
+    torch.cuda.synchronize()
+    sec["predict"] = float(sum(sec["members"])); sec["member_loop"] = time.perf_counter() - t0          # member_loop: predict + symmetries, paste-back, unslice, pack, axpy
+    t0 = time.perf_counter()
+    canvas_div_device(acc, wsum)
+    mask_dev, counts_dev = unslice(acc, threshold, (X, Y, Z), z0, z1)
+    prob_dev = unslice_prob(acc, (X, Y, Z), z0, z1) if (return_prob or prob_path is not None) else None
+    del acc
+    r = vote_reduce_device(words, M, (X, Y, Z), min_votes if min_votes is not None else min_votes_of("majority", M))
+    del words
+    if min_votes is not None:
+        mask_dev, counts_dev = r["mask"], r["counts"][z0:z1].contiguous()          # no member marks a trimmed slice
+    st = _vote_stats(r, M, min_votes if min_votes is not None else min_votes_of("majority", M))
+    voxel_ml = float(np.prod(np.asarray(vol.pixdim, np.float64))) / 1000.0
+    votes = r["votes"].cpu().numpy().reshape((X, Y, Z), order="F")
+    prob = None if prob_dev is None else prob_dev.cpu().numpy().reshape((X, Y, Z), order="F")
+    del r, prob_dev
+    extra = dict(members=members, votes=votes, member_ml=st["member_voxels"].astype(np.float64) * voxel_ml, pairwise_dice=st["pairwise_dice"], vote_pair=st["pair"],
+                 vote_hist=st["hist"], unanimous_ml=float(st["unanimous_voxels"]) * voxel_ml, uncertain_ml=float(st["uncertain_voxels"]) * voxel_ml, combine=combine,
+                 weights=mw, prob=prob)
+    res = _finish_segmentation(vol, lv, truth_mask, mask_dev, counts_dev, z0, z1, has, info, threshold, sec, t0, postprocess, min_lesion_ml, lesions, connectivity, out_path,
+                               **extra)
+    if prob_path is not None:
+        nifti_min.write(prob_path, prob, vol.header)
+    if votes_path is not None:
+        nifti_min.write(votes_path, votes, vol.header)
     return res
