@@ -50,14 +50,18 @@ def edt_sq_brute(vol, nonzero, pixdim):
 def _line_pass(g, axis, w):
     """out[l] = min over ALL l' of fl(g[l'] + fl(w (l - l')^2)) along `axis`"""
     L = g.shape[axis]
-    g = np.moveaxis(g, axis, 0)
+    g = np.ascontiguousarray(np.moveaxis(g, axis, 0))                # (a copy in line order: the long lines of the regime tests scan twice as fast)
     k = np.arange(L, dtype=np.float64)
     t = w * (k * k)
     out = np.full(g.shape, np.inf)
     idx = np.arange(L)
     shape = (L,) + (1,) * (g.ndim - 1)
+    cand = np.empty(g.shape)
     for l2 in range(L):
-        np.minimum(out, g[l2][None] + t[np.abs(idx - l2)].reshape(shape), out=out)
+        if np.isinf(g[l2]).all():
+            continue                                                  # fl(inf + c) = inf lowers no minimum
+        np.add(g[l2][None], t[np.abs(idx - l2)].reshape(shape), out=cand)
+        np.minimum(out, cand, out=out)
     return np.moveaxis(out, 0, axis)
 
 
@@ -142,6 +146,37 @@ def lesion_cover(pred, truth, connectivity=1, min_overlap_voxels=1):
     return {"labels_t": lt, "n_t": nt, "labels_p": lp, "n_p": npred, "cover_t": cover_t, "cover_p": cover_p, "detected": det, "matched": mat,
             "lesion_recall": _ratio(int(det.sum()), nt), "lesion_precision": _ratio(int(mat.sum()), npred),
             "missed_lesions": int(nt - det.sum()), "false_positive_lesions": int(npred - mat.sum())}
+
+
+def cover_tables(lt, nt, lp, np_):
+    """unet_vol_lesion_overlap on ANY two int32 volumes: a voxel counts for its own label when that lies in 1..n and the partner is non-zero there (whatever its value)
+    -> (cover_t int64 [nt], cover_p int64 [np_])"""
+    lt, lp = np.asarray(lt).astype(np.int64), np.asarray(lp).astype(np.int64)
+    ct = np.bincount(lt[(lp != 0) & (lt >= 1) & (lt <= nt)], minlength=nt + 1)[1:]
+    cp = np.bincount(lp[(lt != 0) & (lp >= 1) & (lp <= np_)], minlength=np_ + 1)[1:]
+    return ct.astype(np.int64), cp.astype(np.int64)
+
+
+def _distinct_nonzero(rows):
+    s = np.sort(rows, axis=1)
+    return ((s[:, 1:] != s[:, :-1]) & (s[:, 1:] != 0)).sum(axis=1) + (s[:, 0] != 0)
+
+
+def fallback_counts(own, other, n):
+    """How often the coverage kernel's two fallbacks run for the table of `own` (labels 1..n count where `other` is non-zero), over the Fortran-order flat index:
+    -> (groups of four consecutive indices, aligned to 4, that hold two or more distinct counted labels -- a voxel leaves cover_quad as its own atomic;
+        runs of 256 consecutive indices, aligned to 256, that hold three or more distinct counted labels;
+        the same runs counted by what wave_count sees, the FIRST counted label of each of the 64 groups of four: three or more distinct ones leave a lane to itself).
+    The third implies the second."""
+    o = np.asarray(own).reshape(-1, order="F").astype(np.int64); t = np.asarray(other).reshape(-1, order="F")
+    v = np.where((t != 0) & (o >= 1) & (o <= n), o, 0)
+    quads = np.concatenate([v, np.zeros(-v.size % 4, np.int64)]).reshape(-1, 4)
+    runs = np.concatenate([v, np.zeros(-v.size % 256, np.int64)]).reshape(-1, 256)
+    first = np.zeros(len(quads), np.int64)
+    for i in (3, 2, 1, 0):
+        first = np.where(quads[:, i] != 0, quads[:, i], first)
+    waves = np.concatenate([first, np.zeros(-first.size % 64, np.int64)]).reshape(-1, 64)
+    return int((_distinct_nonzero(quads) >= 2).sum()), int((_distinct_nonzero(runs) >= 3).sum()), int((_distinct_nonzero(waves) >= 3).sum())
 
 
 def score(pred, truth, pixdim=(1, 1, 1), connectivity=1, lesion_connectivity=1, percentile=95.0, min_overlap_voxels=1):
