@@ -716,6 +716,40 @@ int32_t unet_vol_vote_pack(unet_ctx*, const uint8_t* mask, int32_t member, int32
 int32_t unet_vol_vote_reduce(unet_ctx*, const uint32_t* words, int32_t M, int32_t X, int32_t Y, int32_t Z, int32_t min_votes, uint8_t* mask, uint8_t* votes,
                              int64_t* counts, int64_t* member_voxels, int64_t* pair, int64_t* hist, void* stream);
 
+/* ---- what the CT holds under a mask (csrc/kernels_intensity.hip; exact against tests/intensity_oracle.py) ----
+ * vox, dtype, X, Y, Z, scaled, slope, inter: the uploaded volume of unet_vol_slices_f64 (Fortran order [X, Y, Z], native byte order, one of the eight NIfTI codes).  The
+ * value of voxel v is get_fdata()'s: float64(raw), then, when scaled != 0, (. * slope) + inter as two rounded operations.  Groups: exactly one of `labels` (int32, same
+ * layout) and `mask` (uint8, non-zero = group 1) is non-null.  A voxel takes part when its group g lies in 1..n and `region` (uint8, same layout, nullable) is non-zero
+ * there; a label outside 1..n is ignored.  A NaN value takes part only in the NaN column.  X Y Z >= 2^31, an unknown dtype, both or neither of labels / mask, n < 0:
+ * UNET_E_ARG and nothing is launched.  A volume with a zero dimension returns UNET_OK with the outputs in their empty state (counts 0, min / max (+inf, -inf)).
+ *
+ * unet_vol_intensity_bands: `edges` is a HOST array of n_edges doubles, finite and strictly ascending, 1 <= n_edges <= UNET_VOL_INTENSITY_MAX_EDGES (anything else:
+ * UNET_E_ARG).  B = n_edges + 1 bands; band b of a non-NaN value v = the number of edges <= v = np.searchsorted(edges, v, side="right").
+ *   band_counts   device int64 [n][B + 1]: the voxels of group g + 1 in every band; column B counts its NaN voxels
+ *   slice_counts  device int64 [Z][B + 1]: the same over all taking-part voxels of a slice; nullable
+ *   minmax        device double [n][2]: the exact minimum and maximum of the group's non-NaN values (-0.0 orders below +0.0), (+inf, -inf) for a group without one; nullable
+ * All three are overwritten: the caller does not zero them.  All 8-byte aligned.  Integer sums (per wave by ballot, per workgroup in an LDS table while n (B + 1) <= 4096
+ * and n <= 1024, 64-bit atomics beyond) and min / max only: the same bits on every run, for any n >= 0 and any mix of groups inside a wave. */
+#define UNET_VOL_INTENSITY_MAX_EDGES 63
+int32_t unet_vol_intensity_bands(unet_ctx*, const void* vox, int32_t dtype, int32_t X, int32_t Y, int32_t Z, int32_t scaled, double slope, double inter,
+                                 const int32_t* labels, const uint8_t* mask, int32_t n, const uint8_t* region, const double* edges, int32_t n_edges, int64_t* band_counts,
+                                 int64_t* slice_counts, double* minmax, void* stream);
+/* The taking-part non-NaN voxels, compacted: values[k] (double) and groups[k] (int32 1..n; nullable) for k < min(count, capacity), in no particular order (they are sorted
+ * afterwards).  count: device int64, the number of such voxels whatever the capacity; when it exceeds `capacity`, exactly `capacity` pairs are written and nothing past
+ * them (unet_vol_surface_distances's rule). */
+int32_t unet_vol_intensity_gather(unet_ctx*, const void* vox, int32_t dtype, int32_t X, int32_t Y, int32_t Z, int32_t scaled, double slope, double inter,
+                                  const int32_t* labels, const uint8_t* mask, int32_t n, const uint8_t* region, double* values, int32_t* groups, int64_t capacity,
+                                  int64_t* count, void* stream);
+/* values: device doubles already ordered by (group, value ascending); offsets: device int64 [n + 1], offsets[0] = 0, non-decreasing, offsets[n] = total: group g's run is
+ * values[offsets[g] .. offsets[g + 1]).  out: device double [n][2] = (sum, ssd) of every run v_0 .. v_{m-1}:
+ *   partial_c = the left-to-right float64 sum of v[256 c .. min(256 c + 256, m) - 1], starting from its first element (np.cumsum(chunk)[-1]);
+ *   sum = the left-to-right sum of the partials;  mean = sum / m;
+ *   ssd = the same two-level sum over q_i = fl(d_i d_i), d_i = fl(v_i - mean).
+ * An empty group gives (0, 0).  The order is canonical and the tree fixed (no fused multiply-add, no floating-point atomics): bit-identical from run to run.
+ * ws: unet_vol_group_moments_ws_bytes(total, n) bytes, 8-byte aligned (the means and one partial sum per 256-element chunk); nothing is written past ws_bytes. */
+size_t unet_vol_group_moments_ws_bytes(int64_t total, int32_t n);
+int32_t unet_vol_group_moments(unet_ctx*, const double* values, const int64_t* offsets, int32_t n, double* out, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Model level. Replaces the Keras Model built at T1:853-916 and driven by
  * compile/fit/evaluate/predict (T1:1053-1061, 1101, 1137).  A model is a fixed-shape plan:

@@ -24,6 +24,7 @@ DTYPE_F32, DTYPE_BF16 = 0, 1
 ACT_NONE, ACT_RELU, ACT_ELU = 0, 1, 2
 MORPH_OPS = {"dilate": 0, "erode": 1, "open": 2, "close": 3}          # include/unet_hip.h UNET_MORPH_*
 MORPH_MAX_ITERATIONS = 64
+INTENSITY_MAX_EDGES = 63                                              # include/unet_hip.h UNET_VOL_INTENSITY_MAX_EDGES
 MASK_NONE, MASK_RELU, MASK_ELU, MASK_ELU_DROP = 0, 1, 2, 3
 PROG_FWD_TRAIN, PROG_BWD, PROG_FWD_INFER = 0, 1, 2
 SYNC_BN_FWD, SYNC_LOSS, SYNC_BN_BWD, SYNC_GRAD_BUCKET = 0, 1, 2, 3
@@ -205,6 +206,11 @@ _PROTOS = {
     "unet_vol_unslice_prob": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
     "unet_vol_vote_pack": (i32, [vp, vp, i32, i32, vp, i64, vp]),
     "unet_vol_vote_reduce": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
+    # what the CT holds under a mask (csrc/kernels_intensity.hip, volume.intensity_stats)
+    "unet_vol_intensity_bands": (i32, [vp, vp, i32, i32, i32, i32, i32, f64, f64, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp]),
+    "unet_vol_intensity_gather": (i32, [vp, vp, i32, i32, i32, i32, i32, f64, f64, vp, vp, i32, vp, vp, vp, i64, vp, vp]),
+    "unet_vol_group_moments_ws_bytes": (sz, [i64, i32]),
+    "unet_vol_group_moments": (i32, [vp, vp, vp, i32, vp, vp, sz, vp]),
     "unet_model_create": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(vp)]),
     "unet_model_dtype": (i32, [vp]),
     "unet_model_tap_elem_bytes": (i32, [vp, C.c_char_p, i32]),

@@ -16,6 +16,8 @@ the dataset loop around it (T1:390-393, 421-429) and the way back from a predict
     postprocess(mask, steps, pixdim)      a list of (name, kwargs) cleaning steps applied in order on the device; segment_volume(postprocess=steps) runs it
     segment_volume_ensemble(ct, models, tta, combine, weights)     several models x the square's symmetries (TTA) on one CT: mean / voted mask, agreement map and statistics
     vote_volume(masks, rule) / dihedral(x, code) / models_from_weights(paths, input_size)     the pieces: up to 32 masks voted on the device, one symmetry, fold files -> models
+    intensity_stats(ct, mask | labels, n, region, edges)     -> IntensityStats: what the CT holds under a mask or per lesion -- voxels per HU band (HU_BANDS), min / max,
+                                          mean / std, percentiles, per slice; segment_volume(density=True) fills res.density / res.lung_density with it
 
 The voxels are uploaded once as stored (nifti_min reads the file); decode, np.rot90, the slice trim, cv2.resize(float64, INTER_AREA) and the min-max run
 in unet_vol_slices_f64, CLAHE / crop / fuse / resize in the uint8 kernels of preprocess.py on device pointers: between the upload and the returned batch
@@ -288,7 +290,9 @@ class VolumeSegmentation:
     lung_ml and infected_share when a lung mask was given; fell_through / flat: kept-range slice numbers; z0, z1; seconds: where the time went;
     lesions / n_lesions / removed_ml: the component table of the mask, its length and the volume a min_lesion_ml filter removed (None when not asked for);
     score: the VolumeScore of the final mask against the `truth` given to segment_volume (None without one);
-    postprocess_ml: the volume the `postprocess` steps added to the mask (negative: removed; None without steps)."""
+    postprocess_ml: the volume the `postprocess` steps added to the mask (negative: removed; None without steps);
+    density / lung_density: the IntensityStats of the CT under the final mask (per lesion when the lesion table was computed) and under the lung mask (None unless
+    segment_volume was given density=)."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -638,6 +642,13 @@ def _ratio(a, b):
     return float(a) / float(b) if b else float("nan")
 
 
+def _lerp(a, b, t):
+    """numpy's _lerp between two order statistics (floats or arrays): a + (b - a) t, and b - (b - a)(1 - t) from t = 0.5 on"""
+    with np.errstate(invalid="ignore"):
+        d = np.subtract(b, a)
+        return np.where(np.asarray(t) >= 0.5, b - d * (1.0 - t), a + d * t)[()]
+
+
 def _percentile_of_sorted(sorted_dev, q):
     """np.percentile(values, q) (linear interpolation) of sqrt(values) from an ascending device tensor of squared values: the two order statistics come to the host,
     sqrt is monotone, so they are the order statistics of the square roots"""
@@ -645,11 +656,7 @@ def _percentile_of_sorted(sorted_dev, q):
     pos = (float(q) / 100.0) * (n - 1)
     lo = min(int(np.floor(pos)), n - 1); hi = min(lo + 1, n - 1)
     a, b = (float(v) for v in np.sqrt(sorted_dev[[lo, hi]].cpu().numpy()))
-    t = pos - lo
-    r = a + (b - a) * t                                             # numpy's _lerp
-    if t >= 0.5:
-        r = b - (b - a) * (1.0 - t)
-    return float(r)
+    return float(_lerp(a, b, pos - lo))
 
 
 def score_volume(pred, truth, pixdim=(1, 1, 1), connectivity=1, lesion_connectivity=1, percentile=95.0, min_overlap_voxels=1, lesions=True, shape=None):
@@ -1033,7 +1040,7 @@ def _prepare_segmentation(ct, lung_mask, truth, img_size, trim, input_size):
 
 
 def segment_volume(ct, model, lung_mask=None, threshold=0.547, batch_size=32, out_path=None, img_size=512, trim=(0.2, 0.8), min_lesion_ml=None, connectivity=1,
-                   lesions=False, truth=None, postprocess=None):
+                   lesions=False, truth=None, postprocess=None, density=None):
     """CT file (or array) -> VolumeSegmentation.  `model`: a UNetModel or a routed.ClusterRoutedModel (only `predict` is used); lung_mask=None: whole-frame
     boxes (the two halves of the frame); boxes are keyed by slice number (box_indexing="slice"); out_path: the mask as .nii / .nii.gz with the CT's geometry.
     min_lesion_ml: connected components (`connectivity` 1, 2, 3 = 6, 18, 26 neighbours) smaller than that are removed on the device before the mask comes to the
@@ -1044,8 +1051,13 @@ def segment_volume(ct, model, lung_mask=None, threshold=0.547, batch_size=32, ou
     postprocess: a list of steps as volume.postprocess takes them (pixdim: the CT's), run on the device right after the mask volume is formed and before min_lesion_ml,
     lesions and truth: counts, ml_per_slice, total_ml, infected_share, the lesion table and the score then describe the cleaned mask (counts over all Z slices: a
     dilation may reach a trimmed slice), res.postprocess_ml is the volume the steps added (negative: removed) and seconds["postprocess"] their time; None: nothing
-    runs and res.postprocess_ml is None."""
+    runs and res.postprocess_ml is None.
+    density: True, or a dict of intensity_stats keyword arguments (edges, names, percentiles, moments, per_slice): after postprocess / min_lesion_ml, res.density =
+    intensity_stats of the CT under the final mask -- one row per lesion of res.lesions when the lesion table is computed (the device labels are reused, not relabelled),
+    one group otherwise --, res.lung_density the same under the lung mask (None without one), seconds["density"] their time.  The CT's raw voxels are uploaded a second
+    time for it.  None: nothing runs, both fields are None."""
     _check_connectivity(connectivity)
+    density = _check_density(density)
     if postprocess is not None:
         _check_steps(postprocess, (1.0, 1.0, 1.0))                   # the steps' own arguments, before any work (the CT's pixdim takes this one's place below)
     torch = _torch()
@@ -1057,13 +1069,14 @@ def segment_volume(ct, model, lung_mask=None, threshold=0.547, batch_size=32, ou
     t0 = time.perf_counter()
     canvas = paste_back(prob, R1, R2, S)
     mask_dev, counts_dev = unslice(canvas, threshold, (X, Y, Z), z0, z1)
-    return _finish_segmentation(vol, lv, truth_mask, mask_dev, counts_dev, z0, z1, has, info, threshold, sec, t0, postprocess, min_lesion_ml, lesions, connectivity, out_path)
+    return _finish_segmentation(vol, lv, truth_mask, mask_dev, counts_dev, z0, z1, has, info, threshold, sec, t0, postprocess, min_lesion_ml, lesions, connectivity, out_path,
+                                density=density)
 
 
 def _finish_segmentation(vol, lv, truth_mask, mask_dev, counts_dev, z0, z1, has, info, threshold, sec, t0, postprocess, min_lesion_ml, lesions, connectivity, out_path,
-                         **extra):
+                         density=None, **extra):
     """What segment_volume and segment_volume_ensemble do with the mask volume once it is formed (mask_dev, counts_dev [z1 - z0], both on the device): postprocess,
-    min_lesion_ml / lesions, truth, the download, the lung share and out_path -> VolumeSegmentation (+ `extra` fields).  t0: when the paste-back began."""
+    min_lesion_ml / lesions, density (the checked keyword arguments of intensity_stats, or None), truth, the download, the lung share and out_path -> VolumeSegmentation (+ `extra` fields).  t0: when the paste-back began."""
     torch = _torch()
     X, Y, Z = vol.raw.shape
     voxel_mm3 = float(np.prod(np.asarray(vol.pixdim, np.float64)))          # count * prod(pixdim) / 1000 = millilitres
@@ -1078,6 +1091,7 @@ def _finish_segmentation(vol, lv, truth_mask, mask_dev, counts_dev, z0, z1, has,
         postprocess_ml = float(int(counts_dev.sum().item()) - before) * voxel_mm3 / 1000.0
         torch.cuda.synchronize(); sec["postprocess"] = time.perf_counter() - tp
     table, removed_ml = None, None
+    labels_dev, keep = None, None
     if min_lesion_ml is not None or lesions:
         torch.cuda.synchronize(); tc = time.perf_counter()
         labels_dev, n_comp = label_device(mask_dev, (X, Y, Z), connectivity)
@@ -1090,8 +1104,22 @@ def _finish_segmentation(vol, lv, truth_mask, mask_dev, counts_dev, z0, z1, has,
             table = table[keep[1:]]                                  # the kept components keep their order: renumbered, this is the table of the filtered mask
             table["label"] = np.arange(1, len(table) + 1)
             removed_ml = float(before) * voxel_mm3 / 1000.0 - float(counts_dev.sum().item()) * voxel_mm3 / 1000.0
-        del labels_dev
+        if density is None:
+            labels_dev = None
         torch.cuda.synchronize(); sec["components"] = time.perf_counter() - tc
+    dens, lung_dens = None, None
+    if density is not None:
+        torch.cuda.synchronize(); td = time.perf_counter()
+        if labels_dev is not None:                                  # per lesion, on the labels the table came from; a filtered lesion's voxels left the mask (region=)
+            dens = intensity_stats(vol, labels=labels_dev, n=n_comp, region=mask_dev if keep is not None else None, shape=(X, Y, Z), **density)
+            if keep is not None:
+                dens = dens.take_groups(keep[1:])
+            labels_dev = None
+        else:
+            dens = intensity_stats(vol, mask=mask_dev, shape=(X, Y, Z), **density)
+        if lv is not None:
+            lung_dens = intensity_stats(vol, mask=lv.get_fdata() != 0, **density)
+        torch.cuda.synchronize(); sec["density"] = time.perf_counter() - td
     score = None
     if truth_mask is not None:
         torch.cuda.synchronize(); ts = time.perf_counter()
@@ -1104,7 +1132,7 @@ def _finish_segmentation(vol, lv, truth_mask, mask_dev, counts_dev, z0, z1, has,
                              total_ml=float(counts.sum()) * voxel_mm3 / 1000.0, lung_ml=None,
                              infected_share=None, fell_through=[int(i) for i in np.nonzero(~has)[0]], flat=info["flat"], z0=z0, z1=z1, pixdim=vol.pixdim,
                              threshold=float(threshold), seconds=sec, lesions=table, n_lesions=None if table is None else len(table), removed_ml=removed_ml, score=score,
-                             postprocess_ml=postprocess_ml, **extra)
+                             postprocess_ml=postprocess_ml, density=dens, lung_density=lung_dens, **extra)
     if lv is not None:
         lung_vox = int(np.count_nonzero(lv.get_fdata()[:, :, z0:z1]))
         res.lung_ml = lung_vox * voxel_mm3 / 1000.0
@@ -1363,13 +1391,13 @@ def _predict_device(model, x, batch_size):
 
 def segment_volume_ensemble(ct, models, tta=("id",), combine="mean", weights=None, lung_mask=None, threshold=0.547, batch_size=32, out_path=None, img_size=512,
                             trim=(0.2, 0.8), min_lesion_ml=None, connectivity=1, lesions=False, truth=None, postprocess=None, return_prob=False, prob_path=None,
-                            votes_path=None):
+                            votes_path=None, density=None):
     """segment_volume with several members: every (model, symmetry) pair of `models` (each anything segment_volume accepts, all of one input size) and `tta` (names of
     TTA, no repeats), in model-major order, at most 32.  A member sees the prepared batch under its symmetry (transformed once, on the device), its probabilities are
     transformed back, pasted onto the canvas and (a) thresholded into the member's mask, which becomes one bit of a vote word per voxel, (b) added into the weighted
     mean canvas: acc = w_0 c_0, acc = acc + w_m c_m in member order, then acc / wsum, every float32 operation rounded on its own (weights: one per model, None: all 1;
     wsum: the float32 sum of the member weights in order).  combine="mean": the final mask is the thresholded mean probability; "majority" / "any" / "all" / int k: the
-    members' masks voted (vote_volume's rules).  Everything after the mask is formed -- postprocess, min_lesion_ml, lesions, truth, out_path, the lung share -- is
+    members' masks voted (vote_volume's rules).  Everything after the mask is formed -- postprocess, min_lesion_ml, lesions, density, truth, out_path, the lung share -- is
     segment_volume's, and so are the result's fields.  Added: members [(model index, tta name)], votes (uint8 [X, Y, Z]: how many members marked the voxel),
     member_ml, pairwise_dice, vote_hist (voxels with k votes), unanimous_ml (all members), uncertain_ml (some but not all), combine, seconds["members"] (predict time per
     member), and prob (float32 [X, Y, Z], the mean probability in patient space) with return_prob=True or prob_path (None otherwise).  prob_path / votes_path: those two
@@ -1377,6 +1405,7 @@ def segment_volume_ensemble(ct, models, tta=("id",), combine="mean", weights=Non
     majority rule).  One member ("id",) with combine="mean" and weight 1 is segment_volume bit for bit.  Under data parallelism every rank runs every member."""
     _check_connectivity(connectivity)
     models, members, mw, wsum, min_votes, d = _check_ensemble(models, tta, combine, weights)
+    density = _check_density(density)
     if postprocess is not None:
         _check_steps(postprocess, (1.0, 1.0, 1.0))
     torch = _torch()
@@ -1423,9 +1452,296 @@ def segment_volume_ensemble(ct, models, tta=("id",), combine="mean", weights=Non
                  vote_hist=st["hist"], unanimous_ml=float(st["unanimous_voxels"]) * voxel_ml, uncertain_ml=float(st["uncertain_voxels"]) * voxel_ml, combine=combine,
                  weights=mw, prob=prob)
     res = _finish_segmentation(vol, lv, truth_mask, mask_dev, counts_dev, z0, z1, has, info, threshold, sec, t0, postprocess, min_lesion_ml, lesions, connectivity, out_path,
-                               **extra)
+                               density=density, **extra)
     if prob_path is not None:
         nifti_min.write(prob_path, prob, vol.header)
     if votes_path is not None:
         nifti_min.write(votes_path, votes, vol.header)
     return res
+
+
+# ---- what the CT holds under a mask (csrc/kernels_intensity.hip) ---------------------------------------------------------------
+# The default value bands: conventional thresholds of the CT densitometry literature in Hounsfield units -- below -950 (emphysema-like / air), -950 .. -750 (well aerated
+# lung), -750 .. -300 (ground-glass opacity), -300 .. 50 (consolidation), above.  They are configurable (edges=, names=) and NOT clinically validated here; they mean
+# Hounsfield units only when the file's slope / inter decode to them.  A band holds edge[b - 1] <= v < edge[b].
+HU_BAND_NAMES = ("below", "aerated", "ggo", "consolidation", "above")
+HU_BAND_EDGES = (-950.0, -750.0, -300.0, 50.0)
+HU_BANDS = (HU_BAND_NAMES, HU_BAND_EDGES)
+INTENSITY_MAX_EDGES = _lib.INTENSITY_MAX_EDGES                       # UNET_VOL_INTENSITY_MAX_EDGES
+_DENSITY_KEYS = {"edges", "names", "percentiles", "moments", "per_slice"}
+
+
+def intensity_group_dtype(n_bands, n_percentiles):
+    """one row of IntensityStats.groups for B bands and Q percentiles"""
+    B, Q = int(n_bands), int(n_percentiles)
+    return np.dtype([("label", np.int32), ("voxels", np.int64), ("nan_voxels", np.int64), ("ml", np.float64), ("min", np.float64), ("max", np.float64),
+                     ("mean", np.float64), ("std", np.float64), ("percentiles", np.float64, (Q,)), ("band_voxels", np.int64, (B,)), ("band_ml", np.float64, (B,)),
+                     ("band_share", np.float64, (B,)), ("dominant_band", np.int32)])
+
+
+class IntensityStats:
+    """What intensity_stats returns.  names / edges: the B = len(edges) + 1 bands; qs: the percentiles asked for; n: the number of groups.  Of the union of the groups:
+    voxels (taking-part voxels, NaN ones included), nan_voxels, ml, min, max, mean, std (population), percentiles {q: value} -- all over the non-NaN values, nan when
+    there is none, mean / std / percentiles None with moments=False --, band_voxels / band_ml / band_share [B] (share of the non-NaN voxels), slice_band_voxels [Z, B]
+    and slice_nan_voxels [Z] (None with per_slice=False).  groups: one row per label 1..n (intensity_group_dtype): the same quantities + dominant_band (the band with
+    the most voxels, ties to the lower band, -1 for a group without values); with moments=False its mean / std / percentiles are nan."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def band(self, name):
+        """the union's voxel count of the named band"""
+        return int(self.band_voxels[self.names.index(name)])
+
+    def take_groups(self, keep):
+        """the same statistics with only the rows of `keep` (bool [n]), renumbered 1..; for rows that hold no voxel (the union does not change)"""
+        keep = np.asarray(keep, bool)
+        if keep.shape != (len(self.groups),) or self.groups["voxels"][~keep].any() or self.groups["nan_voxels"][~keep].any():
+            raise ValueError("take_groups drops empty groups only")
+        g = self.groups[keep].copy()
+        g["label"] = np.arange(1, len(g) + 1)
+        return IntensityStats(**{**self.__dict__, "groups": g, "n": len(g)})
+
+    def __repr__(self):
+        return f"IntensityStats(voxels={self.voxels}, mean={self.mean}, bands={dict(zip(self.names, self.band_voxels.tolist()))})"
+
+
+def _check_intensity_args(edges=HU_BAND_EDGES, names=HU_BAND_NAMES, percentiles=(5, 25, 50, 75, 95), moments=True, per_slice=True):
+    """-> (edges float64 [E], names tuple [E + 1], percentiles tuple of float), or ValueError: no device is needed"""
+    try:
+        e = np.asarray(edges, np.float64).reshape(-1)
+    except (TypeError, ValueError):
+        raise ValueError(f"edges are finite ascending numbers, not {edges!r}") from None
+    if not 1 <= e.size <= INTENSITY_MAX_EDGES:
+        raise ValueError(f"1 to {INTENSITY_MAX_EDGES} edges are taken, not {e.size}")
+    if not np.isfinite(e).all() or not (np.diff(e) > 0).all():
+        raise ValueError(f"edges must be finite and strictly ascending, not {edges!r}")
+    if names is None:
+        names = tuple(f"band{b}" for b in range(e.size + 1))
+    names = tuple(str(v) for v in names)
+    if len(names) != e.size + 1:
+        raise ValueError(f"{e.size} edges make {e.size + 1} bands, but {len(names)} names were given")
+    try:
+        qs = tuple(float(q) for q in percentiles)
+    except (TypeError, ValueError):
+        raise ValueError(f"percentiles are numbers in [0, 100], not {percentiles!r}") from None
+    if any(not 0.0 <= q <= 100.0 for q in qs):                      # (a NaN fails both comparisons)
+        raise ValueError(f"a percentile must lie in [0, 100], not {percentiles!r}")
+    return e, names, qs
+
+
+def _check_density(density):
+    """segment_volume's density= -> None (off) or the checked keyword arguments of intensity_stats"""
+    if density is None or density is False:
+        return None
+    kw = {} if density is True else dict(density)
+    if set(kw) - _DENSITY_KEYS:
+        raise ValueError(f"density takes {sorted(_DENSITY_KEYS)}, not {sorted(set(kw) - _DENSITY_KEYS)}")
+    _check_intensity_args(**kw)
+    return kw
+
+
+def _check_group_volume(a, what, vshape, shape, want_dtype):
+    """a mask / label / region volume against the CT's shape, on the host: numpy [X, Y, Z] (bool / integer) or a flat device tensor with shape="""
+    torch = _torch()
+    if isinstance(a, torch.Tensor):
+        if shape is None:
+            raise ValueError(f"device {what} is a flat Fortran-order buffer: pass shape=(X, Y, Z)")
+        if tuple(int(v) for v in shape) != vshape:
+            raise ValueError(f"{what} is {tuple(shape)}, the CT {vshape}")
+        if a.dtype != want_dtype or not a.is_cuda or a.numel() != int(np.prod(vshape)):
+            raise ValueError(f"device {what} is a {want_dtype} cuda tensor of prod(shape) = {int(np.prod(vshape))} elements")
+        return
+    a = np.asarray(a)
+    if a.ndim != 3:
+        raise ValueError(f"a volume is [X, Y, Z]; {what} has {a.ndim} dimensions")
+    if a.dtype.kind not in "biu":
+        raise ValueError(f"{what} has a bool or integer dtype, not {a.dtype}")
+    if tuple(a.shape) != vshape:
+        raise ValueError(f"{what} is {tuple(a.shape)}, the CT {vshape}")
+
+
+def _vox_args(vol):
+    """the arguments that describe an uploaded volume to the intensity kernels: dtype code, X, Y, Z, scaled, slope, inter"""
+    X, Y, Z = (int(v) for v in vol.raw.shape)
+    sc = vol.scaling
+    return (_CODE_OF_DTYPE[vol.raw.dtype.str[1:]], X, Y, Z, 1 if sc else 0, sc[0] if sc else 1.0, sc[1] if sc else 0.0)
+
+
+_CODE_OF_DTYPE = {v: k for k, v in nifti_min.DTYPES.items()}
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def intensity_bands_device(vol, dev, labels_dev, mask_dev, n, region_dev, edges, per_slice=True, minmax=True):
+    """unet_vol_intensity_bands on an uploaded volume (dev = upload(vol)) -> (band_counts int64 [n, B + 1], slice_counts int64 [Z, B + 1] or None,
+    minmax float64 [n, 2] or None), numpy; column B counts NaN voxels."""
+    torch = _torch(); lib, ctx = _ctx()
+    e = np.ascontiguousarray(edges, np.float64)
+    W, Z = e.size + 2, int(vol.raw.shape[2])
+    bc = torch.empty((max(n, 1), W), dtype=torch.int64, device="cuda")
+    sc = torch.empty((max(Z, 1), W), dtype=torch.int64, device="cuda") if per_slice else None
+    mm = torch.empty((max(n, 1), 2), dtype=torch.float64, device="cuda") if minmax else None
+    ctx.check(lib.unet_vol_intensity_bands(ctx.handle, dev.data_ptr(), *_vox_args(vol), _ptr(labels_dev), _ptr(mask_dev), int(n), _ptr(region_dev), e.ctypes.data, e.size,
+                                           bc.data_ptr(), _ptr(sc), _ptr(mm), _stream()), "vol_intensity_bands")
+    return bc[:n].cpu().numpy(), (sc[:Z].cpu().numpy() if per_slice else None), (mm[:n].cpu().numpy() if minmax else None)
+
+
+def intensity_gather_device(vol, dev, labels_dev, mask_dev, n, region_dev, capacity, want_groups=True, values=None, groups=None):
+    """unet_vol_intensity_gather -> (count, values, groups): the number of taking-part non-NaN voxels and device tensors of min(count, capacity) doubles / int32 group
+    numbers (None without want_groups), in no particular order.  values / groups: buffers of the caller's to write into (at least `capacity` elements)."""
+    torch = _torch(); lib, ctx = _ctx()
+    capacity = int(capacity)
+    if values is None:
+        values = torch.empty(max(capacity, 1), dtype=torch.float64, device="cuda")
+    if groups is None and want_groups:
+        groups = torch.empty(max(capacity, 1), dtype=torch.int32, device="cuda")
+    if values.numel() < capacity or (groups is not None and groups.numel() < capacity):
+        raise ValueError(f"the gather buffers hold fewer than capacity = {capacity} elements")
+    count = torch.zeros(1, dtype=torch.int64, device="cuda")
+    ctx.check(lib.unet_vol_intensity_gather(ctx.handle, dev.data_ptr(), *_vox_args(vol), _ptr(labels_dev), _ptr(mask_dev), int(n), _ptr(region_dev), values.data_ptr(),
+                                            _ptr(groups), capacity, count.data_ptr(), _stream()), "vol_intensity_gather")
+    c = int(count.item())
+    k = min(c, capacity)
+    return c, values[:k], (groups[:k] if groups is not None else None)
+
+
+def group_moments_device(values_dev, offsets, n):
+    """unet_vol_group_moments: values_dev ordered by (group, value), offsets int64 [n + 1] (numpy) -> float64 [n, 2] numpy: (sum, sum of squared deviations) per group"""
+    torch = _torch(); lib, ctx = _ctx()
+    n = int(n)
+    off = np.ascontiguousarray(offsets, np.int64)
+    if off.shape != (n + 1,) or off[0] != 0 or (np.diff(off) < 0).any() or off[-1] != values_dev.numel():
+        raise ValueError(f"offsets are [n + 1] = {n + 1} non-decreasing positions from 0 to the number of values")
+    if n == 0:
+        return np.zeros((0, 2), np.float64)
+    od = torch.from_numpy(off).cuda()
+    out = torch.empty((n, 2), dtype=torch.float64, device="cuda")
+    ws = torch.empty(max(int(lib.unet_vol_group_moments_ws_bytes(int(off[-1]), n)), 16), dtype=torch.uint8, device="cuda")
+    vals = values_dev.contiguous()
+    ctx.check(lib.unet_vol_group_moments(ctx.handle, vals.data_ptr(), od.data_ptr(), n, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "vol_group_moments")
+    return out.cpu().numpy()
+
+
+def sort_by_group_value(values, groups):
+    """gathered (values, groups) -> (the values in ascending order, the values ordered by (group, value)): one sort of the values, then a stable sort by group"""
+    torch = _torch()
+    sv, order = torch.sort(values)
+    if groups is None:
+        return sv, sv
+    _, perm = torch.sort(groups[order], stable=True)
+    return sv, sv[perm]
+
+
+def _order_statistics(run_dev, starts, sizes, qs):
+    """np.percentile(run, qs) for every run [starts[g], + sizes[g]) of an ascending-per-run device tensor -> float64 [G, Q] (nan for an empty run): the two order
+    statistics of every (run, q) come to the host in one indexing, the interpolation is numpy's linear rule (_lerp)"""
+    torch = _torch()
+    starts, sizes = np.asarray(starts, np.int64), np.asarray(sizes, np.int64)
+    G, Q = starts.size, len(qs)
+    out = np.full((G, Q), np.nan)
+    if G == 0 or Q == 0 or not (sizes > 0).any():
+        return out
+    m1 = np.maximum(sizes - 1, 0).astype(np.float64)[:, None]
+    pos = (np.asarray(qs, np.float64)[None, :] / 100.0) * m1
+    lo = np.minimum(np.floor(pos).astype(np.int64), np.maximum(sizes - 1, 0)[:, None])
+    hi = np.minimum(lo + 1, np.maximum(sizes - 1, 0)[:, None])
+    idx = np.stack([starts[:, None] + lo, starts[:, None] + hi])
+    idx = np.where((sizes > 0)[None, :, None], idx, 0)
+    ab = run_dev[torch.from_numpy(np.ascontiguousarray(idx.reshape(-1))).cuda()].cpu().numpy().reshape(2, G, Q)
+    r = _lerp(ab[0], ab[1], pos - lo)
+    out[sizes > 0] = r[sizes > 0]
+    return out
+
+
+def _moment_fields(sums, sizes):
+    """(sum, ssd) [G, 2] and the run lengths -> (mean, population std), nan for an empty run"""
+    m = np.asarray(sizes, np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean = np.where(m > 0, sums[:, 0] / m, np.nan)
+        std = np.where(m > 0, np.sqrt(sums[:, 1] / m), np.nan)
+    return mean, std
+
+
+def intensity_stats(ct, mask=None, labels=None, n=None, region=None, edges=HU_BAND_EDGES, names=HU_BAND_NAMES, percentiles=(5, 25, 50, 75, 95), moments=True,
+                    per_slice=True, shape=None):
+    """What the CT holds where a mask is set -> IntensityStats.  ct: a path, a NiftiVolume or an [X, Y, Z] array (as for segment_volume); its raw voxels are uploaded and
+    decoded on the device as get_fdata() decodes them.  Exactly one of mask (non-zero = the one group) and labels (int, groups 1..n, n given; other labels take no part);
+    region: only voxels where it is non-zero take part.  mask / labels / region: numpy [X, Y, Z] arrays (bool / integer), or flat device tensors in Fortran order (uint8 /
+    int32 / uint8, what unslice and label_volume return) with shape=.  edges / names: the value bands (default HU_BANDS: conventional literature thresholds in Hounsfield
+    units, configurable, not clinically validated here); band b of a value = np.searchsorted(edges, v, side="right").  A NaN voxel is counted in nan_voxels and nowhere else.
+    Counts, min and max are exact.  mean, std and percentiles come from one sort of the gathered values on the device: a percentile is np.percentile's (linear) on the
+    two order statistics; sum and sum of squared deviations are the fixed two-level tree of unet_vol_group_moments over the ascending values, so they are the same bits on
+    every run.  moments=False skips gather and sort (mean, std, percentiles: None); per_slice=False skips the per-slice counts.  Every argument error is a ValueError
+    raised before anything is uploaded or launched."""
+    torch = _torch()
+    e, names, qs = _check_intensity_args(edges, names, percentiles)
+    if (mask is None) == (labels is None):
+        raise ValueError("pass exactly one of mask, labels")
+    if labels is not None and n is None:
+        raise ValueError("labels need n, the number of groups (what label_volume returned)")
+    n = 1 if labels is None else int(n)
+    if n < 0:
+        raise ValueError(f"n is the number of groups, not {n}")
+    vol = _source(ct)
+    vshape = tuple(int(v) for v in vol.raw.shape)
+    _check_volume_dims(vshape)
+    for a, what, dt in ((mask, "the mask", torch.uint8), (labels, "the label volume", torch.int32), (region, "the region", torch.uint8)):
+        if a is not None:
+            _check_group_volume(a, what, vshape, shape, dt)
+    X, Y, Z = vshape
+    def flat(a):                                                    # (a volume without voxels still hands the entry points a buffer: null means "not given" there)
+        a = torch.from_numpy(np.asfortranarray(a).reshape(-1, order="F")).cuda() if not isinstance(a, torch.Tensor) else a.contiguous().reshape(-1)
+        return a if a.numel() else torch.zeros(16, dtype=a.dtype, device="cuda")
+    as_bytes = lambda a: flat(a if isinstance(a, torch.Tensor) else (np.asarray(a) != 0).astype(np.uint8))
+    mask_dev = as_bytes(mask) if mask is not None else None
+    region_dev = as_bytes(region) if region is not None else None
+    labels_dev = None
+    if labels is not None:
+        if isinstance(labels, torch.Tensor):
+            labels_dev = flat(labels)
+        else:
+            a = np.asarray(labels)
+            labels_dev = flat(np.where((a >= 1) & (a <= n), a, 0).astype(np.int32))          # a label outside 1..n takes no part: it must not wrap into the range
+    dev = flat(upload(vol))
+    B, Q = e.size + 1, len(qs)
+    bc, sc, mm = intensity_bands_device(vol, dev, labels_dev, mask_dev, n, region_dev, e, per_slice=per_slice)
+    sizes, nans = bc[:, :B].sum(axis=1), bc[:, B].copy()              # non-NaN / NaN voxels per group
+    total = int(sizes.sum())
+    voxel_ml = float(np.prod(np.asarray(vol.pixdim, np.float64))) / 1000.0
+    t = np.zeros(n, intensity_group_dtype(B, Q))
+    t["label"] = np.arange(1, n + 1)
+    t["voxels"], t["nan_voxels"] = sizes + nans, nans
+    t["ml"] = (sizes + nans) * voxel_ml
+    t["min"], t["max"] = np.where(sizes > 0, mm[:, 0], np.nan), np.where(sizes > 0, mm[:, 1], np.nan)
+    t["band_voxels"] = bc[:, :B]
+    t["band_ml"] = bc[:, :B] * voxel_ml
+    with np.errstate(invalid="ignore", divide="ignore"):
+        t["band_share"] = np.where(sizes[:, None] > 0, bc[:, :B] / sizes[:, None].astype(np.float64), np.nan)
+    t["dominant_band"] = np.where(sizes > 0, np.argmax(bc[:, :B], axis=1) if n else 0, -1)
+    t["mean"] = t["std"] = np.nan
+    t["percentiles"] = np.nan
+    band = bc[:, :B].sum(axis=0)
+    f = dict(names=names, edges=e, qs=qs, n=n, voxels=total + int(nans.sum()), nan_voxels=int(nans.sum()), ml=(total + int(nans.sum())) * voxel_ml,
+             min=float(mm[:, 0].min()) if total else float("nan"), max=float(mm[:, 1].max()) if total else float("nan"), mean=None, std=None, percentiles=None,
+             band_voxels=band, band_ml=band * voxel_ml, band_share=band / float(total) if total else np.full(B, np.nan),
+             slice_band_voxels=sc[:, :B].copy() if per_slice else None, slice_nan_voxels=sc[:, B].copy() if per_slice else None, voxel_ml=voxel_ml)
+    if moments:
+        count, vals, grps = intensity_gather_device(vol, dev, labels_dev, mask_dev, n, region_dev, total, want_groups=n > 1)
+        if count != total:
+            raise _lib.UNetHipError(f"intensity_stats: the bands hold {total} values but {count} were gathered")
+        sv, gv = sort_by_group_value(vals, grps)                    # plumbing, as in score_volume
+        off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        gsum = group_moments_device(gv, off, n)
+        t["mean"], t["std"] = _moment_fields(gsum, sizes)
+        t["percentiles"] = _order_statistics(gv, off[:-1], sizes, qs)
+        if n == 1:
+            usum, upct = gsum, t["percentiles"]
+        else:
+            usum = group_moments_device(sv, np.array([0, total], np.int64), 1)
+            upct = _order_statistics(sv, [0], [total], qs)
+        um, us = _moment_fields(usum, [total])
+        f.update(mean=float(um[0]), std=float(us[0]), percentiles={q: float(v) for q, v in zip(qs, upct[0])})
+    return IntensityStats(groups=t, **f)
