@@ -750,6 +750,30 @@ int32_t unet_vol_intensity_gather(unet_ctx*, const void* vox, int32_t dtype, int
 size_t unet_vol_group_moments_ws_bytes(int64_t total, int32_t n);
 int32_t unet_vol_group_moments(unet_ctx*, const double* values, const int64_t* offsets, int32_t n, double* out, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- left and right lung (csrc/kernels_lungside.hip; exact against tests/lungside_oracle.py) ----
+ * All volumes: [X, Y, Z] in Fortran order, X Y Z < 2^31 (otherwise UNET_E_ARG, nothing launched); a volume with a zero dimension returns UNET_OK and touches nothing,
+ * the outputs included.  Integer arithmetic only (the distances are compared as order-preserving 64-bit keys of their bit patterns, which is value order for the
+ * non-negative values and +inf that unet_vol_edt_sq writes); integer sums per lane, per wave and per workgroup, then 64-bit atomics: the same bits on every run.
+ *
+ * unet_vol_side_assign: mask uint8 (non-zero = lung), d2_a / d2_b the results of unet_vol_edt_sq to the voxels of seed a / seed b (X Y Z doubles each, 8-byte aligned),
+ * side_a, side_b = 1 and 2 in either order (anything else: UNET_E_ARG).  sides (uint8, X Y Z bytes, not the mask's own buffer):
+ *     sides[v] = 0 where mask[v] == 0, else the side of the seed with the smaller distance; on a tie the seed whose side is 1 -- whichever of a, b that is.
+ * counts: device int64 [3], 8-byte aligned, overwritten: the voxels of sides holding 0, 1, 2 (summed per lane and per wave, one atomic per workgroup and entry).
+ * 17 bytes read and 1 written per voxel: a lane takes four voxels with one 4-byte mask load, two 16-byte loads per distance stream and one 4-byte store when mask /
+ * sides are 4-byte and d2_a / d2_b 16-byte aligned (one voxel per lane otherwise); a wave whose mask bytes are all zero reads no distance. */
+int32_t unet_vol_side_assign(unet_ctx*, const uint8_t* mask, const double* d2_a, const double* d2_b, int32_t X, int32_t Y, int32_t Z, int32_t side_a, int32_t side_b,
+                             uint8_t* sides, int64_t* counts, void* stream);
+/* sides: uint8 0 / 1 / 2 (a value above 2 counts as 0); infection: uint8, non-zero = infected, nullable (nothing is infected); labels: int32, lesions 1..n, nullable, 4-byte
+ * aligned; a label outside 1..n is ignored, never an address.  n < 0: UNET_E_ARG.  All outputs are device int64, 8-byte aligned and overwritten (the caller does not zero them):
+ *   totals       [2][3]  row 0: the voxels of sides by value; row 1: the voxels with infection != 0 by the side value under them (column 0: infected outside both lungs)
+ *   lesion_side  [n][3]  the voxels of lesion i + 1 by side value (all zero without labels); may be null when n == 0
+ *   per_slice    [Z][6]  {lung L, lung R, infected outside, infected L, infected R, 0} of every slice; nullable
+ * One lane per voxel; a wave counts the five slice columns with ballots, and the lanes that share a (lesion, side) key with one ballot whose first lane adds the popcount
+ * (one add per distinct key of a wave) -- to a table in LDS while 3 n <= 4096, flushed once per workgroup with 64-bit atomics, straight to lesion_side beyond that.  The
+ * slice counters sit in LDS and leave when the workgroup's slice changes. */
+int32_t unet_vol_side_table(unet_ctx*, const uint8_t* sides, const uint8_t* infection, const int32_t* labels, int32_t n, int32_t X, int32_t Y, int32_t Z, int64_t* totals,
+                            int64_t* lesion_side, int64_t* per_slice, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Model level. Replaces the Keras Model built at T1:853-916 and driven by
  * compile/fit/evaluate/predict (T1:1053-1061, 1101, 1137).  A model is a fixed-shape plan:

@@ -4,8 +4,17 @@ Public surface:
   runners.holdout_runner_unet_infection_segmentation / runners.runner_lung_segmentation
   keras_like.UNetModel   -- compile / fit / evaluate / predict / save_weights / load_weights
   volume.segment_volume / volume.build_dataset / volume.load_volume -- a NIfTI CT volume in, slice batches / a mask volume out (nifti_min reads the file)
+  split_lungs / lung_burden (LungSides, LungBurden, LungSplitError) -- volume's left / right lung split and per-lung burden, also reachable from the package itself
   engine.HipUNet         -- the HIP backend (libunet_hip.so through the C ABI of include/unet_hip.h)
 Importing this package has no side effects and does not need a GPU; constructing the
 backend does (there is no CPU fallback).
 """
-__all__ = ["runners", "keras_like", "engine", "weights", "data", "volume", "nifti_min"]
+__all__ = ["runners", "keras_like", "engine", "weights", "data", "volume", "nifti_min", "split_lungs", "lung_burden", "LungSides", "LungBurden", "LungSplitError"]
+_FROM_VOLUME = ("split_lungs", "lung_burden", "LungSides", "LungBurden", "LungSplitError")
+
+
+def __getattr__(name):                                              # resolved on first use: importing the package stays free of side effects
+    if name in _FROM_VOLUME:
+        import importlib
+        return getattr(importlib.import_module(__name__ + ".volume"), name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

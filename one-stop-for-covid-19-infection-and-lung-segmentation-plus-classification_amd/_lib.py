@@ -211,6 +211,9 @@ _PROTOS = {
     "unet_vol_intensity_gather": (i32, [vp, vp, i32, i32, i32, i32, i32, f64, f64, vp, vp, i32, vp, vp, vp, i64, vp, vp]),
     "unet_vol_group_moments_ws_bytes": (sz, [i64, i32]),
     "unet_vol_group_moments": (i32, [vp, vp, vp, i32, vp, vp, sz, vp]),
+    # left and right lung (csrc/kernels_lungside.hip, volume.split_lungs / lung_burden)
+    "unet_vol_side_assign": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]),
+    "unet_vol_side_table": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
     "unet_model_create": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(vp)]),
     "unet_model_dtype": (i32, [vp]),
     "unet_model_tap_elem_bytes": (i32, [vp, C.c_char_p, i32]),

@@ -8,6 +8,10 @@ Read:  single-file NIfTI-1 (`.nii`, magic `n+1\\0`), or `.nii.gz` through gzip; 
        (dim[1] fastest).
 Write: a uint8 or float32 volume with the geometry of a source header (dim, pixdim, qform / sform, xyzt_units), scl_slope = 1, scl_inter = 0.
 Everything else is refused with a NiftiFormatError that names the case.
+
+Orientation: `affine` is the sform when sform_code > 0, else the qform (quaternion, pixdim, qfac, qoffset exactly as nifti1.h states them) when qform_code > 0, else
+None; `axcodes` names the direction in which every voxel axis grows, in NIfTI's RAS+ world (+x = the patient's right, +y = anterior, +z = superior).  The rule of
+axcodes_from_affine is stated there; for axis-aligned and mildly oblique affines it gives what nibabel's aff2axcodes gives ("parity unpinned", like the rest).
 """
 from __future__ import annotations
 
@@ -30,10 +34,17 @@ class NiftiFormatError(ValueError):
 
 class NiftiVolume:
     """What a read returns: `raw` (the voxels as stored, numpy [X, Y, Z] in Fortran order, native byte order), `slope` / `inter` (scl_slope, scl_inter as
-    stored), `pixdim` (pixdim[1:4]), `header` (the 348 header bytes, for a mask written with the same geometry), `byteorder` ('<' or '>')."""
+    stored), `pixdim` (pixdim[1:4]), `header` (the 348 header bytes, for a mask written with the same geometry), `byteorder` ('<' or '>'); from the header's
+    orientation fields `affine` (float64 4 x 4, None when qform_code and sform_code are both 0), `affine_source` ("sform", "qform" or None) and `axcodes` (three letters,
+    None without an affine; an affine with a zero or non-finite column raises NiftiFormatError when the codes are asked for)."""
 
     def __init__(self, raw, slope, inter, pixdim, header, byteorder):
         self.raw, self.slope, self.inter, self.pixdim, self.header, self.byteorder = raw, slope, inter, pixdim, header, byteorder
+        self.affine, self.affine_source = affine_of_header(header)
+
+    @property
+    def axcodes(self):
+        return None if self.affine is None else axcodes_from_affine(self.affine)
 
     @property
     def shape(self):
@@ -107,8 +118,99 @@ def parse_header(buf):
     datatype, bitpix = struct.unpack(bo + "2h", buf[70:74])
     pixdim = struct.unpack(bo + "8f", buf[76:108])
     vox_offset, slope, inter = struct.unpack(bo + "3f", buf[108:120])
+    qform_code, sform_code = struct.unpack(bo + "2h", buf[252:256])
+    quatern = struct.unpack(bo + "3f", buf[256:268])
+    qoffset = struct.unpack(bo + "3f", buf[268:280])
+    srow = struct.unpack(bo + "12f", buf[280:328])
     return bo, {"dim": dim, "datatype": datatype, "bitpix": bitpix, "pixdim": pixdim, "vox_offset": vox_offset, "scl_slope": slope, "scl_inter": inter,
-                "xyzt_units": buf[123]}
+                "xyzt_units": buf[123], "qform_code": qform_code, "sform_code": sform_code, "quatern_b": quatern[0], "quatern_c": quatern[1], "quatern_d": quatern[2],
+                "qoffset_x": qoffset[0], "qoffset_y": qoffset[1], "qoffset_z": qoffset[2], "srow_x": srow[0:4], "srow_y": srow[4:8], "srow_z": srow[8:12]}
+
+
+# the two letters of every world axis of RAS+: (negative direction, positive direction)
+AXIS_LETTERS = (("L", "R"), ("P", "A"), ("I", "S"))
+
+
+def affine_from_fields(h):
+    """The voxel -> world matrix of parsed header fields -> (float64 4 x 4, "sform" | "qform"), or (None, None) when both codes are 0.  sform_code > 0: the three srow
+    rows.  Otherwise qform_code > 0, nifti1.h's method 2: a = sqrt(max(0, 1 - b^2 - c^2 - d^2)), R the nine-term rotation matrix of (a, b, c, d), column j scaled by
+    pixdim[j + 1], the third column also by qfac (-1 only when pixdim[0] == -1, else +1), translation qoffset.  All in float64 from the stored float32 values."""
+    if h["sform_code"] > 0:
+        m = np.eye(4)
+        m[0], m[1], m[2] = (np.asarray(h[k], np.float64) for k in ("srow_x", "srow_y", "srow_z"))
+        return m, "sform"
+    if h["qform_code"] > 0:
+        b, c, d = float(h["quatern_b"]), float(h["quatern_c"]), float(h["quatern_d"])
+        a = float(np.sqrt(max(0.0, 1.0 - b * b - c * c - d * d)))
+        R = np.array([[a * a + b * b - c * c - d * d, 2.0 * b * c - 2.0 * a * d, 2.0 * b * d + 2.0 * a * c],
+                      [2.0 * b * c + 2.0 * a * d, a * a + c * c - b * b - d * d, 2.0 * c * d - 2.0 * a * b],
+                      [2.0 * b * d - 2.0 * a * c, 2.0 * c * d + 2.0 * a * b, a * a + d * d - c * c - b * b]], np.float64)
+        qfac = -1.0 if float(h["pixdim"][0]) == -1.0 else 1.0
+        m = np.eye(4)
+        m[:3, :3] = R * np.array([float(h["pixdim"][1]), float(h["pixdim"][2]), float(h["pixdim"][3]) * qfac], np.float64)[None, :]
+        m[:3, 3] = [float(h["qoffset_x"]), float(h["qoffset_y"]), float(h["qoffset_z"])]
+        return m, "qform"
+    return None, None
+
+
+def affine_of_header(header):
+    """(affine, source) of 348 header bytes (see affine_from_fields)"""
+    return affine_from_fields(parse_header(header)[1])
+
+
+def axcodes_from_affine(affine):
+    """Three letters: the world direction in which voxel axes 0, 1, 2 grow.  (1) the three columns of affine[:3, :3] are normalised to unit length -- a zero or
+    non-finite column raises NiftiFormatError; (2) for voxel axes 0, 1, 2 in that order: the world axis with the largest absolute component among those not yet taken,
+    ties to the lowest world axis; (3) R / A / S when that component is positive, L / P / I when it is negative."""
+    m = np.asarray(affine, np.float64)
+    if m.shape not in ((4, 4), (3, 3), (3, 4)) or not np.isfinite(m[:3, :3]).all():
+        raise NiftiFormatError(f"an affine is a finite 4 x 4 matrix, not {m.shape}" if m.shape not in ((4, 4), (3, 3), (3, 4)) else "the affine has a non-finite column")
+    rz = m[:3, :3]
+    norms = np.sqrt((rz * rz).sum(axis=0))
+    if not np.isfinite(norms).all() or (norms == 0).any():
+        raise NiftiFormatError(f"the affine has a zero or non-finite column (column lengths {norms.tolist()}): no orientation can be read from it")
+    unit = rz / norms[None, :]
+    taken, codes = [], []
+    for j in range(3):
+        best = None
+        for w in range(3):
+            if w not in taken and (best is None or abs(unit[w, j]) > abs(unit[best, j])):
+                best = w
+        taken.append(best)
+        codes.append(AXIS_LETTERS[best][1 if unit[best, j] > 0 else 0])
+    return tuple(codes)
+
+
+def check_axcodes(codes):
+    """A 3-letter string or tuple with one letter from each of L/R, P/A, I/S -> [(world axis, sign)] per voxel axis; anything else raises ValueError."""
+    try:
+        letters = tuple(str(c) for c in codes)
+    except TypeError:
+        raise ValueError(f"axis codes are three letters, one from each of L/R, P/A, I/S, not {codes!r}") from None
+    if len(letters) != 3:
+        raise ValueError(f"axis codes are three letters, one from each of L/R, P/A, I/S, not {codes!r}")
+    out = []
+    for c in letters:
+        hit = [(w, 1.0 if pair[1] == c else -1.0) for w, pair in enumerate(AXIS_LETTERS) if c in pair]
+        if len(c) != 1 or not hit:
+            raise ValueError(f"axis codes are three letters, one from each of L/R, P/A, I/S, not {codes!r}")
+        out.append(hit[0])
+    if sorted(w for w, _ in out) != [0, 1, 2]:
+        raise ValueError(f"axis codes take one letter from each of L/R, P/A, I/S, not {codes!r}")
+    return out
+
+
+def affine_from_axcodes(codes, pixdim=(1.0, 1.0, 1.0)):
+    """The axis-aligned affine (float64 4 x 4, no translation) whose axcodes_from_affine is `codes`: voxel axis j grows by pixdim[j] mm along its letter."""
+    axes = check_axcodes(codes)
+    p = np.asarray(pixdim, np.float64).reshape(-1)
+    if p.shape != (3,) or not np.isfinite(p).all() or not (p > 0).all():
+        raise ValueError(f"pixdim is three positive finite numbers, not {pixdim!r}")
+    m = np.zeros((4, 4))
+    m[3, 3] = 1.0
+    for j, (w, sign) in enumerate(axes):
+        m[w, j] = sign * p[j]
+    return m
 
 
 def read(path):

@@ -18,6 +18,10 @@ the dataset loop around it (T1:390-393, 421-429) and the way back from a predict
     vote_volume(masks, rule) / dihedral(x, code) / models_from_weights(paths, input_size)     the pieces: up to 32 masks voted on the device, one symmetry, fold files -> models
     intensity_stats(ct, mask | labels, n, region, edges)     -> IntensityStats: what the CT holds under a mask or per lesion -- voxels per HU band (HU_BANDS), min / max,
                                           mean / std, percentiles, per slice; segment_volume(density=True) fills res.density / res.lung_density with it
+    split_lungs(lung_mask, orientation)   -> LungSides: the lung mask told into the patient's left (1) and right (2) lung from the file's orientation (nifti_min: sform /
+                                          qform); lungs that touch are separated by eroding until two seeds remain, every voxel then goes to the nearer seed
+    lung_burden(infection, sides)         -> LungBurden: lung / infected volume and fraction per lung, every lesion's side, per slice; segment_volume(per_lung=True)
+                                          fills res.per_lung with it
 
 The voxels are uploaded once as stored (nifti_min reads the file); decode, np.rot90, the slice trim, cv2.resize(float64, INTER_AREA) and the min-max run
 in unet_vol_slices_f64, CLAHE / crop / fuse / resize in the uint8 kernels of preprocess.py on device pointers: between the upload and the returned batch
@@ -292,7 +296,8 @@ class VolumeSegmentation:
     score: the VolumeScore of the final mask against the `truth` given to segment_volume (None without one);
     postprocess_ml: the volume the `postprocess` steps added to the mask (negative: removed; None without steps);
     density / lung_density: the IntensityStats of the CT under the final mask (per lesion when the lesion table was computed) and under the lung mask (None unless
-    segment_volume was given density=)."""
+    segment_volume was given density=);
+    per_lung / per_lung_error: the LungBurden of the final mask per lung (None unless segment_volume was given per_lung=) and, when the lungs could not be split, why."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -1040,7 +1045,7 @@ def _prepare_segmentation(ct, lung_mask, truth, img_size, trim, input_size):
 
 
 def segment_volume(ct, model, lung_mask=None, threshold=0.547, batch_size=32, out_path=None, img_size=512, trim=(0.2, 0.8), min_lesion_ml=None, connectivity=1,
-                   lesions=False, truth=None, postprocess=None, density=None):
+                   lesions=False, truth=None, postprocess=None, density=None, per_lung=None):
     """CT file (or array) -> VolumeSegmentation.  `model`: a UNetModel or a routed.ClusterRoutedModel (only `predict` is used); lung_mask=None: whole-frame
     boxes (the two halves of the frame); boxes are keyed by slice number (box_indexing="slice"); out_path: the mask as .nii / .nii.gz with the CT's geometry.
     min_lesion_ml: connected components (`connectivity` 1, 2, 3 = 6, 18, 26 neighbours) smaller than that are removed on the device before the mask comes to the
@@ -1055,9 +1060,15 @@ def segment_volume(ct, model, lung_mask=None, threshold=0.547, batch_size=32, ou
     density: True, or a dict of intensity_stats keyword arguments (edges, names, percentiles, moments, per_slice): after postprocess / min_lesion_ml, res.density =
     intensity_stats of the CT under the final mask -- one row per lesion of res.lesions when the lesion table is computed (the device labels are reused, not relabelled),
     one group otherwise --, res.lung_density the same under the lung mask (None without one), seconds["density"] their time.  The CT's raw voxels are uploaded a second
-    time for it.  None: nothing runs, both fields are None."""
+    time for it.  None: nothing runs, both fields are None.
+    per_lung: True, or a dict of split_lungs keyword arguments (orientation, pixdim, connectivity, min_ratio, erode_mm); needs lung_mask (ValueError before any device
+    work without one).  After postprocess / min_lesion_ml, on the final mask: the lung mask is split (split_lungs; orientation: the lung mask file's own, else the CT's;
+    pixdim: the CT's) and res.per_lung = the LungBurden of the final mask -- its `lesions` rows align with res.lesions when the lesion table is computed (the device labels
+    are reused), `sides` is the LungSides, and with density= as well `density` = intensity_stats(ct, labels=sides, n=2): two rows, left then right.  A LungSplitError does
+    not lose the segmentation: res.per_lung is None and res.per_lung_error holds its message.  seconds["per_lung"]: its time.  None: nothing runs."""
     _check_connectivity(connectivity)
     density = _check_density(density)
+    per_lung = _check_per_lung(per_lung, lung_mask)
     if postprocess is not None:
         _check_steps(postprocess, (1.0, 1.0, 1.0))                   # the steps' own arguments, before any work (the CT's pixdim takes this one's place below)
     torch = _torch()
@@ -1070,13 +1081,13 @@ def segment_volume(ct, model, lung_mask=None, threshold=0.547, batch_size=32, ou
     canvas = paste_back(prob, R1, R2, S)
     mask_dev, counts_dev = unslice(canvas, threshold, (X, Y, Z), z0, z1)
     return _finish_segmentation(vol, lv, truth_mask, mask_dev, counts_dev, z0, z1, has, info, threshold, sec, t0, postprocess, min_lesion_ml, lesions, connectivity, out_path,
-                                density=density)
+                                density=density, per_lung=per_lung)
 
 
 def _finish_segmentation(vol, lv, truth_mask, mask_dev, counts_dev, z0, z1, has, info, threshold, sec, t0, postprocess, min_lesion_ml, lesions, connectivity, out_path,
-                         density=None, **extra):
+                         density=None, per_lung=None, **extra):
     """What segment_volume and segment_volume_ensemble do with the mask volume once it is formed (mask_dev, counts_dev [z1 - z0], both on the device): postprocess,
-    min_lesion_ml / lesions, density (the checked keyword arguments of intensity_stats, or None), truth, the download, the lung share and out_path -> VolumeSegmentation (+ `extra` fields).  t0: when the paste-back began."""
+    min_lesion_ml / lesions, density (the checked keyword arguments of intensity_stats, or None), per_lung (those of split_lungs, or None), truth, the download, the lung share and out_path -> VolumeSegmentation (+ `extra` fields).  t0: when the paste-back began."""
     torch = _torch()
     X, Y, Z = vol.raw.shape
     voxel_mm3 = float(np.prod(np.asarray(vol.pixdim, np.float64)))          # count * prod(pixdim) / 1000 = millilitres
@@ -1104,7 +1115,7 @@ def _finish_segmentation(vol, lv, truth_mask, mask_dev, counts_dev, z0, z1, has,
             table = table[keep[1:]]                                  # the kept components keep their order: renumbered, this is the table of the filtered mask
             table["label"] = np.arange(1, len(table) + 1)
             removed_ml = float(before) * voxel_mm3 / 1000.0 - float(counts_dev.sum().item()) * voxel_mm3 / 1000.0
-        if density is None:
+        if density is None and per_lung is None:
             labels_dev = None
         torch.cuda.synchronize(); sec["components"] = time.perf_counter() - tc
     dens, lung_dens = None, None
@@ -1114,12 +1125,38 @@ def _finish_segmentation(vol, lv, truth_mask, mask_dev, counts_dev, z0, z1, has,
             dens = intensity_stats(vol, labels=labels_dev, n=n_comp, region=mask_dev if keep is not None else None, shape=(X, Y, Z), **density)
             if keep is not None:
                 dens = dens.take_groups(keep[1:])
-            labels_dev = None
         else:
             dens = intensity_stats(vol, mask=mask_dev, shape=(X, Y, Z), **density)
         if lv is not None:
             lung_dens = intensity_stats(vol, mask=lv.get_fdata() != 0, **density)
         torch.cuda.synchronize(); sec["density"] = time.perf_counter() - td
+    burden, burden_error = None, None
+    if per_lung is not None:
+        torch.cuda.synchronize(); tl = time.perf_counter()
+        kw = dict(per_lung)
+        if kw.get("orientation") is None and lv.affine is None and vol.affine is not None:
+            kw["orientation"] = vol.affine                          # the two files share one geometry
+        kw.setdefault("pixdim", vol.pixdim)
+        try:
+            ls = split_lungs(lv, return_device=True, **kw)
+        except LungSplitError as e:
+            burden_error = str(e)
+        else:
+            if labels_dev is not None:                              # the labels the lesion table came from; a filtered lesion's rows go with it
+                totals, les, ps = side_table_device(ls.sides, mask_dev, labels_dev, n_comp, (X, Y, Z))
+                if keep is not None:
+                    les = les[keep[1:]]
+            else:
+                own, n_own = label_device(mask_dev, (X, Y, Z), connectivity)
+                totals, les, ps = side_table_device(ls.sides, mask_dev, own, n_own, (X, Y, Z))
+                del own
+            burden = burden_from_tables(totals, les, ps, vol.pixdim)
+            if density is not None:
+                burden.density = intensity_stats(vol, labels=ls.sides.to(torch.int32), n=2, shape=(X, Y, Z), **density)
+            ls.sides = ls.sides.cpu().numpy().reshape((X, Y, Z), order="F")
+            burden.sides = ls
+        torch.cuda.synchronize(); sec["per_lung"] = time.perf_counter() - tl
+    labels_dev = None
     score = None
     if truth_mask is not None:
         torch.cuda.synchronize(); ts = time.perf_counter()
@@ -1132,7 +1169,7 @@ def _finish_segmentation(vol, lv, truth_mask, mask_dev, counts_dev, z0, z1, has,
                              total_ml=float(counts.sum()) * voxel_mm3 / 1000.0, lung_ml=None,
                              infected_share=None, fell_through=[int(i) for i in np.nonzero(~has)[0]], flat=info["flat"], z0=z0, z1=z1, pixdim=vol.pixdim,
                              threshold=float(threshold), seconds=sec, lesions=table, n_lesions=None if table is None else len(table), removed_ml=removed_ml, score=score,
-                             postprocess_ml=postprocess_ml, density=dens, lung_density=lung_dens, **extra)
+                             postprocess_ml=postprocess_ml, density=dens, lung_density=lung_dens, per_lung=burden, per_lung_error=burden_error, **extra)
     if lv is not None:
         lung_vox = int(np.count_nonzero(lv.get_fdata()[:, :, z0:z1]))
         res.lung_ml = lung_vox * voxel_mm3 / 1000.0
@@ -1391,13 +1428,13 @@ def _predict_device(model, x, batch_size):
 
 def segment_volume_ensemble(ct, models, tta=("id",), combine="mean", weights=None, lung_mask=None, threshold=0.547, batch_size=32, out_path=None, img_size=512,
                             trim=(0.2, 0.8), min_lesion_ml=None, connectivity=1, lesions=False, truth=None, postprocess=None, return_prob=False, prob_path=None,
-                            votes_path=None, density=None):
+                            votes_path=None, density=None, per_lung=None):
     """segment_volume with several members: every (model, symmetry) pair of `models` (each anything segment_volume accepts, all of one input size) and `tta` (names of
     TTA, no repeats), in model-major order, at most 32.  A member sees the prepared batch under its symmetry (transformed once, on the device), its probabilities are
     transformed back, pasted onto the canvas and (a) thresholded into the member's mask, which becomes one bit of a vote word per voxel, (b) added into the weighted
     mean canvas: acc = w_0 c_0, acc = acc + w_m c_m in member order, then acc / wsum, every float32 operation rounded on its own (weights: one per model, None: all 1;
     wsum: the float32 sum of the member weights in order).  combine="mean": the final mask is the thresholded mean probability; "majority" / "any" / "all" / int k: the
-    members' masks voted (vote_volume's rules).  Everything after the mask is formed -- postprocess, min_lesion_ml, lesions, density, truth, out_path, the lung share -- is
+    members' masks voted (vote_volume's rules).  Everything after the mask is formed -- postprocess, min_lesion_ml, lesions, density, per_lung, truth, out_path, the lung share -- is
     segment_volume's, and so are the result's fields.  Added: members [(model index, tta name)], votes (uint8 [X, Y, Z]: how many members marked the voxel),
     member_ml, pairwise_dice, vote_hist (voxels with k votes), unanimous_ml (all members), uncertain_ml (some but not all), combine, seconds["members"] (predict time per
     member), and prob (float32 [X, Y, Z], the mean probability in patient space) with return_prob=True or prob_path (None otherwise).  prob_path / votes_path: those two
@@ -1406,6 +1443,7 @@ def segment_volume_ensemble(ct, models, tta=("id",), combine="mean", weights=Non
     _check_connectivity(connectivity)
     models, members, mw, wsum, min_votes, d = _check_ensemble(models, tta, combine, weights)
     density = _check_density(density)
+    per_lung = _check_per_lung(per_lung, lung_mask)
     if postprocess is not None:
         _check_steps(postprocess, (1.0, 1.0, 1.0))
     torch = _torch()
@@ -1452,7 +1490,7 @@ def segment_volume_ensemble(ct, models, tta=("id",), combine="mean", weights=Non
                  vote_hist=st["hist"], unanimous_ml=float(st["unanimous_voxels"]) * voxel_ml, uncertain_ml=float(st["uncertain_voxels"]) * voxel_ml, combine=combine,
                  weights=mw, prob=prob)
     res = _finish_segmentation(vol, lv, truth_mask, mask_dev, counts_dev, z0, z1, has, info, threshold, sec, t0, postprocess, min_lesion_ml, lesions, connectivity, out_path,
-                               density=density, **extra)
+                               density=density, per_lung=per_lung, **extra)
     if prob_path is not None:
         nifti_min.write(prob_path, prob, vol.header)
     if votes_path is not None:
@@ -1745,3 +1783,291 @@ def intensity_stats(ct, mask=None, labels=None, n=None, region=None, edges=HU_BA
         um, us = _moment_fields(usum, [total])
         f.update(mean=float(um[0]), std=float(us[0]), percentiles={q: float(v) for q, v in zip(qs, upct[0])})
     return IntensityStats(groups=t, **f)
+
+
+# ---- left and right lung (csrc/kernels_lungside.hip) ----------------------------------------------------------------------------
+# The defaults of the split: a second component counts as the other lung once it holds min_ratio of the largest one's voxels, and the mask is eroded by these radii
+# (mm, in order) until that happens.  Conventional values, configurable (min_ratio=, erode_mm=) and NOT clinically validated here.
+LUNG_MIN_RATIO = 0.25
+LUNG_ERODE_MM = (1, 2, 3, 4, 5, 6, 8, 10)
+_PER_LUNG_KEYS = {"orientation", "pixdim", "connectivity", "min_ratio", "erode_mm"}
+LUNG_LESION_DTYPE = np.dtype([("label", np.int32), ("voxels_outside", np.int64), ("voxels_left", np.int64), ("voxels_right", np.int64), ("side", "U5")])
+SIDE_NAMES = ("none", "left", "right")                              # by side value 0, 1, 2
+
+
+class LungSplitError(ValueError):
+    """The lung mask cannot be told into a left and a right lung: no orientation, fewer than two large enough components at every radius, or two seeds at the same
+    world x."""
+
+
+class LungSides:
+    """What split_lungs returns.  sides: uint8 [X, Y, Z], 0 off the mask, 1 = the patient's left lung, 2 = the right (numpy, Fortran order; return_device=True: the
+    flat device tensor); shape; radius_mm: the erosion radius that separated the lungs (0: they were separate already); voxels / ml: (left, right); seed_voxels: (left,
+    right) voxels of the two seeds; axcodes: the direction in which every voxel axis grows; pixdim."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def __repr__(self):
+        return f"LungSides(radius_mm={self.radius_mm}, voxels={self.voxels}, axcodes={self.axcodes})"
+
+
+class LungSideBurden:
+    """One lung of a LungBurden: lung_voxels, infected_voxels, lung_ml, infected_ml, fraction = infected / lung (nan for an empty lung)."""
+
+    def __init__(self, lung_voxels, infected_voxels, voxel_ml):
+        self.lung_voxels, self.infected_voxels = int(lung_voxels), int(infected_voxels)
+        self.lung_ml, self.infected_ml = self.lung_voxels * voxel_ml, self.infected_voxels * voxel_ml
+        self.fraction = (self.infected_ml / self.lung_ml) if self.lung_voxels else float("nan")
+
+    def __repr__(self):
+        return f"LungSideBurden(lung_ml={self.lung_ml:.1f}, infected_ml={self.infected_ml:.1f}, fraction={self.fraction:.3f})"
+
+
+class LungBurden:
+    """What lung_burden returns.  left / right: LungSideBurden; outside_voxels / outside_ml: infected outside both lungs; lesions: LUNG_LESION_DTYPE rows (label,
+    voxels_outside, voxels_left, voxels_right, side = "left" / "right" by where most of the lesion's in-lung voxels lie, a tie to left, "none" when no voxel of it lies in
+    a lung); per_slice: int64 [Z, 6] = {lung left, lung right, infected outside, infected left, infected right, 0}; bilateral: both fractions > 0; voxel_ml.  From
+    segment_volume(per_lung=): also sides (the LungSides, on the host) and density (IntensityStats with two rows, left then right; None without density=)."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def __repr__(self):
+        return f"LungBurden(left={self.left!r}, right={self.right!r}, outside_ml={self.outside_ml:.1f}, bilateral={self.bilateral})"
+
+
+def _check_orientation(orientation):
+    """split_lungs' orientation= -> (float64 3 x 3 linear part or None, axcodes or None): a 3-letter code string / tuple or an affine; ValueError otherwise"""
+    if orientation is None:
+        return None, None
+    if isinstance(orientation, str) or (isinstance(orientation, (tuple, list)) and len(orientation) == 3 and all(isinstance(c, str) for c in orientation)):
+        nifti_min.check_axcodes(orientation)
+        return nifti_min.affine_from_axcodes(orientation)[:3, :3], tuple(str(c) for c in orientation)
+    try:
+        m = np.asarray(orientation, np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"orientation is a 3-letter code such as 'LPS' or a 4 x 4 affine, not {orientation!r}") from None
+    if m.shape != (4, 4):
+        raise ValueError(f"orientation is a 3-letter code such as 'LPS' or a 4 x 4 affine, not an array of shape {m.shape}")
+    try:
+        codes = nifti_min.axcodes_from_affine(m)
+    except nifti_min.NiftiFormatError as e:
+        raise ValueError(f"orientation: {e}") from None
+    return m[:3, :3].copy(), codes
+
+
+def _check_split_args(orientation=None, pixdim=None, connectivity=1, min_ratio=LUNG_MIN_RATIO, erode_mm=LUNG_ERODE_MM):
+    """-> (linear part or None, axcodes or None, pixdim float64 [3] or None, connectivity, min_ratio, radii), or ValueError: no device is needed"""
+    lin, codes = _check_orientation(orientation)
+    p = None if pixdim is None else _check_pixdim(pixdim)
+    connectivity = _check_connectivity(connectivity)
+    try:
+        ratio = float(min_ratio)
+    except (TypeError, ValueError):
+        raise ValueError(f"min_ratio is a number in (0, 1], not {min_ratio!r}") from None
+    if not 0.0 < ratio <= 1.0:
+        raise ValueError(f"min_ratio is a number in (0, 1], not {min_ratio!r}")
+    try:
+        radii = tuple(_check_radius(r) for r in erode_mm)
+    except TypeError:
+        raise ValueError(f"erode_mm is a sequence of ascending radii in mm, not {erode_mm!r}") from None
+    if any(r <= 0.0 for r in radii) or any(b <= a for a, b in zip(radii, radii[1:])):
+        raise ValueError(f"erode_mm must be positive and strictly ascending, not {erode_mm!r}")
+    return lin, codes, p, connectivity, ratio, radii
+
+
+def _check_per_lung(per_lung, lung_mask):
+    """segment_volume's per_lung= -> None (off) or the checked keyword arguments of split_lungs"""
+    if per_lung is None or per_lung is False:
+        return None
+    kw = {} if per_lung is True else dict(per_lung)
+    if set(kw) - _PER_LUNG_KEYS:
+        raise ValueError(f"per_lung takes {sorted(_PER_LUNG_KEYS)}, not {sorted(set(kw) - _PER_LUNG_KEYS)}")
+    _check_split_args(**kw)
+    if lung_mask is None:
+        raise ValueError("per_lung needs lung_mask: the lungs are split from it")
+    return kw
+
+
+def side_assign_device(mask_dev, d2_a, d2_b, shape, side_a=1, side_b=2):
+    """unet_vol_side_assign -> (sides: uint8 device tensor of X*Y*Z bytes in Fortran order, counts int64 [3] numpy: the voxels holding 0, 1, 2)"""
+    torch = _torch(); lib, ctx = _ctx()
+    X, Y, Z = shape
+    _check_volume_dims(shape)
+    sides = torch.empty(X * Y * Z, dtype=torch.uint8, device="cuda")
+    counts = torch.zeros(3, dtype=torch.int64, device="cuda")
+    ctx.check(lib.unet_vol_side_assign(ctx.handle, mask_dev.data_ptr(), d2_a.data_ptr(), d2_b.data_ptr(), X, Y, Z, int(side_a), int(side_b), sides.data_ptr(), counts.data_ptr(),
+                                       _stream()), "vol_side_assign")
+    return sides, counts.cpu().numpy()
+
+
+def side_table_device(sides_dev, infection_dev, labels_dev, n, shape, per_slice=True):
+    """unet_vol_side_table -> (totals int64 [2, 3], lesion_side int64 [n, 3], per_slice int64 [Z, 6] or None), numpy"""
+    torch = _torch(); lib, ctx = _ctx()
+    X, Y, Z = shape
+    _check_volume_dims(shape)
+    n = int(n)
+    totals = torch.zeros((2, 3), dtype=torch.int64, device="cuda")
+    les = torch.zeros((max(n, 1), 3), dtype=torch.int64, device="cuda")
+    ps = torch.zeros((max(Z, 1), 6), dtype=torch.int64, device="cuda") if per_slice else None
+    ctx.check(lib.unet_vol_side_table(ctx.handle, sides_dev.data_ptr(), _ptr(infection_dev), _ptr(labels_dev), n, X, Y, Z, totals.data_ptr(), les.data_ptr(), _ptr(ps), _stream()),
+              "vol_side_table")
+    return totals.cpu().numpy(), les[:n].cpu().numpy(), (ps[:Z].cpu().numpy() if per_slice else None)
+
+
+def split_lungs(lung_mask, orientation=None, pixdim=None, connectivity=1, min_ratio=LUNG_MIN_RATIO, erode_mm=LUNG_ERODE_MM, return_device=False, shape=None, out_path=None):
+    """A lung mask -> LungSides: which of its voxels belong to the patient's left lung (1) and which to the right (2).  lung_mask: a path, a NiftiVolume, a host array or
+    a device uint8 volume with shape=; non-zero = lung.  orientation: None = the volume's own affine (its sform / qform), or a 3-letter code such as "LPS" (the direction
+    in which every voxel axis grows), or a 4 x 4 affine; pixdim: the voxel's edge lengths in mm, default the volume's own.  Without an orientation from either, LungSplitError
+    is raised before any device work: left and right are never guessed.
+      1. Seeds.  For r = 0 and then every radius of erode_mm in order: c_r = the mask (r = 0) or erode_mm(mask, r, pixdim) -- one distance transform to the background,
+         thresholded per radius --, labelled with `connectivity`; A and B = its two components of the most voxels (ties to the lower label).  The first r with at least two
+         components and count(B) >= min_ratio * count(A) ends the search; no such r: LungSplitError naming the largest two counts seen.
+      2. Which seed is left.  xw(c) = affine[0, :3] . centroid(c), centroid = sum / count in float64.  NIfTI's world is RAS+ (+x = the patient's right): the seed with the
+         smaller xw is the patient's LEFT; equal values raise LungSplitError.
+      3. Assignment.  Every non-zero voxel of the ORIGINAL mask gets side 1 when its exact squared distance (unet_vol_edt_sq, w = pixdim^2) to the left seed is <= the one
+         to the right seed, else 2: a tie goes to the patient's left, whichever way the volume is stored.  The distance is Euclidean through the volume, not geodesic
+         through the lung.
+    min_ratio / erode_mm: conventional defaults (LUNG_MIN_RATIO, LUNG_ERODE_MM), configurable and not clinically validated here.  out_path: sides as .nii / .nii.gz with
+    the source's header.  Every argument error is a ValueError raised before anything is uploaded or launched."""
+    torch = _torch()
+    lin, codes, p, connectivity, ratio, radii = _check_split_args(orientation, pixdim, connectivity, min_ratio, erode_mm)
+    src = None
+    if isinstance(lung_mask, torch.Tensor):
+        _check_mask_host(lung_mask, shape)
+    else:
+        src = _source(lung_mask)
+        if lin is None and src.affine is not None:
+            try:
+                lin, codes = src.affine[:3, :3].copy(), src.axcodes
+            except nifti_min.NiftiFormatError as e:
+                raise LungSplitError(f"split_lungs: {e}") from None
+        if p is None:
+            p = _check_pixdim(src.pixdim)
+    if lin is None:
+        raise LungSplitError("split_lungs: neither the lung mask nor orientation= says which voxel direction is the patient's left; pass orientation='LPS' (or the "
+                             "volume's code) or an affine -- left and right are not guessed")
+    if p is None:
+        p = np.ones(3)
+    if src is not None:
+        dev, shape = _mask_to_device(src.get_fdata() != 0, None)
+    else:
+        dev, shape = _mask_to_device(lung_mask, shape)
+    X, Y, Z = shape
+    _check_volume_dims(shape)
+    d2_bg = None
+    best, found = (0, 0), None
+    for r in (0.0,) + radii:
+        if r == 0.0:
+            cand = dev
+        else:
+            lib, ctx = _ctx()
+            if d2_bg is None:
+                d2_bg = edt_sq_device(dev, shape, p, features_nonzero=False)
+            cand = torch.empty(X * Y * Z, dtype=torch.uint8, device="cuda")
+            ctx.check(lib.unet_vol_ball(ctx.handle, d2_bg.data_ptr(), X, Y, Z, r * r, 0, cand.data_ptr(), None, _stream()), "vol_ball")
+        labels, n = label_device(cand, shape, connectivity)
+        st = component_stats_device(labels, shape, n)
+        order = np.lexsort((np.arange(n), -st["voxels"].astype(np.int64)))[:2]          # the two largest, ties to the lower label
+        counts = tuple(int(st["voxels"][k]) for k in order) + (0,) * (2 - len(order))
+        if counts > best:
+            best = counts
+        if n >= 2 and float(counts[1]) >= ratio * float(counts[0]):
+            found = (r, labels, n, st, order)
+            break
+    del d2_bg
+    if found is None:
+        raise LungSplitError(f"split_lungs: no erosion radius of {(0.0,) + radii} mm leaves two components with the second holding {ratio} of the first; the largest "
+                             f"two counts seen were {best[0]} and {best[1]} voxels")
+    r, labels, n, st, order = found
+    xw = []
+    for k in order:
+        cnt = float(st["voxels"][k])
+        c = (float(st["sx"][k]) / cnt, float(st["sy"][k]) / cnt, float(st["sz"][k]) / cnt)
+        xw.append(float(lin[0, 0]) * c[0] + float(lin[0, 1]) * c[1] + float(lin[0, 2]) * c[2])
+    if xw[0] == xw[1]:
+        raise LungSplitError(f"split_lungs: the two seeds have the same world x ({xw[0]}): the orientation does not separate them")
+    left, right = (order[0], order[1]) if xw[0] < xw[1] else (order[1], order[0])
+    d2 = []
+    for k in (left, right):
+        keep = np.zeros(n + 1, bool)
+        keep[k + 1] = True
+        seed, _ = filter_components(labels, keep, n, shape, 0, 0)
+        d2.append(edt_sq_device(seed, shape, p, features_nonzero=True))
+        del seed
+    del labels
+    sides, cnt = side_assign_device(dev, d2[0], d2[1], shape, 1, 2)
+    del d2
+    voxel_ml = float(np.prod(p)) / 1000.0
+    res = LungSides(sides=sides if return_device else sides.cpu().numpy().reshape(shape, order="F"), shape=shape, radius_mm=float(r), voxels=(int(cnt[1]), int(cnt[2])),
+                    ml=(int(cnt[1]) * voxel_ml, int(cnt[2]) * voxel_ml), seed_voxels=(int(st["voxels"][left]), int(st["voxels"][right])), axcodes=codes,
+                    pixdim=tuple(float(v) for v in p))
+    if out_path is not None:
+        host = res.sides.cpu().numpy().reshape(shape, order="F") if return_device else res.sides
+        nifti_min.write(out_path, host, src.header if src is not None else None, res.pixdim)
+    return res
+
+
+def _lesion_sides(lesion_side):
+    """int64 [n, 3] -> LUNG_LESION_DTYPE rows: the side holding most of the lesion's in-lung voxels, a tie to left, "none" when it has none"""
+    t = np.zeros(len(lesion_side), LUNG_LESION_DTYPE)
+    t["label"] = np.arange(1, len(t) + 1)
+    t["voxels_outside"], t["voxels_left"], t["voxels_right"] = lesion_side[:, 0], lesion_side[:, 1], lesion_side[:, 2]
+    code = np.where(lesion_side[:, 1] + lesion_side[:, 2] == 0, 0, np.where(lesion_side[:, 1] >= lesion_side[:, 2], 1, 2))
+    t["side"] = np.asarray(SIDE_NAMES)[code] if len(t) else t["side"]
+    return t
+
+
+def burden_from_tables(totals, lesion_side, per_slice, pixdim=(1, 1, 1)):
+    """the three tables of unet_vol_side_table -> LungBurden"""
+    voxel_ml = float(np.prod(np.asarray(pixdim, np.float64))) / 1000.0
+    left, right = LungSideBurden(totals[0, 1], totals[1, 1], voxel_ml), LungSideBurden(totals[0, 2], totals[1, 2], voxel_ml)
+    return LungBurden(left=left, right=right, outside_voxels=int(totals[1, 0]), outside_ml=int(totals[1, 0]) * voxel_ml, lesions=_lesion_sides(np.asarray(lesion_side, np.int64)),
+                      per_slice=per_slice, bilateral=bool(left.fraction > 0 and right.fraction > 0), voxel_ml=voxel_ml, sides=None, density=None)
+
+
+def lung_burden(infection, sides, labels=None, n=None, pixdim=(1, 1, 1), connectivity=1, shape=None):
+    """How much of each lung an infection mask takes -> LungBurden.  infection: a host [X, Y, Z] mask (non-zero = infected) or a flat device uint8 tensor with shape=;
+    sides: a LungSides or a 0 / 1 / 2 volume of the same shape (host array, or device tensor with shape=); labels / n: the infection's lesions as label_volume returned
+    them (host array or device int32 tensor) -- without them the infection mask is labelled here with `connectivity`; pixdim: the voxel's edge lengths in mm."""
+    torch = _torch()
+    p = _check_pixdim(pixdim)
+    connectivity = _check_connectivity(connectivity)
+    if labels is not None and n is None:
+        raise ValueError("labels need n, the number of lesions (what label_volume returned)")
+    if labels is not None and int(n) < 0:
+        raise ValueError(f"n is the number of lesions, not {n}")
+    if isinstance(sides, LungSides):
+        sides_v, sides_shape = sides.sides, sides.shape
+    else:
+        sides_v, sides_shape = sides, shape
+    _check_mask_host(infection, shape)
+    _check_mask_host(sides_v, sides_shape)
+    if not isinstance(sides_v, torch.Tensor) and not isinstance(infection, torch.Tensor) and np.asarray(sides_v).shape != np.asarray(infection).shape:
+        raise ValueError(f"sides is {np.asarray(sides_v).shape}, the infection mask {np.asarray(infection).shape}")
+    inf_dev, vshape = _mask_to_device(infection, shape)
+    if isinstance(sides_v, torch.Tensor):
+        if tuple(int(v) for v in sides_shape) != vshape or sides_v.dtype != torch.uint8 or sides_v.numel() != int(np.prod(vshape)):
+            raise ValueError(f"device sides are a uint8 cuda tensor of the infection mask's shape {vshape}")
+        sides_dev = sides_v.contiguous().reshape(-1)
+    else:
+        a = np.asarray(sides_v)
+        if tuple(a.shape) != vshape:
+            raise ValueError(f"sides is {tuple(a.shape)}, the infection mask {vshape}")
+        sides_dev = torch.from_numpy(np.asfortranarray(np.where((a >= 0) & (a <= 2), a, 0).astype(np.uint8)).reshape(-1, order="F")).cuda()
+    if labels is None:
+        labels_dev, n = label_device(inf_dev, vshape, connectivity)
+    elif isinstance(labels, torch.Tensor):
+        if labels.dtype != torch.int32 or labels.numel() != int(np.prod(vshape)):
+            raise ValueError(f"device labels are an int32 cuda tensor of the infection mask's shape {vshape}")
+        labels_dev = labels.contiguous().reshape(-1)
+    else:
+        a = np.asarray(labels)
+        if tuple(a.shape) != vshape or a.dtype.kind not in "iu":
+            raise ValueError(f"labels are an integer volume of the infection mask's shape {vshape}")
+        labels_dev = torch.from_numpy(np.asfortranarray(np.where((a >= 1) & (a <= int(n)), a, 0).astype(np.int32)).reshape(-1, order="F")).cuda()
+    totals, les, ps = side_table_device(sides_dev, inf_dev, labels_dev, int(n), vshape)
+    if ps is None or not int(np.prod(vshape)):
+        ps = np.zeros((vshape[2], 6), np.int64)
+    return burden_from_tables(totals, les, ps, p)
