@@ -774,6 +774,45 @@ int32_t unet_vol_side_assign(unet_ctx*, const uint8_t* mask, const double* d2_a,
 int32_t unet_vol_side_table(unet_ctx*, const uint8_t* sides, const uint8_t* infection, const int32_t* labels, int32_t n, int32_t X, int32_t Y, int32_t Z, int64_t* totals,
                             int64_t* lesion_side, int64_t* per_slice, void* stream);
 
+/* ---- a picture of a segmented CT volume (csrc/kernels_render.hip; volume.project_volume / render_planes) ----
+ * The volume is described as for unet_vol_intensity_bands: vox / dtype / X, Y, Z / scaled, slope, inter, decoded as get_fdata() decodes it ((float64(v) * slope) + inter).
+ * Label volumes are uint8 (datatype code 2) or int32 (code 8, 4-byte aligned) of the same shape, device buffers in Fortran order.
+ *
+ * unet_vol_project: the slab [a, b) of `axis` (0, 1, 2) collapsed into one plane.  plane: device float64, 8-byte aligned, one element per column -- the largest (mode 0)
+ * or smallest (mode 1) decoded value of the column, NaN voxels skipped, NaN for a column of NaNs only (-0.0 orders below +0.0): np.fmax.reduce / np.fmin.reduce.  The plane
+ * of axis 0, 1, 2 is laid out as a Fortran-order volume of shape [1, Y, Z], [X, 1, Z], [X, Y, 1] and can be handed to unet_vol_render with datatype code 64.
+ * labels / label_dtypes / label_planes: HOST arrays of n_labels (0..UNET_RENDER_MAX_LAYERS) device pointers / datatype codes / device output pointers; plane l receives
+ * the largest label of every column in the element type of volume l; a null labels[l] is skipped.  Both results are independent of the order of the walk.
+ * Along y or z one lane owns an x and walks the slab; along x one wave owns a column, its lanes stride x and meet in a __shfl_xor butterfly: every load is coalesced.
+ * UNET_E_ARG: axis outside 0..2, a >= b, a slab that leaves the axis, mode outside 0..1, more than UNET_RENDER_MAX_LAYERS label volumes, a volume without voxels. */
+#define UNET_RENDER_MAX_TILES 64
+#define UNET_RENDER_MAX_LAYERS 4
+int32_t unet_vol_project(unet_ctx*, const void* vox, int32_t dtype, int32_t X, int32_t Y, int32_t Z, int32_t scaled, double slope, double inter, int32_t axis, int32_t a,
+                         int32_t b, int32_t mode, const void* const* labels, const int32_t* label_dtypes, void* const* label_planes, int32_t n_labels, double* plane,
+                         void* stream);
+/* One tile of a canvas: plane `index` of `axis` (a voxel index of the volume, inside the region), drawn w x h pixels with its top-left corner at canvas pixel (x0, y0). */
+typedef struct unet_render_tile { int32_t axis, index, x0, y0, w, h; } unet_render_tile;
+/* One overlay: labels (device; dtype 2 = uint8, 8 = int32), palette (device uint8 [palette_size][3], palette_size >= 2), the alphas 0..255 of its inside and its outline. */
+typedef struct unet_render_layer { const void* labels; const uint8_t* palette; int32_t dtype, palette_size, fill_alpha, outline_alpha; } unet_render_layer;
+/* unet_vol_render: canvas = device uint8 [H][W][3] (RGB), H <= 65535, H W 3 < 2^31.  tiles (up to UNET_RENDER_MAX_TILES) and layers (up to UNET_RENDER_MAX_LAYERS) are
+ * HOST arrays: they are checked on the host before anything is launched and travel in the kernel arguments (no copy).  roi: host int32 [6] = x_lo, x_hi, y_lo, y_hi,
+ * z_lo, z_hi, the region of the volume that is shown, with extents n_x, n_y, n_z; table: device uint8 [256][3]; background: 0xRRGGBB.
+ *   geometry   image row i runs against the second in-plane axis, column j along the first (np.rot90 of the slice): axial (axis 2) (x = j, y = n_y - 1 - i), coronal
+ *              (axis 1) (x = j, z = n_z - 1 - i), sagittal (axis 0) (y = j, z = n_z - 1 - i), region coordinates
+ *   sample     float64, half-pixel centres: u = (j + 0.5) n_u / w - 0.5, v = (i + 0.5) n_v / h - 0.5.  interp 0: the voxel min(int(floor((j + 0.5) n_u / w)), n_u - 1);
+ *              interp 1: the four neighbours floor(u), floor(u) + 1 (likewise v) clamped to the region, fx = u - floor(u), top = p00 + (p01 - p00) fx,
+ *              bot = p10 + (p11 - p10) fx, val = top + (bot - top) fy, every operation rounded on its own.  Labels are always sampled as interp 0 samples.
+ *   grey       t = (val - lo) / (hi - lo); g = 0 when t <= 0 or val is NaN, 255 when t >= 1, else (int)floor(t 255 + 0.5); the pixel starts as table[g]
+ *   layers     in order: a sampled label L <= 0 leaves the pixel; else colour = palette[1 + (L - 1) % (palette_size - 1)], alpha = outline_alpha when one of the four
+ *              neighbouring pixels OF THE TILE samples another label (outside the tile: 0), fill_alpha otherwise; channel = (colour alpha + channel (255 - alpha) + 127) / 255
+ *   elsewhere  fill_background != 0: the canvas pixels no tile covers take the background (the caller does not clear the canvas); 0: they are left as they are, so that
+ *              several calls can draw on one canvas
+ * UNET_E_ARG before any launch: more than 64 tiles or 4 layers, an axis or index outside the region, w < 1 or h < 1, a tile that leaves the canvas, two tiles that
+ * overlap, an empty region or one that leaves the volume, hi <= lo or a NaN window, interp outside 0..1, palette_size < 2, an alpha outside 0..255, a null layer. */
+int32_t unet_vol_render(unet_ctx*, const void* vox, int32_t dtype, int32_t X, int32_t Y, int32_t Z, int32_t scaled, double slope, double inter, const int32_t* roi,
+                        double lo, double hi, const uint8_t* table, int32_t interp, int32_t background, int32_t fill_background, const unet_render_layer* layers,
+                        int32_t n_layers, const unet_render_tile* tiles, int32_t n_tiles, uint8_t* canvas, int32_t H, int32_t W, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Model level. Replaces the Keras Model built at T1:853-916 and driven by
  * compile/fit/evaluate/predict (T1:1053-1061, 1101, 1137).  A model is a fixed-shape plan:

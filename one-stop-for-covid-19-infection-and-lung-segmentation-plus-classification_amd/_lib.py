@@ -39,6 +39,17 @@ class SyncPoint(C.Structure):
     _fields_ = [("after_op", i32), ("kind", i32), ("ptr", vp), ("count", i64), ("use_op", i32), ("reserved", i32)]
 
 
+RENDER_MAX_TILES, RENDER_MAX_LAYERS = 64, 4                           # include/unet_hip.h UNET_RENDER_MAX_*
+
+
+class RenderTile(C.Structure):                                        # unet_render_tile
+    _fields_ = [("axis", i32), ("index", i32), ("x0", i32), ("y0", i32), ("w", i32), ("h", i32)]
+
+
+class RenderLayer(C.Structure):                                       # unet_render_layer
+    _fields_ = [("labels", vp), ("palette", vp), ("dtype", i32), ("palette_size", i32), ("fill_alpha", i32), ("outline_alpha", i32)]
+
+
 # name -> (restype, argtypes); pointers to device memory are passed as void* integers
 _PROTOS = {
     "unet_abi_version": (i32, []),
@@ -214,6 +225,9 @@ _PROTOS = {
     # left and right lung (csrc/kernels_lungside.hip, volume.split_lungs / lung_burden)
     "unet_vol_side_assign": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]),
     "unet_vol_side_table": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
+    # a picture of a segmented volume (csrc/kernels_render.hip, volume.project_volume / render_planes); the label / tile / layer lists are host arrays
+    "unet_vol_project": (i32, [vp, vp, i32, i32, i32, i32, i32, f64, f64, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp]),
+    "unet_vol_render": (i32, [vp, vp, i32, i32, i32, i32, i32, f64, f64, vp, f64, f64, vp, i32, i32, i32, vp, i32, vp, i32, vp, i32, i32, vp]),
     "unet_model_create": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(vp)]),
     "unet_model_dtype": (i32, [vp]),
     "unet_model_tap_elem_bytes": (i32, [vp, C.c_char_p, i32]),

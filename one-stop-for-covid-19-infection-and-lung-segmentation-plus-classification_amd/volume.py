@@ -22,6 +22,10 @@ the dataset loop around it (T1:390-393, 421-429) and the way back from a predict
                                           qform); lungs that touch are separated by eroding until two seeds remain, every voxel then goes to the nearer seed
     lung_burden(infection, sides)         -> LungBurden: lung / infected volume and fraction per lung, every lesion's side, per slice; segment_volume(per_lung=True)
                                           fills res.per_lung with it
+    render_planes(ct, planes, layers)     -> RenderedSheet: axial / coronal / sagittal planes and maximum / minimum projections of the CT, windowed and colour-mapped
+                                          (WINDOWS, BONE), with up to four label layers blended and outlined on top (Layer), drawn on the device into one RGB sheet and
+                                          written as a PNG (png_min); segment_volume(render=True) fills res.sheet with the key slices (key_slices) and a coronal projection
+    project_volume(ct, axis, slab, mode)  -> the maximum / minimum of the CT and the largest label of every layer along one axis
 
 The voxels are uploaded once as stored (nifti_min reads the file); decode, np.rot90, the slice trim, cv2.resize(float64, INTER_AREA) and the min-max run
 in unet_vol_slices_f64, CLAHE / crop / fuse / resize in the uint8 kernels of preprocess.py on device pointers: between the upload and the returned batch
@@ -43,7 +47,7 @@ import warnings
 
 import numpy as np
 
-from . import _lib, nifti_min
+from . import _lib, nifti_min, png_min
 from . import preprocess as PRE
 
 KINDS = ("demo", "lungs", "cts", "infections")
@@ -297,7 +301,8 @@ class VolumeSegmentation:
     postprocess_ml: the volume the `postprocess` steps added to the mask (negative: removed; None without steps);
     density / lung_density: the IntensityStats of the CT under the final mask (per lesion when the lesion table was computed) and under the lung mask (None unless
     segment_volume was given density=);
-    per_lung / per_lung_error: the LungBurden of the final mask per lung (None unless segment_volume was given per_lung=) and, when the lungs could not be split, why."""
+    per_lung / per_lung_error: the LungBurden of the final mask per lung (None unless segment_volume was given per_lung=) and, when the lungs could not be split, why;
+    sheet: the RenderedSheet of the final mask over the CT (None unless segment_volume was given render=)."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -1045,7 +1050,7 @@ def _prepare_segmentation(ct, lung_mask, truth, img_size, trim, input_size):
 
 
 def segment_volume(ct, model, lung_mask=None, threshold=0.547, batch_size=32, out_path=None, img_size=512, trim=(0.2, 0.8), min_lesion_ml=None, connectivity=1,
-                   lesions=False, truth=None, postprocess=None, density=None, per_lung=None):
+                   lesions=False, truth=None, postprocess=None, density=None, per_lung=None, render=None):
     """CT file (or array) -> VolumeSegmentation.  `model`: a UNetModel or a routed.ClusterRoutedModel (only `predict` is used); lung_mask=None: whole-frame
     boxes (the two halves of the frame); boxes are keyed by slice number (box_indexing="slice"); out_path: the mask as .nii / .nii.gz with the CT's geometry.
     min_lesion_ml: connected components (`connectivity` 1, 2, 3 = 6, 18, 26 neighbours) smaller than that are removed on the device before the mask comes to the
@@ -1065,10 +1070,16 @@ def segment_volume(ct, model, lung_mask=None, threshold=0.547, batch_size=32, ou
     work without one).  After postprocess / min_lesion_ml, on the final mask: the lung mask is split (split_lungs; orientation: the lung mask file's own, else the CT's;
     pixdim: the CT's) and res.per_lung = the LungBurden of the final mask -- its `lesions` rows align with res.lesions when the lesion table is computed (the device labels
     are reused), `sides` is the LungSides, and with density= as well `density` = intensity_stats(ct, labels=sides, n=2): two rows, left then right.  A LungSplitError does
-    not lose the segmentation: res.per_lung is None and res.per_lung_error holds its message.  seconds["per_lung"]: its time.  None: nothing runs."""
+    not lose the segmentation: res.per_lung is None and res.per_lung_error holds its message.  seconds["per_lung"]: its time.  None: nothing runs.
+    render: True, or a dict of render_planes keyword arguments (window, cmap, mm_per_px, tile_size, roi, cols, gap, background, interp) plus n (the number of key slices,
+    default 6) and out_path (a PNG).  After postprocess / min_lesion_ml / per_lung: res.sheet = the RenderedSheet of the key_slices(counts, n) axial planes -- the middle
+    slice when no slice holds infection -- followed by one coronal maximum projection of the whole volume; its layers are the final mask, taken from the device (fill 128,
+    outline 255, PALETTE_INFECTION), and, with a lung mask, the lungs as an outline only (PALETTE_LUNG).  The sheet does not mark left and right.  seconds["render"]: its
+    time.  None: nothing runs and res.sheet is None."""
     _check_connectivity(connectivity)
     density = _check_density(density)
     per_lung = _check_per_lung(per_lung, lung_mask)
+    render = _check_render(render)
     if postprocess is not None:
         _check_steps(postprocess, (1.0, 1.0, 1.0))                   # the steps' own arguments, before any work (the CT's pixdim takes this one's place below)
     torch = _torch()
@@ -1081,13 +1092,13 @@ def segment_volume(ct, model, lung_mask=None, threshold=0.547, batch_size=32, ou
     canvas = paste_back(prob, R1, R2, S)
     mask_dev, counts_dev = unslice(canvas, threshold, (X, Y, Z), z0, z1)
     return _finish_segmentation(vol, lv, truth_mask, mask_dev, counts_dev, z0, z1, has, info, threshold, sec, t0, postprocess, min_lesion_ml, lesions, connectivity, out_path,
-                                density=density, per_lung=per_lung)
+                                density=density, per_lung=per_lung, render=render)
 
 
 def _finish_segmentation(vol, lv, truth_mask, mask_dev, counts_dev, z0, z1, has, info, threshold, sec, t0, postprocess, min_lesion_ml, lesions, connectivity, out_path,
-                         density=None, per_lung=None, **extra):
+                         density=None, per_lung=None, render=None, **extra):
     """What segment_volume and segment_volume_ensemble do with the mask volume once it is formed (mask_dev, counts_dev [z1 - z0], both on the device): postprocess,
-    min_lesion_ml / lesions, density (the checked keyword arguments of intensity_stats, or None), per_lung (those of split_lungs, or None), truth, the download, the lung share and out_path -> VolumeSegmentation (+ `extra` fields).  t0: when the paste-back began."""
+    min_lesion_ml / lesions, density (the checked keyword arguments of intensity_stats, or None), per_lung (those of split_lungs, or None), render (those of the sheet, or None), truth, the download, the lung share and out_path -> VolumeSegmentation (+ `extra` fields).  t0: when the paste-back began."""
     torch = _torch()
     X, Y, Z = vol.raw.shape
     voxel_mm3 = float(np.prod(np.asarray(vol.pixdim, np.float64)))          # count * prod(pixdim) / 1000 = millilitres
@@ -1157,6 +1168,17 @@ def _finish_segmentation(vol, lv, truth_mask, mask_dev, counts_dev, z0, z1, has,
             burden.sides = ls
         torch.cuda.synchronize(); sec["per_lung"] = time.perf_counter() - tl
     labels_dev = None
+    sheet = None
+    if render is not None:
+        torch.cuda.synchronize(); tr = time.perf_counter()
+        kw = dict(render)
+        per_slice = np.zeros(Z, np.int64); per_slice[cz0:cz1] = counts_dev.cpu().numpy()
+        keys = key_slices(per_slice, kw.pop("n", 6)) or [Z // 2]
+        over = [Layer(mask_dev, PALETTE_INFECTION, 128, 255)]
+        if lv is not None:
+            over.append(Layer((lv.get_fdata() != 0).astype(np.uint8), PALETTE_LUNG, 0, 255))
+        sheet = render_planes(vol, [("axial", z) for z in keys] + [("mip", "coronal", 0, Y)], over, shape=(X, Y, Z), **kw)
+        torch.cuda.synchronize(); sec["render"] = time.perf_counter() - tr
     score = None
     if truth_mask is not None:
         torch.cuda.synchronize(); ts = time.perf_counter()
@@ -1169,7 +1191,7 @@ def _finish_segmentation(vol, lv, truth_mask, mask_dev, counts_dev, z0, z1, has,
                              total_ml=float(counts.sum()) * voxel_mm3 / 1000.0, lung_ml=None,
                              infected_share=None, fell_through=[int(i) for i in np.nonzero(~has)[0]], flat=info["flat"], z0=z0, z1=z1, pixdim=vol.pixdim,
                              threshold=float(threshold), seconds=sec, lesions=table, n_lesions=None if table is None else len(table), removed_ml=removed_ml, score=score,
-                             postprocess_ml=postprocess_ml, density=dens, lung_density=lung_dens, per_lung=burden, per_lung_error=burden_error, **extra)
+                             postprocess_ml=postprocess_ml, density=dens, lung_density=lung_dens, per_lung=burden, per_lung_error=burden_error, sheet=sheet, **extra)
     if lv is not None:
         lung_vox = int(np.count_nonzero(lv.get_fdata()[:, :, z0:z1]))
         res.lung_ml = lung_vox * voxel_mm3 / 1000.0
@@ -1428,7 +1450,7 @@ def _predict_device(model, x, batch_size):
 
 def segment_volume_ensemble(ct, models, tta=("id",), combine="mean", weights=None, lung_mask=None, threshold=0.547, batch_size=32, out_path=None, img_size=512,
                             trim=(0.2, 0.8), min_lesion_ml=None, connectivity=1, lesions=False, truth=None, postprocess=None, return_prob=False, prob_path=None,
-                            votes_path=None, density=None, per_lung=None):
+                            votes_path=None, density=None, per_lung=None, render=None):
     """segment_volume with several members: every (model, symmetry) pair of `models` (each anything segment_volume accepts, all of one input size) and `tta` (names of
     TTA, no repeats), in model-major order, at most 32.  A member sees the prepared batch under its symmetry (transformed once, on the device), its probabilities are
     transformed back, pasted onto the canvas and (a) thresholded into the member's mask, which becomes one bit of a vote word per voxel, (b) added into the weighted
@@ -1444,6 +1466,7 @@ def segment_volume_ensemble(ct, models, tta=("id",), combine="mean", weights=Non
     models, members, mw, wsum, min_votes, d = _check_ensemble(models, tta, combine, weights)
     density = _check_density(density)
     per_lung = _check_per_lung(per_lung, lung_mask)
+    render = _check_render(render)
     if postprocess is not None:
         _check_steps(postprocess, (1.0, 1.0, 1.0))
     torch = _torch()
@@ -1490,7 +1513,7 @@ def segment_volume_ensemble(ct, models, tta=("id",), combine="mean", weights=Non
                  vote_hist=st["hist"], unanimous_ml=float(st["unanimous_voxels"]) * voxel_ml, uncertain_ml=float(st["uncertain_voxels"]) * voxel_ml, combine=combine,
                  weights=mw, prob=prob)
     res = _finish_segmentation(vol, lv, truth_mask, mask_dev, counts_dev, z0, z1, has, info, threshold, sec, t0, postprocess, min_lesion_ml, lesions, connectivity, out_path,
-                               density=density, per_lung=per_lung, **extra)
+                               density=density, per_lung=per_lung, render=render, **extra)
     if prob_path is not None:
         nifti_min.write(prob_path, prob, vol.header)
     if votes_path is not None:
@@ -2071,3 +2094,448 @@ def lung_burden(infection, sides, labels=None, n=None, pixdim=(1, 1, 1), connect
     if ps is None or not int(np.prod(vshape)):
         ps = np.zeros((vshape[2], 6), np.int64)
     return burden_from_tables(totals, les, ps, p)
+
+
+# ---- a picture of the result (csrc/kernels_render.hip) ---------------------------------------------------------------------------------
+# The display windows (lo, hi) in Hounsfield units: conventional values of CT reading rooms, configurable (window=(lo, hi)); they serve DISPLAY ONLY and are not
+# clinically validated here.
+WINDOWS = {"lung": (-1350.0, 150.0), "mediastinum": (-160.0, 240.0)}
+GRAY = np.repeat(np.arange(256, dtype=np.uint8)[:, None], 3, axis=1)
+# matplotlib.colormaps["bone"](np.arange(256), bytes=True)[:, :3], as numbers: a closed-form interpolation of the map's segments differs from matplotlib in 23 of the 768
+# entries, so the table is not derived (tests/test_render_host.py compares it with matplotlib where matplotlib is at hand)
+BONE = np.array([
+    (0, 0, 0), (0, 0, 1), (1, 1, 2), (2, 2, 3), (3, 3, 4), (4, 4, 6), (5, 5, 7), (6, 6, 8),
+    (7, 6, 9), (7, 7, 10), (8, 8, 12), (9, 9, 13), (10, 10, 14), (11, 11, 15), (12, 12, 17), (13, 13, 18),
+    (14, 13, 19), (14, 14, 20), (15, 15, 21), (16, 16, 23), (17, 17, 24), (18, 18, 25), (19, 19, 26), (20, 20, 28),
+    (21, 20, 29), (21, 21, 30), (22, 22, 31), (23, 23, 32), (24, 24, 34), (25, 25, 35), (26, 26, 36), (27, 27, 37),
+    (28, 27, 38), (28, 28, 40), (29, 29, 41), (30, 30, 42), (31, 31, 43), (32, 32, 45), (33, 33, 46), (34, 34, 47),
+    (35, 34, 48), (35, 35, 49), (36, 36, 51), (37, 37, 52), (38, 38, 53), (39, 39, 54), (40, 40, 56), (41, 41, 57),
+    (42, 41, 58), (42, 42, 59), (43, 43, 60), (44, 44, 62), (45, 45, 63), (46, 46, 64), (47, 47, 65), (48, 48, 66),
+    (49, 48, 68), (49, 49, 69), (50, 50, 70), (51, 51, 71), (52, 52, 73), (53, 53, 74), (54, 54, 75), (55, 55, 76),
+    (56, 55, 77), (56, 56, 79), (57, 57, 80), (58, 58, 81), (59, 59, 82), (60, 60, 84), (61, 61, 85), (62, 62, 86),
+    (63, 62, 87), (63, 63, 88), (64, 64, 90), (65, 65, 91), (66, 66, 92), (67, 67, 93), (68, 68, 94), (69, 69, 96),
+    (70, 69, 97), (70, 70, 98), (71, 71, 99), (72, 72, 101), (73, 73, 102), (74, 74, 103), (75, 75, 104), (76, 76, 105),
+    (77, 76, 107), (77, 77, 108), (78, 78, 109), (79, 79, 110), (80, 80, 112), (81, 81, 113), (82, 82, 114), (83, 83, 114),
+    (84, 84, 115), (84, 86, 116), (85, 87, 117), (86, 88, 118), (87, 89, 119), (88, 90, 120), (89, 92, 121), (90, 93, 121),
+    (91, 94, 122), (91, 95, 123), (92, 96, 124), (93, 98, 125), (94, 99, 126), (95, 100, 127), (96, 101, 128), (97, 102, 128),
+    (98, 104, 129), (98, 105, 130), (99, 106, 131), (100, 107, 132), (101, 109, 133), (102, 110, 134), (103, 111, 135), (104, 112, 135),
+    (105, 113, 136), (105, 115, 137), (106, 116, 138), (107, 117, 139), (108, 118, 140), (109, 119, 141), (110, 121, 142), (111, 122, 142),
+    (112, 123, 143), (112, 124, 144), (113, 125, 145), (114, 127, 146), (115, 128, 147), (116, 129, 148), (117, 130, 149), (118, 131, 149),
+    (119, 133, 150), (119, 134, 151), (120, 135, 152), (121, 136, 153), (122, 137, 154), (123, 139, 155), (124, 140, 156), (125, 141, 156),
+    (126, 142, 157), (126, 143, 158), (127, 145, 159), (128, 146, 160), (129, 147, 161), (130, 148, 162), (131, 149, 163), (132, 151, 163),
+    (133, 152, 164), (133, 153, 165), (134, 154, 166), (135, 155, 167), (136, 157, 168), (137, 158, 169), (138, 159, 170), (139, 160, 170),
+    (140, 161, 171), (140, 163, 172), (141, 164, 173), (142, 165, 174), (143, 166, 175), (144, 167, 176), (145, 169, 177), (146, 170, 177),
+    (147, 171, 178), (147, 172, 179), (148, 173, 180), (149, 175, 181), (150, 176, 182), (151, 177, 183), (152, 178, 184), (153, 179, 184),
+    (154, 181, 185), (154, 182, 186), (155, 183, 187), (156, 184, 188), (157, 186, 189), (158, 187, 190), (159, 188, 191), (160, 189, 191),
+    (161, 190, 192), (161, 192, 193), (162, 193, 194), (163, 194, 195), (164, 195, 196), (165, 196, 197), (166, 198, 198), (167, 199, 198),
+    (168, 199, 199), (170, 200, 200), (171, 201, 201), (172, 202, 202), (174, 203, 203), (175, 204, 204), (177, 205, 205), (178, 206, 205),
+    (179, 206, 206), (181, 207, 207), (182, 208, 208), (183, 209, 209), (185, 210, 210), (186, 211, 211), (188, 212, 212), (189, 213, 212),
+    (190, 213, 213), (192, 214, 214), (193, 215, 215), (194, 216, 216), (196, 217, 217), (197, 218, 218), (198, 219, 219), (200, 220, 219),
+    (201, 220, 220), (203, 221, 221), (204, 222, 222), (205, 223, 223), (207, 224, 224), (208, 225, 225), (209, 226, 226), (211, 227, 226),
+    (212, 227, 227), (213, 228, 228), (215, 229, 229), (216, 230, 230), (218, 231, 231), (219, 232, 232), (220, 233, 233), (222, 234, 233),
+    (223, 234, 234), (224, 235, 235), (226, 236, 236), (227, 237, 237), (229, 238, 238), (230, 239, 239), (231, 240, 240), (233, 241, 240),
+    (234, 241, 241), (235, 242, 242), (237, 243, 243), (238, 244, 244), (239, 245, 245), (241, 246, 246), (242, 247, 247), (244, 248, 247),
+    (245, 248, 248), (246, 249, 249), (248, 250, 250), (249, 251, 251), (250, 252, 252), (252, 253, 253), (253, 254, 254), (255, 255, 255)], np.uint8)
+COLORMAPS = {"bone": BONE, "gray": GRAY}
+PALETTE_INFECTION = np.array([(0, 0, 0), (255, 0, 0)], np.uint8)               # entry 0 is never drawn: label L > 0 takes palette[1 + (L - 1) % (P - 1)]
+PALETTE_LUNG = np.array([(0, 0, 0), (0, 255, 255)], np.uint8)
+PALETTE_LESIONS = np.array([(0, 0, 0), (230, 25, 75), (60, 180, 75), (255, 225, 25), (0, 130, 200), (245, 130, 48), (145, 30, 180), (70, 240, 240), (240, 50, 230)], np.uint8)
+VIEWS = {"sagittal": 0, "coronal": 1, "axial": 2}                   # the axis a view looks along
+PROJECTIONS = {"mip": 0, "minip": 1}                                # unet_vol_project's mode
+INTERP = {"nearest": 0, "linear": 1}
+RENDER_MAX_TILES, RENDER_MAX_LAYERS = _lib.RENDER_MAX_TILES, _lib.RENDER_MAX_LAYERS
+ROI_MARGIN = 8                                                      # voxels around the first layer's bounding box for roi="layers"
+_IN_PLANE = ((1, 2), (0, 2), (0, 1))                                # by axis: the axis along the image columns, the axis against the image rows
+_RENDER_KEYS = {"n", "out_path", "window", "cmap", "mm_per_px", "tile_size", "roi", "cols", "gap", "background", "interp"}
+
+
+def _check_alpha(a, what):
+    if isinstance(a, bool) or not isinstance(a, (int, np.integer)) or not 0 <= int(a) <= 255:
+        raise ValueError(f"{what} is an integer in 0..255, not {a!r}")
+    return int(a)
+
+
+def _check_palette(palette):
+    p = palette if isinstance(palette, np.ndarray) else np.asarray(palette)
+    if p.dtype != np.uint8:
+        raise ValueError(f"a palette is a uint8 array [P, 3], not {p.dtype}")
+    if p.ndim != 2 or p.shape[1] != 3 or p.shape[0] < 2:
+        raise ValueError(f"a palette is uint8 [P, 3] with P >= 2 (entry 0 stands for the background and is never drawn), not {p.shape}")
+    return np.ascontiguousarray(p)
+
+
+class Layer:
+    """One overlay of render_planes: labels (a label or mask volume of the CT's shape: a host array of bool / integer dtype, a path, a NiftiVolume, or a flat uint8 / int32
+    device tensor in Fortran order together with render_planes' shape=), palette (uint8 [P, 3], P >= 2: label L > 0 is drawn in palette[1 + (L - 1) % (P - 1)], L <= 0 not
+    at all), fill_alpha and outline_alpha in 0..255 (default 128: the reference's alpha=0.5 of plot_sample; the one-pixel outline solid)."""
+
+    def __init__(self, labels, palette=PALETTE_INFECTION, fill_alpha=128, outline_alpha=255):
+        self.labels, self.palette = labels, _check_palette(palette)
+        self.fill_alpha, self.outline_alpha = _check_alpha(fill_alpha, "fill_alpha"), _check_alpha(outline_alpha, "outline_alpha")
+
+
+class SheetTile:
+    """plane: as it was asked for; axis; index (None for a projection) / slab (a, b) (None for a plain plane); x0, y0, w, h: its rectangle on the canvas;
+    mm_per_px: (along the columns, along the rows); roi: the voxel ranges (lo, hi) of the two in-plane axes it shows."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def __repr__(self):
+        return f"SheetTile({self.plane!r} at ({self.x0}, {self.y0}) {self.w} x {self.h})"
+
+
+class RenderedSheet:
+    """image: uint8 [H, W, 3] RGB (numpy; return_device=True: the device tensor); tiles: one SheetTile per plane, in the order asked for; window (lo, hi); roi
+    ((x_lo, x_hi), (y_lo, y_hi), (z_lo, z_hi)); mm_per_px; background; interp; launches: the unet_vol_render calls made.  The sheet does not mark left and right."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def _check_layers(layers):
+    layers = [l if isinstance(l, Layer) else Layer(l) for l in (layers or ())]
+    if len(layers) > RENDER_MAX_LAYERS:
+        raise ValueError(f"at most {RENDER_MAX_LAYERS} layers are drawn, not {len(layers)}")
+    for l in layers:                                                # (a Layer's fields may have been changed since it was built)
+        _check_palette(l.palette); _check_alpha(l.fill_alpha, "fill_alpha"); _check_alpha(l.outline_alpha, "outline_alpha")
+    return layers
+
+
+def _check_view(view):
+    if not isinstance(view, str) or view not in VIEWS:
+        raise ValueError(f"a view is one of {sorted(VIEWS)}, not {view!r}")
+    return VIEWS[view]
+
+
+def _check_planes(planes, vshape):
+    """-> [(plane as given, axis, index or None, (a, b) or None, mode or None)]"""
+    out = []
+    for p in planes:
+        p = tuple(p)
+        if len(p) == 2:
+            axis = _check_view(p[0])
+            k = p[1]
+            if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 0 <= int(k) < vshape[axis]:
+                raise ValueError(f"plane {p!r}: the index lies outside the volume's 0..{vshape[axis] - 1}")
+            out.append((p, axis, int(k), None, None))
+        elif len(p) == 4 and isinstance(p[0], str) and p[0] in PROJECTIONS:
+            axis = _check_view(p[1])
+            a, b = p[2], p[3]
+            if any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in (a, b)) or not 0 <= int(a) < int(b) <= vshape[axis]:
+                raise ValueError(f"plane {p!r}: the slab [a, b) is empty or leaves the volume's 0..{vshape[axis]}")
+            out.append((p, axis, None, (int(a), int(b)), PROJECTIONS[p[0]]))
+        else:
+            raise ValueError(f"a plane is (view, index) or ('mip' | 'minip', view, a, b), not {p!r}")
+    if not out:
+        raise ValueError("no plane to draw")
+    return out
+
+
+def _minmax_window(vol):
+    raw = vol.raw
+    if raw.dtype.kind == "f":
+        raw = raw[np.isfinite(raw)]
+    if raw.size == 0:
+        raise ValueError("window='minmax': the volume has no finite voxel")
+    dec = nifti_min.apply_scaling(np.array([raw.min(), raw.max()]), vol.slope, vol.inter)          # decoding is monotone: a negative slope swaps the two
+    lo, hi = float(dec.min()), float(dec.max())
+    if not lo < hi:
+        raise ValueError(f"window='minmax': the volume is constant ({lo})")
+    return lo, hi
+
+
+def _check_window(window, vol=None):
+    if isinstance(window, str):
+        if window == "minmax":
+            return _minmax_window(vol) if vol is not None else None
+        if window not in WINDOWS:
+            raise ValueError(f"a window is one of {sorted(WINDOWS)}, 'minmax' or a (lo, hi) pair, not {window!r}")
+        return WINDOWS[window]
+    try:
+        lo, hi = (float(v) for v in window)
+    except (TypeError, ValueError):
+        raise ValueError(f"a window is one of {sorted(WINDOWS)}, 'minmax' or a (lo, hi) pair, not {window!r}") from None
+    if not lo < hi:                                                 # (a NaN fails the comparison)
+        raise ValueError(f"a window needs lo < hi, not {window!r}")
+    return lo, hi
+
+
+def _check_cmap(cmap):
+    if isinstance(cmap, str):
+        if cmap not in COLORMAPS:
+            raise ValueError(f"a colour map is one of {sorted(COLORMAPS)} or a uint8 [256, 3] table, not {cmap!r}")
+        return COLORMAPS[cmap]
+    t = np.asarray(cmap)
+    if t.dtype != np.uint8 or t.shape != (256, 3):
+        raise ValueError(f"a colour table is uint8 [256, 3], not {t.dtype} {t.shape}")
+    return np.ascontiguousarray(t)
+
+
+def _check_background(background):
+    try:
+        bg = tuple(background)
+    except TypeError:
+        bg = ()
+    if len(bg) != 3 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= 255 for v in bg):
+        raise ValueError(f"the background is three integers in 0..255, not {background!r}")
+    return tuple(int(v) for v in bg)
+
+
+def _check_sheet_args(window="lung", cmap="bone", mm_per_px=None, tile_size=None, roi=None, cols=None, gap=2, background=(0, 0, 0), interp="linear", vshape=None):
+    """the arguments of render_planes that need no volume -> (table, interp code, background, tile_size, cols, gap, roi), or ValueError"""
+    table, bg = _check_cmap(cmap), _check_background(background)
+    _check_window(window)
+    if not isinstance(interp, str) or interp not in INTERP:
+        raise ValueError(f"interp is one of {sorted(INTERP)}, not {interp!r}")
+    if mm_per_px is not None and not (isinstance(mm_per_px, (int, float, np.integer, np.floating)) and np.isfinite(mm_per_px) and mm_per_px > 0):
+        raise ValueError(f"mm_per_px is a positive number, not {mm_per_px!r}")
+    if tile_size is not None:
+        try:
+            tile_size = tuple(int(v) for v in tile_size)
+        except (TypeError, ValueError):
+            tile_size = ()
+        if len(tile_size) != 2 or min(tile_size) < 1:
+            raise ValueError("tile_size is (w, h) in pixels, both at least 1")
+    for v, what, least in ((cols, "cols", 1), (gap, "gap", 0)):
+        if v is not None and (isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < least):
+            raise ValueError(f"{what} is an integer of at least {least}, not {v!r}")
+    if roi is not None and not (isinstance(roi, str) and roi == "layers"):
+        try:
+            roi = tuple((int(a), int(b)) for a, b in roi)
+        except (TypeError, ValueError):
+            roi = ()
+        if len(roi) != 3 or any(a >= b or a < 0 for a, b in roi) or (vshape is not None and any(b > n for (a, b), n in zip(roi, vshape))):
+            raise ValueError("roi is None, 'layers' or three non-empty voxel ranges ((x_lo, x_hi), (y_lo, y_hi), (z_lo, z_hi)) inside the volume")
+    return table, INTERP[interp], bg, tile_size, cols, int(gap), roi
+
+
+def _check_render(render):
+    """segment_volume's render= -> None (off) or the checked keyword arguments of the sheet"""
+    if render is None or render is False:
+        return None
+    kw = {} if render is True else dict(render)
+    if set(kw) - _RENDER_KEYS:
+        raise ValueError(f"render takes {sorted(_RENDER_KEYS)}, not {sorted(set(kw) - _RENDER_KEYS)}")
+    n = kw.get("n", 6)
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+        raise ValueError(f"render: n is the number of key slices, at least 1, not {n!r}")
+    _check_sheet_args(**{k: v for k, v in kw.items() if k not in ("n", "out_path")})
+    return kw
+
+
+def _label_source(labels, what, vshape, shape):
+    """a layer's volume, checked against the CT's shape on the host -> a device tensor as given, or a host array uint8 / int32 [X, Y, Z]"""
+    torch = _torch()
+    if isinstance(labels, torch.Tensor):
+        if shape is None:
+            raise ValueError(f"device {what} is a flat Fortran-order buffer: pass shape=(X, Y, Z)")
+        if tuple(int(v) for v in shape) != vshape:
+            raise ValueError(f"{what} is {tuple(shape)}, the CT {vshape}")
+        if labels.dtype not in (torch.uint8, torch.int32) or not labels.is_cuda or labels.numel() != int(np.prod(vshape)):
+            raise ValueError(f"device {what} is a uint8 or int32 cuda tensor of prod(shape) = {int(np.prod(vshape))} elements")
+        return labels
+    if isinstance(labels, (str, os.PathLike, nifti_min.NiftiVolume)):
+        v = _source(labels)
+        a = v.raw if v.scaling is None and v.raw.dtype.kind in "biu" else np.rint(v.get_fdata())
+    else:
+        a = np.asarray(labels)
+        if a.dtype.kind not in "biu":
+            raise ValueError(f"{what} has a bool or integer dtype, not {a.dtype}")
+    if a.ndim != 3 or tuple(a.shape) != vshape:
+        raise ValueError(f"{what} is {tuple(a.shape)}, the CT {vshape}")
+    return a.astype(np.uint8) if a.dtype.kind == "b" or a.dtype == np.uint8 else a.astype(np.int32)
+
+
+def _label_device(a):
+    """-> (flat device tensor, NIfTI datatype code 2 | 8)"""
+    torch = _torch()
+    t = a.contiguous().reshape(-1) if isinstance(a, torch.Tensor) else torch.from_numpy(np.asfortranarray(a).reshape(-1, order="F")).cuda()
+    return t, (2 if t.dtype == torch.uint8 else 8)
+
+
+def project_device(vargs, dev, axis, a, b, mode, labels=()):
+    """unet_vol_project on an uploaded volume (vargs = _vox_args(vol), dev = upload(vol)); labels: (flat device tensor, datatype code) pairs or None ->
+    (plane: float64 device tensor, [label planes or None]), each a flat Fortran-order volume with extent 1 along `axis`."""
+    torch = _torch(); lib, ctx = _ctx()
+    import ctypes as C
+    dims = list(vargs[1:4]); dims[axis] = 1
+    n = int(np.prod(dims))
+    plane = torch.empty(max(n, 1), dtype=torch.float64, device="cuda")
+    k = len(labels)
+    outs = [None if l is None else torch.empty(max(n, 1), dtype=l[0].dtype, device="cuda") for l in labels]
+    lp = (C.c_void_p * max(k, 1))(*[None if l is None else l[0].data_ptr() for l in labels])
+    lo = (C.c_void_p * max(k, 1))(*[None if o is None else o.data_ptr() for o in outs])
+    ld = (C.c_int32 * max(k, 1))(*[0 if l is None else int(l[1]) for l in labels])
+    ctx.check(lib.unet_vol_project(ctx.handle, dev.data_ptr(), *vargs, int(axis), int(a), int(b), int(mode), lp, ld, lo, k, plane.data_ptr(), _stream()), "vol_project")
+    return plane, outs
+
+
+def render_device(vargs, dev, roi, window, table_dev, interp, background, fill_background, layers, tiles, canvas):
+    """unet_vol_render: layers = (labels device tensor, datatype code, palette device tensor [P, 3], fill_alpha, outline_alpha) tuples, tiles = (axis, index, x0, y0, w, h)
+    tuples, roi = ((x_lo, x_hi), (y_lo, y_hi), (z_lo, z_hi)), canvas = uint8 device tensor [H, W, 3], drawn in place."""
+    lib, ctx = _ctx()
+    import ctypes as C
+    L = (_lib.RenderLayer * max(len(layers), 1))()
+    for i, (t, code, pal, fa, oa) in enumerate(layers):
+        L[i] = _lib.RenderLayer(t.data_ptr(), pal.data_ptr(), int(code), int(pal.shape[0]), int(fa), int(oa))
+    T = (_lib.RenderTile * max(len(tiles), 1))()
+    for i, t in enumerate(tiles):
+        T[i] = _lib.RenderTile(*(int(v) for v in t))
+    r = (C.c_int32 * 6)(*[int(v) for ab in roi for v in ab])
+    bg = (background[0] << 16) | (background[1] << 8) | background[2]
+    ctx.check(lib.unet_vol_render(ctx.handle, dev.data_ptr(), *vargs, r, float(window[0]), float(window[1]), table_dev.data_ptr(), int(interp), bg, 1 if fill_background else 0,
+                                  L, len(layers), T, len(tiles), canvas.data_ptr(), int(canvas.shape[0]), int(canvas.shape[1]), _stream()), "vol_render")
+
+
+def project_volume(ct, axis, slab=None, mode="max", layers=(), shape=None):
+    """The maximum (mode="max") or minimum ("min") of the CT along `axis` (0, 1, 2 or a view name: the axis the view looks along) over the slab [a, b) (None: the whole
+    axis), NaN voxels skipped -- np.fmax.reduce / np.fmin.reduce of get_fdata() --, and for every layer (a Layer or a label volume as Layer takes it; None is passed
+    through) the largest label of each column -> (plane float64, [label planes]) as numpy volumes with extent 1 along `axis`.  Both are independent of the order of the
+    walk; mean projections are not offered (a float sum is not).  Every argument error is a ValueError raised before any device work."""
+    axis = _check_view(axis) if isinstance(axis, str) else axis
+    if isinstance(axis, bool) or not isinstance(axis, (int, np.integer)) or not 0 <= axis <= 2:
+        raise ValueError(f"axis is 0, 1, 2 or one of {sorted(VIEWS)}, not {axis!r}")
+    if mode not in ("max", "min"):
+        raise ValueError(f"mode is 'max' or 'min', not {mode!r}")
+    layers = list(layers or ())
+    if len(layers) > RENDER_MAX_LAYERS:
+        raise ValueError(f"at most {RENDER_MAX_LAYERS} label volumes are projected, not {len(layers)}")
+    vol = _source(ct)
+    vshape = tuple(int(v) for v in vol.raw.shape)
+    _check_volume_dims(vshape)
+    a, b = (0, vshape[axis]) if slab is None else (int(slab[0]), int(slab[1]))
+    if not 0 <= a < b <= vshape[axis]:
+        raise ValueError(f"the slab [{a}, {b}) is empty or leaves the axis of {vshape[axis]} voxels")
+    src = [None if l is None else _label_source(l.labels if isinstance(l, Layer) else l, f"layer {i}", vshape, shape) for i, l in enumerate(layers)]
+    dev = upload(vol)
+    plane, outs = project_device(_vox_args(vol), dev, int(axis), a, b, 0 if mode == "max" else 1, [None if s is None else _label_device(s) for s in src])
+    pshape = tuple(1 if d == axis else n for d, n in enumerate(vshape))
+    host = lambda t: t.cpu().numpy().reshape(pshape, order="F")
+    return host(plane), [None if o is None else host(o) for o in outs]
+
+
+def key_slices(per_slice_counts, n=6):
+    """The n slices that hold the most infected voxels (ties to the lower z), in ascending z; fewer when fewer slices hold any.  Host arithmetic."""
+    c = np.asarray(per_slice_counts).reshape(-1)
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 0:
+        raise ValueError(f"n is a number of slices, not {n!r}")
+    z = [int(k) for k in np.lexsort((np.arange(c.size), -c.astype(np.int64))) if c[k] > 0][:int(n)]
+    return sorted(z)
+
+
+def tile_pixels(extent_vox, spacing_mm, mm_per_px):
+    """max(1, round(n * pixdim / mm_per_px)): Python's round of the float quotient"""
+    return max(1, round(extent_vox * spacing_mm / mm_per_px))
+
+
+def sheet_layout(sizes, cols=None, gap=2):
+    """Tiles of sizes [(w, h)] on a grid of `cols` columns (None: ceil(sqrt(count))), row-major in the order given; a column is as wide as its widest tile, a row as high as
+    its highest, `gap` pixels lie between cells and around the sheet, a tile sits in the top-left corner of its cell -> ([(x0, y0)], H, W)."""
+    k = len(sizes)
+    cols = int(cols) if cols is not None else int(np.ceil(np.sqrt(k)))
+    cols = max(1, min(cols, k))
+    rows = (k + cols - 1) // cols
+    colw = [max(sizes[i][0] for i in range(c, k, cols)) for c in range(cols)]
+    rowh = [max(sizes[i][1] for i in range(r * cols, min(k, (r + 1) * cols))) for r in range(rows)]
+    pos = [(gap + sum(colw[:i % cols]) + gap * (i % cols), gap + sum(rowh[:i // cols]) + gap * (i // cols)) for i in range(k)]
+    return pos, gap + sum(rowh) + gap * rows, gap + sum(colw) + gap * cols
+
+
+def _bbox(a, vshape):
+    """the bounding box of the non-zero voxels of a host [X, Y, Z] array or a flat device tensor -> [(lo, hi)] per axis, or None when there is none"""
+    torch = _torch()
+    if isinstance(a, torch.Tensor):
+        X, Y, Z = vshape
+        nz = (a.reshape(Z, Y, X) != 0)                              # plumbing: three any-reductions and 3 short downloads
+        hit = [nz.any(0).any(0).cpu().numpy(), nz.any(0).any(1).cpu().numpy(), nz.any(1).any(1).cpu().numpy()]
+    else:
+        nz = a != 0
+        hit = [nz.any((1, 2)), nz.any((0, 2)), nz.any((0, 1))]
+    if not hit[0].any():
+        return None
+    return [(int(np.nonzero(h)[0][0]), int(np.nonzero(h)[0][-1]) + 1) for h in hit]
+
+
+def render_planes(ct, planes, layers=(), window="lung", cmap="bone", mm_per_px=None, tile_size=None, roi=None, cols=None, gap=2, background=(0, 0, 0), interp="linear",
+                  out_path=None, return_device=False, shape=None, _dev=None):
+    """Planes of a CT with label layers on top, drawn on the device into one RGB sheet -> RenderedSheet.  The reference's plot_sample (imshow(ct, cmap='bone') under
+    imshow(mask, alpha=0.5)) and its np.hstack grids, without a download of the volume.
+    ct: a path, a NiftiVolume or an [X, Y, Z] array, as for segment_volume.  planes: ("axial" | "coronal" | "sagittal", index) -- the plane z / y / x = index -- and
+    ("mip" | "minip", view, a, b) -- the maximum / minimum of the slab [a, b) along the view's axis (project_volume), with the largest label of every layer.  Every
+    view shows np.rot90 of its slice, as the reference does: image columns run along the first in-plane axis, rows against the second.
+    layers: up to 4 Layer objects (or bare label volumes: Layer's defaults), blended in order; window: a name of WINDOWS, a (lo, hi) pair or "minmax" (the finite minimum
+    and maximum of the decoded volume; a constant volume is a ValueError) -- display only, not clinically validated; cmap: "bone", "gray" or a uint8 [256, 3] table.
+    Tile size: w = max(1, round(n_u pixdim_u / mm_per_px)), h likewise, n_u, n_v the extents of the region in the plane; mm_per_px defaults to the smallest spacing among
+    the in-plane axes of the planes asked for, so anisotropic scans come out undistorted; tile_size=(w, h) sets every tile's size instead.  roi: None (the whole volume),
+    three voxel ranges, or "layers": the bounding box of the first layer's non-zero voxels plus ROI_MARGIN voxels, clipped to the volume and widened to hold every plain
+    plane asked for.  The tiles are laid out by sheet_layout(sizes, cols, gap) on `background`; interp: "linear" or "nearest" for the CT (labels are always sampled
+    nearest; outlines are one output pixel wide at any zoom).  out_path: the sheet as a PNG (png_min).  shape=: the (X, Y, Z) of layers given as flat device tensors.
+    All plain planes go into one unet_vol_render call per 64 tiles, every projected plane costs one unet_vol_project and one more call.  The sheet does not mark the
+    patient's left and right.  Every argument error is a ValueError raised before any device work."""
+    torch = _torch()
+    layers = _check_layers(layers)
+    vol = _source(ct)
+    vshape = tuple(int(v) for v in vol.raw.shape)
+    _check_volume_dims(vshape)
+    table, interp, bg, tile_size, cols, gap, roi = _check_sheet_args(window, cmap, mm_per_px, tile_size, roi, cols, gap, background, interp, vshape)
+    plist = _check_planes(planes, vshape)
+    pix = tuple(float(v) for v in vol.pixdim)
+    _check_pixdim(pix)
+    src = [_label_source(l.labels, f"layer {i}", vshape, shape) for i, l in enumerate(layers)]
+    win = _check_window(window, vol)
+    if roi is not None and roi != "layers":
+        for p, axis, index, slab, mode in plist:
+            if index is not None and not roi[axis][0] <= index < roi[axis][1]:
+                raise ValueError(f"plane {p!r} lies outside the region {roi[axis]} of its axis")
+    # ---- device work from here
+    dev = _dev if _dev is not None else upload(vol)
+    ldev = [_label_device(s) for s in src]
+    if roi is None:
+        roi = tuple((0, n) for n in vshape)
+    elif roi == "layers":
+        box = _bbox(ldev[0][0], vshape) if ldev else None
+        box = [(0, n) for n in vshape] if box is None else [(max(0, a - ROI_MARGIN), min(n, b + ROI_MARGIN)) for (a, b), n in zip(box, vshape)]
+        for p, axis, index, slab, mode in plist:
+            if index is not None:
+                box[axis] = (min(box[axis][0], index), max(box[axis][1], index + 1))
+        roi = tuple(box)
+    if mm_per_px is None:
+        mm_per_px = min(pix[d] for p, axis, *_ in plist for d in _IN_PLANE[axis])
+    sizes = []
+    for p, axis, index, slab, mode in plist:
+        au, av = _IN_PLANE[axis]
+        nu, nv = roi[au][1] - roi[au][0], roi[av][1] - roi[av][0]
+        sizes.append(tile_size if tile_size is not None else (tile_pixels(nu, pix[au], mm_per_px), tile_pixels(nv, pix[av], mm_per_px)))
+    pos, H, W = sheet_layout(sizes, cols, gap)
+    if H > 65535 or H * W * 3 >= 2 ** 31:
+        raise ValueError(f"a sheet of {H} x {W} pixels is too large (at most 65535 rows and 2^31 bytes)")
+    canvas = torch.empty((H, W, 3), dtype=torch.uint8, device="cuda")
+    table_dev = torch.from_numpy(table).cuda()
+    pals = [torch.from_numpy(l.palette).cuda() for l in layers]
+    lspec = [(t, code, pal, l.fill_alpha, l.outline_alpha) for (t, code), pal, l in zip(ldev, pals, layers)]
+    vargs = _vox_args(vol)
+    tiles, plain, launches = [], [], 0
+    for k, (p, axis, index, slab, mode) in enumerate(plist):
+        au, av = _IN_PLANE[axis]
+        (x0, y0), (w, h) = pos[k], sizes[k]
+        tiles.append(SheetTile(plane=p, axis=axis, index=index, slab=slab, x0=x0, y0=y0, w=w, h=h, roi=(roi[au], roi[av]),
+                               mm_per_px=((roi[au][1] - roi[au][0]) * pix[au] / w, (roi[av][1] - roi[av][0]) * pix[av] / h)))
+        if index is not None:
+            plain.append((axis, index, x0, y0, w, h))
+    for i in range(0, len(plain), RENDER_MAX_TILES):                # the first call fills what no tile of its own covers; the later ones draw over that
+        render_device(vargs, dev, roi, win, table_dev, interp, bg, launches == 0, lspec, plain[i:i + RENDER_MAX_TILES], canvas)
+        launches += 1
+    for t in tiles:
+        if t.slab is None:
+            continue
+        plane, lplanes = project_device(vargs, dev, t.axis, t.slab[0], t.slab[1], PROJECTIONS[t.plane[0]], ldev)
+        pargs = (64,) + tuple(1 if d == t.axis else n for d, n in enumerate(vshape)) + (0, 1.0, 0.0)
+        proi = tuple((0, 1) if d == t.axis else r for d, r in enumerate(roi))
+        pl = [(lp, code, pal, fa, oa) for lp, (_, code, pal, fa, oa) in zip(lplanes, lspec)]
+        render_device(pargs, plane, proi, win, table_dev, interp, bg, launches == 0, pl, [(t.axis, 0, t.x0, t.y0, t.w, t.h)], canvas)
+        launches += 1
+    image = canvas if return_device else canvas.cpu().numpy()
+    if out_path is not None:
+        png_min.write(out_path, canvas.cpu().numpy())
+    return RenderedSheet(image=image, tiles=tiles, window=win, roi=roi, mm_per_px=float(mm_per_px), background=bg, interp=("nearest", "linear")[interp], launches=launches)
