@@ -67,8 +67,11 @@ int32_t unet_ctx_set_profiling(unet_ctx* ctx, int32_t on);
  *   DETERMINISTIC (0)      1 = no floating-point atomics anywhere, so reruns are bit-identical: the reductions of the stand-alone passes go through per-workgroup slots
  *                          folded in index order; the sums a kernel EPILOGUE takes (BatchNorm statistics, the fused head's loss / gradient sums, the pooled sums -- launches
  *                          with far more workgroups than slots) leave as exact integer window sums, four 64-bit words per value, whose addition is associative
- *                          (ABI v15: the same fused graph as the default mode; 1.6 % of the step, 9 % before).  Domain of an epilogue partial sum: |t| < 2^39,
- *                          bits below 2^-80 dropped; outside it (and for Inf / NaN) the folded value is NaN
+ *                          (ABI v15: the same fused graph as the default mode; 1.6 % of the step, 9 % before).  Domain of an epilogue partial sum: |t| < 2^60,
+ *                          bits below 2^-80 dropped; outside it (and for Inf / NaN) the folded value is NaN.  What goes into the windows is a workgroup's fp32
+ *                          partial sum: of one tile in the h2 kernels; in the persistent schedule (CONV_PP) of ALL tiles of a workgroup, added per lane in fp32 --
+ *                          its statistics are reproducible on a given device (the tile walk follows the CU count) but carry the rounding of that longer fp32
+ *                          chain (tiles per half-workgroup x 8 additions per lane, relative to sum |y|), they are not exact sums of the stored tensor
  *   HEAD_FUSED (1)         fp32 U-Net, h2 kernels: the 1x1 sigmoid head (T1:913), the loss sums and the per-channel sums of the head's weight gradient come out of
  *                          the epilogue of the last conv3x3 (no pass over its 32-channel output in forward; backward writes dL/d(conv output) from p, the labels
  *                          and one bit per element); 0 = the separate head_fwd / head_bwd passes
@@ -140,6 +143,12 @@ int32_t unet_ctx_max_kernel_scratch_bytes(unet_ctx*);
 int32_t unet_conv3x3_fwd(unet_ctx*, const float* x, const float* w, const float* bias, float* y,
                          int32_t n, int32_t h, int32_t wd, int32_t cin, int32_t cout,
                          int32_t act, float drop_rate, uint64_t drop_seed, int32_t algo, float* w_ws, void* stream);
+/* unet_conv3x3_fwd into a channel slice of a wider NHWC buffer: y points at the slice's first channel, ldy = floats per pixel of that buffer (ldy >= cout, ldy % 4 == 0;
+ * else UNET_E_ARG) -- the second conv of an encoder block writing into the skip half of its concat (T1:860 -> T1:908, SKIP_RAW).  No dropout.  Only on the fp32 h2 kernels
+ * (UNET_ALGO_AUTO, cin and cout multiples of 16, w_ws given; else UNET_E_STATE).  Armed statistics / sign bits / K slices are honoured and cleared as by unet_conv3x3_fwd;
+ * the unet_bn_stats call that follows an armed launch takes ldx = ldy. */
+int32_t unet_conv3x3_fwd_ld(unet_ctx*, const float* x, const float* w, const float* bias, float* y, int32_t ldy,
+                            int32_t n, int32_t h, int32_t wd, int32_t cin, int32_t cout, int32_t act, int32_t algo, float* w_ws, void* stream);
 /* dx = conv3x3(dy, flip/transposed w) * mask_factor(mask_src): the derivative of the activation (+dropout) of the layer
  * that PRODUCED x is fused here (backward of the T1:859-860 conv pairs).  mask_rate/mask_seed: UNET_MASK_ELU_DROP only.
  * wt_ws: unet_conv3x3_w_ws_floats(cin, cout) floats of scratch for the flipped / transposed weights or their split image. */

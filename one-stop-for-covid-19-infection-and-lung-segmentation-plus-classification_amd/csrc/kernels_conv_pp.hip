@@ -445,6 +445,7 @@ bool pp_conv3x3_selected(const unet_ctx* ctx, int K, int M, int n, int h, int wd
   const long long tiles = (long long)((wd + 31) / 32) * ((h + 7) / 8) * n;
   if (tiles < 4LL * 2 * ctx->num_cu && ctx->opt_conv_pp < 2) return false;          // (fewer than four tiles per half-workgroup: the pipeline's fill and drain would dominate)
   if ((long long)n * h * wd * K * 4 + (long long)(wd + 1) * K * 4 >= (1LL << 31)) return false;          // 32-bit buffer offsets over the whole tensor
+  if ((long long)n * h * wd * ldy * 4 >= (1LL << 31)) return false;          // ... and over the output's span (pixel stride ldy): the store's scalar row offset is a signed 32-bit byte count
   return true;
 }
 
@@ -452,6 +453,7 @@ int32_t k_conv3x3_pp_fwd(unet_ctx* ctx, const float* x, const void* wimg, const 
                          int act, hipStream_t s, bool vdy) {
   if (K != 32 || M != 32) UNET_FAIL(ctx, UNET_E_SHAPE, "conv pp: K=%d M=%d", K, M);
   constexpr int KC = 2;
+  ctx->k_slices_ok = 0;          // (one-shot, unet_allow_k_slices: this schedule never slices, and the arm must not wait for a later h2 launch)
   if (!mask) mask_mode = MASK_NONE;
   const int tiles_x = (wd + 31) / 32, tiles_y = (h + 7) / 8;
   const long long total = (long long)tiles_x * tiles_y * n;

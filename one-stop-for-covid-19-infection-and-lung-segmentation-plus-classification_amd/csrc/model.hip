@@ -191,6 +191,23 @@ int32_t unet_conv3x3_fwd(unet_ctx* ctx, const float* x, const float* w, const fl
   return r;
 }
 
+// unet_conv3x3_fwd into a channel slice of a wider NHWC buffer (pixel stride ldy floats; no dropout): what an encoder conv that writes into the skip half of its concat
+// launches (SKIP_RAW), with the image built here instead of by a program's batch launch
+int32_t unet_conv3x3_fwd_ld(unet_ctx* ctx, const float* x, const float* w, const float* bias, float* y, int32_t ldy, int32_t n, int32_t h, int32_t wd, int32_t cin, int32_t cout,
+                            int32_t act, int32_t algo, float* w_ws, void* stream) {
+  if (!ctx || !x || !w || !y || n < 1 || h < 1 || wd < 1 || cin < 1 || cout < 1 || act < 0 || act > 2 || ldy < cout || (ldy & 3)) UNET_FAIL(ctx, UNET_E_ARG, "conv3x3_fwd_ld: bad args");
+  const void* armed = ctx->signs_req;
+  if (!use_h2(algo, cin, cout, w_ws)) {
+    ctx->signs_req = nullptr; ctx->k_slices_ok = 0;
+    UNET_FAIL(ctx, UNET_E_STATE, "conv3x3_fwd_ld: a strided output (ldy %d) exists on the h2 kernels only (UNET_ALGO_AUTO, cin and cout multiples of 16, w_ws given)", ldy);
+  }
+  int32_t r = k_h2_weights(ctx, w, w_ws, cin, cout, 0, as_stream(stream));
+  if (!r) r = k_conv3x3_h2_fwd(ctx, x, w_ws, bias, nullptr, MASK_NONE, y, n, h, wd, cin, cout, act, 0.0f, 0, as_stream(stream), 1 << 30, ldy);          // (ldy < cout, ldy % 4: UNET_E_ARG)
+  ctx->signs_req = nullptr; ctx->k_slices_ok = 0;
+  if (!r && armed && ctx->signs_done != armed) UNET_FAIL(ctx, UNET_E_SHAPE, "conv3x3_fwd_ld: armed with unet_request_relu_bits but this launch cannot write them (unet_relu_bits_supported, act = ReLU)");
+  return r;
+}
+
 // T1:911-913 in one launch (include/unet_hip.h): the last conv3x3 + the 1x1 sigmoid head + loss sums + the sums of the head's weight gradient
 int32_t unet_conv3x3_head_supported(unet_ctx* ctx, int32_t algo, int32_t wd, int32_t cin, int32_t cout) { return ctx && h2_conv3x3_head_selected(ctx, algo, wd, cin, cout) ? 1 : 0; }
 int32_t unet_conv3x3_head_fwd_ex(unet_ctx* ctx, const float* x, const float* w, const float* bias, float* y, const float* w_head, const float* b_head, float* p,
@@ -230,8 +247,9 @@ int32_t unet_conv3x3_bwd_data_dzm(unet_ctx* ctx, const void* dzm, const float* w
   if (!ctx || !dzm || !w || !w_head || !dx || !wt_ws || n < 1 || h < 1 || wd < 1) UNET_FAIL(ctx, UNET_E_ARG, "conv3x3_bwd_data_dzm: bad args");
   if (!unet_head_bwd_stream_supported(ctx, UNET_ALGO_AUTO, wd, cin)) UNET_FAIL(ctx, UNET_E_SHAPE, "conv3x3_bwd_data_dzm: not supported here (unet_head_bwd_stream_supported)");
   int32_t r = k_h2_weights(ctx, w, wt_ws, cin, 32, 1, as_stream(stream), w_head);          // (the head's weights: a per-contraction-channel factor of the image)
-  if (r) return r;
-  return k_conv3x3_h2_dgrad_dzm(ctx, dzm, wt_ws, static_cast<const float*>(relu_bits_in), relu_bits_in ? MASK_RELU_BITS : MASK_NONE, dx, n, h, wd, cin, as_stream(stream));
+  if (!r) r = k_conv3x3_h2_dgrad_dzm(ctx, dzm, wt_ws, static_cast<const float*>(relu_bits_in), relu_bits_in ? MASK_RELU_BITS : MASK_NONE, dx, n, h, wd, cin, as_stream(stream));
+  ctx->k_slices_ok = 0;          // (one-shot: this launch never slices its contraction and must not leave the arm for a later one)
+  return r;
 }
 int32_t unet_conv3x3_bwd_weights_dzm(unet_ctx* ctx, const float* x, const void* dzm, const float* w_head, float* dw, float* db, void* ws, size_t ws_bytes, int32_t n, int32_t h,
                                      int32_t wd, int32_t cin, void* stream) {
@@ -321,7 +339,9 @@ int32_t unet_conv3x3_bnfold_fwd(unet_ctx* ctx, const float* x, const float* bnp,
   r = k_h2_weights(ctx, w, u, cin, cout, 0, s, bnp);          // (the image kernel applies the BatchNorm scale per input channel)
   if (r) return r;
   const float* tab = ws + (size_t)9 * cin * cout;
-  return k_conv3x3_h2_fwd(ctx, x, u, tab, tab, MASK_BIAS_TAB, y, n, h, wd, cin, cout, act, 0.0f, 0, s);
+  r = k_conv3x3_h2_fwd(ctx, x, u, tab, tab, MASK_BIAS_TAB, y, n, h, wd, cin, cout, act, 0.0f, 0, s);
+  ctx->k_slices_ok = 0;          // (one-shot, as unet_conv3x3_fwd)
+  return r;
 }
 int32_t unet_conv3x3_bnfold_bwd_weights(unet_ctx* ctx, const float* x, const float* bnp, const float* dy, const float* w, float* dw, float* db, double* bn_bwd_sums, void* gws,
                                         size_t gws_bytes, float* ws, int32_t n, int32_t h, int32_t wd, int32_t cin, int32_t cout, int32_t algo, void* stream) {

@@ -17,6 +17,7 @@ def test_every_binding_has_the_declared_argument_count():
     wrong = {name: (seen[name], len(args)) for name, (_, args) in _lib._PROTOS.items() if name in seen and seen[name] != len(args)}
     assert not wrong, f"(declared, bound) argument counts differ: {wrong}"
     assert "unet_gather_samples" in seen and "unet_augment_samples" in seen
+    assert "unet_conv3x3_fwd_ld" in seen and "unet_conv3x3_fwd_ld" in _lib._PROTOS
 
 
 def test_every_bf16_entry_is_called_by_a_gpu_test():
