@@ -822,6 +822,28 @@ int32_t unet_vol_render(unet_ctx*, const void* vox, int32_t dtype, int32_t X, in
                         double lo, double hi, const uint8_t* table, int32_t interp, int32_t background, int32_t fill_background, const unet_render_layer* layers,
                         int32_t n_layers, const unet_render_tile* tiles, int32_t n_tiles, uint8_t* canvas, int32_t H, int32_t W, void* stream);
 
+/* ---- a volume on another grid (csrc/kernels_resample.hip; new: the reference never leaves the grid of the file) -------------------------------
+ * Source [X, Y, Z] and output [X2, Y2, Z2] are device volumes in Fortran order.  M: HOST, 12 finite doubles, row-major 3 x 4: output voxel (i, j, k) looks at the source
+ * coordinate s_r = ((M[r][0] i + M[r][1] j) + M[r][2] k) + M[r][3], float64, every operation rounded on its own.  mode 0 = "nearest" (the edge voxel repeats), 1 =
+ * "constant" (outside reads cval; scipy.ndimage's grid-constant).  A coordinate is compared as a double before anything is converted to an integer: entries of 1e300
+ * are safe; a coordinate that overflows to +-inf is clamped (mode 0) or outside (mode 1) like any other, and a NaN coordinate (inf - inf of an M that overflows) counts as 0
+ * in mode 0 and as outside in mode 1: both entry points then write cval (the linear one takes the weight 0 on an axis whose two neighbours are both outside).
+ * UNET_E_ARG before any launch, the output untouched: a non-finite entry of M, an output extent < 1, X Y Z >= 2^31 on either side, a negative source extent, mode outside
+ * 0..1, an unknown dtype / dst_dtype / element size, a null or misaligned buffer, a source without voxels in mode 0.  A source with a zero extent (whatever its other
+ * two extents are) fills the output with cval in mode 1.
+ *   unet_vol_resample_nearest  elements of elem_bytes = 1, 2, 4 or 8 bytes, moved untouched: q_r = floor(s_r + 0.5); mode 0 clamps q_r to [0, n_r - 1], mode 1 writes the
+ *                              low elem_bytes bytes of cval_bits where any q_r is outside.
+ *   unet_vol_resample_linear   the source is described and decoded as for unet_vol_intensity_bands ((float64(v) slope) + inter when scaled); cval is a decoded value.
+ *                              Mode 0 first clamps s_r to [0, n_r - 1].  f = floor(s), t = s - f; the eight neighbours f, f + 1 per axis are clamped to the volume
+ *                              (mode 0) or read cval outside it (mode 1); lerp(a, b, w) = a + (b - a) w along x (c00 = lerp(p000, p100, tx), c10 at y + 1, c01 at z + 1,
+ *                              c11), then y (lerp(c00, c10, ty), lerp(c01, c11, ty)), then z.  NaN and +-inf propagate as IEEE says: a NaN neighbour makes the output
+ *                              NaN even at weight 0, as scipy.ndimage does.  dst_dtype 64 = that float64, 16 = it rounded once to float32, 2 = uint8 (result >= 0.5):
+ *                              a 0 / 1 mask resampled smoothly. */
+int32_t unet_vol_resample_nearest(unet_ctx*, const void* src, int32_t elem_bytes, int32_t X, int32_t Y, int32_t Z, const double* M, int32_t mode, uint64_t cval_bits,
+                                  void* dst, int32_t X2, int32_t Y2, int32_t Z2, void* stream);
+int32_t unet_vol_resample_linear(unet_ctx*, const void* vox, int32_t dtype, int32_t X, int32_t Y, int32_t Z, int32_t scaled, double slope, double inter, const double* M,
+                                 int32_t mode, double cval, void* dst, int32_t dst_dtype, int32_t X2, int32_t Y2, int32_t Z2, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Model level. Replaces the Keras Model built at T1:853-916 and driven by
  * compile/fit/evaluate/predict (T1:1053-1061, 1101, 1137).  A model is a fixed-shape plan:

@@ -6,13 +6,17 @@ Public surface:
   volume.segment_volume / volume.build_dataset / volume.load_volume -- a NIfTI CT volume in, slice batches / a mask volume out (nifti_min reads the file)
   split_lungs / lung_burden (LungSides, LungBurden, LungSplitError) -- volume's left / right lung split and per-lung burden, also reachable from the package itself
   render_planes / project_volume / key_slices (Layer, RenderedSheet) -- volume's pictures of a segmented CT, also reachable from the package itself; png_min writes them
+  resample_volume / resample_mask / resample_labels / reorient_volume / change_between (Grid, ResampledVolume, VolumeChange) -- volume's resampling onto another grid,
+                            also reachable from the package itself
   engine.HipUNet         -- the HIP backend (libunet_hip.so through the C ABI of include/unet_hip.h)
 Importing this package has no side effects and does not need a GPU; constructing the
 backend does (there is no CPU fallback).
 """
 __all__ = ["runners", "keras_like", "engine", "weights", "data", "volume", "nifti_min", "png_min", "split_lungs", "lung_burden", "LungSides", "LungBurden", "LungSplitError",
-           "render_planes", "project_volume", "key_slices", "Layer", "RenderedSheet"]
-_FROM_VOLUME = ("split_lungs", "lung_burden", "LungSides", "LungBurden", "LungSplitError", "render_planes", "project_volume", "key_slices", "Layer", "RenderedSheet")
+           "render_planes", "project_volume", "key_slices", "Layer", "RenderedSheet", "resample_volume", "resample_mask", "resample_labels", "reorient_volume", "change_between",
+           "Grid", "ResampledVolume", "VolumeChange"]
+_FROM_VOLUME = ("split_lungs", "lung_burden", "LungSides", "LungBurden", "LungSplitError", "render_planes", "project_volume", "key_slices", "Layer", "RenderedSheet",
+                "resample_volume", "resample_mask", "resample_labels", "reorient_volume", "change_between", "Grid", "ResampledVolume", "VolumeChange")
 
 
 def __getattr__(name):                                              # resolved on first use: importing the package stays free of side effects

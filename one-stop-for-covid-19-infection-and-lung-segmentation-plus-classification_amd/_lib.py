@@ -229,6 +229,9 @@ _PROTOS = {
     # a picture of a segmented volume (csrc/kernels_render.hip, volume.project_volume / render_planes); the label / tile / layer lists are host arrays
     "unet_vol_project": (i32, [vp, vp, i32, i32, i32, i32, i32, f64, f64, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp]),
     "unet_vol_render": (i32, [vp, vp, i32, i32, i32, i32, i32, f64, f64, vp, f64, f64, vp, i32, i32, i32, vp, i32, vp, i32, vp, i32, i32, vp]),
+    # a volume on another grid (csrc/kernels_resample.hip, volume.resample_volume / reorient_volume / change_between); M is a host array of 12 doubles
+    "unet_vol_resample_nearest": (i32, [vp, vp, i32, i32, i32, i32, vp, i32, u64, vp, i32, i32, i32, vp]),
+    "unet_vol_resample_linear": (i32, [vp, vp, i32, i32, i32, i32, i32, f64, f64, vp, i32, f64, vp, i32, i32, i32, i32, vp]),
     "unet_model_create": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(vp)]),
     "unet_model_dtype": (i32, [vp]),
     "unet_model_tap_elem_bytes": (i32, [vp, C.c_char_p, i32]),

@@ -1,0 +1,236 @@
+// A volume put onto another grid: spacing, shape, an oblique affine, a signed axis permutation.
+//   elements of 1, 2, 4 or 8 bytes moved untouched from the nearest source voxel                                       unet_vol_resample_nearest
+//   the decoded voxels (kernels_intensity.hip's iv_dec, restated here) blended trilinearly -> float64 / float32 / a uint8 mask      unet_vol_resample_linear
+// Volumes are [X, Y, Z] in Fortran order (f = x + X (y + Y z)), X Y Z < 2^31 on both sides.  M (12 doubles, row-major 3 x 4, in the kernel arguments) maps an output
+// voxel index to a source voxel coordinate: s_r = ((M[r][0] i + M[r][1] j) + M[r][2] k) + M[r][3], every operation a rounded float64 one (-ffp-contract=off and the
+// __d*_rn forms: numpy restates them bit for bit).  A coordinate becomes an integer only after it was found inside [-1, n] as a double: |s| = 1e300 or a NaN (inf - inf
+// of an overflowing M) never reaches a conversion.
+// One lane per output voxel, and ONE per-voxel function (rs_near / rs_lin) under two lane-to-voxel mappings, so the mapping never changes a bit of the result:
+//   rs_direct_kernel   x along the lanes; a bounded grid strides the output.  Taken when source x depends most on output x (the largest |M[0][c]| is c = 0): a wave's
+//                      loads run along source x, forwards or backwards, and its stores are one run.
+//   rs_tiled_kernel    source x depends most on output axis a = 1 or 2, at least TILED_MIN voxels long (an axis permutation, a rotation past 45 degrees): a workgroup owns 64 x 64 outputs (x, a) of one
+//                      plane; its waves first put `a` along the lanes -- the loads run along source x --, leave the values in LDS, and then store them with x along the
+//                      lanes.  Both sides of a wave are runs of consecutive elements; the tile's row pitch is an odd number of dwords (8-byte elements: 130 dwords, which
+//                      ds_read_b64's 64 banks also take without a conflict).
+// A lane whose neighbours all lie outside (mode 1) loads nothing, so a wave of such lanes issues no load.  No atomics, no scratch buffers, plain vector stores.
+#include "common.h"
+
+#include <cmath>
+
+namespace {
+constexpr int TPB = 256;
+constexpr int TILE = 64;
+constexpr long long GRID_CAP = 256 * 32;
+
+// (X Y is tested before it is multiplied by Z: three extents near 2^31 overflow a 64-bit product; a source with a zero extent has no voxels whatever the others are)
+inline bool rs_dims_ok(int X, int Y, int Z) {
+  return X >= 0 && Y >= 0 && Z >= 0 && (X == 0 || Y == 0 || Z == 0 || ((long long)X * Y < 0x80000000LL && (long long)X * Y * Z < 0x80000000LL));
+}
+inline bool rs_out_ok(int X, int Y, int Z) { return X > 0 && Y > 0 && Z > 0 && (long long)X * Y < 0x80000000LL && (long long)X * Y * Z < 0x80000000LL; }
+inline int rs_itemsize(int dt) {
+  switch (dt) { case 2: case 256: return 1; case 4: case 512: return 2; case 8: case 768: case 16: return 4; case 64: return 8; default: return 0; }
+}
+inline unsigned rs_blocks(long long items) { long long b = (items + TPB - 1) / TPB; return (unsigned)(b < 1 ? 1 : (b > GRID_CAP ? GRID_CAP : b)); }
+
+struct rs_mat { double m[12]; };
+struct rs_geom { rs_mat M; int X, Y, Z, mode; };
+__device__ __forceinline__ double rs_coord(const rs_mat& M, int r, int i, int j, int k) {
+  return __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(M.m[4 * r], (double)i), __dmul_rn(M.m[4 * r + 1], (double)j)), __dmul_rn(M.m[4 * r + 2], (double)k)), M.m[4 * r + 3]);
+}
+
+// ---- nearest: q = floor(s + 0.5); mode 0 clamps q into the volume (a NaN goes to 0), mode 1 reads cval outside ---------------------------------------------------
+template <typename T>
+struct rs_near {
+  rs_geom g; const T* src; T cval;
+  __device__ __forceinline__ T operator()(int i, int j, int k) const {
+    const int n[3] = {g.X, g.Y, g.Z};
+    int q[3];
+    bool inside = true;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      const double v = floor(__dadd_rn(rs_coord(g.M, r, i, j, k), 0.5)), top = (double)(n[r] - 1);
+      if (g.mode == 0) q[r] = !(v >= 0.0) ? 0 : (v > top ? n[r] - 1 : (int)v);
+      else { const bool in = v >= 0.0 && v <= top; inside = inside && in; q[r] = in ? (int)v : 0; }
+    }
+    if (!inside) return cval;
+    return src[q[0] + (long long)g.X * (q[1] + (long long)g.Y * q[2])];
+  }
+};
+
+// ---- linear: the decode of kernels_intensity.hip (NIfTI-1 datatype codes; (float64(v) * slope) + inter, two rounded operations) ----------------------------------
+struct rs_src { const void* p; int dt; int scaled; double slope, inter; };
+__device__ __forceinline__ double rs_dec(const rs_src& s, long long i) {
+  double v;
+  switch (s.dt) {                                                     // (wave-uniform: one datatype per launch)
+    case 2: v = (double)static_cast<const uint8_t*>(s.p)[i]; break;
+    case 256: v = (double)static_cast<const int8_t*>(s.p)[i]; break;
+    case 4: v = (double)static_cast<const int16_t*>(s.p)[i]; break;
+    case 512: v = (double)static_cast<const uint16_t*>(s.p)[i]; break;
+    case 8: v = (double)static_cast<const int32_t*>(s.p)[i]; break;
+    case 768: v = (double)static_cast<const uint32_t*>(s.p)[i]; break;
+    case 16: v = (double)static_cast<const float*>(s.p)[i]; break;
+    default: v = static_cast<const double*>(s.p)[i]; break;           // 64
+  }
+  return s.scaled ? __dadd_rn(__dmul_rn(v, s.slope), s.inter) : v;
+}
+__device__ __forceinline__ double rs_lerp(double a, double b, double w) { return __dadd_rn(a, __dmul_rn(__dsub_rn(b, a), w)); }
+template <typename D> __device__ __forceinline__ D rs_store(double v);
+template <> __device__ __forceinline__ double rs_store<double>(double v) { return v; }
+template <> __device__ __forceinline__ float rs_store<float>(double v) { return (float)v; }                  // one rounding to nearest even
+template <> __device__ __forceinline__ uint8_t rs_store<uint8_t>(double v) { return v >= 0.5 ? 1 : 0; }      // (a NaN is not >= 0.5)
+
+template <typename D>
+struct rs_lin {
+  rs_geom g; rs_src src; double cval;
+  __device__ __forceinline__ D operator()(int i, int j, int k) const {
+    const int n[3] = {g.X, g.Y, g.Z};
+    int a0[3], a1[3];                                                 // the two neighbours of every axis, as indices that are always inside
+    bool in0[3], in1[3];
+    double t[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      double s = rs_coord(g.M, r, i, j, k);
+      const double top = (double)(n[r] - 1);
+      if (g.mode == 0) s = !(s >= 0.0) ? 0.0 : (s > top ? top : s);          // (a NaN goes to 0)
+      const double f = floor(s);
+      if (g.mode == 0) {                                              // 0 <= f <= n - 1 here
+        a0[r] = (int)f; a1[r] = min(a0[r] + 1, n[r] - 1); in0[r] = in1[r] = true;
+        t[r] = __dsub_rn(s, f);
+      } else {                                                        // f outside [-1, n - 1] (or a NaN): both neighbours are outside, nothing is converted
+        in0[r] = f >= 0.0 && f <= top; in1[r] = f >= -1.0 && f <= top - 1.0;
+        const int fi = (f >= -1.0 && f <= top) ? (int)f : 0;
+        a0[r] = in0[r] ? fi : 0; a1[r] = in1[r] ? fi + 1 : 0;
+        t[r] = (in0[r] || in1[r]) ? __dsub_rn(s, f) : 0.0;            // both outside: all eight read cval, and a weight of inf - inf or NaN must not turn it into a NaN
+      }
+    }
+    double p[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {                                     // c = dx + 2 dy + 4 dz
+      const bool in = ((c & 1) ? in1[0] : in0[0]) && ((c & 2) ? in1[1] : in0[1]) && ((c & 4) ? in1[2] : in0[2]);
+      const long long f = ((c & 1) ? a1[0] : a0[0]) + (long long)g.X * (((c & 2) ? a1[1] : a0[1]) + (long long)g.Y * ((c & 4) ? a1[2] : a0[2]));
+      p[c] = in ? rs_dec(src, f) : cval;
+    }
+    const double c00 = rs_lerp(p[0], p[1], t[0]), c10 = rs_lerp(p[2], p[3], t[0]), c01 = rs_lerp(p[4], p[5], t[0]), c11 = rs_lerp(p[6], p[7], t[0]);
+    return rs_store<D>(rs_lerp(rs_lerp(c00, c10, t[1]), rs_lerp(c01, c11, t[1]), t[2]));
+  }
+};
+
+// ---- the two mappings ------------------------------------------------------------------------------------------------------------------------------------
+template <typename T, typename Op>
+__global__ __launch_bounds__(TPB) void rs_direct_kernel(Op op, T* __restrict__ dst, int X2, int Y2, int Z2) {
+  const long long outs = (long long)X2 * Y2 * Z2;
+  for (long long o = (long long)blockIdx.x * TPB + threadIdx.x; o < outs; o += (long long)gridDim.x * TPB) {
+    const long long c = o / X2;
+    const int i = (int)(o - c * X2), k = (int)(c / Y2), j = (int)(c - (long long)k * Y2);
+    dst[o] = op(i, j, k);
+  }
+}
+
+// tile t = (bx, ba, b): outputs x in [64 bx, 64 bx + 64), axis a in [64 ba, 64 ba + 64), the third axis at b.  The trip count and both barriers are uniform over the workgroup.
+template <typename T, typename Op>
+__global__ __launch_bounds__(TPB) void rs_tiled_kernel(Op op, T* __restrict__ dst, int X2, int Y2, int Z2, int a, int tx, int ta, long long tiles) {
+  constexpr int PAD = sizeof(T) >= 4 ? 1 : 4 / (int)sizeof(T);
+  __shared__ T tile[TILE][TILE + PAD];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int nA = a == 1 ? Y2 : Z2;
+  for (long long t = blockIdx.x; t < tiles; t += gridDim.x) {
+    const int bx = (int)(t % tx);
+    const long long rest = t / tx;
+    const int ba = (int)(rest % ta), b = (int)(rest / ta);
+    const int x0 = bx * TILE, a0 = ba * TILE;
+    const int av = a0 + lane;
+    for (int r = w; r < TILE; r += TPB / 64) {
+      const int x = x0 + r;
+      if (x < X2 && av < nA) tile[r][lane] = a == 1 ? op(x, av, b) : op(x, b, av);
+    }
+    __syncthreads();
+    const int xv = x0 + lane;
+    for (int r = w; r < TILE; r += TPB / 64) {
+      const int ar = a0 + r;
+      if (xv < X2 && ar < nA) {
+        const int j = a == 1 ? ar : b, k = a == 1 ? b : ar;
+        dst[xv + (long long)X2 * (j + (long long)Y2 * k)] = tile[lane][r];
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// the output axis that source x depends on most (ties to the lower axis); 0 also when that axis has fewer than TILED_MIN voxels: a 64 x 64 tile would then load with
+// a few lanes of every wave (a choice by the shape, not measured)
+constexpr int TILED_MIN = 16;
+inline int rs_lane_axis(const double* M, int Y2, int Z2) {
+  int a = 0;
+  for (int c = 1; c < 3; ++c) if (fabs(M[c]) > fabs(M[a])) a = c;
+  if ((a == 1 && Y2 < TILED_MIN) || (a == 2 && Z2 < TILED_MIN)) a = 0;
+  return a;
+}
+template <typename T, typename Op>
+void rs_launch(const Op& op, void* dst, int X2, int Y2, int Z2, int a, hipStream_t s) {
+  if (a == 0) {
+    hipLaunchKernelGGL((rs_direct_kernel<T, Op>), dim3(rs_blocks((long long)X2 * Y2 * Z2)), dim3(TPB), 0, s, op, static_cast<T*>(dst), X2, Y2, Z2);
+    return;
+  }
+  const int tx = (X2 + TILE - 1) / TILE, ta = ((a == 1 ? Y2 : Z2) + TILE - 1) / TILE;
+  const long long tiles = (long long)tx * ta * (a == 1 ? Z2 : Y2);
+  hipLaunchKernelGGL((rs_tiled_kernel<T, Op>), dim3((unsigned)(tiles > GRID_CAP ? GRID_CAP : tiles)), dim3(TPB), 0, s, op, static_cast<T*>(dst), X2, Y2, Z2, a, tx, ta, tiles);
+}
+inline bool rs_fill_geom(rs_geom& g, const double* M, int X, int Y, int Z, int mode) {
+  for (int i = 0; i < 12; ++i) { if (!std::isfinite(M[i])) return false; g.M.m[i] = M[i]; }
+  g.X = X; g.Y = Y; g.Z = Z; g.mode = mode;
+  return true;
+}
+}  // namespace
+
+extern "C" {
+
+int32_t unet_vol_resample_nearest(unet_ctx* ctx, const void* src, int32_t elem_bytes, int32_t X, int32_t Y, int32_t Z, const double* M, int32_t mode, uint64_t cval_bits,
+                                  void* dst, int32_t X2, int32_t Y2, int32_t Z2, void* stream) {
+  if (!ctx) return UNET_E_ARG;
+  if (!rs_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_resample_nearest: a source dimension is negative or the source has 2^31 voxels or more");
+  if (!rs_out_ok(X2, Y2, Z2)) UNET_FAIL(ctx, UNET_E_ARG, "vol_resample_nearest: an output of %d x %d x %d (every extent is at least 1, fewer than 2^31 voxels)", X2, Y2, Z2);
+  if (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4 && elem_bytes != 8) UNET_FAIL(ctx, UNET_E_ARG, "vol_resample_nearest: elements of %d bytes, not 1, 2, 4 or 8", elem_bytes);
+  if (mode < 0 || mode > 1) UNET_FAIL(ctx, UNET_E_ARG, "vol_resample_nearest: mode %d is not 0 (nearest edge) or 1 (constant)", mode);
+  const bool empty = (long long)X * Y * Z == 0;
+  if (empty && mode == 0) UNET_FAIL(ctx, UNET_E_ARG, "vol_resample_nearest: the source has no voxels and mode 0 has no edge to repeat");
+  rs_geom g{};
+  if (!M || !rs_fill_geom(g, M, X, Y, Z, mode)) UNET_FAIL(ctx, UNET_E_ARG, "vol_resample_nearest: M is 12 finite doubles");
+  if ((!empty && (!src || (reinterpret_cast<uintptr_t>(src) % elem_bytes) != 0)) || !dst || (reinterpret_cast<uintptr_t>(dst) % elem_bytes) != 0)
+    UNET_FAIL(ctx, UNET_E_ARG, "vol_resample_nearest: a null buffer, or one not aligned to its element size");
+  hipStream_t s = as_stream(stream);
+  const int a = rs_lane_axis(M, Y2, Z2);
+  switch (elem_bytes) {
+    case 1: rs_launch<uint8_t>(rs_near<uint8_t>{g, static_cast<const uint8_t*>(src), (uint8_t)cval_bits}, dst, X2, Y2, Z2, a, s); break;
+    case 2: rs_launch<uint16_t>(rs_near<uint16_t>{g, static_cast<const uint16_t*>(src), (uint16_t)cval_bits}, dst, X2, Y2, Z2, a, s); break;
+    case 4: rs_launch<uint32_t>(rs_near<uint32_t>{g, static_cast<const uint32_t*>(src), (uint32_t)cval_bits}, dst, X2, Y2, Z2, a, s); break;
+    default: rs_launch<uint64_t>(rs_near<uint64_t>{g, static_cast<const uint64_t*>(src), (uint64_t)cval_bits}, dst, X2, Y2, Z2, a, s); break;
+  }
+  UNET_CHECK_LAUNCH(ctx, "vol_resample_nearest"); return UNET_OK;
+}
+
+int32_t unet_vol_resample_linear(unet_ctx* ctx, const void* vox, int32_t dtype, int32_t X, int32_t Y, int32_t Z, int32_t scaled, double slope, double inter, const double* M,
+                                 int32_t mode, double cval, void* dst, int32_t dst_dtype, int32_t X2, int32_t Y2, int32_t Z2, void* stream) {
+  if (!ctx) return UNET_E_ARG;
+  if (!rs_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_resample_linear: a source dimension is negative or the source has 2^31 voxels or more");
+  if (!rs_out_ok(X2, Y2, Z2)) UNET_FAIL(ctx, UNET_E_ARG, "vol_resample_linear: an output of %d x %d x %d (every extent is at least 1, fewer than 2^31 voxels)", X2, Y2, Z2);
+  if (rs_itemsize(dtype) == 0) UNET_FAIL(ctx, UNET_E_ARG, "vol_resample_linear: the NIfTI datatype code is not one of 2, 256, 4, 512, 8, 768, 16, 64");
+  if (dst_dtype != 64 && dst_dtype != 16 && dst_dtype != 2) UNET_FAIL(ctx, UNET_E_ARG, "vol_resample_linear: dst_dtype %d is not 64 (float64), 16 (float32) or 2 (uint8 mask)", dst_dtype);
+  if (mode < 0 || mode > 1) UNET_FAIL(ctx, UNET_E_ARG, "vol_resample_linear: mode %d is not 0 (nearest edge) or 1 (constant)", mode);
+  const bool empty = (long long)X * Y * Z == 0;
+  if (empty && mode == 0) UNET_FAIL(ctx, UNET_E_ARG, "vol_resample_linear: the source has no voxels and mode 0 has no edge to repeat");
+  rs_geom g{};
+  if (!M || !rs_fill_geom(g, M, X, Y, Z, mode)) UNET_FAIL(ctx, UNET_E_ARG, "vol_resample_linear: M is 12 finite doubles");
+  if ((!empty && (!vox || (reinterpret_cast<uintptr_t>(vox) % rs_itemsize(dtype)) != 0)) || !dst || (reinterpret_cast<uintptr_t>(dst) % rs_itemsize(dst_dtype)) != 0)
+    UNET_FAIL(ctx, UNET_E_ARG, "vol_resample_linear: a null buffer, or one not aligned to its element size");
+  const rs_src sv{vox, dtype, scaled ? 1 : 0, slope, inter};
+  hipStream_t s = as_stream(stream);
+  const int a = rs_lane_axis(M, Y2, Z2);
+  switch (dst_dtype) {
+    case 64: rs_launch<double>(rs_lin<double>{g, sv, cval}, dst, X2, Y2, Z2, a, s); break;
+    case 16: rs_launch<float>(rs_lin<float>{g, sv, cval}, dst, X2, Y2, Z2, a, s); break;
+    default: rs_launch<uint8_t>(rs_lin<uint8_t>{g, sv, cval}, dst, X2, Y2, Z2, a, s); break;
+  }
+  UNET_CHECK_LAUNCH(ctx, "vol_resample_linear"); return UNET_OK;
+}
+
+}  // extern "C"

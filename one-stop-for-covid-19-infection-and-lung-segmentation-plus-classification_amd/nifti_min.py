@@ -253,6 +253,22 @@ def default_header(shape, pixdim=(1.0, 1.0, 1.0)):
     return bytes(h)
 
 
+def header_with_affine(shape, affine):
+    """The 348 bytes of a little-endian NIfTI-1 header for an [X, Y, Z] volume that lies at `affine` (voxel -> RAS+ world, 4 x 4 or its top 3 x 4): sform_code = 1 with
+    the three srow rows (stored as float32, so a read gives the affine back rounded to float32), pixdim = the lengths of the three columns, qform_code = 0, millimetres.
+    A non-finite affine or a zero column raises NiftiFormatError."""
+    m = np.asarray(affine, np.float64)
+    if m.shape not in ((4, 4), (3, 4)) or not np.isfinite(m).all():
+        raise NiftiFormatError(f"an affine is a finite 4 x 4 (or 3 x 4) matrix, not {m.shape}" if m.shape not in ((4, 4), (3, 4)) else "the affine has a non-finite entry")
+    norms = np.sqrt((m[:3, :3] * m[:3, :3]).sum(axis=0))
+    if not np.isfinite(norms).all() or (norms == 0).any():
+        raise NiftiFormatError(f"the affine has a zero or non-finite column (column lengths {norms.tolist()})")
+    h = bytearray(default_header(shape, norms))
+    struct.pack_into("<2h", h, 252, 0, 1)                        # qform_code, sform_code (NIFTI_XFORM_SCANNER_ANAT)
+    struct.pack_into("<12f", h, 280, *(float(v) for v in m[:3, :4].reshape(-1)))
+    return bytes(h)
+
+
 def write(path, volume, header=None, pixdim=(1.0, 1.0, 1.0)):
     """Write a uint8 or float32 [X, Y, Z] volume as `.nii`, or gzip-compressed when the path ends in `.gz`.  `header`: the 348 bytes of the source
     (NiftiVolume.header) -- its dim, pixdim, qform / sform fields, xyzt_units and byte order are kept byte for byte; datatype, bitpix, vox_offset = 352,

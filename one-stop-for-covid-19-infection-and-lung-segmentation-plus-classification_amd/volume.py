@@ -26,6 +26,10 @@ the dataset loop around it (T1:390-393, 421-429) and the way back from a predict
                                           (WINDOWS, BONE), with up to four label layers blended and outlined on top (Layer), drawn on the device into one RGB sheet and
                                           written as a PNG (png_min); segment_volume(render=True) fills res.sheet with the key slices (key_slices) and a coronal projection
     project_volume(ct, axis, slab, mode)  -> the maximum / minimum of the CT and the largest label of every layer along one axis
+    resample_volume(ct, spacing | shape | like | grid)     -> ResampledVolume: the CT on another grid (trilinear or nearest, on the device); resample_mask / resample_labels
+                                          for masks and label volumes; Grid, resample_target, resample_matrix: the grids and the matrices between them
+    reorient_volume(vol, "RAS")           -> the volume stored under other axis codes (a signed axis permutation, the stored elements kept)
+    change_between(mask_a, grid_a, mask_b, grid_b)     -> VolumeChange: persistent / new / resolved voxels and millilitres of two masks on two grids, and their Dice
 
 The voxels are uploaded once as stored (nifti_min reads the file); decode, np.rot90, the slice trim, cv2.resize(float64, INTER_AREA) and the min-max run
 in unet_vol_slices_f64, CLAHE / crop / fuse / resize in the uint8 kernels of preprocess.py on device pointers: between the upload and the returned batch
@@ -2539,3 +2543,445 @@ def render_planes(ct, planes, layers=(), window="lung", cmap="bone", mm_per_px=N
     if out_path is not None:
         png_min.write(out_path, canvas.cpu().numpy())
     return RenderedSheet(image=image, tiles=tiles, window=win, roi=roi, mm_per_px=float(mm_per_px), background=bg, interp=("nearest", "linear")[interp], launches=launches)
+
+
+# ---- a volume on another grid: spacing, shape, an affine, an orientation --------------------------------------------------------------------
+RESAMPLE_ORDERS = ("nearest", "linear")
+RESAMPLE_MODES = {"nearest": 0, "constant": 1}                      # unet_vol_resample_*'s mode: the edge voxel repeats / outside reads cval (scipy's grid-constant)
+RESAMPLE_DTYPES = ("float32", "float64", "raw")
+_RESAMPLE_DST = {"float64": 64, "float32": 16}                      # unet_vol_resample_linear's dst_dtype (2 = the uint8 mask of resample_mask)
+_TORCH_OF_CODE = {2: "uint8", 256: "int8", 4: "int16", 8: "int32", 16: "float32", 64: "float64"}
+
+
+class Grid:
+    """Where a volume's voxels lie: shape (X, Y, Z) and affine (float64 4 x 4, voxel index -> RAS+ world in mm, as nifti_min reads it; a 3 x 4 is completed).  pixdim:
+    the lengths of the affine's three columns; axcodes: nifti_min.axcodes_from_affine (None for an unoriented grid); voxel_ml: |det| / 1000.
+    oriented=False marks a grid whose affine only carries a spacing (Grid.of of a volume without sform / qform: diag(pixdim)): it can be resampled to a spacing or a
+    shape of its own, but every operation BETWEEN two grids (like=, grid=, resample_matrix, change_between, reorient_volume) refuses it -- left and right are never
+    guessed (section 4u)."""
+
+    def __init__(self, shape, affine, oriented=True):
+        try:
+            shp = tuple(int(v) for v in shape)
+            exact = all(int(v) == v for v in shape)
+        except (TypeError, ValueError):
+            shp, exact = (), False
+        if len(shp) != 3 or not exact or any(v < 1 for v in shp):
+            raise ValueError(f"a grid's shape is three positive integers (X, Y, Z), not {shape!r}")
+        try:
+            m = np.array(affine, np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"a grid's affine is a finite 4 x 4 matrix, not {affine!r}") from None
+        if m.shape == (3, 4):
+            m = np.vstack([m, [0.0, 0.0, 0.0, 1.0]])
+        if m.shape != (4, 4) or not np.isfinite(m).all() or not np.array_equal(m[3], [0.0, 0.0, 0.0, 1.0]):
+            raise ValueError("a grid's affine is a finite 4 x 4 matrix whose last row is (0, 0, 0, 1)")
+        det = float(np.linalg.det(m[:3, :3]))
+        if not np.isfinite(det) or det == 0.0:
+            raise ValueError("a grid's affine must be invertible (its three columns span the space)")
+        self.shape, self.affine, self.oriented = shp, m, bool(oriented)
+
+    @property
+    def pixdim(self):
+        return tuple(float(v) for v in np.sqrt((self.affine[:3, :3] * self.affine[:3, :3]).sum(axis=0)))
+
+    @property
+    def axcodes(self):
+        return nifti_min.axcodes_from_affine(self.affine) if self.oriented else None
+
+    @property
+    def voxel_ml(self):
+        return abs(float(np.linalg.det(self.affine[:3, :3]))) / 1000.0
+
+    @classmethod
+    def of(cls, vol, pixdim=None, affine=None):
+        """The grid of a path, a NiftiVolume or an [X, Y, Z] array: affine= when given, else the file's affine (sform, else qform), else diag(pixdim or the file's
+        pixdim), marked oriented=False."""
+        v = _source(vol)
+        if affine is not None:
+            return cls(v.raw.shape, affine, True)
+        if pixdim is None and v.affine is not None:
+            return cls(v.raw.shape, v.affine, True)
+        p = _check_pixdim(v.pixdim if pixdim is None else pixdim)
+        return cls(v.raw.shape, np.diag([p[0], p[1], p[2], 1.0]), False)
+
+    def __repr__(self):
+        return f"Grid(shape={self.shape}, pixdim={tuple(round(p, 4) for p in self.pixdim)}, axcodes={self.axcodes}, oriented={self.oriented})"
+
+
+class ResampledVolume:
+    """data: the volume on the new grid -- numpy [X', Y', Z'] in Fortran order, or with return_device=True the flat device tensor --; grid: its Grid; matrix: float64
+    3 x 4, output voxel index -> source voxel coordinate, the 12 numbers the kernel received; slope, inter: the scaling of the stored elements (dtype="raw" and
+    reorient_volume keep the source's, everything else is decoded: 0, 0)."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def __repr__(self):
+        return f"ResampledVolume({self.grid!r})"
+
+
+class VolumeChange:
+    """What change_between returns, on a's grid: persistent (in both), new (in b only), resolved (in a only) -- voxels, and *_ml at a's voxel volume --, dice between a
+    and b-on-a's-grid (nan when both are empty), per_slice int64 [Z, 3] (persistent, new, resolved), b_on_a: b's mask on a's grid (uint8; the device tensor with
+    return_device=True), grid: a's."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def __repr__(self):
+        return f"VolumeChange(persistent_ml={self.persistent_ml:.2f}, new_ml={self.new_ml:.2f}, resolved_ml={self.resolved_ml:.2f}, dice={self.dice:.4f})"
+
+
+def _need_oriented(g, what):
+    if not isinstance(g, Grid):
+        raise ValueError(f"{what} is a Grid, not {type(g).__name__}")
+    if not g.oriented:
+        raise ValueError(f"{what} has no orientation (its volume carries neither sform nor qform and no affine= was given): two grids are only related through their "
+                         "affines -- left and right are not guessed")
+    return g
+
+
+def _check_matrix(M):
+    """-> float64 [3, 4], C order: the 12 finite numbers the kernels take; ValueError otherwise"""
+    try:
+        m = np.array(M, np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"a resampling matrix is 3 x 4 (or 4 x 4), not {M!r}") from None
+    if m.shape == (4, 4):
+        m = m[:3]
+    if m.shape != (3, 4):
+        raise ValueError(f"a resampling matrix is 3 x 4 (or 4 x 4), not {m.shape}")
+    if not np.isfinite(m).all():
+        raise ValueError("the resampling matrix has a non-finite entry")
+    return np.ascontiguousarray(m)
+
+
+def resample_matrix(src_grid, dst_grid):
+    """inv(A_src) @ A_dst in float64, its top three rows [3, 4]: the source voxel coordinate of every voxel index of dst_grid.  Both grids must be oriented."""
+    a, b = _need_oriented(src_grid, "the source grid"), _need_oriented(dst_grid, "the target grid")
+    with np.errstate(over="ignore", invalid="ignore"):              # (an overflow is reported by _check_matrix, as a ValueError)
+        return _check_matrix((np.linalg.inv(a.affine) @ b.affine)[:3])
+
+
+def _zoom_target(g, new_shape):
+    """the grid of the same field of view with new_shape voxels: output voxel i has its centre at s = (i + 0.5)(n / n') - 0.5 (half-voxel centres, section 4v)"""
+    z = np.array([n / m for n, m in zip(g.shape, new_shape)], np.float64)
+    M = np.zeros((3, 4))
+    M[:, :3] = np.diag(z)
+    M[:, 3] = 0.5 * z - 0.5
+    return Grid(new_shape, g.affine @ np.vstack([M, [0.0, 0.0, 0.0, 1.0]]), g.oriented), _check_matrix(M)
+
+
+def resample_target(src_grid, spacing=None, shape=None, like=None, grid=None):
+    """-> (the target Grid, M float64 [3, 4]) of resample_volume's spacing= / shape= / like= / grid=; exactly one of them.  Host arithmetic, no device.
+    spacing=(p'x, p'y, p'z) and shape=(n'x, n'y, n'z) keep the field of view: n' = max(1, round(n p / p')) (Python's round) for spacing=, M = [diag(n / n') | 0.5 n / n'
+    - 0.5] and the new affine is A [M; 0 0 0 1] -- these work on an unoriented grid too, and hand its mark on.  like= (a Grid, a path or a NiftiVolume) and grid= (a
+    Grid) name another grid: M = resample_matrix(src_grid, target), and both must be oriented."""
+    if not isinstance(src_grid, Grid):
+        raise ValueError(f"the source grid is a Grid, not {type(src_grid).__name__}")
+    given = [k for k, v in (("spacing", spacing), ("shape", shape), ("like", like), ("grid", grid)) if v is not None]
+    if len(given) != 1:
+        raise ValueError(f"exactly one of spacing=, shape=, like= and grid= names the target grid; got {given if given else 'none'}")
+    if spacing is not None:
+        p = _check_pixdim(spacing)
+        new_shape = tuple(max(1, int(round(n * q / float(v)))) for n, q, v in zip(src_grid.shape, src_grid.pixdim, p))
+        return _zoom_target(src_grid, new_shape)
+    if shape is not None:
+        return _zoom_target(src_grid, Grid(shape, np.eye(4)).shape)
+    if grid is not None:
+        target = grid
+    else:
+        target = like if isinstance(like, Grid) else Grid.of(like)
+    return target, resample_matrix(src_grid, _need_oriented(target, "the target grid"))
+
+
+def reorient_matrix(shape, src_codes, dst_codes):
+    """The signed axis permutation that stores a volume of `shape` with axis codes src_codes under dst_codes -> (M float64 [3, 4], the new shape): output axis j runs
+    along the source axis a with the same world axis, s_a = i_j when the two letters agree and (n_a - 1) - i_j when they are opposite.  Integers, exact in float64."""
+    src, dst = nifti_min.check_axcodes(src_codes), nifti_min.check_axcodes(dst_codes)
+    shp = Grid(shape, np.eye(4)).shape
+    M, new_shape = np.zeros((3, 4)), [0, 0, 0]
+    for j, (w, sign) in enumerate(dst):
+        a = [k for k, (ws, _) in enumerate(src) if ws == w][0]
+        new_shape[j] = shp[a]
+        if src[a][1] == sign:
+            M[a, j] = 1.0
+        else:
+            M[a, j], M[a, 3] = -1.0, float(shp[a] - 1)
+    return _check_matrix(M), tuple(new_shape)
+
+
+class _ResampleSource:
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def _resample_source(x, pixdim=None, affine=None, src_shape=None, kind="volume"):
+    """What resample_* take -> _ResampleSource(vol: the NiftiVolume still to upload, or None; tensor: the flat device tensor given, or None; shape; vargs: dtype code, X,
+    Y, Z, scaled, slope, inter; grid; header: the file's 348 bytes or None).  kind "mask": foreground = non-zero, as uint8 0 / 1; "labels": as int32; no device work."""
+    torch = _torch()
+    if pixdim is not None and affine is not None:
+        raise ValueError("pixdim= and affine= both describe the source grid: give one")
+    if isinstance(x, torch.Tensor):
+        if src_shape is None:
+            raise ValueError("a device volume is a flat Fortran-order buffer: pass src_shape=(X, Y, Z)")
+        shp = Grid(src_shape, np.eye(4)).shape
+        code = {getattr(torch, v): k for k, v in _TORCH_OF_CODE.items()}.get(x.dtype)
+        want = {"mask": (2,), "labels": (8,)}.get(kind, tuple(_TORCH_OF_CODE))
+        if code not in want or not x.is_cuda or x.numel() != int(np.prod(shp)):
+            raise ValueError(f"a device {kind} is a cuda tensor of dtype {' / '.join(_TORCH_OF_CODE[c] for c in want)} with prod(src_shape) = {int(np.prod(shp))} elements")
+        _check_volume_dims(shp)
+        if affine is not None:
+            g = Grid(shp, affine, True)
+        else:
+            p = _check_pixdim((1.0, 1.0, 1.0) if pixdim is None else pixdim)
+            g = Grid(shp, np.diag([p[0], p[1], p[2], 1.0]), False)
+        return _ResampleSource(vol=None, tensor=x.contiguous().reshape(-1), shape=shp, vargs=(code,) + shp + (0, 1.0, 0.0), grid=g, header=None)
+    if src_shape is not None:
+        raise ValueError("src_shape= describes a flat device tensor; a host volume carries its own shape")
+    vol = _source(x)
+    g = Grid.of(vol, pixdim, affine)
+    header = vol.header if isinstance(x, (str, os.PathLike, nifti_min.NiftiVolume)) else None
+    if kind in ("mask", "labels"):
+        dec = vol.raw if vol.scaling is None else vol.get_fdata()
+        if dec.dtype.kind not in "biu":
+            if isinstance(x, (str, os.PathLike, nifti_min.NiftiVolume)):
+                dec = np.rint(dec)                                  # (a mask file stored as float, or scaled: as _label_source reads it)
+            else:
+                raise ValueError(f"a {kind} volume has a bool or integer dtype, not {dec.dtype}")
+        a = np.asfortranarray((dec != 0).astype(np.uint8) if kind == "mask" else dec.astype(np.int32))
+        vol = nifti_min.NiftiVolume(a, 0.0, 0.0, vol.pixdim, vol.header, "<")
+    shp = tuple(int(v) for v in vol.raw.shape)
+    _check_volume_dims(shp)
+    return _ResampleSource(vol=vol, tensor=None, shape=shp, vargs=_vox_args(vol), grid=g, header=header)
+
+
+def _check_resample_args(order="linear", mode="nearest", cval=None, dtype="float32", orders=RESAMPLE_ORDERS):
+    if not isinstance(order, str) or order not in orders:
+        raise ValueError(f"order is one of {list(orders)}, not {order!r}")
+    if not isinstance(mode, str) or mode not in RESAMPLE_MODES:
+        raise ValueError(f"mode is one of {sorted(RESAMPLE_MODES)}, not {mode!r}")
+    if not isinstance(dtype, str) or dtype not in RESAMPLE_DTYPES:
+        raise ValueError(f"dtype is one of {list(RESAMPLE_DTYPES)}, not {dtype!r}")
+    if dtype == "raw" and order != "nearest":
+        raise ValueError("dtype='raw' keeps the stored elements, which only order='nearest' can move; order='linear' blends decoded values")
+    if cval is not None and (isinstance(cval, (bool, str)) or not isinstance(cval, (int, float, np.integer, np.floating))):
+        raise ValueError(f"cval is a number, not {cval!r}")
+
+
+def _stored_extreme(src, lowest=True):
+    """the stored element that decodes to the volume's minimum (lowest) -- NaNs aside --, as a numpy scalar of the stored dtype; no finite element: ValueError"""
+    code, scaled, slope = src.vargs[0], src.vargs[4], src.vargs[5]
+    take_min = lowest == (not scaled or slope > 0)
+    if src.vol is not None:
+        raw = src.vol.raw
+        if raw.dtype.kind == "f":
+            raw = raw[~np.isnan(raw)]
+        if raw.size == 0:
+            raise ValueError("cval: the volume has no voxel that is not NaN; pass cval=")
+        return raw.min() if take_min else raw.max()
+    t = src.tensor
+    if t.dtype.is_floating_point:
+        t = t[~t.isnan()]
+    if t.numel() == 0:
+        raise ValueError("cval: the volume has no voxel that is not NaN; pass cval=")
+    return np.array((t.min() if take_min else t.max()).item(), nifti_min.DTYPES[code])[()]
+
+
+def _decode_scalar(src, v):
+    sc = (src.vargs[5], src.vargs[6]) if src.vargs[4] else None
+    return float(v) if sc is None else float(np.float64(v) * sc[0] + sc[1])
+
+
+def resample_nearest_device(dev, elem_bytes, src_shape, M, mode, cval_bits, out_shape):
+    """unet_vol_resample_nearest -> a uint8 device tensor of prod(out_shape) * elem_bytes bytes (the moved elements, Fortran order)"""
+    M = _check_matrix(M)
+    torch = _torch(); lib, ctx = _ctx()
+    out = torch.empty(int(np.prod(out_shape)) * int(elem_bytes), dtype=torch.uint8, device="cuda")
+    ctx.check(lib.unet_vol_resample_nearest(ctx.handle, dev.data_ptr(), int(elem_bytes), *(int(v) for v in src_shape), M.ctypes.data, int(mode), int(cval_bits), out.data_ptr(),
+                                            *(int(v) for v in out_shape), _stream()), "vol_resample_nearest")
+    return out
+
+
+def resample_linear_device(dev, vargs, M, mode, cval, out_shape, dst_dtype):
+    """unet_vol_resample_linear -> a float64 (dst_dtype 64), float32 (16) or uint8 (2) device tensor of prod(out_shape) elements in Fortran order"""
+    M = _check_matrix(M)
+    torch = _torch(); lib, ctx = _ctx()
+    out = torch.empty(int(np.prod(out_shape)), dtype={64: torch.float64, 16: torch.float32, 2: torch.uint8}[dst_dtype], device="cuda")
+    ctx.check(lib.unet_vol_resample_linear(ctx.handle, dev.data_ptr(), *vargs, M.ctypes.data, int(mode), float(cval), out.data_ptr(), int(dst_dtype),
+                                           *(int(v) for v in out_shape), _stream()), "vol_resample_linear")
+    return out
+
+
+def _bits_of(v, np_dtype):
+    """the stored bytes of one element as an unsigned integer (unet_vol_resample_nearest's cval_bits)"""
+    return int.from_bytes(np.array(v).astype(np_dtype).tobytes(), "little")
+
+
+def _resample_raw(src, M, mode, cval_stored, out_shape):
+    """the nearest kernel on the source as stored -> a flat device tensor of the stored dtype"""
+    torch = _torch()
+    code = src.vargs[0]
+    npdt = np.dtype(nifti_min.DTYPES[code])
+    dev = src.tensor if src.tensor is not None else upload(src.vol)
+    out = resample_nearest_device(dev, npdt.itemsize, src.shape, M, mode, _bits_of(cval_stored, npdt), out_shape)
+    if code in _TORCH_OF_CODE:
+        return out.view(getattr(torch, _TORCH_OF_CODE[code]))
+    return out                                                      # (uint16 / uint32: torch has no arithmetic type for them; the bytes)
+
+
+def _host_of(t, np_dtype, shape):
+    a = t.cpu().numpy()
+    if a.dtype != np.dtype(np_dtype):
+        a = a.view(np_dtype)
+    return a.reshape(shape, order="F")
+
+
+def _write_resampled(out_path, host, g):
+    nifti_min.write(out_path, host, nifti_min.header_with_affine(g.shape, g.affine))
+
+
+def _check_out_path(out_path, stored_dtype):
+    if out_path is not None and np.dtype(stored_dtype) not in (np.dtype(np.uint8), np.dtype(np.float32)):
+        raise ValueError(f"out_path: nifti_min writes uint8 and float32 volumes, not {np.dtype(stored_dtype)}; ask for dtype='float32'")
+
+
+def resample_volume(ct, spacing=None, shape=None, like=None, grid=None, order="linear", mode="nearest", cval=None, dtype="float32", return_device=False, out_path=None,
+                    pixdim=None, affine=None, src_shape=None):
+    """A CT on another grid, computed on the device -> ResampledVolume(data, grid, matrix).  ct: a path, a NiftiVolume, an [X, Y, Z] array (its grid then from pixdim=
+    or affine=, default 1 mm unoriented) or a flat device tensor in Fortran order with src_shape=(X, Y, Z) (uint8, int8, int16, int32, float32 or float64, not scaled).
+    The target, exactly one of (resample_target): spacing= or shape= (the same field of view with other voxels; they also work on a volume without an orientation), like=
+    (a Grid, a path or a NiftiVolume) or grid= (a Grid) -- then both the volume and the target must carry an orientation.
+    order "linear": trilinear blend of the decoded voxels ((float64(v) slope) + inter, as get_fdata), a + (b - a) w along x, then y, then z, in float64; a NaN voxel makes
+    every output that touches it NaN, even at weight 0, as scipy.ndimage does.  "nearest": the voxel at floor(s + 0.5).  mode "nearest": outside the volume the edge
+    voxel repeats; "constant": outside reads cval (scipy's grid-constant), which defaults to the volume's decoded minimum (NaNs aside; air, for a CT).
+    dtype "float32" (the float64 result rounded once) or "float64"; "raw" needs order="nearest" and keeps the stored element type with its slope and inter -- cval= is then a
+    STORED value, by default the stored element that decodes to the minimum; with every other dtype cval= is a decoded value, in both orders.  order="nearest" with a
+    float dtype moves the stored elements on the device and decodes them on the host (an explicit cval= is written there, where the same kernel finds a volume of ones
+    outside), so it cannot be combined with return_device=True.  out_path: the result as .nii / .nii.gz with the new grid as its sform (float32 or uint8 data).
+    Neither order filters before it coarsens: coarsening by more than 2x aliases.  Every argument error is a ValueError raised before any device work."""
+    _check_resample_args(order, mode, cval, dtype)
+    if order == "nearest" and dtype != "raw" and return_device:
+        raise ValueError("order='nearest' moves stored elements; with return_device=True ask for dtype='raw' (the decode to a float dtype happens on the host)")
+    src = _resample_source(ct, pixdim, affine, src_shape)
+    target, M = resample_target(src.grid, spacing, shape, like, grid)
+    _check_volume_dims(target.shape)
+    npdt = np.dtype(nifti_min.DTYPES[src.vargs[0]])
+    _check_out_path(out_path, npdt if dtype == "raw" else dtype)
+    m = RESAMPLE_MODES[mode]
+    if order == "nearest":
+        decoded_cval = m == 1 and cval is not None and dtype != "raw"          # the outside of a decoded result reads cval itself, which need not be a stored value
+        stored = 0 if m == 0 or decoded_cval else (_stored_extreme(src) if cval is None else cval)
+        if npdt.kind in "iu" and not (np.isfinite(float(stored)) and float(stored) == int(stored) and np.iinfo(npdt).min <= int(stored) <= np.iinfo(npdt).max):
+            raise ValueError(f"cval {stored!r} is not a value of the stored dtype {npdt}")
+        out = _resample_raw(src, M, m, stored, target.shape)
+        if dtype == "raw":
+            data = out if return_device else _host_of(out, npdt, target.shape)
+            res = ResampledVolume(data=data, grid=target, matrix=M, slope=src.vargs[5] if src.vargs[4] else 0.0, inter=src.vargs[6] if src.vargs[4] else 0.0)
+        else:
+            host = nifti_min.apply_scaling(_host_of(out, npdt, target.shape), *((src.vargs[5], src.vargs[6]) if src.vargs[4] else (0.0, 0.0)))
+            if decoded_cval:                                        # where the outputs lie inside: the same kernel on a volume of ones, background 0
+                ones = _torch().ones(int(np.prod(src.shape)), dtype=_torch().uint8, device="cuda")
+                inside = _host_of(resample_nearest_device(ones, 1, src.shape, M, 1, 0, target.shape), np.uint8, target.shape)
+                host[inside == 0] = float(cval)
+            res = ResampledVolume(data=np.asfortranarray(host.astype(dtype)), grid=target, matrix=M, slope=0.0, inter=0.0)
+    else:
+        c = 0.0 if m == 0 else (_decode_scalar(src, _stored_extreme(src)) if cval is None else float(cval))
+        dev = src.tensor if src.tensor is not None else upload(src.vol)
+        out = resample_linear_device(dev, src.vargs, M, m, c, target.shape, _RESAMPLE_DST[dtype])
+        res = ResampledVolume(data=out if return_device else _host_of(out, dtype, target.shape), grid=target, matrix=M, slope=0.0, inter=0.0)
+    if out_path is not None:
+        _write_resampled(out_path, _host_of(res.data, npdt if dtype == "raw" else dtype, target.shape) if return_device else res.data, target)
+    return res
+
+
+def _label_mode(mode, spacing, shape):
+    """masks and labels: by default the edge repeats where the field of view is kept (spacing= / shape=) and the outside is background (0) on another grid"""
+    return ("nearest" if (spacing is not None or shape is not None) else "constant") if mode is None else mode
+
+
+def resample_mask(mask, spacing=None, shape=None, like=None, grid=None, order="nearest", mode=None, return_device=False, out_path=None, pixdim=None, affine=None,
+                  src_shape=None):
+    """A mask on another grid -> ResampledVolume whose data is uint8 0 / 1.  mask: as resample_volume takes a volume; non-zero = foreground (a device mask is a uint8
+    tensor of 0 / 1 with src_shape=).  order "nearest": the voxel at floor(s + 0.5); "linear": the 0 / 1 mask blended trilinearly and cut at 0.5 (result >= 0.5), which
+    keeps smooth borders when the voxels shrink.  mode: "nearest" / "constant" (background outside); default: "nearest" for spacing= / shape=, "constant" for like= /
+    grid=.  The targets, out_path and the errors are resample_volume's."""
+    mode = _label_mode(mode, spacing, shape)
+    _check_resample_args(order, mode, None, "raw" if order == "nearest" else "float32")
+    src = _resample_source(mask, pixdim, affine, src_shape, "mask")
+    target, M = resample_target(src.grid, spacing, shape, like, grid)
+    _check_volume_dims(target.shape)
+    m = RESAMPLE_MODES[mode]
+    if order == "nearest":
+        out = _resample_raw(src, M, m, 0, target.shape)
+    else:
+        dev = src.tensor if src.tensor is not None else upload(src.vol)
+        out = resample_linear_device(dev, src.vargs, M, m, 0.0, target.shape, 2)
+    res = ResampledVolume(data=out if return_device else _host_of(out, np.uint8, target.shape), grid=target, matrix=M, slope=0.0, inter=0.0)
+    if out_path is not None:
+        _write_resampled(out_path, _host_of(out, np.uint8, target.shape), target)
+    return res
+
+
+def resample_labels(labels, spacing=None, shape=None, like=None, grid=None, order="nearest", mode=None, return_device=False, pixdim=None, affine=None, src_shape=None):
+    """A label volume on another grid -> ResampledVolume whose data is int32: every output takes the label at floor(s + 0.5).  Nearest only: labels are names, not
+    amounts (no majority vote, no per-label blending); outside the volume: mode, as for resample_mask, with label 0 as the constant."""
+    if order != "nearest":
+        raise ValueError(f"labels are resampled with order='nearest' only (a blend of two labels is no label), not {order!r}")
+    mode = _label_mode(mode, spacing, shape)
+    _check_resample_args("nearest", mode, None, "raw")
+    src = _resample_source(labels, pixdim, affine, src_shape, "labels")
+    target, M = resample_target(src.grid, spacing, shape, like, grid)
+    _check_volume_dims(target.shape)
+    out = _resample_raw(src, M, RESAMPLE_MODES[mode], 0, target.shape)
+    return ResampledVolume(data=out if return_device else _host_of(out, np.int32, target.shape), grid=target, matrix=M, slope=0.0, inter=0.0)
+
+
+def reorient_volume(vol, codes="RAS", orientation=None, return_device=False, src_shape=None):
+    """The volume stored under other axis codes (default "RAS", the canonical orientation: the axes grow to the patient's right, anterior, superior) -> ResampledVolume:
+    a signed permutation of the axes through the nearest kernel -- its coordinates are integers, exact in float64 --, the stored element type, slope and inter kept.
+    vol: a path, a NiftiVolume, an array or a flat device tensor with src_shape=; orientation: None = the volume's own affine, or its axis codes such as "LPS", or a 4 x 4
+    affine.  The new grid carries the permuted affine (A [M; 0 0 0 1]) and pixdim; for an oblique affine the codes are those of axcodes_from_affine and the affine stays
+    oblique.  A volume without an orientation from either is a ValueError: left and right are never guessed."""
+    lin, src_codes = _check_orientation(orientation)
+    nifti_min.check_axcodes(codes)
+    src = _resample_source(vol, None, None, src_shape)
+    if orientation is not None:
+        named = isinstance(orientation, str) or all(isinstance(c, str) for c in orientation)
+        g = Grid(src.shape, nifti_min.affine_from_axcodes(src_codes, src.grid.pixdim) if named else np.asarray(orientation, np.float64), True)
+    else:
+        g = _need_oriented(src.grid, "the volume's grid")
+        try:
+            src_codes = g.axcodes
+        except nifti_min.NiftiFormatError as e:
+            raise ValueError(f"reorient_volume: {e}") from None
+    M, new_shape = reorient_matrix(src.shape, src_codes, codes)
+    target = Grid(new_shape, g.affine @ np.vstack([M, [0.0, 0.0, 0.0, 1.0]]), True)
+    npdt = np.dtype(nifti_min.DTYPES[src.vargs[0]])
+    out = _resample_raw(src, M, 0, 0, new_shape)
+    return ResampledVolume(data=out if return_device else _host_of(out, npdt, new_shape), grid=target, matrix=M, slope=src.vargs[5] if src.vargs[4] else 0.0,
+                           inter=src.vargs[6] if src.vargs[4] else 0.0)
+
+
+def change_between(mask_a, grid_a, mask_b, grid_b, return_device=False):
+    """Two masks of one patient on two grids (a baseline a and a follow-up b, a prediction and a truth drawn at another slice thickness) -> VolumeChange on a's grid.
+    b is put on a's grid with the nearest kernel, background outside b's volume; unet_vol_confusion then counts persistent (a and b), new (b only) and resolved (a only)
+    voxels per slice; millilitres at a's voxel volume; dice = 2 persistent / (2 persistent + new + resolved).  mask_a / mask_b: host arrays (non-zero = foreground) or
+    uint8 device tensors of prod(grid.shape) elements; both grids must be oriented Grids.  No registration: the two affines are taken as they are."""
+    ga, gb = _need_oriented(grid_a, "grid_a"), _need_oriented(grid_b, "grid_b")
+    torch = _torch()
+    srcs = []
+    for mk, g, what in ((mask_a, ga, "mask_a"), (mask_b, gb, "mask_b")):
+        s = _resample_source(mk, None, g.affine, g.shape if isinstance(mk, torch.Tensor) else None, "mask")
+        if s.shape != g.shape:
+            raise ValueError(f"{what} is {s.shape}, its grid {g.shape}")
+        srcs.append(s)
+    M = resample_matrix(gb, ga)
+    dev_a = srcs[0].tensor if srcs[0].tensor is not None else upload(srcs[0].vol)
+    b_on_a = _resample_raw(srcs[1], M, 1, 0, ga.shape)
+    counts = confusion_device(b_on_a, dev_a, ga.shape)
+    tp, fp, fn = (int(v) for v in counts.sum(axis=0))
+    ml = ga.voxel_ml
+    return VolumeChange(persistent=tp, new=fp, resolved=fn, persistent_ml=tp * ml, new_ml=fp * ml, resolved_ml=fn * ml, dice=_ratio(2 * tp, 2 * tp + fp + fn),
+                        per_slice=counts, b_on_a=b_on_a if return_device else _host_of(b_on_a, np.uint8, ga.shape), grid=ga, matrix=M)
