@@ -844,6 +844,24 @@ int32_t unet_vol_resample_nearest(unet_ctx*, const void* src, int32_t elem_bytes
 int32_t unet_vol_resample_linear(unet_ctx*, const void* vox, int32_t dtype, int32_t X, int32_t Y, int32_t Z, int32_t scaled, double slope, double inter, const double* M,
                                  int32_t mode, double cval, void* dst, int32_t dst_dtype, int32_t X2, int32_t Y2, int32_t Z2, void* stream);
 
+/* ---- the similarity of two volumes under candidate transforms (csrc/kernels_register.hip; new: the reference never compares two scans) --------
+ * unet_vol_joint_hist: the joint intensity histogram of a fixed volume [X, Y, Z] and a moving volume [Xm, Ym, Zm] (device, Fortran order, each described and decoded
+ * as for unet_vol_resample_linear: dtype, scaled, slope, inter) under K matrices at once.  M: HOST, K x 12 finite doubles, 1 <= K <= UNET_VOL_JOINT_HIST_MAX_K, each
+ * row-major 3 x 4 in section 4w's convention: fixed voxel (i, j, k) looks at the moving coordinate s_r = ((M[r][0] i + M[r][1] j) + M[r][2] k) + M[r][3].  mask: uint8
+ * on the fixed grid, or NULL.  A fixed voxel is counted for candidate c iff the mask is NULL or non-zero there, its decoded value is not NaN, every s_r satisfies
+ * 0 <= s_r <= n_r - 1 compared as doubles (a NaN or inf coordinate is outside; entries of 1e300 are safe) and the moving sample is not NaN.  The moving sample is the
+ * float64 unet_vol_resample_linear writes in mode 0 with dst_dtype 64 at that coordinate (f = floor(s), t = s - f, the upper neighbour clamped, lerp along x, y, z, one
+ * rounding per operation; the two share their code).  bin(v) = floor((v - lo) scale), scale = bins / (hi - lo) computed once on the host in float64, the subtraction and
+ * the product rounded separately; the product is compared as a double first: below 0 -> bin 0, >= bins -> bins - 1, so +-inf values clamp.  counts: device uint32
+ * [K][bins][bins], fixed bin major; the entry point clears it, and the counts are exact integers whatever the order of accumulation.
+ * UNET_E_ARG before any launch, counts untouched: K outside 1..16, bins outside 2..UNET_VOL_JOINT_HIST_MAX_BINS, a non-finite matrix entry or window, hi <= lo (or a
+ * hi - lo that overflows), an unknown dtype, a null (fixed, moving, M, counts) or misaligned buffer, either volume with no voxels or with 2^31 or more. */
+#define UNET_VOL_JOINT_HIST_MAX_K 16
+#define UNET_VOL_JOINT_HIST_MAX_BINS 64
+int32_t unet_vol_joint_hist(unet_ctx*, const void* fixed, int32_t f_dtype, int32_t X, int32_t Y, int32_t Z, int32_t f_scaled, double f_slope, double f_inter,
+                            const uint8_t* mask, const void* moving, int32_t m_dtype, int32_t Xm, int32_t Ym, int32_t Zm, int32_t m_scaled, double m_slope, double m_inter,
+                            const double* M, int32_t K, int32_t bins, double f_lo, double f_hi, double m_lo, double m_hi, uint32_t* counts, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Model level. Replaces the Keras Model built at T1:853-916 and driven by
  * compile/fit/evaluate/predict (T1:1053-1061, 1101, 1137).  A model is a fixed-shape plan:

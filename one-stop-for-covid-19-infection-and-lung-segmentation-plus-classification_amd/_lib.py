@@ -25,6 +25,7 @@ ACT_NONE, ACT_RELU, ACT_ELU = 0, 1, 2
 MORPH_OPS = {"dilate": 0, "erode": 1, "open": 2, "close": 3}          # include/unet_hip.h UNET_MORPH_*
 MORPH_MAX_ITERATIONS = 64
 INTENSITY_MAX_EDGES = 63                                              # include/unet_hip.h UNET_VOL_INTENSITY_MAX_EDGES
+JOINT_HIST_MAX_K, JOINT_HIST_MAX_BINS = 16, 64                        # UNET_VOL_JOINT_HIST_MAX_K, UNET_VOL_JOINT_HIST_MAX_BINS
 MASK_NONE, MASK_RELU, MASK_ELU, MASK_ELU_DROP = 0, 1, 2, 3
 PROG_FWD_TRAIN, PROG_BWD, PROG_FWD_INFER = 0, 1, 2
 SYNC_BN_FWD, SYNC_LOSS, SYNC_BN_BWD, SYNC_GRAD_BUCKET = 0, 1, 2, 3
@@ -232,6 +233,8 @@ _PROTOS = {
     # a volume on another grid (csrc/kernels_resample.hip, volume.resample_volume / reorient_volume / change_between); M is a host array of 12 doubles
     "unet_vol_resample_nearest": (i32, [vp, vp, i32, i32, i32, i32, vp, i32, u64, vp, i32, i32, i32, vp]),
     "unet_vol_resample_linear": (i32, [vp, vp, i32, i32, i32, i32, i32, f64, f64, vp, i32, f64, vp, i32, i32, i32, i32, vp]),
+    # the joint histogram of two volumes under K candidate matrices (csrc/kernels_register.hip, volume.joint_histogram / register_volumes); M is a host array of K x 12 doubles
+    "unet_vol_joint_hist": (i32, [vp, vp, i32, i32, i32, i32, i32, f64, f64, vp, vp, i32, i32, i32, i32, i32, f64, f64, vp, i32, i32, f64, f64, f64, f64, vp, vp]),
     "unet_model_create": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(vp)]),
     "unet_model_dtype": (i32, [vp]),
     "unet_model_tap_elem_bytes": (i32, [vp, C.c_char_p, i32]),

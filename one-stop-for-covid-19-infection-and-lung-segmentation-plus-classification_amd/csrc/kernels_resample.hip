@@ -14,6 +14,7 @@
 //                      ds_read_b64's 64 banks also take without a conflict).
 // A lane whose neighbours all lie outside (mode 1) loads nothing, so a wave of such lanes issues no load.  No atomics, no scratch buffers, plain vector stores.
 #include "common.h"
+#include "vol_trilinear.h"
 
 #include <cmath>
 
@@ -22,21 +23,9 @@ constexpr int TPB = 256;
 constexpr int TILE = 64;
 constexpr long long GRID_CAP = 256 * 32;
 
-// (X Y is tested before it is multiplied by Z: three extents near 2^31 overflow a 64-bit product; a source with a zero extent has no voxels whatever the others are)
-inline bool rs_dims_ok(int X, int Y, int Z) {
-  return X >= 0 && Y >= 0 && Z >= 0 && (X == 0 || Y == 0 || Z == 0 || ((long long)X * Y < 0x80000000LL && (long long)X * Y * Z < 0x80000000LL));
-}
-inline bool rs_out_ok(int X, int Y, int Z) { return X > 0 && Y > 0 && Z > 0 && (long long)X * Y < 0x80000000LL && (long long)X * Y * Z < 0x80000000LL; }
-inline int rs_itemsize(int dt) {
-  switch (dt) { case 2: case 256: return 1; case 4: case 512: return 2; case 8: case 768: case 16: return 4; case 64: return 8; default: return 0; }
-}
 inline unsigned rs_blocks(long long items) { long long b = (items + TPB - 1) / TPB; return (unsigned)(b < 1 ? 1 : (b > GRID_CAP ? GRID_CAP : b)); }
 
-struct rs_mat { double m[12]; };
 struct rs_geom { rs_mat M; int X, Y, Z, mode; };
-__device__ __forceinline__ double rs_coord(const rs_mat& M, int r, int i, int j, int k) {
-  return __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(M.m[4 * r], (double)i), __dmul_rn(M.m[4 * r + 1], (double)j)), __dmul_rn(M.m[4 * r + 2], (double)k)), M.m[4 * r + 3]);
-}
 
 // ---- nearest: q = floor(s + 0.5); mode 0 clamps q into the volume (a NaN goes to 0), mode 1 reads cval outside ---------------------------------------------------
 template <typename T>
@@ -57,23 +46,7 @@ struct rs_near {
   }
 };
 
-// ---- linear: the decode of kernels_intensity.hip (NIfTI-1 datatype codes; (float64(v) * slope) + inter, two rounded operations) ----------------------------------
-struct rs_src { const void* p; int dt; int scaled; double slope, inter; };
-__device__ __forceinline__ double rs_dec(const rs_src& s, long long i) {
-  double v;
-  switch (s.dt) {                                                     // (wave-uniform: one datatype per launch)
-    case 2: v = (double)static_cast<const uint8_t*>(s.p)[i]; break;
-    case 256: v = (double)static_cast<const int8_t*>(s.p)[i]; break;
-    case 4: v = (double)static_cast<const int16_t*>(s.p)[i]; break;
-    case 512: v = (double)static_cast<const uint16_t*>(s.p)[i]; break;
-    case 8: v = (double)static_cast<const int32_t*>(s.p)[i]; break;
-    case 768: v = (double)static_cast<const uint32_t*>(s.p)[i]; break;
-    case 16: v = (double)static_cast<const float*>(s.p)[i]; break;
-    default: v = static_cast<const double*>(s.p)[i]; break;           // 64
-  }
-  return s.scaled ? __dadd_rn(__dmul_rn(v, s.slope), s.inter) : v;
-}
-__device__ __forceinline__ double rs_lerp(double a, double b, double w) { return __dadd_rn(a, __dmul_rn(__dsub_rn(b, a), w)); }
+// ---- linear: the decode, the coordinate and the blend are vol_trilinear.h's (shared with kernels_register.hip) ---------------------------------------------------------
 template <typename D> __device__ __forceinline__ D rs_store(double v);
 template <> __device__ __forceinline__ double rs_store<double>(double v) { return v; }
 template <> __device__ __forceinline__ float rs_store<float>(double v) { return (float)v; }                  // one rounding to nearest even

@@ -30,6 +30,9 @@ the dataset loop around it (T1:390-393, 421-429) and the way back from a predict
                                           for masks and label volumes; Grid, resample_target, resample_matrix: the grids and the matrices between them
     reorient_volume(vol, "RAS")           -> the volume stored under other axis codes (a signed axis permutation, the stored elements kept)
     change_between(mask_a, grid_a, mask_b, grid_b)     -> VolumeChange: persistent / new / resolved voxels and millilitres of two masks on two grids, and their Dice
+    register_volumes(fixed, moving)       -> Registration: the rigid transform (RigidTransform) that takes a baseline CT's world onto a follow-up's, found by maximising
+                                          the mutual information of their joint histogram (joint_histogram, mutual_information) on the device; Registration.resample
+                                          and change_between(transform=) then compare the two scans in one frame
 
 The voxels are uploaded once as stored (nifti_min reads the file); decode, np.rot90, the slice trim, cv2.resize(float64, INTER_AREA) and the min-max run
 in unet_vol_slices_f64, CLAHE / crop / fuse / resize in the uint8 kernels of preprocess.py on device pointers: between the upload and the returned batch
@@ -2964,12 +2967,16 @@ def reorient_volume(vol, codes="RAS", orientation=None, return_device=False, src
                            inter=src.vargs[6] if src.vargs[4] else 0.0)
 
 
-def change_between(mask_a, grid_a, mask_b, grid_b, return_device=False):
+def change_between(mask_a, grid_a, mask_b, grid_b, return_device=False, transform=None):
     """Two masks of one patient on two grids (a baseline a and a follow-up b, a prediction and a truth drawn at another slice thickness) -> VolumeChange on a's grid.
     b is put on a's grid with the nearest kernel, background outside b's volume; unet_vol_confusion then counts persistent (a and b), new (b only) and resolved (a only)
     voxels per slice; millilitres at a's voxel volume; dice = 2 persistent / (2 persistent + new + resolved).  mask_a / mask_b: host arrays (non-zero = foreground) or
-    uint8 device tensors of prod(grid.shape) elements; both grids must be oriented Grids.  No registration: the two affines are taken as they are."""
+    uint8 device tensors of prod(grid.shape) elements; both grids must be oriented Grids.  transform=None: the two affines are taken as they are (two re-griddings of one
+    acquisition).  transform= a RigidTransform, a Registration (register_volumes(ct_a, ct_b)) or a 4 x 4 matrix T, a's world -> b's world: b's affine is replaced by
+    inv(T) @ A_b first, so a follow-up in which the patient lies differently is compared in the baseline's frame (section 4x)."""
     ga, gb = _need_oriented(grid_a, "grid_a"), _need_oriented(grid_b, "grid_b")
+    if transform is not None:
+        gb = Grid(gb.shape, np.linalg.inv(_world_matrix(transform)) @ gb.affine, True)
     torch = _torch()
     srcs = []
     for mk, g, what in ((mask_a, ga, "mask_a"), (mask_b, gb, "mask_b")):
@@ -2985,3 +2992,406 @@ def change_between(mask_a, grid_a, mask_b, grid_b, return_device=False):
     ml = ga.voxel_ml
     return VolumeChange(persistent=tp, new=fp, resolved=fn, persistent_ml=tp * ml, new_ml=fp * ml, resolved_ml=fn * ml, dice=_ratio(2 * tp, 2 * tp + fp + fn),
                         per_slice=counts, b_on_a=b_on_a if return_device else _host_of(b_on_a, np.uint8, ga.shape), grid=ga, matrix=M)
+
+
+# ---- a follow-up onto its baseline: rigid registration by mutual information (csrc/kernels_register.hip) --------------------------------------
+JOINT_HIST_MAX_K = _lib.JOINT_HIST_MAX_K                             # UNET_VOL_JOINT_HIST_MAX_K: candidates per launch
+JOINT_HIST_MAX_BINS = _lib.JOINT_HIST_MAX_BINS                       # UNET_VOL_JOINT_HIST_MAX_BINS
+REGISTER_METRICS = ("mi", "nmi")
+REGISTER_LEVELS_MM = (8.0, 4.0, 2.0)
+REGISTER_WINDOW = (-1000.0, 400.0)                                  # air to dense tissue: everything above clamps into the last bin
+REGISTER_MAX_BATCHES = 400
+REGISTER_STOP = 0.05                                                # a level ends when its translation step falls below this share of its spacing
+
+
+def _rotation(rx, ry, rz):
+    """R = Rz Ry Rx (radians): about x first, then y, then z"""
+    cx, sx, cy, sy, cz, sz = np.cos(rx), np.sin(rx), np.cos(ry), np.sin(ry), np.cos(rz), np.sin(rz)
+    Rx = np.array([[1.0, 0.0, 0.0], [0.0, cx, -sx], [0.0, sx, cx]])
+    Ry = np.array([[cy, 0.0, sy], [0.0, 1.0, 0.0], [-sy, 0.0, cy]])
+    Rz = np.array([[cz, -sz, 0.0], [sz, cz, 0.0], [0.0, 0.0, 1.0]])
+    return Rz @ (Ry @ Rx)
+
+
+class RigidTransform:
+    """A rigid motion of the world, fixed world -> moving world, in millimetres and radians: x_m = R (x - c) + c + t with R = Rz(rz) Ry(ry) Rx(rx), params = (tx, ty,
+    tz, rx, ry, rz) and centre c (the point the rotation turns about; it only changes how the same motion splits into R and t).  matrix: the 4 x 4 of that map --
+    the identity, exactly, for params of zero.  inverse() and compose() return RigidTransforms about the same centre; from_matrix reads the six numbers back from a
+    4 x 4 (|ry| < 90 degrees)."""
+
+    def __init__(self, params=(0.0, 0.0, 0.0, 0.0, 0.0, 0.0), centre=(0.0, 0.0, 0.0)):
+        try:
+            p, c = np.array(params, np.float64).reshape(-1), np.array(centre, np.float64).reshape(-1)
+        except (TypeError, ValueError):
+            raise ValueError(f"a rigid transform is six numbers (tx, ty, tz in mm, rx, ry, rz in radians) and a centre of three, not {params!r}, {centre!r}") from None
+        if p.shape != (6,) or c.shape != (3,) or not np.isfinite(p).all() or not np.isfinite(c).all():
+            raise ValueError(f"a rigid transform is six finite numbers (tx, ty, tz in mm, rx, ry, rz in radians) and a finite centre of three, not {params!r}, {centre!r}")
+        self.params, self.centre = p, c
+
+    @property
+    def rotation(self):
+        return _rotation(*self.params[3:])
+
+    @property
+    def matrix(self):
+        R, c, t = self.rotation, self.centre, self.params[:3]
+        m = np.eye(4)
+        m[:3, :3] = R
+        m[:3, 3] = (c + t) - R @ c
+        return m
+
+    @classmethod
+    def from_matrix(cls, matrix, centre=(0.0, 0.0, 0.0), tol=1e-9):
+        """the RigidTransform about `centre` whose matrix is `matrix` (4 x 4 or 3 x 4): R must be a rotation (R^T R = 1 and det R = +1 within tol) -- a zoom, a shear or a
+        mirror is a ValueError."""
+        m = _world_matrix(matrix)
+        c = cls((0.0,) * 6, centre).centre
+        R = m[:3, :3]
+        if not np.allclose(R.T @ R, np.eye(3), rtol=0.0, atol=tol) or abs(float(np.linalg.det(R)) - 1.0) > tol:
+            raise ValueError("the matrix is not rigid: its 3 x 3 part is no rotation (a zoom, a shear or a mirror)")
+        ry = float(np.arcsin(min(1.0, max(-1.0, -R[2, 0]))))
+        rx, rz = float(np.arctan2(R[2, 1], R[2, 2])), float(np.arctan2(R[1, 0], R[0, 0]))
+        t = (m[:3, 3] - c) + R @ c
+        return cls((t[0], t[1], t[2], rx, ry, rz), c)
+
+    def inverse(self):
+        """moving world -> fixed world, about the same centre"""
+        return RigidTransform.from_matrix(np.linalg.inv(self.matrix), self.centre)
+
+    def compose(self, first):
+        """self after `first`: x -> self(first(x)), about self's centre"""
+        return RigidTransform.from_matrix(self.matrix @ _world_matrix(first), self.centre)
+
+    def __repr__(self):
+        t, r = self.params[:3], np.rad2deg(self.params[3:])
+        return f"RigidTransform(t=({t[0]:.3f}, {t[1]:.3f}, {t[2]:.3f}) mm, r=({r[0]:.3f}, {r[1]:.3f}, {r[2]:.3f}) deg, centre=({self.centre[0]:.2f}, {self.centre[1]:.2f}, {self.centre[2]:.2f}))"
+
+
+def _world_matrix(t):
+    """a RigidTransform, a Registration or a 4 x 4 (3 x 4) world matrix -> float64 4 x 4, finite, invertible, last row (0, 0, 0, 1); ValueError otherwise"""
+    if isinstance(t, Registration):
+        t = t.transform
+    if isinstance(t, RigidTransform):
+        return t.matrix
+    try:
+        m = np.array(t, np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"a world transform is a RigidTransform, a Registration or a 4 x 4 matrix, not {t!r}") from None
+    if m.shape == (3, 4):
+        m = np.vstack([m, [0.0, 0.0, 0.0, 1.0]])
+    if m.shape != (4, 4) or not np.isfinite(m).all() or not np.array_equal(m[3], [0.0, 0.0, 0.0, 1.0]):
+        raise ValueError("a world transform is a finite 4 x 4 matrix whose last row is (0, 0, 0, 1)")
+    det = float(np.linalg.det(m[:3, :3]))
+    if not np.isfinite(det) or det == 0.0:
+        raise ValueError("a world transform must be invertible")
+    return m
+
+
+def voxel_matrix(fixed_grid, moving_grid, transform=None):
+    """inv(A_moving) @ T @ A_fixed in float64, its top three rows [3, 4]: the moving voxel coordinate of every fixed voxel index under the world transform T (None: the
+    identity, which makes it resample_matrix(moving_grid, fixed_grid)).  Both grids must be oriented."""
+    f, m = _need_oriented(fixed_grid, "the fixed grid"), _need_oriented(moving_grid, "the moving grid")
+    T = np.eye(4) if transform is None else _world_matrix(transform)
+    with np.errstate(over="ignore", invalid="ignore"):
+        return _check_matrix((np.linalg.inv(m.affine) @ T @ f.affine)[:3])
+
+
+def _check_bins(bins):
+    if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or not 2 <= int(bins) <= JOINT_HIST_MAX_BINS:
+        raise ValueError(f"bins is an integer from 2 to {JOINT_HIST_MAX_BINS}, not {bins!r}")
+    return int(bins)
+
+
+def _check_hist_window(window, what="window"):
+    try:
+        w = np.array(window, np.float64).reshape(-1)
+    except (TypeError, ValueError):
+        w = np.zeros(0)
+    with np.errstate(over="ignore"):
+        bad = w.shape != (2,) or not np.isfinite(w).all() or not w[1] > w[0] or not np.isfinite(w[1] - w[0])
+    if bad:
+        raise ValueError(f"{what} is two finite numbers (lo, hi) with hi > lo, not {window!r}")
+    return float(w[0]), float(w[1])
+
+
+def _check_fixed_mask(mask, shape):
+    """a mask on the fixed grid, checked on the host (no device work): a host array [X, Y, Z] of a bool or integer dtype, or a uint8 device tensor of prod(shape) elements"""
+    if mask is None:
+        return None
+    torch = _torch()
+    if isinstance(mask, torch.Tensor):
+        if mask.dtype != torch.uint8 or not mask.is_cuda or mask.numel() != int(np.prod(shape)):
+            raise ValueError(f"a device mask is a uint8 cuda tensor of prod(shape) = {int(np.prod(shape))} elements")
+        return mask
+    a = np.asarray(mask)
+    if a.dtype.kind not in "biu" or tuple(a.shape) != tuple(shape):
+        raise ValueError(f"mask is a bool or integer array on the fixed grid {tuple(shape)}, not {a.dtype} {tuple(a.shape)}")
+    return a
+
+
+def joint_hist_device(fixed_dev, fixed_vargs, mask_dev, moving_dev, moving_vargs, matrices, bins, window, moving_window):
+    """unet_vol_joint_hist on uploaded volumes -> uint32 numpy [K, B, B] (fixed bin major) for matrices [K, 3, 4]; K beyond JOINT_HIST_MAX_K takes several launches"""
+    torch = _torch(); lib, ctx = _ctx()
+    Ms = np.ascontiguousarray(np.asarray(matrices, np.float64).reshape(-1, 3, 4))
+    K = len(Ms)
+    counts = torch.empty((K, bins, bins), dtype=torch.int32, device="cuda")
+    for k0 in range(0, K, JOINT_HIST_MAX_K):
+        part = np.ascontiguousarray(Ms[k0:k0 + JOINT_HIST_MAX_K])
+        ctx.check(lib.unet_vol_joint_hist(ctx.handle, fixed_dev.data_ptr(), *fixed_vargs, _ptr(mask_dev), moving_dev.data_ptr(), *moving_vargs, part.ctypes.data, len(part),
+                                          int(bins), window[0], window[1], moving_window[0], moving_window[1], counts[k0:].data_ptr(), _stream()), "vol_joint_hist")
+    return counts.cpu().numpy().view(np.uint32)
+
+
+def _world_matrices(transforms):
+    """None (the identity), one world transform or a sequence of them -> a list of 4 x 4"""
+    if transforms is None:
+        return [np.eye(4)]
+    if isinstance(transforms, (RigidTransform, Registration)) or (isinstance(transforms, np.ndarray) and transforms.ndim == 2):
+        return [_world_matrix(transforms)]
+    try:
+        ts = list(transforms)
+    except TypeError:
+        raise ValueError(f"transforms is None, a world transform or a sequence of them, not {transforms!r}") from None
+    if len(ts) and not isinstance(ts[0], (RigidTransform, Registration)) and np.ndim(ts[0]) == 1:          # (one matrix given as nested lists)
+        return [_world_matrix(transforms)]
+    if not ts:
+        raise ValueError("transforms is empty")
+    return [_world_matrix(t) for t in ts]
+
+
+def joint_histogram(fixed, moving, transforms=None, bins=32, window=REGISTER_WINDOW, moving_window=None, mask=None, fixed_affine=None, moving_affine=None, fixed_shape=None,
+                    moving_shape=None):
+    """The joint intensity histogram of two CTs under candidate world transforms, on the device -> uint32 [K, B, B], fixed bin major.  fixed, moving: as resample_volume
+    takes a volume -- a path, a NiftiVolume, an [X, Y, Z] array with fixed_affine= / moving_affine=, or a flat device tensor with the affine and fixed_shape= /
+    moving_shape= --; both must carry an orientation.  transforms: None (the identity), a RigidTransform, a 4 x 4 world matrix (fixed world -> moving world) or a
+    sequence of them; candidate c counts every fixed voxel whose moving coordinate inv(A_moving) @ T_c @ A_fixed (i, j, k) lies inside the moving volume, whose value and
+    trilinear moving sample are not NaN, and which mask (on the fixed grid; non-zero = take) admits, in cell (bin(fixed), bin(sample)): bin(v) = floor((v - lo) B / (hi -
+    lo)) clamped to [0, B - 1], window for the fixed and moving_window (default: the same) for the moving volume.  Every argument error is a ValueError before any device
+    work."""
+    B, wf = _check_bins(bins), _check_hist_window(window)
+    wm = wf if moving_window is None else _check_hist_window(moving_window, "moving_window")
+    f, m = _resample_source(fixed, None, fixed_affine, fixed_shape), _resample_source(moving, None, moving_affine, moving_shape)
+    Ms = [voxel_matrix(f.grid, m.grid, T) for T in _world_matrices(transforms)]
+    mk = _check_fixed_mask(mask, f.shape)
+    fd = f.tensor if f.tensor is not None else upload(f.vol)
+    md = m.tensor if m.tensor is not None else upload(m.vol)
+    mask_dev = None if mk is None else _mask_to_device(mk, f.shape)[0]
+    return joint_hist_device(fd, f.vargs, mask_dev, md, m.vargs, Ms, B, wf, wm)
+
+
+def mutual_information(hist, normalized=False):
+    """Host float64, from the integer counts alone.  hist [B, B] -> a float; [K, B, B] -> float64 [K].  p = h / sum h, p_f and p_m its row and column sums:
+    MI = sum p log(p / (p_f p_m)) over the non-zero cells (nats); normalized: (H_f + H_m) / H_fm, from 1 (independent) to 2 (one determines the other), and 1 when every
+    counted voxel fell into one cell (all three entropies are 0).  An empty histogram scores -inf."""
+    h = np.asarray(hist)
+    if h.ndim == 3:
+        return np.array([mutual_information(x, normalized) for x in h], np.float64)
+    if h.ndim != 2 or h.shape[0] != h.shape[1] or h.dtype.kind not in "iu" or (h.dtype.kind == "i" and (h < 0).any()):
+        raise ValueError(f"a joint histogram is a square array of non-negative integer counts [B, B] (or [K, B, B]), not {h.dtype} {h.shape}")
+    h = h.astype(np.float64)
+    n = float(h.sum())
+    if n == 0.0:
+        return float("-inf")
+    p = h / n
+    pf, pm = p.sum(axis=1), p.sum(axis=0)
+    nz = p > 0.0
+    if normalized:
+        hf, hm = -float((pf[pf > 0.0] * np.log(pf[pf > 0.0])).sum()), -float((pm[pm > 0.0] * np.log(pm[pm > 0.0])).sum())
+        hfm = -float((p[nz] * np.log(p[nz])).sum())
+        return (hf + hm) / hfm if hfm > 0.0 else 1.0
+    return float((p[nz] * np.log(p[nz] / np.outer(pf, pm)[nz])).sum())
+
+
+class RegistrationLevel:
+    """One level of the search: spacing (mm, sets the steps), grid (where the level's fixed volume lies), voxels (how many fixed voxels the level's mask admits: what
+    min_overlap is a share of) and evaluate: matrices float64 [K, 3, 4] (level voxel index -> moving voxel coordinate) -> counts uint32 [K, B, B]."""
+
+    def __init__(self, spacing, grid, voxels, evaluate):
+        self.spacing, self.grid, self.voxels, self.evaluate = float(spacing), grid, int(voxels), evaluate
+
+
+class Registration:
+    """What register_volumes returns.  transform: the RigidTransform found, fixed world -> moving world, about the centre of the fixed field of view; voxel_matrix:
+    inv(A_moving) @ T @ A_fixed [3, 4] on the two native grids; metric / metric_init: the metric at the result and at the start, both on the last level; overlap: the
+    share of the last level's voxels counted at the result; batches: 12-neighbour launches; evaluations: histograms in all; converged: False when max_batches ended the
+    search; history: one dict per level (spacing, shape, batches, evaluations, metric, params); seconds; fixed_grid, moving_grid."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def resample(self, moving, kind="volume", order=None, **kw):
+        """The moving scan (kind "volume"), or a mask ("mask") or a label volume ("labels") drawn on it, on the fixed grid: resample_volume / resample_mask /
+        resample_labels with the moving grid's affine replaced by inv(T) @ A_moving and grid= the fixed grid.  order and the other keywords are theirs (a device
+        tensor needs src_shape=)."""
+        fn = {"volume": resample_volume, "mask": resample_mask, "labels": resample_labels}.get(kind)
+        if fn is None:
+            raise ValueError(f"kind is 'volume', 'mask' or 'labels', not {kind!r}")
+        for k in ("spacing", "shape", "like", "grid", "pixdim", "affine"):
+            if k in kw:
+                raise ValueError(f"Registration.resample sets {k}= itself: the target is the fixed grid, the source affine inv(T) @ A_moving")
+        if order is not None:
+            kw["order"] = order
+        return fn(moving, grid=self.fixed_grid, affine=np.linalg.inv(self.transform.matrix) @ self.moving_grid.affine, **kw)
+
+    def __repr__(self):
+        return f"Registration({self.transform!r}, metric={self.metric:.4f} from {self.metric_init:.4f}, overlap={self.overlap:.3f}, batches={self.batches}, converged={self.converged})"
+
+
+def _grid_centre(g):
+    """the world position of the centre of a grid's field of view"""
+    return (g.affine @ np.array([(g.shape[0] - 1) / 2.0, (g.shape[1] - 1) / 2.0, (g.shape[2] - 1) / 2.0, 1.0]))[:3]
+
+
+def _check_register_args(levels_mm=REGISTER_LEVELS_MM, bins=32, window=REGISTER_WINDOW, moving_window=None, init="geometry", min_overlap=0.25,
+                         max_batches=REGISTER_MAX_BATCHES, metric="mi"):
+    try:
+        lv = tuple(float(v) for v in levels_mm)
+    except (TypeError, ValueError):
+        lv = ()
+    if not lv or not all(np.isfinite(v) and v > 0 for v in lv) or any(b >= a for a, b in zip(lv, lv[1:])):
+        raise ValueError(f"levels_mm is a strictly descending sequence of positive spacings in mm, not {levels_mm!r}")
+    B, wf = _check_bins(bins), _check_hist_window(window)
+    wm = wf if moving_window is None else _check_hist_window(moving_window, "moving_window")
+    if not (isinstance(init, RigidTransform) or (isinstance(init, str) and init in ("geometry", "identity"))):
+        raise ValueError(f"init is 'geometry', 'identity' or a RigidTransform, not {init!r}")
+    if isinstance(min_overlap, (bool, str)) or not isinstance(min_overlap, (int, float, np.integer, np.floating)) or not 0.0 < float(min_overlap) <= 1.0:
+        raise ValueError(f"min_overlap is a share in (0, 1], not {min_overlap!r}")
+    if isinstance(max_batches, bool) or not isinstance(max_batches, (int, np.integer)) or int(max_batches) < 1:
+        raise ValueError(f"max_batches is a positive integer, not {max_batches!r}")
+    if not isinstance(metric, str) or metric not in REGISTER_METRICS:
+        raise ValueError(f"metric is one of {list(REGISTER_METRICS)}, not {metric!r}")
+    return lv, B, wf, wm
+
+
+def registration_level_grids(fixed_grid, levels_mm=REGISTER_LEVELS_MM):
+    """Host arithmetic: per level (spacing, Grid, M): the isotropic grid of that spacing over the fixed field of view (resample_target(spacing=)) with the matrix that
+    resamples the fixed volume onto it, or (spacing, fixed_grid, None) -- the fixed volume itself -- for a level whose spacing does not exceed the fixed volume's
+    smallest: resampling would coarsen no axis."""
+    g = _need_oriented(fixed_grid, "the fixed grid")
+    out = []
+    for L in levels_mm:
+        if L <= min(g.pixdim):
+            out.append((float(L), g, None))
+        else:
+            target, M = resample_target(g, spacing=(L, L, L))
+            out.append((float(L), target, M))
+    return out
+
+
+def initial_transform(fixed_grid, moving_grid, init="geometry"):
+    """-> the RigidTransform a search starts from, about the centre of the fixed field of view.  "geometry": the translation that puts the centre of the fixed field of
+    view onto the centre of the moving one, no rotation; "identity": the two world frames as they are; a RigidTransform: that motion, re-expressed about the centre."""
+    c = _grid_centre(_need_oriented(fixed_grid, "the fixed grid"))
+    if isinstance(init, RigidTransform):
+        return RigidTransform.from_matrix(init.matrix, c)
+    if init == "identity":
+        return RigidTransform((0.0,) * 6, c)
+    t = _grid_centre(_need_oriented(moving_grid, "the moving grid")) - c
+    return RigidTransform((t[0], t[1], t[2], 0.0, 0.0, 0.0), c)
+
+
+def rigid_search(levels, fixed_grid, moving_grid, init="geometry", min_overlap=0.25, max_batches=REGISTER_MAX_BATCHES, metric="mi"):
+    """The deterministic pattern search of register_volumes over caller-supplied evaluators (levels: RegistrationLevels, coarse to fine) -> Registration.  No device
+    work of its own: register_volumes hands it unet_vol_joint_hist, the tests the numpy oracle -- the same loop, the same counts, the same transform.
+    Per level the six parameters (about the centre of the fixed field of view) start from the previous level's result with steps of 2 x spacing mm for tx, ty, tz and
+    the same number in degrees for rx, ry, rz.  A batch scores the 12 neighbours (+step, -step per parameter, in parameter order) with one call of evaluate; a
+    candidate that counts fewer than min_overlap x level.voxels voxels scores -inf.  The best neighbour (ties: the lowest index) is taken if it is strictly better than
+    the current point; otherwise all steps are halved.  The level ends when the translation step falls below 0.05 x spacing, the search when max_batches are spent."""
+    _check_register_args(init=init, min_overlap=min_overlap, max_batches=max_batches, metric=metric)
+    fg, mg = _need_oriented(fixed_grid, "the fixed grid"), _need_oriented(moving_grid, "the moving grid")
+    if not levels:
+        raise ValueError("no levels to search")
+    t0 = time.perf_counter()
+    start = initial_transform(fg, mg, init)
+    centre, params = start.centre, start.params.copy()
+    normalized = metric == "nmi"
+    inv_m = np.linalg.inv(mg.affine)
+
+    def score(level, plist):
+        Ms = np.stack([_check_matrix((inv_m @ RigidTransform(p, centre).matrix @ level.grid.affine)[:3]) for p in plist])
+        counts = np.asarray(level.evaluate(Ms))
+        if counts.shape[0] != len(plist) or counts.ndim != 3:
+            raise ValueError(f"evaluate returned {counts.shape} for {len(plist)} matrices")
+        n = counts.reshape(len(plist), -1).sum(axis=1, dtype=np.int64)
+        val = mutual_information(counts, normalized)
+        val[n < min_overlap * level.voxels] = -np.inf
+        return val, n
+
+    batches = evaluations = 0
+    converged, history = True, []
+    cur = -np.inf
+    for level in levels:
+        step = np.array([2.0 * level.spacing] * 3 + [np.deg2rad(2.0 * level.spacing)] * 3)
+        cur = float(score(level, [params])[0][0])
+        lb, le = 0, 1
+        while step[0] >= REGISTER_STOP * level.spacing:
+            if batches >= max_batches:
+                converged = False
+                break
+            cand = []
+            for q in range(6):
+                for sign in (1.0, -1.0):
+                    c = params.copy()
+                    c[q] += sign * step[q]
+                    cand.append(c)
+            val, _ = score(level, cand)
+            batches += 1; lb += 1; le += len(cand)
+            best = int(np.argmax(val))                               # (the first of equal maxima)
+            if val[best] > cur:
+                params, cur = cand[best], float(val[best])
+            else:
+                step = step * 0.5
+        evaluations += le
+        history.append(dict(spacing=level.spacing, shape=level.grid.shape, batches=lb, evaluations=le, metric=cur, params=params.copy()))
+        if not converged:
+            break
+    last = levels[len(history) - 1]
+    val0, _ = score(last, [start.params])
+    _, n_end = score(last, [params])
+    evaluations += 2
+    T = RigidTransform(params, centre)
+    return Registration(transform=T, voxel_matrix=voxel_matrix(fg, mg, T), metric=cur, metric_init=float(val0[0]), overlap=float(n_end[0]) / max(last.voxels, 1),
+                        batches=batches, evaluations=evaluations, converged=converged, history=history, seconds=time.perf_counter() - t0, fixed_grid=fg, moving_grid=mg,
+                        metric_name=metric)
+
+
+def register_volumes(fixed, moving, levels_mm=REGISTER_LEVELS_MM, bins=32, window=REGISTER_WINDOW, mask=None, init="geometry", min_overlap=0.25,
+                     max_batches=REGISTER_MAX_BATCHES, metric="mi", moving_window=None, fixed_affine=None, moving_affine=None, fixed_shape=None, moving_shape=None):
+    """Register a follow-up CT (moving) to its baseline (fixed) on the device -> Registration: the rigid transform, fixed world -> moving world, that maximises the mutual
+    information ("mi") or its normalised form ("nmi") of the joint histogram (joint_histogram: bins, window, moving_window, mask on the fixed grid).  fixed, moving: as
+    joint_histogram takes them; both must carry an orientation.
+    The search is rigid_search's and deterministic: the same inputs give the same transform on every run.  Per level of levels_mm (coarse to fine) the fixed volume is put
+    on an isotropic grid of that spacing over the same field of view with resample_volume (linear, float32) -- a level whose spacing does not exceed the fixed volume's
+    smallest uses the fixed volume itself --, the mask with resample_mask (nearest); the moving volume stays on its own grid.  init: "geometry" (the centres of the two
+    fields of view aligned), "identity" or a RigidTransform.  Registration.resample and change_between(transform=) apply the result.
+    Rigid only, hard bins, no gradients (section 4x).  Every argument error is a ValueError before any device work."""
+    lv, B, wf, wm = _check_register_args(levels_mm, bins, window, moving_window, init, min_overlap, max_batches, metric)
+    f, m = _resample_source(fixed, None, fixed_affine, fixed_shape), _resample_source(moving, None, moving_affine, moving_shape)
+    fg, mg = _need_oriented(f.grid, "the fixed volume's grid"), _need_oriented(m.grid, "the moving volume's grid")
+    mk = _check_fixed_mask(mask, f.shape)
+    grids = registration_level_grids(fg, lv)
+    for _, g, _ in grids:
+        _check_volume_dims(g.shape)
+    torch = _torch()
+    t0 = time.perf_counter()
+    fd = f.tensor if f.tensor is not None else upload(f.vol)
+    md = m.tensor if m.tensor is not None else upload(m.vol)
+    mask_dev = None if mk is None else _mask_to_device(mk, f.shape)[0]
+    levels = []
+    for L, g, M in grids:
+        if M is None:
+            ldev, lvargs, lmask = fd, f.vargs, mask_dev
+        else:
+            ldev = resample_linear_device(fd, f.vargs, M, 0, 0.0, g.shape, 16)
+            lvargs = (16,) + g.shape + (0, 1.0, 0.0)
+            lmask = None if mask_dev is None else resample_nearest_device(mask_dev, 1, f.shape, M, 0, 0, g.shape)
+        voxels = int(np.prod(g.shape)) if lmask is None else int(torch.count_nonzero(lmask).item())
+
+        def evaluate(Ms, ldev=ldev, lvargs=lvargs, lmask=lmask):
+            return joint_hist_device(ldev, lvargs, lmask, md, m.vargs, Ms, B, wf, wm)
+
+        levels.append(RegistrationLevel(L, g, voxels, evaluate))
+    reg = rigid_search(levels, fg, mg, init, min_overlap, max_batches, metric)
+    torch.cuda.synchronize()
+    reg.seconds = time.perf_counter() - t0
+    return reg
