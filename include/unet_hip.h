@@ -173,6 +173,16 @@ int32_t unet_conv3x3_bnfold_fwd(unet_ctx*, const float* x, const float* bnp, con
 int32_t unet_conv3x3_bnfold_bwd_weights(unet_ctx*, const float* x, const float* bnp, const float* dy, const float* w, float* dw, float* db,
                                         double* bn_bwd_sums, void* gws, size_t gws_bytes, float* ws, int32_t n, int32_t h, int32_t wd,
                                         int32_t cin, int32_t cout, int32_t algo, void* stream);
+/* The data gradient of that conv with the BatchNorm's backward in its epilogue -- dz is never stored (what the conv3x3_dgrad_bn_bwd ops of the training programs launch in
+ * fp32):  dx = f(x) (K0 dz + K1 x + K2),  dz = conv3x3(dy, flipped / transposed w),  K0 = scale, K1 = -scale invstd k2, K2 = scale (mean invstd k2 - k1) with
+ * k1 = bn_bwd_sums[c] / count, k2 = bn_bwd_sums[cin + c] / count (bnp = scale, shift, mean, invstd: float[4*cin]; bn_bwd_sums = double[2*cin] as
+ * unet_conv3x3_bnfold_bwd_weights leaves them; count = pixels the statistics ran over, >= 1).  f = the derivative of what produced x: mask_mode UNET_MASK_NONE (1),
+ * _RELU (x > 0), _ELU, _ELU_DROP (mask_rate / mask_seed of that dropout).  x_channels = cin, or -- UNET_MASK_NONE only -- a multiple of 32 below it: channels from
+ * there on do not read x and leave as K0 dz + K2 (the skip half of a concat whose consumer adds K1 x); anything else is UNET_E_ARG.  wt_ws: as unet_conv3x3_bwd_data;
+ * coef: 3*cin floats of scratch.  UNET_E_SHAPE where unet_conv3x3_bnfold_supported() says no. */
+int32_t unet_conv3x3_bnfold_bwd_data(unet_ctx*, const float* dy, const float* w, const float* bnp, const double* bn_bwd_sums, double count, const float* x,
+                                     int32_t x_channels, int32_t mask_mode, float mask_rate, uint64_t mask_seed, float* dx, float* wt_ws, float* coef,
+                                     int32_t n, int32_t h, int32_t wd, int32_t cin, int32_t cout, int32_t algo, void* stream);
 /* dw[a,b,c,o] = sum x[n,i+a-1,j+b-1,c]*dy[n,i,j,o];  db[o] = sum dy.  dy already ReLU-masked.
  * ws: split-K scratch (unet_conv3x3_bwd_weights_ws_bytes). dw/db are OVERWRITTEN. */
 size_t unet_conv3x3_bwd_weights_ws_bytes(int32_t n, int32_t h, int32_t wd, int32_t cin, int32_t cout);

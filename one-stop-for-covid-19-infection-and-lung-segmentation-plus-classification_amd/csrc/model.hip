@@ -354,6 +354,28 @@ int32_t unet_conv3x3_bnfold_bwd_weights(unet_ctx* ctx, const float* x, const flo
   return k_wgrad_bn_fold_fix(ctx, dy, n, h, wd, cin, cout, bnp, bnp + cin, dw, db, ws + bn_fold_scratch_floats(cin, cout) + unet_conv3x3_w_ws_floats(cin, cout), s,
                              bn_bwd_sums ? w : nullptr, bn_bwd_sums ? bnp + 2 * cin : nullptr, bn_bwd_sums ? bnp + 3 * cin : nullptr, bn_bwd_sums);
 }
+// the data gradient of that conv with the BatchNorm backward in its epilogue, as the conv3x3_dgrad_bn_bwd:* ops of the programs below launch it in fp32: coefficients,
+// flipped weight image, one h2 launch (include/unet_hip.h)
+int32_t unet_conv3x3_bnfold_bwd_data(unet_ctx* ctx, const float* dy, const float* w, const float* bnp, const double* bn_bwd_sums, double count, const float* x, int32_t x_channels,
+                                     int32_t mask_mode, float mask_rate, uint64_t mask_seed, float* dx, float* wt_ws, float* coef, int32_t n, int32_t h, int32_t wd, int32_t cin,
+                                     int32_t cout, int32_t algo, void* stream) {
+  if (!ctx || !dy || !w || !bnp || !bn_bwd_sums || !x || !dx || !wt_ws || !coef || n < 1 || !(count >= 1) || mask_mode < MASK_NONE || mask_mode > MASK_ELU_DROP || !(mask_rate >= 0) ||
+      mask_rate >= 1)
+    UNET_FAIL(ctx, UNET_E_ARG, "conv3x3_bnfold_bwd_data: bad args");
+  if (!unet_conv3x3_bnfold_supported(algo, h, wd, cin, cout))
+    UNET_FAIL(ctx, UNET_E_SHAPE, "conv3x3_bnfold_bwd_data: no folded form for h=%d w=%d cin=%d cout=%d (unet_conv3x3_bnfold_supported)", h, wd, cin, cout);
+  // (above the limit the epilogue has no x: the derivative of x's producer cannot be applied there, so a limit goes with UNET_MASK_NONE only)
+  if (x_channels != cin && (x_channels < 32 || x_channels > cin || (x_channels % 32) || mask_mode != MASK_NONE))
+    UNET_FAIL(ctx, UNET_E_ARG, "conv3x3_bnfold_bwd_data: x_channels %d (cin = %d, or a multiple of 32 below it with UNET_MASK_NONE)", x_channels, cin);
+  static const int modes[4] = {MASK_BN_BWD, MASK_BN_BWD_RELU, MASK_BN_BWD_ELU, MASK_BN_BWD_ELU_DROP};
+  hipStream_t s = as_stream(stream);
+  int32_t r = k_bn_bwd_coef(ctx, bnp, bn_bwd_sums, count, coef, cin, s);
+  if (!r) r = k_h2_weights(ctx, w, wt_ws, cin, cout, 1, s);
+  const bool drop = mask_mode == MASK_ELU_DROP;
+  if (!r) r = k_conv3x3_h2_fwd(ctx, dy, wt_ws, coef, x, modes[mask_mode], dx, n, h, wd, cout, cin, ACT_NONE, drop ? mask_rate : 0.0f, drop ? mask_seed : 0, s, x_channels < cin ? x_channels : 1 << 30);
+  ctx->k_slices_ok = 0;          // (one-shot, as unet_conv3x3_bwd_data)
+  return r;
+}
 
 size_t unet_conv3x3_bwd_weights_ws_bytes(int32_t n, int32_t h, int32_t wd, int32_t cin, int32_t cout) {
   if (cin == 1 && (cout % 4) == 0 && 256 % (cout / 4) == 0 && cout <= 256) return c1_wgrad_ws_bytes(cout);

@@ -37,6 +37,10 @@ class Ops:
         torch.cuda.synchronize()
 
 
+def cu_count():
+    return torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count          # (what the context reads: hipDeviceProp_t::multiProcessorCount)
+
+
 def relerr(a, b):
     a = np.asarray(a, np.float64); b = np.asarray(b, np.float64)
     return float(np.linalg.norm(a - b) / (np.linalg.norm(b) + 1e-30))

@@ -18,6 +18,7 @@ def test_every_binding_has_the_declared_argument_count():
     assert not wrong, f"(declared, bound) argument counts differ: {wrong}"
     assert "unet_gather_samples" in seen and "unet_augment_samples" in seen
     assert "unet_conv3x3_fwd_ld" in seen and "unet_conv3x3_fwd_ld" in _lib._PROTOS
+    assert "unet_conv3x3_bnfold_bwd_data" in seen and "unet_conv3x3_bnfold_bwd_data" in _lib._PROTOS
 
 
 def test_every_bf16_entry_is_called_by_a_gpu_test():

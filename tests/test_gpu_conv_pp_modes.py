@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_util import cu_count
 from oracle import unet_oracle as O
 from test_gpu_conv_pp import PPOps, T64
 
@@ -37,10 +38,6 @@ def pp():
 @pytest.fixture(scope="module")
 def h2():
     return PPOps(0)
-
-
-def cu_count():
-    return torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count          # (what the context reads: hipDeviceProp_t::multiProcessorCount)
 
 
 def pp_tile_walk(cu, n, h, w):

@@ -716,7 +716,7 @@ def test_encoder_tail_backward_without_a_statistics_pass(ops, shape, rate, seed)
     assert relerr(got.cpu().numpy(), want.cpu().numpy()) < 2e-5
 
 
-@pytest.mark.parametrize("shape", [(2, 16, 64, 64, 32), (1, 9, 70, 128, 64), (3, 2, 33, 32, 32), (2, 12, 40, 512, 256), (1, 64, 64, 16, 128), (2, 5, 1, 32, 64)])
+@pytest.mark.parametrize("shape", [(2, 16, 64, 64, 32), (1, 9, 70, 128, 64), (3, 2, 33, 32, 32), (2, 12, 40, 512, 256), (1, 64, 64, 16, 128), (2, 5, 1, 32, 64), (5, 6, 7, 32, 32)])
 def test_conv3x3_bnfold_matches_bn_apply_then_conv(ops, shape):
     """decoder BN -> Conv (T1:888-889): the BatchNorm folded into the conv (scaled weights + a bias per border class, weight gradient corrected
     from db and the border sums of dy) against the fp64 oracle of conv3x3(zero-padded BN(x)), forward and weight gradient -- odd sizes, two-row and
