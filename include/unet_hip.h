@@ -536,13 +536,16 @@ int32_t unet_dense_bwd(unet_ctx*, const float* x, const float* w, const float* d
                        int32_t n, void* stream);
 /* Replaces: Dense(1, sigmoid) T2:776 fused with loss='binary_crossentropy' (T2:829, optional class weights T2:801-803, 835) and the
  * sums of the f1 metric T2:688-703.  p[b] = sigmoid(h[b,:].w + bias).  If y_true != NULL, sums (double[4], accumulated) +=
- * (sum cw(t)*bce, sum round(t*p), sum round(t), sum round(p)). */
+ * (sum cw(t)*bce, sum round(t*p), sum round(t), sum round(p)); round = to nearest, ties to even; bce clips p to [1e-7, 1 - 1e-7] (fp32).
+ * One workgroup; the forward takes any n that is a multiple of 4 (n >= 4). */
 int32_t unet_cls_head_fwd(unet_ctx*, const float* h, const float* w, const float* bias, float* p, const float* y_true, float class_w0,
                           float class_w1, double* sums, int32_t batch, int32_t n, void* stream);
 /* out float[2] = (loss = sums[0]/count, f1) from (globally reduced) sums; count = GLOBAL batch size */
 int32_t unet_cls_loss_finalize(unet_ctx*, const double* sums, double count, float* out, void* stream);
 /* backward of loss + sigmoid + Dense(n->1) + the Dropout/ReLU of the hidden layer h = dropout(relu(a)):
- * dw[n], db[1]; dh[batch,n] = dL/da (ready for unet_dense_bwd); dbias_prev[n] = sum_b dh[b,:] (bias gradient of the hidden Dense). */
+ * dw[n], db[1]; dh[batch,n] = dL/da (ready for unet_dense_bwd); dbias_prev[n] = sum_b dh[b,:] (bias gradient of the hidden Dense).
+ * dz_b = cw(t_b) (p_b - t_b) / count where p_b lies inside the clip range of the loss, exactly 0 outside it.  Unlike the forward, the backward needs n to be a
+ * power of two in 4..32 (as unet_dense_fwd / _bwd); any other n: UNET_E_ARG, nothing is launched. */
 int32_t unet_cls_head_bwd(unet_ctx*, const float* h, const float* w, const float* p, const float* y_true, float class_w0, float class_w1,
                           double count, float drop_rate, float* dh, float* dw, float* db, float* dbias_prev, int32_t batch, int32_t n,
                           void* stream);
