@@ -87,10 +87,18 @@ int32_t unet_ctx_set_profiling(unet_ctx* ctx, int32_t on);
  *                          kernels_conv_pp.hip: one 512-thread workgroup per CU, the layer's split weight image resident in LDS, one half's MFMAs over the other half's
  *                          loads, split and stores.  Same arithmetic as the h2 kernels (one block exponent per 8 x 32 pixel tile); taken by launches of at least four tiles per
  *                          half-workgroup (2048 tiles: 512 x 512 from batch 2 up).  0 = conv_h2_kernel everywhere; 2 = also smaller launches (tests)
+ *   ENC_TAIL_DGRAD (14; default 1) fp32 U-Net with SKIP_RAW, ENC_BN_FUSED and the folded decoder BatchNorm backward: the data gradient of a decoder block's first conv is split by
+ *                          output-channel range.  conv3x3_dgrad_bn_bwd:c<10-k>a writes only the upsampled half of the concat's gradient; the skip half runs where the encoder
+ *                          tail's backward ran (the op keeps the name bn_pool_bwd_apply:bn<k>) and finishes pool backward + K1 y + BatchNorm backward + ReLU mask on the tile it
+ *                          holds -- the skip half of the concat's gradient is never written or read (one full-resolution tensor of the level's encoder width less per level and
+ *                          step; a gradient tap of bn<k> is UNET_E_STATE there).  Taken by the levels whose undivided launch runs the 8-row tiles
+ *                          (the split then computes bit for bit what the two launches computed) and whose two half launches each fill the resident workgroup slots at least
+ *                          twice (at 512 x 512 x 16 on 256 CUs: the 512 and 256 pixel levels); 0 = the two launches of before everywhere;
+ *                          2 = every level, whatever its size (tests)
  *   (options 11 / 12 of ABI v13-v14 -- WGRAD_ATOMIC, C1A_RECOMPUTE -- were same-box A/B losers and left the library in v15; DESIGN.md keeps the measurements)
  */
 enum { UNET_OPT_RELU_BITS = 1, UNET_OPT_BN_FOLD = 2, UNET_OPT_ENC_BN_FUSED = 3, UNET_OPT_BN_CONCAT_ANALYTIC = 4, UNET_OPT_BN_FUSE_STATS = 5, UNET_OPT_DETERMINISTIC = 6,
-       UNET_OPT_HEAD_FUSED = 7, UNET_OPT_SKIP_RAW = 8, UNET_OPT_POOL_SUMS_FUSED = 9, UNET_OPT_HEAD_BWD_FUSED = 10, UNET_OPT_CONV_PP = 13 };
+       UNET_OPT_HEAD_FUSED = 7, UNET_OPT_SKIP_RAW = 8, UNET_OPT_POOL_SUMS_FUSED = 9, UNET_OPT_HEAD_BWD_FUSED = 10, UNET_OPT_CONV_PP = 13, UNET_OPT_ENC_TAIL_DGRAD = 14 };
 int32_t unet_ctx_set_option(unet_ctx* ctx, int32_t option, int32_t value);
 int32_t unet_ctx_get_option(unet_ctx* ctx, int32_t option);   /* >= 0: the value; < 0: error */
 
@@ -183,6 +191,21 @@ int32_t unet_conv3x3_bnfold_bwd_weights(unet_ctx*, const float* x, const float* 
 int32_t unet_conv3x3_bnfold_bwd_data(unet_ctx*, const float* dy, const float* w, const float* bnp, const double* bn_bwd_sums, double count, const float* x,
                                      int32_t x_channels, int32_t mask_mode, float mask_rate, uint64_t mask_seed, float* dx, float* wt_ws, float* coef,
                                      int32_t n, int32_t h, int32_t wd, int32_t cin, int32_t cout, int32_t algo, void* stream);
+/* The skip half of that data gradient with the encoder tail's backward in its epilogue (added without an ABI bump; what the bn_pool_bwd_apply ops of the training programs
+ * launch where UNET_OPT_ENC_TAIL_DGRAD applies).  The conv has 2 c input channels -- the concat [upsampled | skip] -- and c output channels: dy [n,h,wd,c], w [3][3][2c][c],
+ * bnp / bn_bwd_sums / count of the decoder BatchNorm as above (float[8 c], double[4 c]).  Only the output channels [c, 2 c) are computed, and instead of g = K0 dz + K2 the call
+ * writes the gradient of the encoder conv output x behind BatchNorm -> max-pool 2x2 + dropout, exactly as unet_conv3x3_bnfold_bwd_data (x_channels = c) followed by
+ * unet_bn_maxpool_bwd_apply (g_skip = that skip half) evaluates it, operation for operation:
+ *   y = scale_e x + shift_e;  t = k1s y + g + (this pixel is the FIRST maximum of y over its 2x2 window ? dy_pooled keep : 0);
+ *   dx = x > 0 ? scale_e (t - k1 - (x - mean_e) invstd_e k2) : 0,   k1 = enc_sums[j] / enc_count, k2 = enc_sums[c + j] / enc_count
+ * x: the skip channels of the raw concat (pointer to channel c of pixel 0, pixel stride ldx >= c, ldx % 4 == 0); enc_bnp = scale, shift, mean, invstd of the encoder BatchNorm
+ * (float[4 c]); enc_sums double[2 c] = its reduced backward sums; skip_k1 float[c] = the decoder's K1 of the skip channels (coef + 3 c of a unet_conv3x3_bnfold_bwd_data call
+ * on the same sums) or NULL for k1s = 0; dy_pooled [n,h/2,wd/2,c]; rate / seed: the dropout behind the pool (keep = 0 or 1 / (1 - rate), unet_bn_apply_maxpool_dropout_fwd's
+ * stream); dx [n,h,wd,c] dense.  wt_ws: unet_conv3x3_w_ws_floats(2 c, c) floats; coef: 6 c floats of scratch.  h and wd even, c a multiple of 32, and
+ * unet_conv3x3_bnfold_supported(algo, h, wd, 2 c, c); else UNET_E_SHAPE. */
+int32_t unet_conv3x3_bnfold_bwd_data_enc_tail(unet_ctx*, const float* dy, const float* w, const float* bnp, const double* bn_bwd_sums, double count, const float* x, int32_t ldx,
+                                              const float* enc_bnp, const double* enc_sums, double enc_count, const float* skip_k1, const float* dy_pooled, float rate,
+                                              uint64_t seed, float* dx, float* wt_ws, float* coef, int32_t n, int32_t h, int32_t wd, int32_t c, int32_t algo, void* stream);
 /* dw[a,b,c,o] = sum x[n,i+a-1,j+b-1,c]*dy[n,i,j,o];  db[o] = sum dy.  dy already ReLU-masked.
  * ws: split-K scratch (unet_conv3x3_bwd_weights_ws_bytes). dw/db are OVERWRITTEN. */
 size_t unet_conv3x3_bwd_weights_ws_bytes(int32_t n, int32_t h, int32_t wd, int32_t cin, int32_t cout);

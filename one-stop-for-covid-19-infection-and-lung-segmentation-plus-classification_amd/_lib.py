@@ -16,7 +16,7 @@ COMM_HANDLE_BYTES, COMM_MAX_WORLD, COMM_MAX_DOUBLES = 64, 8, 2048          # inc
 
 ALGO_AUTO, ALGO_NAIVE, ALGO_MFMA = 0, 1, 2          # fp16-split h2 kernels where the shape allows / VALU kernels / strict fp32 MFMA kernels
 # unet_ctx_set_option (include/unet_hip.h UNET_OPT_*)
-OPTIONS = {"relu_bits": 1, "bn_fold": 2, "enc_bn_fused": 3, "bn_concat_analytic": 4, "bn_fuse_stats": 5, "deterministic": 6, "head_fused": 7, "skip_raw": 8, "pool_sums_fused": 9, "head_bwd_fused": 10, "conv_pp": 13}
+OPTIONS = {"relu_bits": 1, "bn_fold": 2, "enc_bn_fused": 3, "bn_concat_analytic": 4, "bn_fuse_stats": 5, "deterministic": 6, "head_fused": 7, "skip_raw": 8, "pool_sums_fused": 9, "head_bwd_fused": 10, "conv_pp": 13, "enc_tail_dgrad": 14}
 ARCH_UNET, ARCH_UNETPP, ARCH_CLASSIFIER = 0, 1, 2
 # include/unet_hip.h UNET_LOSS_*: the segmentation losses a U-Net / U-Net++ trains on (unet_model_set_loss), by their Keras names
 LOSSES = {"bce_dice_loss": 0, "binary_crossentropy": 1, "dice_loss": 2, "tversky_loss": 3, "weighted_bce_dice_loss": 4}
@@ -99,6 +99,7 @@ _PROTOS = {
     "unet_conv3x3_bnfold_fwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
     "unet_conv3x3_bnfold_bwd_weights": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, i32, i32, i32, i32, i32, i32, vp]),
     "unet_conv3x3_bnfold_bwd_data": (i32, [vp, vp, vp, vp, vp, f64, vp, i32, i32, f32, u64, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "unet_conv3x3_bnfold_bwd_data_enc_tail": (i32, [vp, vp, vp, vp, vp, f64, vp, i32, vp, vp, f64, vp, vp, f32, u64, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "unet_bn_stats_concat": (i32, [vp, vp, i32, vp, f64, vp, vp, vp, i64, i32, i32, vp]),
     "unet_bn_stats_concat_bf16": (i32, [vp, vp, i32, vp, f64, vp, vp, vp, i64, i32, i32, vp]),
     "unet_bn_finalize_train": (i32, [vp, vp, f64, vp, vp, vp, vp, vp, i32, vp]),

@@ -40,6 +40,7 @@ struct unet_ctx {
   int opt_skip_raw = 1;             // fp32 U-Net: an encoder block's second conv writes straight into the skip half of its concat; the encoder BatchNorm is composed into the folded decoder one
   int opt_head_fused = 1;           // the 1x1 sigmoid head + loss sums + the head's weight-gradient sums in the epilogue of the last conv3x3 (fp32 h2 kernels)
   int opt_head_bwd_fused = 1;       // the head's backward as an 8-byte-per-pixel {dz, mask} stream that the last conv's two gradients expand (no fp32 dY tensor)
+  int opt_enc_tail_dgrad = 1;       // fp32 U-Net: the skip half of a folded decoder BatchNorm's data gradient deferred into the encoder tail's backward (no gskip tensor); 2: also levels whose half launches do not fill the device (tests)
   int opt_conv_pp = 1;              // shallow conv3x3 forward / data-gradient launches on the persistent two-half schedule (kernels_conv_pp.hip)
   int opt_deterministic = 0;        // fixed-order reductions everywhere (no floating-point atomics): bit-identical reruns
   double* bn_slots = nullptr;       // device, UNET_BN_SLOTS_DET x UNET_BN_SLOT_DOUBLES (16 MB), all zero between launches
@@ -270,6 +271,16 @@ __device__ __forceinline__ float4 keep_scale(long long quad_idx, float rate, uin
                      u32_to_unit(r.z) >= rate ? s : 0.f, u32_to_unit(r.w) >= rate ? s : 0.f);
 }
 
+// arg-max of a 2 x 2 pooling window in the order (row 0: left, right; row 1: left, right): the FIRST maximum wins -- every kernel that routes a pooled gradient shares this
+// tie rule (kernels_pointwise.hip; the encoder-tail epilogue of kernels_conv_h2.hip)
+__device__ __forceinline__ int argmax4(float a, float b, float c, float d) {
+  int k = 0; float m = a;
+  if (b > m) { m = b; k = 1; }
+  if (c > m) { m = c; k = 2; }
+  if (d > m) { m = d; k = 3; }
+  return k;
+}
+
 // activations of the conv epilogues (Keras 'relu' T1:859 / 'elu' task1_unet_plus_plus.py:876)
 enum { ACT_NONE = 0, ACT_RELU = 1, ACT_ELU = 2 };
 __device__ __forceinline__ float apply_act(float v, int act) {
@@ -354,6 +365,14 @@ int32_t k_slot_fold(unet_ctx*, double* sums, int count, hipStream_t s, bool xs =
 // the pooled sums a MASK_POOL_SUMS launch left in the slot copies -> sums[2 c] (+=), + the closed-form skip term (unet_bn_bwd_skip_term) + the BatchNorm's parameter gradients: one launch
 int32_t k_enc_tail_finish(unet_ctx*, double* sums, const double* dec_sum_dyxhat, const float* dec_invstd, const float* dec_gamma, const float* gamma, float* dgamma, float* dbeta, int c,
                           double frac, hipStream_t s);
+// The folded decoder BatchNorm's data gradient split by output-channel range: conv c<10-k>a has C output and 2 C input channels, dy [n,h,wd,C], coef [3][2 C]
+// (k_bn_bwd_coef), wimg its data-gradient image.  _up: channels [0, C) of dx = K0 dz + K1 x + K2, x and dx the concat's tensors (pixel stride 2 C).  _enc_tail: channels
+// [C, 2 C) finished into the encoder tail's dx [n,h,wd,C] (dense): x = the raw encoder conv output (the concat's skip slice, pixel stride ldx), enc_bnp / enc_sums / count
+// / dy_pooled / rate / seed as k_bn_maxpool_bwd_apply_k1 takes them, skip_k1 [C] or null.  force: also shapes whose half launches leave resident slots empty (tests)
+bool h2_enc_tail_dgrad_selected(const unet_ctx* ctx, int algo, int n, int h, int wd, int C, bool force);
+int32_t k_conv3x3_h2_dgrad_bn_bwd_up(unet_ctx*, const float* dy, const void* wimg, const float* coef, const float* x, float* dx, int n, int h, int wd, int C, hipStream_t s);
+int32_t k_conv3x3_h2_dgrad_enc_tail(unet_ctx*, const float* dy, const void* wimg, const float* coef, const float* x, int ldx, const float* enc_bnp, const double* enc_sums, double count,
+                                    const float* skip_k1, const float* dy_pooled, float* dx, int n, int h, int wd, int C, float rate, uint64_t seed, hipStream_t s);
 bool h2_pool_sums_selected(const unet_ctx* ctx, int algo, int wd, int K, int M);
 int32_t k_conv3x3_h2_dgrad_pool_sums(unet_ctx*, const float* dy, const void* wimg, const float* pooled, const float* gamma, const float* beta, float rate, float* dx, double* sums,
                                      int n, int h, int wd, int K, int M, hipStream_t s);
@@ -364,7 +383,8 @@ int32_t k_bn_finalize_compose(unet_ctx*, int training, const double* sums, doubl
 int32_t k_loss_finalize(unet_ctx*, const double* loss_sums, double count, float* loss_out, float* loss_out2, hipStream_t s, unet_loss_sel ls = {});
 int32_t k_cls_loss_finalize(unet_ctx*, const double* sums, double count, float* out, float* out2, hipStream_t s);
 int32_t k_bn_compose(unet_ctx*, const float* bnp_dec, const float* bnp_enc, float* comp, int c, hipStream_t s);
-struct h2_head_args { const float* w = nullptr; const float* b = nullptr; float* p = nullptr; const float* t = nullptr; double* slots = nullptr; float aux = 0.0f; const float* wm = nullptr; };          // (MASK_POOL_SUMS: w = gamma, b = beta, aux = dropout rate)
+struct h2_head_args { const float* w = nullptr; const float* b = nullptr; float* p = nullptr; const float* t = nullptr; double* slots = nullptr; float aux = 0.0f; const float* wm = nullptr; double inv_count = 0.0; };          // (MASK_POOL_SUMS: w = gamma, b = beta, aux = dropout rate; the encoder-tail epilogue, EPI 5: w = the encoder
+                                                                      //  BatchNorm's [scale | shift | mean | invstd], b = dy_pooled, wm = the skip channels' K1 or null, slots = its reduced backward sums, inv_count = 1 / count)
 bool h2_conv3x3_head_selected(const unet_ctx* ctx, int algo, int wd, int K, int M);
 int32_t k_conv3x3_h2_head_fwd(unet_ctx*, const float* x, const void* wimg, const float* bias, float* y, const float* wh, const float* bh, float* p, const float* t,
                               int n, int h, int wd, int K, hipStream_t s, const float* wm = nullptr);          // wm: weighted_bce_dice_loss's map (EPI 4: {w l, ..| w a, ..., w}, 104 sums)

@@ -165,12 +165,21 @@ __global__ __launch_bounds__(256, WPS) void conv_h2_kernel(const float* __restri
                                                            const float* __restrict__ mask, float* __restrict__ y, int ldy, int N, int H, int W, int K, int M, int act,
                                                            int mask_mode, float rate, unsigned long long seed, int tiles_x, int tiles_y, int groups,
                                                            int total_blocks, double* __restrict__ stats, int stats_c, unsigned long long* __restrict__ signs,
-                                                           int mask_climit, h2_head_args hd, int img_nb, int xs, int kcps, long long y_split) {
+                                                           int mask_climit, h2_head_args hd, int img_nb, int xs, int kcps, long long y_split, int g0, int gtot, int ldm, int c_off) {
+  // g0 / gtot: the launch runs the channel groups [g0, g0 + groups) of an image of gtot groups (all of them: g0 = 0, groups = gtot); coefficient rows, sign bits and the
+  // weight slabs keep the image's absolute channel numbers.  ldm: pixel stride of `mask` (= ldy unless the mask tensor and the output are laid out differently);
+  // c_off: subtracted from the absolute channel where `mask` and `y` are addressed (EPI 5: both are the skip half's own tensors)
   constexpr bool HEAD = EPI == 1 || EPI == 4, WHEAD = EPI == 4, POOLS = EPI == 2;          // EPI 4: HEAD for weighted_bce_dice_loss (its weight map hd.wm weighs the BCE terms)          // EPI: 0 the general epilogue, 1 + the 1x1 sigmoid head (below), 2 + the pooled-path sums of an encoder tail (MASK_POOL_SUMS)
   // EPI 3 (VDY): the general epilogue behind a VIRTUAL input -- the gradient of the last conv3x3's output, dy[p][c] = dz_p w_c [y_pc > 0] (T1:911-913 backwards), staged from
   // the 8-byte-per-pixel stream {dz_p, 32 mask bits} of head_dzm_kernel (x = that stream, ldx = 2): one value is scaled and split per staged piece, the mask bits pick
   // the channels it goes to; w_c is a per-contraction-channel factor of the weight image (h2_prep::cs).  K = 32.
   constexpr bool VDY = EPI == 3;
+  // EPI 5 (ETAIL): the skip half of a folded decoder BatchNorm's data gradient finished on the tile into the encoder tail's dx: gs = K0 dz + K2 is never
+  // stored -- max-pool backward (dy_pooled = hd.b, the 2 x 2 window = this lane's two rows and lane ^ 1), the K1 y term (hd.wm), the encoder BatchNorm's backward
+  // (hd.w = its [scale | shift | mean | invstd], hd.slots = its reduced sums, hd.inv_count) and the ReLU mask of x (= `mask`, the raw conv output) follow in registers
+  constexpr bool ETAIL = EPI == 5;
+  static_assert(!ETAIL || (MODE == 0 && RW == 2 && !GEN && !SPLITK), "the encoder-tail epilogue rides on the 8-row conv3x3 data-gradient launches");
+  if (ETAIL) { mask_mode = MASK_BN_BWD; act = ACT_NONE; stats = nullptr; signs = nullptr; }
   static_assert(!VDY || (MODE == 0 && NB == 1 && RW == 2 && !GEN), "the virtual head gradient feeds the 32-channel data-gradient launch");
   static_assert(!HEAD || (MODE == 0 && NB == 1 && RW == 2 && !GEN), "the fused head rides on the 32-channel forward kernel");
   static_assert(!POOLS || (MODE == 0 && !GEN), "the pooled sums ride on a plain conv3x3 data-gradient launch");
@@ -207,7 +216,7 @@ __global__ __launch_bounds__(256, WPS) void conv_h2_kernel(const float* __restri
   const int per = gridDim.x >> 3;
   const int wi = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
   if (wi >= total_blocks) return;
-  const int g = wi % groups; int t = wi / groups;
+  const int g = g0 + wi % groups; int t = wi / groups;
   const int tx = t % tiles_x; t /= tiles_x;
   const int ty = t % tiles_y; const int n = t / tiles_y;
   const int x0 = tx * 32, y0 = ty * TH;
@@ -227,7 +236,7 @@ __global__ __launch_bounds__(256, WPS) void conv_h2_kernel(const float* __restri
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
 
   const __amdgpu_buffer_rsrc_t rs_x = make_rsrc(x + (long long)n * HI * WI * ldx, (long long)HI * WI * ldx * 4);
-  const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<unet_bf16*>(wimg), 0, (int)((long long)groups * nchunks * W_BYTES), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<unet_bf16*>(wimg), 0, (int)((long long)gtot * nchunks * W_BYTES), 0x00020000);
   int poff[PL];
 #pragma unroll
   for (int k = 0; k < PL; ++k) {
@@ -344,7 +353,7 @@ __global__ __launch_bounds__(256, WPS) void conv_h2_kernel(const float* __restri
       const float gm = ok ? hd.w[ch] : 0.f;
       s_bias[NB * 32 + tid] = gm != 0.f ? 1.0f / gm : 0.f; s_bias[2 * NB * 32 + tid] = ok ? hd.b[ch] : 0.f;
     } else {
-    s_bias[NB * 32 + tid] = HEAD ? hd.w[tid] : coef ? bias[M + ch] : 0.f;          // (HEAD: row 1 = the 32 weights of the 1x1 head, row 2 [0] = its bias)
+    s_bias[NB * 32 + tid] = HEAD ? hd.w[tid] : ETAIL ? (hd.wm && ok ? hd.wm[ch - c_off] : 0.f) : coef ? bias[M + ch] : 0.f;          // (ETAIL: row 1 = the K1 of the skip channels, or 0; HEAD: row 1 = the 32 weights of the 1x1 head, row 2 [0] = its bias)
     s_bias[2 * NB * 32 + tid] = HEAD ? hd.b[0] : coef ? bias[2 * M + ch] : 0.f;
     }
   }
@@ -460,10 +469,32 @@ __global__ __launch_bounds__(256, WPS) void conv_h2_kernel(const float* __restri
           const int pxj = x0 + j * 8 + (lane >> 3);
           // (mask_climit: output-channel blocks from there on do not read `mask` -- a folded-BatchNorm gradient whose K1 x term is added by the consumer)
           const bool ok = mb0 + (lane & 7) * 4 < M && mb0 < mask_climit && py < H && pxj < W;
-          const long long o = (((long long)n * H + py) * W + pxj) * ldy + mb0 + (lane & 7) * 4;
+          const long long o = (((long long)n * H + py) * W + pxj) * ldm + (mb0 - c_off) + (lane & 7) * 4;
           mpre[nb][r][j] = ok ? *reinterpret_cast<const float4*>(mask + o) : make_float4(0.f, 0.f, 0.f, 0.f);
         }
       }
+    }
+  }
+  // ETAIL: the pooled gradient of this wave's pooled row (16 pixels x the block's 32 channels, line layout: two 16-B pieces per lane) and, in the first NB * 32 threads,
+  // the encoder BatchNorm's six per-channel operands travel with the x prefetch; the rows go to LDS behind the barrier below (the slab is dead there: no LDS of their own,
+  // which would cost the 32-channel instance its fourth workgroup per CU)
+  float4 dpre[ETAIL ? NB : 1][2];
+  float eco[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if constexpr (ETAIL) {
+    const int Ho = H >> 1, Wo = W >> 1, Cd = M - c_off, pr = (y0 + wave * RW) >> 1;
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+      for (int jj = 0; jj < 2; ++jj) {
+        const int ppx = (x0 >> 1) + jj * 8 + (lane >> 3), ca = (g * NB + nb) * 32 + (lane & 7) * 4;
+        const bool ok = ca < M && pr < Ho && ppx < Wo;
+        dpre[nb][jj] = ok ? *reinterpret_cast<const float4*>(hd.b + (((long long)n * Ho + pr) * Wo + ppx) * Cd + (ca - c_off)) : make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+    if (tid < NB * 32 && g * NB * 32 + tid < M) {
+      const int cr = g * NB * 32 + tid - c_off;
+      const double* const sums = hd.slots;
+      eco[0] = hd.w[cr]; eco[1] = hd.w[Cd + cr]; eco[2] = hd.w[2 * Cd + cr]; eco[3] = hd.w[3 * Cd + cr];
+      eco[4] = (float)(sums[cr] * hd.inv_count); eco[5] = (float)(sums[Cd + cr] * hd.inv_count);          // k1, k2 of pool_bn_bwd_apply_kernel
     }
   }
   // HEAD: lane (l31, hi) does the sigmoid / loss arithmetic of pixel (row hi of its wave's two, column l31); its label travels under the last MFMAs
@@ -592,6 +623,92 @@ __global__ __launch_bounds__(256, WPS) void conv_h2_kernel(const float* __restri
     H2_STAMP(8);
     return;
   }
+  if constexpr (ETAIL) {
+    // LDS (planes and slab are dead): per wave two 4-KB rows [32 pixels][128 B] (x of its two image rows; the first one also turns the pooled gradient before and
+    // the output rows after) | s_co [6][NB * 32]: scale, shift, mean, invstd, k1, k2 of the encoder BatchNorm
+    char* const s_x = smem + wave * 8192;
+    float* const s_co = reinterpret_cast<float*>(smem + 32768);
+    if (tid < NB * 32) {
+#pragma unroll
+      for (int k = 0; k < 6; ++k) s_co[k * NB * 32 + tid] = eco[k];
+    }
+    __syncthreads();
+    const int py0 = y0 + wave * RW, odd = l31 & 1;
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb) {
+      const int mb0 = (g * NB + nb) * 32;
+      if (mb0 >= M || py0 >= H) continue;                  // (wave-uniform; H is even: a wave's two rows are inside the image or not at all)
+      // the pooled gradient (times the dropout keep factor of its element, as pool_bn_bwd_apply_kernel multiplies it) -> this lane's 16 channels of pooled pixel l31 / 2
+#pragma unroll
+      for (int jj = 0; jj < 2; ++jj) {
+        float4 gq = dpre[nb][jj];
+        if (rate > 0.0f) {
+          const int Ho = H >> 1, Wo = W >> 1, Cd = M - c_off, ppx = (x0 >> 1) + jj * 8 + (lane >> 3);
+          const float4 ks = keep_scale(((((long long)n * Ho + (py0 >> 1)) * Wo + ppx) * Cd + (mb0 - c_off)) / 4 + (lane & 7), rate, seed);
+          gq.x *= ks.x; gq.y *= ks.y; gq.z *= ks.z; gq.w *= ks.w;
+        }
+        *reinterpret_cast<float4*>(s_x + out_cell(jj * 8 + (lane >> 3), lane & 7)) = gq;
+      }
+      float gp[16];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const float4 g4 = *reinterpret_cast<const float4*>(s_x + out_cell(l31 >> 1, hi * 4 + q));
+        gp[q * 4] = g4.x; gp[q * 4 + 1] = g4.y; gp[q * 4 + 2] = g4.z; gp[q * 4 + 3] = g4.w;
+      }
+      // (LDS executes a wave's instructions in order: the rows of x may overwrite what was just read)
+#pragma unroll
+      for (int r = 0; r < RW; ++r)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) *reinterpret_cast<float4*>(s_x + r * 4096 + out_cell(j * 8 + (lane >> 3), lane & 7)) = mpre[nb][r][j];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int cc = nb * 32 + hi * 16 + q * 4;
+        const float4 xa4 = *reinterpret_cast<const float4*>(s_x + out_cell(l31, hi * 4 + q)), xb4 = *reinterpret_cast<const float4*>(s_x + 4096 + out_cell(l31, hi * 4 + q));
+        const float4 c0 = *reinterpret_cast<const float4*>(s_bias + cc), ck = *reinterpret_cast<const float4*>(s_bias + NB * 32 + cc), c2 = *reinterpret_cast<const float4*>(s_bias + 2 * NB * 32 + cc);
+        const float4 sc4 = *reinterpret_cast<const float4*>(s_co + cc), sh4 = *reinterpret_cast<const float4*>(s_co + NB * 32 + cc), mn4 = *reinterpret_cast<const float4*>(s_co + 2 * NB * 32 + cc);
+        const float4 is4 = *reinterpret_cast<const float4*>(s_co + 3 * NB * 32 + cc), k14 = *reinterpret_cast<const float4*>(s_co + 4 * NB * 32 + cc), k24 = *reinterpret_cast<const float4*>(s_co + 5 * NB * 32 + cc);
+        const float xa[4] = {xa4.x, xa4.y, xa4.z, xa4.w}, xb[4] = {xb4.x, xb4.y, xb4.z, xb4.w};
+        const float K0[4] = {c0.x, c0.y, c0.z, c0.w}, kk[4] = {ck.x, ck.y, ck.z, ck.w}, K2[4] = {c2.x, c2.y, c2.z, c2.w}, sc[4] = {sc4.x, sc4.y, sc4.z, sc4.w}, sh[4] = {sh4.x, sh4.y, sh4.z, sh4.w};
+        const float mean[4] = {mn4.x, mn4.y, mn4.z, mn4.w}, istd[4] = {is4.x, is4.y, is4.z, is4.w}, k1[4] = {k14.x, k14.y, k14.z, k14.w}, k2[4] = {k24.x, k24.y, k24.z, k24.w};
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const int i = q * 4 + c;
+          // gs = K0 dz + K2 as the MASK_BN_BWD branch leaves it for a channel above mask_climit; then pool_bn_bwd_apply_kernel's expressions, operation for operation
+          const float gsa = fmaf(K0[c], acc[0][nb][i] * unscale, K2[c]), gsb = fmaf(K0[c], acc[1][nb][i] * unscale, K2[c]);
+          const float ya = fmaf(xa[c], sc[c], sh[c]), yb = fmaf(xb[c], sc[c], sh[c]);
+          // the other column of the 2 x 2 window sits in lane ^ 1 (quad_perm [1,0,3,2]); window order = (row 0: even, odd column; row 1: even, odd column), argmax4's tie rule
+          const float pa = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(ya), 0xB1, 0xF, 0xF, true));
+          const float pb = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(yb), 0xB1, 0xF, 0xF, true));
+          const int kmax = argmax4(odd ? pa : ya, odd ? ya : pa, odd ? pb : yb, odd ? yb : pb);
+          const float ta = fmaf(kk[c], ya, gsa) + (kmax == odd ? gp[i] : 0.f);
+          const float tb = fmaf(kk[c], yb, gsb) + (kmax == 2 + odd ? gp[i] : 0.f);
+          acc[0][nb][i] = xa[c] > 0.f ? sc[c] * (ta - k1[c] - (xa[c] - mean[c]) * istd[c] * k2[c]) : 0.f;
+          acc[1][nb][i] = xb[c] > 0.f ? sc[c] * (tb - k1[c] - (xb[c] - mean[c]) * istd[c] * k2[c]) : 0.f;
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < RW; ++r) {
+        const int py = py0 + r;
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          *reinterpret_cast<float4*>(s_x + out_cell(l31, hi * 4 + q)) = make_float4(acc[r][nb][q * 4], acc[r][nb][q * 4 + 1], acc[r][nb][q * 4 + 2], acc[r][nb][q * 4 + 3]);
+        float4 t4s[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) t4s[j] = *reinterpret_cast<const float4*>(s_x + out_cell(j * 8 + (lane >> 3), lane & 7));
+        asm volatile("" :: "v"(t4s[0].x), "v"(t4s[1].x), "v"(t4s[2].x), "v"(t4s[3].x));
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int pxj = x0 + j * 8 + (lane >> 3), cj = lane & 7;
+          if (pxj < W && mb0 + cj * 4 < M) {
+            float* const q = y + (((long long)n * H + py) * W + pxj) * ldy + (mb0 - c_off) + cj * 4;
+            __builtin_nontemporal_store(t4s[j].x, q); __builtin_nontemporal_store(t4s[j].y, q + 1); __builtin_nontemporal_store(t4s[j].z, q + 2); __builtin_nontemporal_store(t4s[j].w, q + 3);
+          }
+        }
+      }
+    }
+    H2_STAMP(8);
+    return;
+  }
   // ---- epilogue: lane (l31, hi) holds, for pixel column l31 of each of its RW rows, channels mb + 0..15
 #pragma unroll
   for (int nb = 0; nb < NB; ++nb) {
@@ -643,7 +760,7 @@ __global__ __launch_bounds__(256, WPS) void conv_h2_kernel(const float* __restri
         for (int q = 0; q < 4; ++q) {
           float4 m4;
           if (MPF) m4 = *reinterpret_cast<const float4*>(s_out + out_cell(l31, hi * 4 + q));
-          else m4 = (live && mb0 < mask_climit) ? *reinterpret_cast<const float4*>(mask + o + q * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+          else m4 = (live && mb0 < mask_climit) ? *reinterpret_cast<const float4*>(mask + (((long long)n * H + py) * W + px_) * ldm + (mb - c_off) + q * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
           mv[q * 4] = m4.x; mv[q * 4 + 1] = m4.y; mv[q * 4 + 2] = m4.z; mv[q * 4 + 3] = m4.w;
         }
       }
@@ -814,15 +931,17 @@ __global__ __launch_bounds__(256, WPS) void conv_h2_kernel(const float* __restri
 template <int MODE, int NB, int RW, int WPS, int EPI = 0>
 int32_t launch_h2(unet_ctx* ctx, const float* x, int ldx, const unet_bf16* wimg, const float* bias, const float* mask, int mask_mode, float* y, int ldy, int n, int h, int wd,
                   int K, int M, int act, float rate, unsigned long long seed, hipStream_t s, int mask_climit = 1 << 30, h2_head_args hd = h2_head_args(), int img_nb = 0,
-                  int splits = 1) {
+                  int splits = 1, int g0 = 0, int ng = 0, int ldm = 0, int c_off = 0) {          // (g0, ng: the channel groups [g0, g0 + ng) of the image only; ng 0 = all.  ldm, c_off: conv_h2_kernel)
   constexpr int T = MODE == 0 ? 9 : 1, KS = MODE == 0 ? 1 : 2;
   if (img_nb == 0) img_nb = NB;                              // (the image's blocks per group: NB unless a one-block launch reads a two-block image, conv_h2_kernel)
-  if (img_nb != NB && !(MODE != 2 && NB == 1 && (img_nb == 2 || img_nb == 4) && (M % (32 * img_nb)) == 0 && EPI == 0)) UNET_FAIL(ctx, UNET_E_ARG, "conv h2: image of %d blocks per group on a %d-block launch", img_nb, NB);
+  if (img_nb != NB && !(MODE != 2 && NB == 1 && (img_nb == 2 || img_nb == 4) && (M % (32 * img_nb)) == 0 && (EPI == 0 || EPI == 5))) UNET_FAIL(ctx, UNET_E_ARG, "conv h2: image of %d blocks per group on a %d-block launch", img_nb, NB);
   constexpr int TH = 4 * RW;
   constexpr int NPIX = MODE == 0 ? (TH + 2) * 34 : TH * 32;
   constexpr size_t smem = (size_t)2 * KS * 2 * (NPIX * 16 + (MODE == 0 ? 0 : 64)) + (NB != 1 || MODE != 0 ? (size_t)((KS * T * NB * 2 * 2 * 32 + 255) / 256) * 256 * 16 : (size_t)KS * T * NB * 2 * 2 * 32 * 16) + 16 + 3 * NB * 32 * 4;
   if (!mask) mask_mode = MASK_NONE;
-  const int tiles_x = (wd + 31) / 32, tiles_y = (h + TH - 1) / TH, groups = (M + 32 * NB - 1) / (32 * NB);
+  const int tiles_x = (wd + 31) / 32, tiles_y = (h + TH - 1) / TH, gtot = (M + 32 * NB - 1) / (32 * NB), groups = ng ? ng : gtot;
+  if (g0 < 0 || groups < 1 || g0 + groups > gtot || (splits > 1 && groups != gtot)) UNET_FAIL(ctx, UNET_E_ARG, "conv h2: channel groups [%d, %d) of %d", g0, g0 + groups, gtot);
+  if (ldm == 0) ldm = ldy;
   const long long total = (long long)tiles_x * tiles_y * n * groups;
   if (total >= (1LL << 28)) UNET_FAIL(ctx, UNET_E_SHAPE, "conv h2: too many tiles");
   const unsigned grid = (unsigned)(8 * ((total + 7) / 8));
@@ -852,7 +971,7 @@ int32_t launch_h2(unet_ctx* ctx, const float* x, int ldx, const unet_bf16* wimg,
     if (smem > 65536) UNET_BIG_LDS(ctx, kern, smem, "conv_h2");
     unet_note_kernel(ctx, reinterpret_cast<const void*>(kern));
     hipLaunchKernelGGL(kern, dim3(grid, (unsigned)((nchunks_ + kcps - 1) / kcps)), dim3(256), smem, s, x, ldx, wimg, bias, mask, y, ldy, n, h, wd, K, M, act, mask_mode, rate, seed, tiles_x,
-                       tiles_y, groups, (int)total, stats, stats_c, signs, mask_climit, hd, img_nb, ctx->opt_deterministic ? 1 : 0, kcps, (long long)n * h * wd * ldy);
+                       tiles_y, groups, (int)total, stats, stats_c, signs, mask_climit, hd, img_nb, ctx->opt_deterministic ? 1 : 0, kcps, (long long)n * h * wd * ldy, g0, gtot, ldm, c_off);
     return UNET_OK;
   };
   int32_t r;
@@ -870,6 +989,9 @@ int32_t launch_h2(unet_ctx* ctx, const float* x, int ldx, const unet_bf16* wimg,
     r = go(conv_h2_kernel<MODE, NB, RW, false, WPS, EPI>);
   } else if (EPI == 2) {
     if (gen || mask_mode != MASK_POOL_SUMS || act != ACT_NONE) UNET_FAIL(ctx, UNET_E_ARG, "conv h2 + pooled sums: a plain data-gradient launch only");
+    r = go(conv_h2_kernel<MODE, NB, RW, false, WPS, EPI>);
+  } else if (EPI == 5) {
+    if (!mask || !bias || !hd.w || !hd.b || !hd.slots || act != ACT_NONE || (h & 1) || (wd & 1) || rate < 0.0f || rate >= 1.0f) UNET_FAIL(ctx, UNET_E_ARG, "conv h2 + encoder tail: a plain data-gradient launch over an even image only");
     r = go(conv_h2_kernel<MODE, NB, RW, false, WPS, EPI>);
   } else if (EPI == 3) {
     if (gen || K != 32 || ldx != 2 || act != ACT_NONE || mask_mode == MASK_POOL_SUMS) UNET_FAIL(ctx, UNET_E_ARG, "conv h2 behind the head's {dz, mask} stream: a plain 32-channel data-gradient launch only");
@@ -1053,6 +1175,54 @@ int32_t k_conv3x3_h2_fwd(unet_ctx* ctx, const float* x, const void* wimg, const 
   const long long wgs16 = (long long)((wd + 31) / 32) * ((h + 15) / 16) * n * ((M + 63) / 64);
   if (h <= 128 && wgs16 >= 512) return launch_h2<0, 2, 4, 2>(ctx, x, K, img, bias, mask, mask_mode, y, ldy, n, h, wd, K, M, act, rate, seed, s, mask_climit);
   return launch_h2<0, 2, 2, 2>(ctx, x, K, img, bias, mask, mask_mode, y, ldy, n, h, wd, K, M, act, rate, seed, s, mask_climit);
+}
+
+// ---- the folded decoder BatchNorm's data gradient in two launches by output-channel range (common.h).  Both run on the ONE image of the 2 C output channels: C = 32 (and every
+// C that is no multiple of 64) as one-block workgroups on the two-block image, otherwise a contiguous range of its two-block groups
+static long long h2_half_wgs(int n, int h, int wd, int C, bool up, int* slots_per_cu) {
+  const long long tx = (wd + 31) / 32;
+  if (C % 64) { *slots_per_cu = 4; return tx * ((h + 7) / 8) * n * (C / 32); }
+  *slots_per_cu = 2;
+  const long long wgs16 = tx * ((h + 15) / 16) * n * (C / 64);
+  if (up && h <= 128 && wgs16 >= 512) return wgs16;          // (the 16-row tiles, as k_conv3x3_h2_fwd picks them)
+  return tx * ((h + 7) / 8) * n * (C / 64);
+}
+bool h2_enc_tail_dgrad_selected(const unet_ctx* ctx, int algo, int n, int h, int wd, int C, bool force) {
+  if (!ctx || C < 32 || (C % 32) || (h & 1) || (wd & 1) || !h2_conv3x3_selected(algo, C, 2 * C) || (long long)h * wd * 2 * C * 4 >= (1LL << 30)) return false;
+  if (force) return true;
+  // The deferred half runs 8-row tiles.  A level whose undivided launch runs the 16-row tiles (k_conv3x3_h2_fwd: h <= 128 and 512 of them) would get other tiles, i.e. other
+  // block exponents for its skip channels: results that differ from the two-launch form in the last bits, which a training run then amplifies.  Such a level keeps the old pair
+  // -- the split must not change what a step computes
+  if (C % 64 == 0 && h <= 128 && (long long)((wd + 31) / 32) * ((h + 15) / 16) * n * (2 * C / 64) >= 512) return false;
+  // Each half launch must fill the resident slots of its tile shape TWICE: with a single round every CU ends on the same tile, nothing is left to run under the last tiles'
+  // epilogues -- and the deferred half's is the longer one
+  for (int up = 0; up < 2; ++up) {
+    int spc; const long long wgs = h2_half_wgs(n, h, wd, C, up != 0, &spc);
+    if (wgs < 2LL * spc * ctx->num_cu) return false;
+  }
+  return true;
+}
+int32_t k_conv3x3_h2_dgrad_bn_bwd_up(unet_ctx* ctx, const float* dy, const void* wimg, const float* coef, const float* x, float* dx, int n, int h, int wd, int C, hipStream_t s) {
+  if (!dy || !wimg || !coef || !x || !dx || C < 32 || (C % 32)) UNET_FAIL(ctx, UNET_E_ARG, "conv3x3 dgrad, up half: bad args (C = %d)", C);
+  if ((long long)h * wd * 2 * C * 4 >= (1LL << 30)) UNET_FAIL(ctx, UNET_E_SHAPE, "conv3x3 h2: one image must stay below 1 GiB (32-bit buffer offsets)");
+  const unet_bf16* img = static_cast<const unet_bf16*>(wimg);
+  const int M = 2 * C;
+  if (C % 64) return launch_h2<0, 1, 2, 4>(ctx, dy, C, img, coef, x, MASK_BN_BWD, dx, M, n, h, wd, C, M, ACT_NONE, 0.0f, 0, s, 1 << 30, h2_head_args(), 2, 1, 0, C / 32);
+  if (h <= 128 && (long long)((wd + 31) / 32) * ((h + 15) / 16) * n * (C / 64) >= 512)          // (as h2_half_wgs counts them)
+    return launch_h2<0, 2, 4, 2>(ctx, dy, C, img, coef, x, MASK_BN_BWD, dx, M, n, h, wd, C, M, ACT_NONE, 0.0f, 0, s, 1 << 30, h2_head_args(), 0, 1, 0, C / 64);
+  return launch_h2<0, 2, 2, 2>(ctx, dy, C, img, coef, x, MASK_BN_BWD, dx, M, n, h, wd, C, M, ACT_NONE, 0.0f, 0, s, 1 << 30, h2_head_args(), 0, 1, 0, C / 64);
+}
+int32_t k_conv3x3_h2_dgrad_enc_tail(unet_ctx* ctx, const float* dy, const void* wimg, const float* coef, const float* x, int ldx, const float* enc_bnp, const double* enc_sums, double count,
+                                    const float* skip_k1, const float* dy_pooled, float* dx, int n, int h, int wd, int C, float rate, uint64_t seed, hipStream_t s) {
+  if (!dy || !wimg || !coef || !x || !enc_bnp || !enc_sums || !dy_pooled || !dx || C < 32 || (C % 32) || ldx < C || (ldx & 3) || (h & 1) || (wd & 1) || !(count >= 1) || rate < 0.f || rate >= 1.f)
+    UNET_FAIL(ctx, UNET_E_ARG, "conv3x3 dgrad + encoder tail: bad args (C = %d, h = %d, w = %d)", C, h, wd);
+  if ((long long)h * wd * std::max(2 * C, ldx) * 4 >= (1LL << 30)) UNET_FAIL(ctx, UNET_E_SHAPE, "conv3x3 h2: one image must stay below 1 GiB (32-bit buffer offsets)");
+  h2_head_args hd; hd.w = enc_bnp; hd.b = dy_pooled; hd.wm = skip_k1; hd.slots = const_cast<double*>(enc_sums); hd.inv_count = 1.0 / count;
+  const unet_bf16* img = static_cast<const unet_bf16*>(wimg);
+  const int M = 2 * C;
+  // (8-row tiles at every level: the prefetch of x and dy_pooled needs the registers the 16-row tiles do not have)
+  if (C % 64) return launch_h2<0, 1, 2, 4, 5>(ctx, dy, C, img, coef, x, MASK_BN_BWD, dx, C, n, h, wd, C, M, ACT_NONE, rate, seed, s, 1 << 30, hd, 2, 1, C / 32, C / 32, ldx, C);
+  return launch_h2<0, 2, 2, 2, 5>(ctx, dy, C, img, coef, x, MASK_BN_BWD, dx, C, n, h, wd, C, M, ACT_NONE, rate, seed, s, 1 << 30, hd, 0, 1, C / 64, C / 64, ldx, C);
 }
 
 bool h2_pool_sums_selected(const unet_ctx* ctx, int algo, int wd, int K, int M) {

@@ -222,13 +222,6 @@ __global__ __launch_bounds__(TPB) void pool_fwd_kernel(const T* __restrict__ x, 
   }
 }
 
-__device__ __forceinline__ int argmax4(float a, float b, float c, float d) {
-  int k = 0; float m = a;
-  if (b > m) { m = b; k = 1; }
-  if (c > m) { m = c; k = 2; }
-  if (d > m) { m = d; k = 3; }
-  return k;
-}
 
 template <bool ACC, typename T>
 __global__ __launch_bounds__(TPB) void pool_bwd_kernel(const T* __restrict__ x, int ldx,

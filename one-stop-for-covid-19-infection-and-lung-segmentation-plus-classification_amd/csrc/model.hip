@@ -72,13 +72,14 @@ static int* ctx_option(unet_ctx* ctx, int32_t option) {
     case UNET_OPT_POOL_SUMS_FUSED: return &ctx->opt_pool_sums_fused;
     case UNET_OPT_HEAD_BWD_FUSED: return &ctx->opt_head_bwd_fused;
     case UNET_OPT_CONV_PP: return &ctx->opt_conv_pp;
+    case UNET_OPT_ENC_TAIL_DGRAD: return &ctx->opt_enc_tail_dgrad;
     default: return nullptr;
   }
 }
 int32_t unet_ctx_set_option(unet_ctx* ctx, int32_t option, int32_t value) {
   if (!ctx) return UNET_E_ARG;
   int* p = ctx_option(ctx, option);
-  const int hi = option == UNET_OPT_BN_FOLD ? 3 : option == UNET_OPT_CONV_PP ? 2 : 1;          // (CONV_PP 2: also the launches too small to fill the persistent grid -- tests)
+  const int hi = option == UNET_OPT_BN_FOLD ? 3 : (option == UNET_OPT_CONV_PP || option == UNET_OPT_ENC_TAIL_DGRAD) ? 2 : 1;          // (CONV_PP / ENC_TAIL_DGRAD 2: also the launches too small to fill the device -- tests)
   if (!p || value < 0 || value > hi) UNET_FAIL(ctx, UNET_E_ARG, "ctx_set_option: option %d value %d", option, value);
   *p = value;
   return UNET_OK;
@@ -376,6 +377,20 @@ int32_t unet_conv3x3_bnfold_bwd_data(unet_ctx* ctx, const float* dy, const float
   ctx->k_slices_ok = 0;          // (one-shot, as unet_conv3x3_bwd_data)
   return r;
 }
+// the skip half of that data gradient finished into the encoder tail's dx, as the bn_pool_bwd_apply:* ops launch it where ENC_TAIL_DGRAD applies (include/unet_hip.h)
+int32_t unet_conv3x3_bnfold_bwd_data_enc_tail(unet_ctx* ctx, const float* dy, const float* w, const float* bnp, const double* bn_bwd_sums, double count, const float* x, int32_t ldx,
+                                              const float* enc_bnp, const double* enc_sums, double enc_count, const float* skip_k1, const float* dy_pooled, float rate, uint64_t seed,
+                                              float* dx, float* wt_ws, float* coef, int32_t n, int32_t h, int32_t wd, int32_t c, int32_t algo, void* stream) {
+  if (!ctx || !dy || !w || !bnp || !bn_bwd_sums || !x || !enc_bnp || !enc_sums || !dy_pooled || !dx || !wt_ws || !coef || n < 1 || !(count >= 1) || !(enc_count >= 1) || !(rate >= 0) || rate >= 1)
+    UNET_FAIL(ctx, UNET_E_ARG, "conv3x3_bnfold_bwd_data_enc_tail: bad args");
+  if (c < 32 || (c % 32) || (h & 1) || (wd & 1) || !unet_conv3x3_bnfold_supported(algo, h, wd, 2 * c, c) || !h2_enc_tail_dgrad_selected(ctx, algo, n, h, wd, c, true))
+    UNET_FAIL(ctx, UNET_E_SHAPE, "conv3x3_bnfold_bwd_data_enc_tail: h=%d w=%d c=%d (even h and w, c a multiple of 32, unet_conv3x3_bnfold_supported(2 c -> c))", h, wd, c);
+  hipStream_t s = as_stream(stream);
+  int32_t r = k_bn_bwd_coef(ctx, bnp, bn_bwd_sums, count, coef, 2 * c, s);
+  if (!r) r = k_h2_weights(ctx, w, wt_ws, 2 * c, c, 1, s);
+  if (!r) r = k_conv3x3_h2_dgrad_enc_tail(ctx, dy, wt_ws, coef, x, ldx, enc_bnp, enc_sums, enc_count, skip_k1, dy_pooled, dx, n, h, wd, c, rate, seed, s);
+  return r;
+}
 
 size_t unet_conv3x3_bwd_weights_ws_bytes(int32_t n, int32_t h, int32_t wd, int32_t cin, int32_t cout) {
   if (cin == 1 && (cout % 4) == 0 && 256 % (cout / 4) == 0 && cout <= 256) return c1_wgrad_ws_bytes(cout);
@@ -531,6 +546,8 @@ struct unet_model {
   std::map<std::string, std::pair<std::string, int>> folded_bn;
   std::map<std::string, size_t> skip_k1_off;          // U-Net fp32: encoder BatchNorm name -> offset (floats) of the decoder's K1 coefficients of its skip channels: the decoder's
                                                       // data gradient did not read the skip tensor, bn_pool_bwd_apply adds K1 * y (common.h: mask_climit)
+  std::set<std::string> enc_tail_dgrad;          // U-Net fp32: encoder BatchNorms bn<k> whose decoder data gradient is split -- the skip half runs inside the encoder tail's backward and
+                                                 // writes dx of c<k>b directly: the skip half of the concat's gradient is never written (ENC_TAIL_DGRAD)
   std::vector<Op> prog[3];
   std::vector<unet_sync_point> sync[3];
   struct SyncRef { int after_op, kind; bool in_ws; size_t off_bytes; int64_t count; int use_op = -1; };          // use_op -1: the op right behind after_op
@@ -1141,9 +1158,13 @@ void build_programs(unet_model* m) {
         const size_t syi = SY.size() - 1;
         flush_def();                                          // (the block's second conv's weight gradient runs while the sums are reduced)
         SY[syi].use_op = (int)BW.size();
-        ADD_OP(BW, "conv3x3_dgrad_bn_bwd:" + name, 2.0 * 9 * cin * cout * px, eb * px * (cout + 2 * cin) + 4.0 * 9.0 * cin * cout, {
+        // ENC_TAIL_DGRAD: only the upsampled half of the output channels here (reads dy and the up half of x, writes the up half of the concat's gradient: 3 of the 4 cin / 2
+        // it moved; half the matrix work) -- the skip half runs as the bn_pool_bwd_apply op of the encoder level and is booked there
+        const bool half = !dt && name.size() == 3 && m->enc_tail_dgrad.count("bn" + std::to_string(10 - (name[1] - '0'))) != 0;
+        ADD_OP(BW, "conv3x3_dgrad_bn_bwd:" + name, (half ? 0.5 : 1.0) * 2.0 * 9 * cin * cout * px, half ? eb * px * (cout + cin) + 4.0 * 9.0 * (cin / 2) * cout : eb * px * (cout + 2 * cin) + 4.0 * 9.0 * cin * cout, {
           int32_t r = k_bn_bwd_coef(ctx, m->wsf(bo), m->wsd(m->off_bn_bsums) + so, px * gcount, m->wsf(co), cin, s);
           if (r) return r;
+          if (half) return k_conv3x3_h2_dgrad_bn_bwd_up(ctx, m->D(name), m->wsf(m->wprep_b.at(name)), m->wsf(co), m->A(xraw), m->D(xraw), ob.n, ob.h, ob.w, cout, s);
           if (dt) return k_conv3x3_bf16_fwd(ctx, CBF(m->Dv(name)), m->P(name + "/kernel"), m->wsf(co), CBF(m->Av(xraw)), MASK_BN_BWD, WBF(m->Dv(xraw)), ob.n, ob.h, ob.w, cout, cin, ACT_NONE, 0.0f, 0,
                                             WBF(static_cast<void*>(m->wsf(m->off_wt))), 1, s, CBF(static_cast<void*>(m->wsf(m->wprep_b.at(name)))));
           // the skip half of the concat's gradient leaves without its K1 * x term when the encoder tail's fused backward adds it (it recomputes y = BN(x) anyway):
@@ -1215,6 +1236,15 @@ void build_programs(unet_model* m) {
       const TInfo a = m->tinfo.at(first), b = m->tinfo.at(last_tensor);
       SY.push_back({(int)BW.size() - 1, 3, false, (size_t)a.off * 4, b.off + b.count - a.off});
     };
+    // ENC_TAIL_DGRAD: which levels split the decoder's folded data gradient (kernels_conv_h2.hip: h2_enc_tail_dgrad_selected -- a rule on the launch shapes and the CU count)
+    if (!dt && m->skip_raw && ctx->opt_enc_bn_fused && ctx->opt_enc_tail_dgrad)
+      for (int k = 1; k <= 4; ++k) {
+        const std::string bnn = "bn" + std::to_string(k), dca = "c" + std::to_string(10 - k) + "a", cb = "c" + std::to_string(k) + "b";
+        const Buf xb = m->act.at(bnn), cg = m->grad.at(cb);
+        if (m->fold_c_off.count(dca) && m->skip_k1_off.count(bnn) && m->wprep_b.count(dca) && cg.ld == xb.c && m->act.at(dca).c == xb.c &&
+            h2_enc_tail_dgrad_selected(ctx, algo, xb.n, xb.h, xb.w, xb.c, ctx->opt_enc_tail_dgrad == 2))
+          m->enc_tail_dgrad.insert(bnn);
+      }
     bool enc_split = false;
     const int dec[4] = {256, 128, 64, 32};
     for (int k = 9; k >= 6; --k) {
@@ -1282,7 +1312,17 @@ void build_programs(unet_model* m) {
         // all-reduce nothing can hide -- is the 0.3 MB of levels 1 and 2
         if (k == 2) { bucket("c3a/kernel", "bn4/beta"); enc_split = true; }
         SY[syi].use_op = (int)BW.size();
-        ADD_OP(BW, "bn_pool_bwd_apply:" + bnn, 0, eb * 3.25 * nel(xb), {
+        // ENC_TAIL_DGRAD: the skip half of c<10-k>a's data gradient with this op's arithmetic in its epilogue -- the same 3.25 tensors (dy in the place of g_skip) plus its
+        // half of the weight image, and the half of that conv's matrix work the conv3x3_dgrad_bn_bwd op no longer does.  That work is booked as its fp32-MFMA-time
+        // EQUIVALENT (unet_conv3x3_exec_ratio: 3 fp16 products per multiply at the fp16 rate): a reader of the op table applies that ratio to the conv3x3_* names only
+        // (bench.py's step floor), and under this op's name the plain count would be charged at the fp32 matrix rate -- five times the time the launch can take
+        const bool tail = m->enc_tail_dgrad.count(bnn) != 0;
+        const std::string dca = "c" + std::to_string(10 - k) + "a";
+        ADD_OP(BW, "bn_pool_bwd_apply:" + bnn, tail ? 2.0 * 9 * c * c * (double)pixels * unet_conv3x3_exec_ratio(algo, xb.h, xb.w, c, 2 * c) : 0.0, eb * 3.25 * nel(xb) + (tail ? 4.0 * 9.0 * c * c : 0.0), {
+          if (tail)
+            return k_conv3x3_h2_dgrad_enc_tail(ctx, m->D(dca), m->wsf(m->wprep_b.at(dca)), m->wsf(m->fold_c_off.at(dca)), m->A(cb), cbuf.ld, m->wsf(bo), m->wsd(m->off_bn_bsums) + so,
+                                               (double)pixels * gcount, m->wsf(m->skip_k1_off.at(bnn)), m->D(pn), m->D(cb), xb.n, xb.h, xb.w, xb.c, m->drop_rate,
+                                               m->drop_seed + (uint64_t)k * 0x9E3779B97F4A7C15ull, s);
           if (dt) return unet_bn_maxpool_bwd_apply_bf16(ctx, CBF(m->Av(cb)), cbuf.ld, m->wsf(bo), m->wsd(m->off_bn_bsums) + so, (double)pixels * gcount, CBF(m->Dv(bnn)), gb.ld, CBF(m->Dv(pn)),
                                                         WBF(m->Dv(cb)), cg.ld, xb.n, xb.h, xb.w, xb.c, m->drop_rate, m->drop_seed + (uint64_t)k * 0x9E3779B97F4A7C15ull, s);
           const auto k1o = m->skip_k1_off.find(bnn);
@@ -2268,6 +2308,7 @@ int32_t unet_model_tap(const unet_model* m, const char* name, int32_t grad, cons
     if (r) return r;
     if (hipStreamSynchronize(nullptr) != hipSuccess) return UNET_E_HIP;
   }
+  if (grad && m->enc_tail_dgrad.count(nm_)) return UNET_E_STATE;          // the skip half of the concat's gradient is never written (ENC_TAIL_DGRAD)
   if (grad && m->head_bwd_fused && nm_ == "c9b") return UNET_E_STATE;          // the head's backward leaves the {dz, mask} stream there, not the tensor (HEAD_BWD_FUSED)
   if (!grad && m->skip_raw && nm_.size() == 3 && nm_[0] == 'b' && nm_[2] >= '1' && nm_[2] <= '4') {
     // skip_raw: an encoder BatchNorm's output is never stored -- a tap materialises it from the raw conv output (inside the concat) into the tap scratch
