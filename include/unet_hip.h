@@ -898,6 +898,45 @@ int32_t unet_vol_joint_hist(unet_ctx*, const void* fixed, int32_t f_dtype, int32
                             const uint8_t* mask, const void* moving, int32_t m_dtype, int32_t Xm, int32_t Ym, int32_t Zm, int32_t m_scaled, double m_slope, double m_inter,
                             const double* M, int32_t K, int32_t bins, double f_lo, double f_hi, double m_lo, double m_hi, uint32_t* counts, void* stream);
 
+/* ---- the deformable refinement of a registered follow-up (csrc/kernels_deform.hip; new: the reference never compares two scans) -----------------
+ * A displacement field u lives on a field grid [Xf, Yf, Zf]: device float32 [3][Xf Yf Zf], component major, each component a volume in Fortran order (NIfTI code 16), in
+ * millimetres of the fixed world frame.  A fixed world point p corresponds to the moving world point T (p + u(p)), T the rigid transform.  For a target voxel (i, j, k)
+ * the moving voxel coordinate is s_r = ((c_r + L[r][0] u_0) + L[r][1] u_1) + L[r][2] u_2 with c_r = ((W[r][0] i + W[r][1] j) + W[r][2] k) + W[r][3] of section 4w.
+ * W: HOST, 12 doubles, row-major 3 x 4 (inv(A_moving) T A_target); L: HOST, 9 doubles, row-major 3 x 3 ((inv(A_moving) T)[:3, :3]: millimetres -> moving voxels).  u is the
+ * stored element when the target grid is the field grid, else the three components sampled trilinearly (vol_trilinear.h's blend, float64, not rounded) at the field
+ * coordinate F (i, j, k) clamped into the field.  Every float64 operation is rounded on its own; a field element is rounded to float32 once, on store.  All host matrices
+ * must be finite.  UNET_E_ARG before any launch, the outputs untouched: a null or misaligned buffer, an extent outside the ranges of unet_vol_resample_linear, an unknown
+ * datatype code, a non-finite matrix entry, and what each entry names below.
+ *   unet_vol_smooth_axis   dst <- one pass of a (2 R + 1)-tap filter along `axis` (0 = x, 1 = y, 2 = z) of C float32 volumes [X, Y, Z] stored one after the other (1 <= C
+ *                          <= 1024): dst[p] = float32(sum_t weights[t] src[clamp(p + t - R, 0, n - 1)]) -- the edge voxel repeats --, the sum in float64 from 0 in
+ *                          ascending t, acc + fl(w v).  weights: HOST, 2 R + 1 finite doubles (a normalised Gaussian, computed once by the caller), 0 <= R <=
+ *                          UNET_VOL_SMOOTH_MAX_RADIUS; R = 0 with weight 1 is a copy.  src != dst.
+ *   unet_vol_demons_step   field_out <- u + v, one launch, the warped image is never stored.  fixed [X, Y, Z] (the field grid) and moving [Xm, Ym, Zm] are described and
+ *                          decoded as for unet_vol_resample_linear; mask: uint8 on the fixed grid, or NULL.  m_w = the moving sample at s (rs_blend_inside, as
+ *                          unet_vol_joint_hist), d = f - m_w, g = Ginv (the index-space differences of f) with Ginv: HOST, 9 doubles, row-major inv(A_fixed[:3, :3])^T;
+ *                          a difference is central ((f[p + 1] - f[p - 1]) 0.5), one-sided at a border (denominator 1) and 0 on an axis of extent 1.
+ *                          v = d g / (|g|^2 + d^2 / delta^2), delta > 0 the step bound in mm (delta^2 computed once on the host); v = 0 where the mask byte is 0, f or
+ *                          m_w is NaN, a coordinate is not within 0 <= s_r <= n_r - 1 (compared as doubles) or the denominator is not above 1e-9 (a NaN one is not).
+ *                          field_in != field_out.
+ *   unet_vol_warp_field    dst [X2, Y2, Z2] <- the source [X, Y, Z] at s.  field: [3][Xf Yf Zf]; F: HOST, 12 doubles, output voxel index -> field voxel coordinate, or
+ *                          NULL: the field lies on the output grid and (Xf, Yf, Zf) must be (X2, Y2, Z2).  order 1: the blend of unet_vol_resample_linear (dtype, scaled,
+ *                          slope, inter, mode, cval; dst_dtype 64, 16 or 2 = result >= 0.5); order 0: the stored element at floor(s + 0.5) moved untouched as in
+ *                          unet_vol_resample_nearest (elements of the size of dtype, mode 1 writes the low bytes of cval_bits outside; dst_dtype = dtype).  With a field
+ *                          of zeros the result is, bit for bit, that of unet_vol_resample_linear / _nearest with matrix W: the samplers are shared.
+ *   unet_vol_jacobian      det <- float32(det(I + D Ainv)) per field voxel, D[c][a] the index-space difference of u_c along axis a (as the demons step takes those of
+ *                          f), Ainv: HOST, 9 doubles, row-major inv(A_field[:3, :3]); the determinant by its first row, in float64.  folded: device uint32, cleared by
+ *                          the entry point: the number of voxels whose float64 determinant is <= 0 (integer atomics; a NaN is not counted). */
+#define UNET_VOL_SMOOTH_MAX_RADIUS 32
+int32_t unet_vol_smooth_axis(unet_ctx*, const float* src, int32_t C, int32_t X, int32_t Y, int32_t Z, int32_t axis, int32_t R, const double* weights, float* dst,
+                             void* stream);
+int32_t unet_vol_demons_step(unet_ctx*, const void* fixed, int32_t f_dtype, int32_t X, int32_t Y, int32_t Z, int32_t f_scaled, double f_slope, double f_inter,
+                             const uint8_t* mask, const void* moving, int32_t m_dtype, int32_t Xm, int32_t Ym, int32_t Zm, int32_t m_scaled, double m_slope, double m_inter,
+                             const double* W, const double* L, const double* Ginv, double delta, const float* field_in, float* field_out, void* stream);
+int32_t unet_vol_warp_field(unet_ctx*, const void* src, int32_t dtype, int32_t X, int32_t Y, int32_t Z, int32_t scaled, double slope, double inter, const double* W,
+                            const double* L, const float* field, int32_t Xf, int32_t Yf, int32_t Zf, const double* F, int32_t order, int32_t mode, double cval,
+                            uint64_t cval_bits, void* dst, int32_t dst_dtype, int32_t X2, int32_t Y2, int32_t Z2, void* stream);
+int32_t unet_vol_jacobian(unet_ctx*, const float* field, int32_t X, int32_t Y, int32_t Z, const double* Ainv, float* det, uint32_t* folded, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Model level. Replaces the Keras Model built at T1:853-916 and driven by
  * compile/fit/evaluate/predict (T1:1053-1061, 1101, 1137).  A model is a fixed-shape plan:

@@ -26,6 +26,7 @@ MORPH_OPS = {"dilate": 0, "erode": 1, "open": 2, "close": 3}          # include/
 MORPH_MAX_ITERATIONS = 64
 INTENSITY_MAX_EDGES = 63                                              # include/unet_hip.h UNET_VOL_INTENSITY_MAX_EDGES
 JOINT_HIST_MAX_K, JOINT_HIST_MAX_BINS = 16, 64                        # UNET_VOL_JOINT_HIST_MAX_K, UNET_VOL_JOINT_HIST_MAX_BINS
+SMOOTH_MAX_RADIUS = 32                                                # UNET_VOL_SMOOTH_MAX_RADIUS
 MASK_NONE, MASK_RELU, MASK_ELU, MASK_ELU_DROP = 0, 1, 2, 3
 PROG_FWD_TRAIN, PROG_BWD, PROG_FWD_INFER = 0, 1, 2
 SYNC_BN_FWD, SYNC_LOSS, SYNC_BN_BWD, SYNC_GRAD_BUCKET = 0, 1, 2, 3
@@ -237,6 +238,12 @@ _PROTOS = {
     "unet_vol_resample_linear": (i32, [vp, vp, i32, i32, i32, i32, i32, f64, f64, vp, i32, f64, vp, i32, i32, i32, i32, vp]),
     # the joint histogram of two volumes under K candidate matrices (csrc/kernels_register.hip, volume.joint_histogram / register_volumes); M is a host array of K x 12 doubles
     "unet_vol_joint_hist": (i32, [vp, vp, i32, i32, i32, i32, i32, f64, f64, vp, vp, i32, i32, i32, i32, i32, f64, f64, vp, i32, i32, f64, f64, f64, f64, vp, vp]),
+    # a displacement field: Gaussian pass, demons step, warp, Jacobian (csrc/kernels_deform.hip, volume.refine_registration / DisplacementField); weights, W, L, Ginv, F
+    # and Ainv are host arrays of doubles
+    "unet_vol_smooth_axis": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
+    "unet_vol_demons_step": (i32, [vp, vp, i32, i32, i32, i32, i32, f64, f64, vp, vp, i32, i32, i32, i32, i32, f64, f64, vp, vp, vp, f64, vp, vp, vp]),
+    "unet_vol_warp_field": (i32, [vp, vp, i32, i32, i32, i32, i32, f64, f64, vp, vp, vp, i32, i32, i32, vp, i32, i32, f64, u64, vp, i32, i32, i32, i32, vp]),
+    "unet_vol_jacobian": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp]),
     "unet_model_create": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(vp)]),
     "unet_model_dtype": (i32, [vp]),
     "unet_model_tap_elem_bytes": (i32, [vp, C.c_char_p, i32]),

@@ -2973,9 +2973,16 @@ def change_between(mask_a, grid_a, mask_b, grid_b, return_device=False, transfor
     voxels per slice; millilitres at a's voxel volume; dice = 2 persistent / (2 persistent + new + resolved).  mask_a / mask_b: host arrays (non-zero = foreground) or
     uint8 device tensors of prod(grid.shape) elements; both grids must be oriented Grids.  transform=None: the two affines are taken as they are (two re-griddings of one
     acquisition).  transform= a RigidTransform, a Registration (register_volumes(ct_a, ct_b)) or a 4 x 4 matrix T, a's world -> b's world: b's affine is replaced by
-    inv(T) @ A_b first, so a follow-up in which the patient lies differently is compared in the baseline's frame (section 4x)."""
+    inv(T) @ A_b first, so a follow-up in which the patient lies differently is compared in the baseline's frame (section 4x).  transform= a DeformableRegistration
+    (refine_registration, or register_volumes(..., deformable=True)) of a onto b: b's mask goes onto a's grid through its displacement field as well
+    (unet_vol_warp_field, nearest, background outside; section 4y) -- grid_a and grid_b must then be the grids the field was found on."""
     ga, gb = _need_oriented(grid_a, "grid_a"), _need_oriented(grid_b, "grid_b")
-    if transform is not None:
+    deform = transform if isinstance(transform, DeformableRegistration) else None
+    if deform is not None:
+        for g, want, what in ((ga, deform.field.fixed_grid, "grid_a"), (gb, deform.field.moving_grid, "grid_b")):
+            if g.shape != want.shape or not np.array_equal(g.affine, want.affine):
+                raise ValueError(f"{what} is not the grid the deformable registration was found on ({g!r} for {want!r})")
+    elif transform is not None:
         gb = Grid(gb.shape, np.linalg.inv(_world_matrix(transform)) @ gb.affine, True)
     torch = _torch()
     srcs = []
@@ -2984,9 +2991,13 @@ def change_between(mask_a, grid_a, mask_b, grid_b, return_device=False, transfor
         if s.shape != g.shape:
             raise ValueError(f"{what} is {s.shape}, its grid {g.shape}")
         srcs.append(s)
-    M = resample_matrix(gb, ga)
     dev_a = srcs[0].tensor if srcs[0].tensor is not None else upload(srcs[0].vol)
-    b_on_a = _resample_raw(srcs[1], M, 1, 0, ga.shape)
+    if deform is not None:
+        M = deform.field.voxel_matrix
+        b_on_a = deform.field._warp(srcs[1], 0, 1, 0.0, 0, 2)
+    else:
+        M = resample_matrix(gb, ga)
+        b_on_a = _resample_raw(srcs[1], M, 1, 0, ga.shape)
     counts = confusion_device(b_on_a, dev_a, ga.shape)
     tp, fp, fn = (int(v) for v in counts.sum(axis=0))
     ml = ga.voxel_ml
@@ -3356,7 +3367,8 @@ def rigid_search(levels, fixed_grid, moving_grid, init="geometry", min_overlap=0
 
 
 def register_volumes(fixed, moving, levels_mm=REGISTER_LEVELS_MM, bins=32, window=REGISTER_WINDOW, mask=None, init="geometry", min_overlap=0.25,
-                     max_batches=REGISTER_MAX_BATCHES, metric="mi", moving_window=None, fixed_affine=None, moving_affine=None, fixed_shape=None, moving_shape=None):
+                     max_batches=REGISTER_MAX_BATCHES, metric="mi", moving_window=None, fixed_affine=None, moving_affine=None, fixed_shape=None, moving_shape=None,
+                     deformable=None):
     """Register a follow-up CT (moving) to its baseline (fixed) on the device -> Registration: the rigid transform, fixed world -> moving world, that maximises the mutual
     information ("mi") or its normalised form ("nmi") of the joint histogram (joint_histogram: bins, window, moving_window, mask on the fixed grid).  fixed, moving: as
     joint_histogram takes them; both must carry an orientation.
@@ -3364,8 +3376,18 @@ def register_volumes(fixed, moving, levels_mm=REGISTER_LEVELS_MM, bins=32, windo
     on an isotropic grid of that spacing over the same field of view with resample_volume (linear, float32) -- a level whose spacing does not exceed the fixed volume's
     smallest uses the fixed volume itself --, the mask with resample_mask (nearest); the moving volume stays on its own grid.  init: "geometry" (the centres of the two
     fields of view aligned), "identity" or a RigidTransform.  Registration.resample and change_between(transform=) apply the result.
-    Rigid only, hard bins, no gradients (section 4x).  Every argument error is a ValueError before any device work."""
+    Hard bins, no gradients (section 4x).  deformable=None: rigid only, a Registration.  deformable=True, or a dict of refine_registration's keywords (levels_mm,
+    iterations, field_sigma, image_sigma, max_step): the rigid result is refined with a demons displacement field (section 4y; the same mask) and the
+    DeformableRegistration is returned, its .rigid the Registration.  Every argument error is a ValueError before any device work."""
     lv, B, wf, wm = _check_register_args(levels_mm, bins, window, moving_window, init, min_overlap, max_batches, metric)
+    if deformable is not None and deformable is not True and not isinstance(deformable, dict):
+        raise ValueError(f"deformable is None, True or a dict of refine_registration's keywords, not {deformable!r}")
+    dkw = dict(deformable) if isinstance(deformable, dict) else {}
+    if deformable is not None:
+        bad = sorted(set(dkw) - {"levels_mm", "iterations", "field_sigma", "image_sigma", "max_step"})
+        if bad:
+            raise ValueError(f"deformable= takes levels_mm, iterations, field_sigma, image_sigma and max_step, not {bad}")
+        _check_deform_args(**dkw)
     f, m = _resample_source(fixed, None, fixed_affine, fixed_shape), _resample_source(moving, None, moving_affine, moving_shape)
     fg, mg = _need_oriented(f.grid, "the fixed volume's grid"), _need_oriented(m.grid, "the moving volume's grid")
     mk = _check_fixed_mask(mask, f.shape)
@@ -3394,4 +3416,307 @@ def register_volumes(fixed, moving, levels_mm=REGISTER_LEVELS_MM, bins=32, windo
     reg = rigid_search(levels, fg, mg, init, min_overlap, max_batches, metric)
     torch.cuda.synchronize()
     reg.seconds = time.perf_counter() - t0
+    if deformable is not None:
+        return refine_registration(fixed, moving, reg, mask=mask, fixed_affine=fixed_affine, moving_affine=moving_affine, fixed_shape=fixed_shape, moving_shape=moving_shape, **dkw)
     return reg
+
+
+# ---- the deformable refinement of a registered follow-up: demons on the device (csrc/kernels_deform.hip) ------------------------------------------
+SMOOTH_MAX_RADIUS = _lib.SMOOTH_MAX_RADIUS                           # UNET_VOL_SMOOTH_MAX_RADIUS: taps either side of a Gaussian pass
+DEFORM_LEVELS_MM = (8.0, 4.0)                                       # conventional, configurable starting values; not clinically validated (section 4y)
+DEFORM_ITERATIONS = (30, 15)
+
+
+def gaussian_weights(sigma):
+    """The 2 R + 1 weights of one pass of a normalised Gaussian of width sigma (in voxels), R = ceil(3 sigma): exp(-t^2 / (2 sigma^2)) / their sum, float64, computed
+    once on the host -> float64 [2 R + 1]; sigma = 0 -> None (no pass)."""
+    if isinstance(sigma, (bool, str)) or not isinstance(sigma, (int, float, np.integer, np.floating)) or not np.isfinite(sigma) or sigma < 0:
+        raise ValueError(f"a Gaussian width is a finite number of voxels >= 0, not {sigma!r}")
+    if sigma == 0:
+        return None
+    R = int(np.ceil(3.0 * float(sigma)))
+    if R > SMOOTH_MAX_RADIUS:
+        raise ValueError(f"a Gaussian width of {sigma} voxels needs {R} taps either side; a pass takes {SMOOTH_MAX_RADIUS} (coarsen the level instead)")
+    t = np.arange(-R, R + 1, dtype=np.float64)
+    w = np.exp(-(t * t) / (2.0 * float(sigma) * float(sigma)))
+    return w / w.sum()
+
+
+def _check_deform_args(levels_mm=DEFORM_LEVELS_MM, iterations=DEFORM_ITERATIONS, field_sigma=1.5, image_sigma=1.0, max_step=1.0):
+    """-> (levels, iterations per level, the field's weights or None, the images' weights or None, max_step); ValueError otherwise"""
+    try:
+        lv = tuple(float(v) for v in levels_mm)
+    except (TypeError, ValueError):
+        lv = ()
+    if not lv or not all(np.isfinite(v) and v > 0 for v in lv) or any(b >= a for a, b in zip(lv, lv[1:])):
+        raise ValueError(f"levels_mm is a strictly descending sequence of positive spacings in mm, not {levels_mm!r}")
+    try:
+        its = tuple(iterations)
+    except TypeError:
+        its = ()
+    if len(its) != len(lv) or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 0 for v in its):
+        raise ValueError(f"iterations is one non-negative integer per level ({len(lv)}), not {iterations!r}")
+    if isinstance(max_step, (bool, str)) or not isinstance(max_step, (int, float, np.integer, np.floating)) or not np.isfinite(max_step) or not max_step > 0:
+        raise ValueError(f"max_step is a finite positive number of level voxels, not {max_step!r}")
+    return lv, tuple(int(v) for v in its), gaussian_weights(field_sigma), gaussian_weights(image_sigma), float(max_step)
+
+
+def _check_mat3(m, what):
+    """-> float64 [3, 3], C order, finite; ValueError otherwise"""
+    a = np.ascontiguousarray(np.asarray(m, np.float64))
+    if a.shape != (3, 3) or not np.isfinite(a).all():
+        raise ValueError(f"{what} is a finite 3 x 3 matrix")
+    return a
+
+
+def smooth_axis_device(x, C, shape, axis, weights):
+    """unet_vol_smooth_axis -> a new float32 device tensor: one pass of `weights` along `axis` of the C volumes of `shape` stored one after the other in x"""
+    torch = _torch(); lib, ctx = _ctx()
+    w = np.ascontiguousarray(weights, np.float64)
+    out = torch.empty_like(x)
+    ctx.check(lib.unet_vol_smooth_axis(ctx.handle, x.data_ptr(), int(C), *(int(v) for v in shape), int(axis), (w.size - 1) // 2, w.ctypes.data, out.data_ptr(), _stream()),
+              "vol_smooth_axis")
+    return out
+
+
+def demons_step_device(fixed_dev, fixed_vargs, mask_dev, moving_dev, moving_vargs, W, L, Ginv, delta, field):
+    """unet_vol_demons_step -> u + v, a new float32 device tensor [3 X Y Z]"""
+    torch = _torch(); lib, ctx = _ctx()
+    W, L, G = _check_matrix(W), _check_mat3(L, "L"), _check_mat3(Ginv, "Ginv")
+    out = torch.empty_like(field)
+    ctx.check(lib.unet_vol_demons_step(ctx.handle, fixed_dev.data_ptr(), *fixed_vargs, _ptr(mask_dev), moving_dev.data_ptr(), *moving_vargs, W.ctypes.data, L.ctypes.data,
+                                       G.ctypes.data, float(delta), field.data_ptr(), out.data_ptr(), _stream()), "vol_demons_step")
+    return out
+
+
+def warp_field_device(dev, vargs, W, L, field, field_shape, F, order, mode, cval, cval_bits, out_shape, dst_dtype):
+    """unet_vol_warp_field -> order 1: a float64 (dst_dtype 64), float32 (16) or uint8 (2) device tensor of prod(out_shape) elements; order 0: the moved elements as a
+    uint8 tensor of prod(out_shape) x the element size bytes (dst_dtype = the source's code)"""
+    torch = _torch(); lib, ctx = _ctx()
+    W, L = _check_matrix(W), _check_mat3(L, "L")
+    F = None if F is None else _check_matrix(F)
+    n = int(np.prod(out_shape))
+    if order == 1:
+        out = torch.empty(n, dtype={64: torch.float64, 16: torch.float32, 2: torch.uint8}[dst_dtype], device="cuda")
+    else:
+        out = torch.empty(n * np.dtype(nifti_min.DTYPES[vargs[0]]).itemsize, dtype=torch.uint8, device="cuda")
+    ctx.check(lib.unet_vol_warp_field(ctx.handle, dev.data_ptr(), *vargs, W.ctypes.data, L.ctypes.data, field.data_ptr(), *(int(v) for v in field_shape),
+                                      None if F is None else F.ctypes.data, int(order), int(mode), float(cval), int(cval_bits), out.data_ptr(), int(dst_dtype),
+                                      *(int(v) for v in out_shape), _stream()), "vol_warp_field")
+    return out
+
+
+def jacobian_device(field, shape, Ainv):
+    """unet_vol_jacobian -> (det: float32 device tensor of prod(shape) elements, the number of voxels with det <= 0)"""
+    torch = _torch(); lib, ctx = _ctx()
+    Ai = _check_mat3(Ainv, "Ainv")
+    det = torch.empty(int(np.prod(shape)), dtype=torch.float32, device="cuda")
+    folded = torch.empty(1, dtype=torch.int32, device="cuda")
+    ctx.check(lib.unet_vol_jacobian(ctx.handle, field.data_ptr(), *(int(v) for v in shape), Ai.ctypes.data, det.data_ptr(), folded.data_ptr(), _stream()), "vol_jacobian")
+    return det, int(folded.item()) & 0xFFFFFFFF
+
+
+class DeformOps:
+    """The operations refine_registration's loop is written over, on the device: volumes and fields are flat device tensors in Fortran order.  tests/deform_oracle.py
+    has the same methods over numpy arrays, so the host test and the device test run the SAME loop (as rigid_search takes its evaluators)."""
+
+    def upload(self, src):
+        return src.tensor if src.tensor is not None else upload(src.vol)
+
+    def upload_mask(self, mask, shape):
+        return None if mask is None else _mask_to_device(mask, shape)[0]
+
+    def linear(self, dev, vargs, M, out_shape):
+        """the volume on a level grid: unet_vol_resample_linear, clamped, float32"""
+        return resample_linear_device(dev, vargs, M, 0, 0.0, out_shape, 16)
+
+    def nearest_mask(self, dev, shape, M, out_shape):
+        return resample_nearest_device(dev, 1, shape, M, 0, 0, out_shape)
+
+    def zeros(self, n):
+        return _torch().zeros(int(n), dtype=_torch().float32, device="cuda")
+
+    def stack(self, parts):
+        return _torch().cat(list(parts))
+
+    smooth_axis = staticmethod(smooth_axis_device)
+    demons_step = staticmethod(demons_step_device)
+    warp_field = staticmethod(warp_field_device)
+    jacobian = staticmethod(jacobian_device)
+
+    def rms(self, f, warped, mask):
+        """-> (the RMS of f - warped over the voxels the mask admits where neither is NaN, in float64; how many those are)"""
+        d = f.double() - warped
+        ok = ~d.isnan() if mask is None else (~d.isnan() & (mask != 0))
+        n = int(ok.sum().item())
+        return (float((d[ok] * d[ok]).sum().sqrt().item() / np.sqrt(n)) if n else float("nan")), n
+
+    def minmax(self, det):
+        return float(det.min().item()), float(det.max().item())
+
+    def sync(self):
+        _torch().cuda.synchronize()
+
+
+class DisplacementField:
+    """A dense displacement field u (section 4y).  tensor: float32 [3 X Y Z] on the device, component major, each component in Fortran order on `grid` (a level grid over
+    the fixed field of view), in millimetres of the fixed world frame; rigid: the world transform T it refines, fixed world -> moving world (what was given:
+    a Registration, a RigidTransform or a 4 x 4), matrix its 4 x 4; fixed_grid, moving_grid: the two volumes' grids.  A fixed world point p corresponds to the moving
+    world point T (p + u(p)); voxel_matrix = inv(A_moving) T A_fixed [3, 4]."""
+
+    def __init__(self, tensor, grid, rigid, fixed_grid, moving_grid):
+        self.tensor, self.grid, self.rigid, self.fixed_grid, self.moving_grid = tensor, grid, rigid, fixed_grid, moving_grid
+        self.matrix = _world_matrix(rigid)
+        self.voxel_matrix = voxel_matrix(fixed_grid, moving_grid, self.matrix)
+        self.mm_to_voxels = _check_mat3((np.linalg.inv(moving_grid.affine) @ self.matrix)[:3, :3], "L")
+        same = grid.shape == fixed_grid.shape and np.array_equal(grid.affine, fixed_grid.affine)
+        self.field_matrix = None if same else resample_matrix(grid, fixed_grid)          # F: fixed voxel index -> field voxel coordinate
+
+    def _warp(self, src, order, mode, cval, cval_bits, dst_dtype):
+        dev = src.tensor if src.tensor is not None else upload(src.vol)
+        return warp_field_device(dev, src.vargs, self.voxel_matrix, self.mm_to_voxels, self.tensor, self.grid.shape, self.field_matrix, order, mode, cval, cval_bits,
+                                 self.fixed_grid.shape, dst_dtype)
+
+    def resample(self, moving, kind="volume", order=None, mode=None, cval=None, dtype="float32", return_device=False, src_shape=None):
+        """The moving scan (kind "volume"), or a mask ("mask") or a label volume ("labels") drawn on it, on the fixed grid through T and the field: unet_vol_warp_field
+        -> ResampledVolume (matrix: the rigid voxel matrix).  It mirrors Registration.resample: order "linear" (default for a volume; a mask is then blended and cut at
+        0.5) or "nearest" (default for masks and labels, the only one for labels; a volume then needs dtype="raw": the stored elements move); mode "nearest" (default for
+        a volume) or "constant" (default for masks and labels: background outside); cval, dtype and return_device as resample_volume has them; a device tensor needs
+        src_shape=.  moving must lie on the moving grid."""
+        if kind not in ("volume", "mask", "labels"):
+            raise ValueError(f"kind is 'volume', 'mask' or 'labels', not {kind!r}")
+        order = ("linear" if kind == "volume" else "nearest") if order is None else order
+        mode = ("nearest" if kind == "volume" else "constant") if mode is None else mode
+        if kind == "labels" and order != "nearest":
+            raise ValueError(f"labels are resampled with order='nearest' only (a blend of two labels is no label), not {order!r}")
+        if kind != "volume":
+            dtype = "raw" if order == "nearest" else "float32"
+        _check_resample_args(order, mode, cval, dtype)
+        if order == "nearest" and dtype != "raw":
+            raise ValueError("order='nearest' moves stored elements: ask for dtype='raw'")
+        src = _resample_source(moving, None, self.moving_grid.affine, src_shape, kind)
+        if src.shape != self.moving_grid.shape:
+            raise ValueError(f"the {kind} is {src.shape}, the moving grid {self.moving_grid.shape}")
+        m = RESAMPLE_MODES[mode]
+        code = src.vargs[0]
+        npdt = np.dtype(nifti_min.DTYPES[code])
+        shape = self.fixed_grid.shape
+        if order == "nearest":
+            stored = 0 if m == 0 or kind != "volume" else (_stored_extreme(src) if cval is None else cval)
+            if npdt.kind in "iu" and not (np.isfinite(float(stored)) and float(stored) == int(stored) and np.iinfo(npdt).min <= int(stored) <= np.iinfo(npdt).max):
+                raise ValueError(f"cval {stored!r} is not a value of the stored dtype {npdt}")
+            out = self._warp(src, 0, m, 0.0, _bits_of(stored, npdt), code)
+            if code in _TORCH_OF_CODE:
+                out = out.view(getattr(_torch(), _TORCH_OF_CODE[code]))
+            keep = kind == "volume" and src.vargs[4]
+            return ResampledVolume(data=out if return_device else _host_of(out, npdt, shape), grid=self.fixed_grid, matrix=self.voxel_matrix,
+                                   slope=src.vargs[5] if keep else 0.0, inter=src.vargs[6] if keep else 0.0)
+        if kind == "mask":
+            out, host_dt = self._warp(src, 1, m, 0.0, 0, 2), np.uint8
+        else:
+            c = 0.0 if m == 0 else (_decode_scalar(src, _stored_extreme(src)) if cval is None else float(cval))
+            out, host_dt = self._warp(src, 1, m, c, 0, _RESAMPLE_DST[dtype]), dtype
+        return ResampledVolume(data=out if return_device else _host_of(out, host_dt, shape), grid=self.fixed_grid, matrix=self.voxel_matrix, slope=0.0, inter=0.0)
+
+    def jacobian(self, return_device=False):
+        """-> (det(I + du/dp) per field voxel: float32 [X, Y, Z] on the field grid -- the flat device tensor with return_device=True --, folded: how many are <= 0)"""
+        det, folded = jacobian_device(self.tensor, self.grid.shape, np.linalg.inv(self.grid.affine[:3, :3]))
+        return (det if return_device else _host_of(det, np.float32, self.grid.shape)), folded
+
+    def magnitude(self):
+        """-> (the largest, the mean) |u| in mm over the field grid"""
+        u = self.tensor.reshape(3, -1).double()
+        norm = (u * u).sum(dim=0).sqrt()
+        return float(norm.max().item()), float(norm.mean().item())
+
+    def host(self):
+        """-> float32 [3, X, Y, Z]"""
+        a = self.tensor if isinstance(self.tensor, np.ndarray) else self.tensor.cpu().numpy()
+        return np.stack([c.reshape(self.grid.shape, order="F") for c in a.reshape(3, -1)])
+
+    def __repr__(self):
+        return f"DisplacementField({self.grid!r})"
+
+
+class DeformableRegistration:
+    """What refine_registration returns.  field: the DisplacementField on the last level's grid; rigid: the transform it started from, as given; residual_init /
+    residual: the RMS of f - m_w on the last level with the rigid transform alone and with the field (over the voxels the mask admits where the fixed level image and
+    the warped moving level image -- unet_vol_warp_field, linear, NaN outside, float64 -- are both numbers); jacobian_min, jacobian_max, folded: of the final field;
+    history: one dict per level (spacing, shape, iterations, residual_start, residual, voxels); seconds.  resample() is the field's."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def resample(self, moving, kind="volume", order=None, **kw):
+        return self.field.resample(moving, kind, order, **kw)
+
+    def __repr__(self):
+        return (f"DeformableRegistration(residual={self.residual:.2f} from {self.residual_init:.2f}, jacobian=[{self.jacobian_min:.3f}, {self.jacobian_max:.3f}], "
+                f"folded={self.folded})")
+
+
+def refine_registration(fixed, moving, rigid, levels_mm=DEFORM_LEVELS_MM, iterations=DEFORM_ITERATIONS, field_sigma=1.5, image_sigma=1.0, max_step=1.0, mask=None,
+                        fixed_affine=None, moving_affine=None, fixed_shape=None, moving_shape=None, ops=None):
+    """Refine a rigid registration of a follow-up CT (moving) onto its baseline (fixed) with a dense displacement field, on the device -> DeformableRegistration.  A
+    demons iteration (Thirion's additive force of the squared difference, diffusion-regularised): u <- G_sigma * (u + v), v = d g / (|g|^2 + d^2 / delta^2) with d = f -
+    m(T (p + u)), g the world gradient of f and delta = max_step x the level spacing, which bounds a step to delta / 2.  fixed, moving: as register_volumes takes them;
+    rigid: a Registration, a RigidTransform or a 4 x 4, fixed world -> moving world.  field_sigma, image_sigma and max_step are in level voxels; a sigma of 0 means no
+    smoothing.  mask: on the fixed grid, the voxels that may pull.
+    Per level of levels_mm, coarse to fine: both volumes are put on isotropic grids of the level spacing over their own fields of view (unet_vol_resample_linear,
+    float32; point-sampled, no anti-aliasing filter: the Gaussian comes after), the mask with the nearest kernel; both level images are smoothed with image_sigma; the
+    field starts from zeros, or from the previous level's field put on this level's grid component by component; then iterations[level] times: one
+    unet_vol_demons_step and three unet_vol_smooth_axis passes over the field.  There is no convergence test: the loop is the specification.  The starting values of
+    levels_mm, iterations and the three widths are conventional and not clinically validated.
+    ops: the operations the loop runs over (default: DeformOps(), the device); the tests hand in the numpy restatement.  Every argument error is a ValueError before any
+    device work."""
+    lv, its, wf, wi, step = _check_deform_args(levels_mm, iterations, field_sigma, image_sigma, max_step)
+    T = _world_matrix(rigid)
+    f, m = _resample_source(fixed, None, fixed_affine, fixed_shape), _resample_source(moving, None, moving_affine, moving_shape)
+    fg, mg = _need_oriented(f.grid, "the fixed volume's grid"), _need_oriented(m.grid, "the moving volume's grid")
+    mk = _check_fixed_mask(mask, f.shape)
+    fgrids, mgrids = registration_level_grids(fg, lv), registration_level_grids(mg, lv)
+    for _, g, _ in fgrids + mgrids:
+        _check_volume_dims(g.shape)
+    ops = DeformOps() if ops is None else ops
+    t0 = time.perf_counter()
+    fd, md, mask_dev = ops.upload(f), ops.upload(m), ops.upload_mask(mk, f.shape)
+    eye = np.eye(4)[:3]
+    field = prev = None
+    history = []
+
+    def residual(fl, ml, mv, lmask, W, L, u, g):
+        warped = ops.warp_field(ml, mv, W, L, u, g.shape, None, 1, 1, float("nan"), 0, g.shape, 64)
+        return ops.rms(fl, warped, lmask)
+
+    for (spacing, g, M), (_, gm, Mm), n_it in zip(fgrids, mgrids, its):
+        fl = ops.linear(fd, f.vargs, eye if M is None else M, g.shape)
+        ml = ops.linear(md, m.vargs, eye if Mm is None else Mm, gm.shape)
+        lmask = mask_dev if (mask_dev is None or M is None) else ops.nearest_mask(mask_dev, f.shape, M, g.shape)
+        if wi is not None:
+            for axis in range(3):
+                fl, ml = ops.smooth_axis(fl, 1, g.shape, axis, wi), ops.smooth_axis(ml, 1, gm.shape, axis, wi)
+        fv, mv = (16,) + g.shape + (0, 1.0, 0.0), (16,) + gm.shape + (0, 1.0, 0.0)
+        W = voxel_matrix(g, gm, T)
+        L = _check_mat3((np.linalg.inv(gm.affine) @ T)[:3, :3], "L")
+        Ginv = _check_mat3(np.linalg.inv(g.affine[:3, :3]).T, "Ginv")
+        n = int(np.prod(g.shape))
+        if prev is None:
+            field = ops.zeros(3 * n)
+        else:
+            pn, Mf = int(np.prod(prev.shape)), resample_matrix(prev, g)
+            field = ops.stack([ops.linear(field[c * pn:(c + 1) * pn], (16,) + prev.shape + (0, 1.0, 0.0), Mf, g.shape) for c in range(3)])
+        r_start, _ = residual(fl, ml, mv, lmask, W, L, field, g)
+        for _ in range(n_it):
+            field = ops.demons_step(fl, fv, lmask, ml, mv, W, L, Ginv, step * spacing, field)
+            if wf is not None:
+                for axis in range(3):
+                    field = ops.smooth_axis(field, 3, g.shape, axis, wf)
+        r_end, counted = residual(fl, ml, mv, lmask, W, L, field, g)
+        history.append(dict(spacing=spacing, shape=g.shape, iterations=n_it, residual_start=r_start, residual=r_end, voxels=counted))
+        prev = g
+    r_init, _ = residual(fl, ml, mv, lmask, W, L, ops.zeros(3 * n), prev)
+    det, folded = ops.jacobian(field, prev.shape, np.linalg.inv(prev.affine[:3, :3]))
+    jmin, jmax = ops.minmax(det)
+    ops.sync()
+    return DeformableRegistration(field=DisplacementField(field, prev, rigid, fg, mg), rigid=rigid, residual_init=r_init, residual=history[-1]["residual"], jacobian_min=jmin,
+                                  jacobian_max=jmax, folded=folded, history=history, seconds=time.perf_counter() - t0)
