@@ -937,6 +937,37 @@ int32_t unet_vol_warp_field(unet_ctx*, const void* src, int32_t dtype, int32_t X
                             uint64_t cval_bits, void* dst, int32_t dst_dtype, int32_t X2, int32_t Y2, int32_t Z2, void* stream);
 int32_t unet_vol_jacobian(unet_ctx*, const float* field, int32_t X, int32_t Y, int32_t Z, const double* Ainv, float* det, uint32_t* folded, void* stream);
 
+/* ---- the surface of a mask, a label volume or a scalar volume as a triangle mesh (csrc/kernels_mesh.hip; bit-exact against tests/mesh_oracle.py) ----
+ * Marching tetrahedra on the Freudenthal split of every lattice cell (six tetrahedra per cube, one per axis order; face diagonals agree between neighbouring cubes, so there
+ * is no ambiguous case).  src: a volume [X, Y, Z] in Fortran order.  kind 0: a uint8 mask (dtype 2), inside = non-zero byte, any alignment; kind 1: int32 labels (dtype 8),
+ * inside = label == select, or any non-zero label when select = 0; kind 2: a scalar volume of any of the eight NIfTI codes, decoded as unet_vol_resample_linear decodes it
+ * (scaled, slope, inter), inside = value > iso (a NaN is outside, a value equal to iso is outside).  closed != 0 surrounds the volume with one layer of virtual outside
+ * samples of value pad_value (finite, <= iso), so that a surface that touches the border is closed; the lattice is then [X + 2, Y + 2, Z + 2] and a virtual point lies at
+ * voxel index -1 or n.  There is one vertex per crossed lattice edge, owned by the edge's lower endpoint q with an edge type 0..6 for the directions (1,0,0) (0,1,0) (0,0,1)
+ * (1,1,0) (1,0,1) (0,1,1) (1,1,1); vertex id = rank of (q in Fortran order of the lattice, type); triangles are ordered by (cell, tetrahedron, table order) and wound so
+ * that their normals point out of the inside.  The vertex of an edge lies at voxel coordinate q + t d: t = 0.5 for kinds 0 and 1 and for an edge with a non-finite endpoint,
+ * else t = fl(fl(iso - a) / fl(b - a)), a the value at q and b at q + d; it is stored as float32(((m0 x + m1 y) + m2 z) + m3) per row of M (HOST, 12 doubles, row-major
+ * 3 x 4: the grid's affine, or diag(pixdim)), every float64 operation rounded on its own.  group[t] = the label at the inside endpoint of triangle t's first edge (1 for
+ * kinds 0 and 2).  UNET_E_ARG before any launch, the outputs untouched: a null or misaligned buffer (the volume to its element size, the workspace to 16 bytes, totals to 8,
+ * the outputs to 4), an unknown kind or datatype code, a negative extent or a lattice of 2^31 points or more, a non-finite iso, pad_value or matrix entry, pad_value > iso,
+ * select < 0, a workspace below unet_vol_mesh_ws_bytes, a capacity that is negative or 2^31 or more.  A volume with a zero dimension, or an unpadded one with an extent of 1
+ * (no cells), gives totals (0, 0) and touches nothing else.
+ *   unet_vol_mesh_count    fills ws (one flag byte per lattice point, bit e = edge type e is crossed and both ends exist; one byte per cell, 0..12 triangles; the chunk
+ *                          offsets of both prefix sums) and totals: device int64 [2] = (vertices, triangles).  Integer arithmetic, no atomics: the same bits on every run.
+ *   unet_vol_mesh_emit     the same volume, arguments and ws again, after the host has read totals (and refused 2^31 or more).  vertices: float32 [capacity_v][3];
+ *                          triangles: int32 [capacity_t][3]; groups: int32 [capacity_t] or NULL.  With a capacity below the total exactly `capacity` items are written
+ *                          and nothing past them (unet_vol_surface_distances's rule); a zero capacity writes none and its pointer may be NULL.
+ *   unet_vol_mesh_measure  per triangle, in float64 from the stored float32 vertices a, b, c: area[t] = fl(0.5 sqrt((x_x^2 + x_y^2) + x_z^2)) with x = (b - a) x (c - a), each
+ *                          component fl(fl(u_y v_z) - fl(u_z v_y)); signed_volume[t] = fl(((a_x n_x + a_y n_y) + a_z n_z) / 6) with n = b x c.  Either output may be NULL.  A
+ *                          vertex index outside 0..nv - 1 is never an address: that triangle measures NaN.  The sums are the caller's (unet_vol_group_moments). */
+size_t unet_vol_mesh_ws_bytes(int32_t X, int32_t Y, int32_t Z, int32_t closed);
+int32_t unet_vol_mesh_count(unet_ctx*, const void* src, int32_t kind, int32_t dtype, int32_t X, int32_t Y, int32_t Z, int32_t scaled, double slope, double inter, double iso,
+                            int32_t select, int32_t closed, double pad_value, void* ws, size_t ws_bytes, int64_t* totals, void* stream);
+int32_t unet_vol_mesh_emit(unet_ctx*, const void* src, int32_t kind, int32_t dtype, int32_t X, int32_t Y, int32_t Z, int32_t scaled, double slope, double inter, double iso,
+                           int32_t select, int32_t closed, double pad_value, const double* M, const void* ws, size_t ws_bytes, float* vertices, int64_t capacity_v,
+                           int32_t* triangles, int32_t* groups, int64_t capacity_t, void* stream);
+int32_t unet_vol_mesh_measure(unet_ctx*, const float* vertices, int64_t nv, const int32_t* triangles, int64_t nt, double* area, double* signed_volume, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Model level. Replaces the Keras Model built at T1:853-916 and driven by
  * compile/fit/evaluate/predict (T1:1053-1061, 1101, 1137).  A model is a fixed-shape plan:

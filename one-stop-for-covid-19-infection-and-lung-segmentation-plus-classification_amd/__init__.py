@@ -8,15 +8,18 @@ Public surface:
   render_planes / project_volume / key_slices (Layer, RenderedSheet) -- volume's pictures of a segmented CT, also reachable from the package itself; png_min writes them
   resample_volume / resample_mask / resample_labels / reorient_volume / change_between (Grid, ResampledVolume, VolumeChange) -- volume's resampling onto another grid,
                             also reachable from the package itself
+  extract_surface / lesion_shapes (SurfaceMesh) -- volume's triangle meshes of a mask, a label volume or a scalar volume, also reachable from the package itself;
+                            mesh_min writes them as STL / PLY / OBJ
   engine.HipUNet         -- the HIP backend (libunet_hip.so through the C ABI of include/unet_hip.h)
 Importing this package has no side effects and does not need a GPU; constructing the
 backend does (there is no CPU fallback).
 """
-__all__ = ["runners", "keras_like", "engine", "weights", "data", "volume", "nifti_min", "png_min", "split_lungs", "lung_burden", "LungSides", "LungBurden", "LungSplitError",
+__all__ = ["runners", "keras_like", "engine", "weights", "data", "volume", "nifti_min", "png_min", "mesh_min", "split_lungs", "lung_burden", "LungSides", "LungBurden", "LungSplitError",
            "render_planes", "project_volume", "key_slices", "Layer", "RenderedSheet", "resample_volume", "resample_mask", "resample_labels", "reorient_volume", "change_between",
-           "Grid", "ResampledVolume", "VolumeChange"]
+           "Grid", "ResampledVolume", "VolumeChange", "extract_surface", "lesion_shapes", "SurfaceMesh"]
 _FROM_VOLUME = ("split_lungs", "lung_burden", "LungSides", "LungBurden", "LungSplitError", "render_planes", "project_volume", "key_slices", "Layer", "RenderedSheet",
-                "resample_volume", "resample_mask", "resample_labels", "reorient_volume", "change_between", "Grid", "ResampledVolume", "VolumeChange")
+                "resample_volume", "resample_mask", "resample_labels", "reorient_volume", "change_between", "Grid", "ResampledVolume", "VolumeChange",
+                "extract_surface", "lesion_shapes", "SurfaceMesh")
 
 
 def __getattr__(name):                                              # resolved on first use: importing the package stays free of side effects

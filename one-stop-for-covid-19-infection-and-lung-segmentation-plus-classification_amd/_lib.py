@@ -244,6 +244,11 @@ _PROTOS = {
     "unet_vol_demons_step": (i32, [vp, vp, i32, i32, i32, i32, i32, f64, f64, vp, vp, i32, i32, i32, i32, i32, f64, f64, vp, vp, vp, f64, vp, vp, vp]),
     "unet_vol_warp_field": (i32, [vp, vp, i32, i32, i32, i32, i32, f64, f64, vp, vp, vp, i32, i32, i32, vp, i32, i32, f64, u64, vp, i32, i32, i32, i32, vp]),
     "unet_vol_jacobian": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp]),
+    # the surface of a mask / label volume / scalar volume as a triangle mesh (csrc/kernels_mesh.hip, volume.extract_surface / lesion_shapes); M is a host array of 12 doubles
+    "unet_vol_mesh_ws_bytes": (sz, [i32, i32, i32, i32]),
+    "unet_vol_mesh_count": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, f64, f64, f64, i32, i32, f64, vp, sz, vp, vp]),
+    "unet_vol_mesh_emit": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, f64, f64, f64, i32, i32, f64, vp, vp, sz, vp, i64, vp, vp, i64, vp]),
+    "unet_vol_mesh_measure": (i32, [vp, vp, i64, vp, i64, vp, vp, vp]),
     "unet_model_create": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(vp)]),
     "unet_model_dtype": (i32, [vp]),
     "unet_model_tap_elem_bytes": (i32, [vp, C.c_char_p, i32]),

@@ -30,6 +30,9 @@ the dataset loop around it (T1:390-393, 421-429) and the way back from a predict
                                           for masks and label volumes; Grid, resample_target, resample_matrix: the grids and the matrices between them
     reorient_volume(vol, "RAS")           -> the volume stored under other axis codes (a signed axis permutation, the stored elements kept)
     change_between(mask_a, grid_a, mask_b, grid_b)     -> VolumeChange: persistent / new / resolved voxels and millilitres of two masks on two grids, and their Dice
+    extract_surface(x, iso | select)      -> SurfaceMesh: the surface of a mask, a label volume or a scalar volume as an indexed triangle mesh (marching tetrahedra on the
+                                          device), its area in mm^2, enclosed volume in ml, Euler characteristic; .measure() per group, .write() as STL / PLY / OBJ
+                                          (mesh_min); lesion_shapes(labels, n): area, volume, sphericity per lesion; segment_volume(mesh=True) fills res.mesh
     register_volumes(fixed, moving)       -> Registration: the rigid transform (RigidTransform) that takes a baseline CT's world onto a follow-up's, found by maximising
                                           the mutual information of their joint histogram (joint_histogram, mutual_information) on the device; Registration.resample
                                           and change_between(transform=) then compare the two scans in one frame
@@ -54,7 +57,7 @@ import warnings
 
 import numpy as np
 
-from . import _lib, nifti_min, png_min
+from . import _lib, mesh_min, nifti_min, png_min
 from . import preprocess as PRE
 
 KINDS = ("demo", "lungs", "cts", "infections")
@@ -309,7 +312,8 @@ class VolumeSegmentation:
     density / lung_density: the IntensityStats of the CT under the final mask (per lesion when the lesion table was computed) and under the lung mask (None unless
     segment_volume was given density=);
     per_lung / per_lung_error: the LungBurden of the final mask per lung (None unless segment_volume was given per_lung=) and, when the lungs could not be split, why;
-    sheet: the RenderedSheet of the final mask over the CT (None unless segment_volume was given render=)."""
+    sheet: the RenderedSheet of the final mask over the CT (None unless segment_volume was given render=);
+    mesh / lung_mesh: the SurfaceMesh of the final mask and of the lung mask (None unless segment_volume was given mesh=)."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -1057,7 +1061,7 @@ def _prepare_segmentation(ct, lung_mask, truth, img_size, trim, input_size):
 
 
 def segment_volume(ct, model, lung_mask=None, threshold=0.547, batch_size=32, out_path=None, img_size=512, trim=(0.2, 0.8), min_lesion_ml=None, connectivity=1,
-                   lesions=False, truth=None, postprocess=None, density=None, per_lung=None, render=None):
+                   lesions=False, truth=None, postprocess=None, density=None, per_lung=None, render=None, mesh=None):
     """CT file (or array) -> VolumeSegmentation.  `model`: a UNetModel or a routed.ClusterRoutedModel (only `predict` is used); lung_mask=None: whole-frame
     boxes (the two halves of the frame); boxes are keyed by slice number (box_indexing="slice"); out_path: the mask as .nii / .nii.gz with the CT's geometry.
     min_lesion_ml: connected components (`connectivity` 1, 2, 3 = 6, 18, 26 neighbours) smaller than that are removed on the device before the mask comes to the
@@ -1082,11 +1086,17 @@ def segment_volume(ct, model, lung_mask=None, threshold=0.547, batch_size=32, ou
     default 6) and out_path (a PNG).  After postprocess / min_lesion_ml / per_lung: res.sheet = the RenderedSheet of the key_slices(counts, n) axial planes -- the middle
     slice when no slice holds infection -- followed by one coronal maximum projection of the whole volume; its layers are the final mask, taken from the device (fill 128,
     outline 255, PALETTE_INFECTION), and, with a lung mask, the lungs as an outline only (PALETTE_LUNG).  The sheet does not mark left and right.  seconds["render"]: its
-    time.  None: nothing runs and res.sheet is None."""
+    time.  None: nothing runs and res.sheet is None.
+    mesh: True, or a dict {what: "infection" (default) | "lung" | "both", out_path: an .stl / .ply / .obj file, lesions: bool}.  After render: res.mesh = the
+    SurfaceMesh (extract_surface, closed) of the final mask, taken from the device, in the CT's world frame (its affine; "scaled voxel" by its pixdim without one);
+    lesions=True labels the final mask (`connectivity`) and meshes the labels with groups, res.mesh.lesions = lesion_shapes' table, its rows aligned with res.lesions;
+    res.lung_mesh = the mesh of the lung mask for what "lung" / "both" (needs lung_mask: ValueError before any device work).  out_path receives the infection mesh (the
+    lung mesh for what="lung"; with "both" the lung mesh goes to <stem>_lung<suffix>).  seconds["mesh"]: its time.  None: nothing runs, both fields are None."""
     _check_connectivity(connectivity)
     density = _check_density(density)
     per_lung = _check_per_lung(per_lung, lung_mask)
     render = _check_render(render)
+    mesh = _check_mesh(mesh, lung_mask)
     if postprocess is not None:
         _check_steps(postprocess, (1.0, 1.0, 1.0))                   # the steps' own arguments, before any work (the CT's pixdim takes this one's place below)
     torch = _torch()
@@ -1099,13 +1109,13 @@ def segment_volume(ct, model, lung_mask=None, threshold=0.547, batch_size=32, ou
     canvas = paste_back(prob, R1, R2, S)
     mask_dev, counts_dev = unslice(canvas, threshold, (X, Y, Z), z0, z1)
     return _finish_segmentation(vol, lv, truth_mask, mask_dev, counts_dev, z0, z1, has, info, threshold, sec, t0, postprocess, min_lesion_ml, lesions, connectivity, out_path,
-                                density=density, per_lung=per_lung, render=render)
+                                density=density, per_lung=per_lung, render=render, mesh=mesh)
 
 
 def _finish_segmentation(vol, lv, truth_mask, mask_dev, counts_dev, z0, z1, has, info, threshold, sec, t0, postprocess, min_lesion_ml, lesions, connectivity, out_path,
-                         density=None, per_lung=None, render=None, **extra):
+                         density=None, per_lung=None, render=None, mesh=None, **extra):
     """What segment_volume and segment_volume_ensemble do with the mask volume once it is formed (mask_dev, counts_dev [z1 - z0], both on the device): postprocess,
-    min_lesion_ml / lesions, density (the checked keyword arguments of intensity_stats, or None), per_lung (those of split_lungs, or None), render (those of the sheet, or None), truth, the download, the lung share and out_path -> VolumeSegmentation (+ `extra` fields).  t0: when the paste-back began."""
+    min_lesion_ml / lesions, density (the checked keyword arguments of intensity_stats, or None), per_lung (those of split_lungs, or None), render (those of the sheet, or None), mesh (the checked dict of _check_mesh, or None), truth, the download, the lung share and out_path -> VolumeSegmentation (+ `extra` fields).  t0: when the paste-back began."""
     torch = _torch()
     X, Y, Z = vol.raw.shape
     voxel_mm3 = float(np.prod(np.asarray(vol.pixdim, np.float64)))          # count * prod(pixdim) / 1000 = millilitres
@@ -1186,6 +1196,11 @@ def _finish_segmentation(vol, lv, truth_mask, mask_dev, counts_dev, z0, z1, has,
             over.append(Layer((lv.get_fdata() != 0).astype(np.uint8), PALETTE_LUNG, 0, 255))
         sheet = render_planes(vol, [("axial", z) for z in keys] + [("mip", "coronal", 0, Y)], over, shape=(X, Y, Z), **kw)
         torch.cuda.synchronize(); sec["render"] = time.perf_counter() - tr
+    surf, lung_surf = None, None
+    if mesh is not None:
+        torch.cuda.synchronize(); tm = time.perf_counter()
+        surf, lung_surf = _segmentation_meshes(mesh, vol, lv, mask_dev, (X, Y, Z), connectivity)
+        torch.cuda.synchronize(); sec["mesh"] = time.perf_counter() - tm
     score = None
     if truth_mask is not None:
         torch.cuda.synchronize(); ts = time.perf_counter()
@@ -1198,7 +1213,7 @@ def _finish_segmentation(vol, lv, truth_mask, mask_dev, counts_dev, z0, z1, has,
                              total_ml=float(counts.sum()) * voxel_mm3 / 1000.0, lung_ml=None,
                              infected_share=None, fell_through=[int(i) for i in np.nonzero(~has)[0]], flat=info["flat"], z0=z0, z1=z1, pixdim=vol.pixdim,
                              threshold=float(threshold), seconds=sec, lesions=table, n_lesions=None if table is None else len(table), removed_ml=removed_ml, score=score,
-                             postprocess_ml=postprocess_ml, density=dens, lung_density=lung_dens, per_lung=burden, per_lung_error=burden_error, sheet=sheet, **extra)
+                             postprocess_ml=postprocess_ml, density=dens, lung_density=lung_dens, per_lung=burden, per_lung_error=burden_error, sheet=sheet, mesh=surf, lung_mesh=lung_surf, **extra)
     if lv is not None:
         lung_vox = int(np.count_nonzero(lv.get_fdata()[:, :, z0:z1]))
         res.lung_ml = lung_vox * voxel_mm3 / 1000.0
@@ -1457,19 +1472,20 @@ def _predict_device(model, x, batch_size):
 
 def segment_volume_ensemble(ct, models, tta=("id",), combine="mean", weights=None, lung_mask=None, threshold=0.547, batch_size=32, out_path=None, img_size=512,
                             trim=(0.2, 0.8), min_lesion_ml=None, connectivity=1, lesions=False, truth=None, postprocess=None, return_prob=False, prob_path=None,
-                            votes_path=None, density=None, per_lung=None, render=None):
+                            votes_path=None, density=None, per_lung=None, render=None, mesh=None):
     """segment_volume with several members: every (model, symmetry) pair of `models` (each anything segment_volume accepts, all of one input size) and `tta` (names of
     TTA, no repeats), in model-major order, at most 32.  A member sees the prepared batch under its symmetry (transformed once, on the device), its probabilities are
     transformed back, pasted onto the canvas and (a) thresholded into the member's mask, which becomes one bit of a vote word per voxel, (b) added into the weighted
     mean canvas: acc = w_0 c_0, acc = acc + w_m c_m in member order, then acc / wsum, every float32 operation rounded on its own (weights: one per model, None: all 1;
     wsum: the float32 sum of the member weights in order).  combine="mean": the final mask is the thresholded mean probability; "majority" / "any" / "all" / int k: the
-    members' masks voted (vote_volume's rules).  Everything after the mask is formed -- postprocess, min_lesion_ml, lesions, density, per_lung, truth, out_path, the lung share -- is
+    members' masks voted (vote_volume's rules).  Everything after the mask is formed -- postprocess, min_lesion_ml, lesions, density, per_lung, render, mesh, truth, out_path, the lung share -- is
     segment_volume's, and so are the result's fields.  Added: members [(model index, tta name)], votes (uint8 [X, Y, Z]: how many members marked the voxel),
     member_ml, pairwise_dice, vote_hist (voxels with k votes), unanimous_ml (all members), uncertain_ml (some but not all), combine, seconds["members"] (predict time per
     member), and prob (float32 [X, Y, Z], the mean probability in patient space) with return_prob=True or prob_path (None otherwise).  prob_path / votes_path: those two
     volumes as .nii / .nii.gz with the CT's header.  The vote statistics describe the members' masks at `threshold` in both modes (combine="mean" counts them under the
     majority rule).  One member ("id",) with combine="mean" and weight 1 is segment_volume bit for bit.  Under data parallelism every rank runs every member."""
     _check_connectivity(connectivity)
+    mesh = _check_mesh(mesh, lung_mask)
     models, members, mw, wsum, min_votes, d = _check_ensemble(models, tta, combine, weights)
     density = _check_density(density)
     per_lung = _check_per_lung(per_lung, lung_mask)
@@ -1520,7 +1536,7 @@ def segment_volume_ensemble(ct, models, tta=("id",), combine="mean", weights=Non
                  vote_hist=st["hist"], unanimous_ml=float(st["unanimous_voxels"]) * voxel_ml, uncertain_ml=float(st["uncertain_voxels"]) * voxel_ml, combine=combine,
                  weights=mw, prob=prob)
     res = _finish_segmentation(vol, lv, truth_mask, mask_dev, counts_dev, z0, z1, has, info, threshold, sec, t0, postprocess, min_lesion_ml, lesions, connectivity, out_path,
-                               density=density, per_lung=per_lung, render=render, **extra)
+                               density=density, per_lung=per_lung, render=render, mesh=mesh, **extra)
     if prob_path is not None:
         nifti_min.write(prob_path, prob, vol.header)
     if votes_path is not None:
@@ -3720,3 +3736,285 @@ def refine_registration(fixed, moving, rigid, levels_mm=DEFORM_LEVELS_MM, iterat
     ops.sync()
     return DeformableRegistration(field=DisplacementField(field, prev, rigid, fg, mg), rigid=rigid, residual_init=r_init, residual=history[-1]["residual"], jacobian_min=jmin,
                                   jacobian_max=jmax, folded=folded, history=history, seconds=time.perf_counter() - t0)
+
+
+# ---- the surface of a mask, a label volume or a scalar volume as a triangle mesh (csrc/kernels_mesh.hip) ---------------------------------------
+# Marching tetrahedra on the Freudenthal split of every lattice cell: an indexed, consistently wound mesh whose vertices, triangle order and float32 coordinates are defined
+# bit for bit by tests/mesh_oracle.py.  The surface has the topology of the lattice's 14-neighbourhood (6 axis neighbours, 6 face diagonals of one orientation, 2 body
+# diagonals): two lesions that touch along such a diagonal share a surface.  The mesh of a BINARY mask is a staircase: its area is 26-27 % above a sphere's at every
+# radius (it does not converge) and the sphericity of a binary ball is about 0.79, not 1; meshing a probability volume (segment_volume_ensemble's prob) at the threshold is
+# the smooth alternative.  The shape figures are conventional, configurable (iso, pixdim / affine) and NOT clinically validated.
+MESH_KINDS = ("mask", "labels", "scalar")
+MESH_WHAT = ("infection", "lung", "both")
+_MESH_KEYS = {"what", "out_path", "lesions"}
+SHAPE_DTYPE = np.dtype([("label", np.int64), ("triangles", np.int64), ("area_mm2", np.float64), ("mesh_ml", np.float64), ("sphericity", np.float64),
+                        ("surface_to_volume", np.float64)])
+
+
+def shape_descriptors(area_mm2, volume_mm3):
+    """-> (sphericity = pi^(1/3) (6 V)^(2/3) / A, surface_to_volume = A / V in 1 / mm), nan where the area or the volume is not positive"""
+    a, v = np.asarray(area_mm2, np.float64), np.asarray(volume_mm3, np.float64)
+    with np.errstate(all="ignore"):
+        sph = np.where((a > 0) & (v > 0), np.pi ** (1.0 / 3.0) * np.power(6.0 * np.abs(v), 2.0 / 3.0) / a, np.nan)
+        s2v = np.where(v > 0, a / v, np.nan)
+    return sph, s2v
+
+
+class SurfaceMesh:
+    """vertices: float32 [nv, 3] (numpy, or the device tensor with return_device=True), in the frame named by `frame`: "world" (RAS+ millimetres of the grid's affine) or
+    "scaled voxel" (voxel index times pixdim: the volume carried no orientation, and left and right are not guessed); triangles: int32 [nt, 3], wound so that normals point
+    out of the inside; groups: int32 [nt] (the label at the inside end of the triangle's first edge) or None; closed: whether the volume was padded with a layer of outside
+    samples; euler: nv - nt / 2 for a closed mesh (2 per sphere-like component, 0 for a torus), else None; area_mm2: the sum of the triangle areas; volume_ml: the sum of
+    the signed volumes / 1000; group_ids / group_triangles / group_area_mm2 / group_volume_ml: the same per group (one group, 1, without groups=True; volume_mm3 / group_volume_mm3: the sums before the division); kind: "mask" |
+    "labels" | "scalar"; iso; launches: the kernel calls made; seconds."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def measure(self):
+        """-> SHAPE_DTYPE rows, one per group: label, triangles, area_mm2, mesh_ml, sphericity, surface_to_volume"""
+        t = np.zeros(len(self.group_ids), SHAPE_DTYPE)
+        t["label"], t["triangles"], t["area_mm2"] = self.group_ids, self.group_triangles, self.group_area_mm2
+        t["mesh_ml"] = self.group_volume_ml
+        t["sphericity"], t["surface_to_volume"] = shape_descriptors(self.group_area_mm2, self.group_volume_mm3)
+        return t
+
+    def _host(self, a):
+        return a if a is None or isinstance(a, np.ndarray) else a.cpu().numpy()
+
+    def write(self, path):
+        """the mesh as .stl (binary), .ply (binary_little_endian, with the groups as a face property) or .obj, by the suffix"""
+        mesh_min.write(path, self._host(self.vertices), self._host(self.triangles), self._host(self.groups))
+
+    def __repr__(self):
+        return (f"SurfaceMesh({len(self.vertices)} vertices, {len(self.triangles)} triangles, frame={self.frame!r}, closed={self.closed}, euler={self.euler}, "
+                f"area_mm2={self.area_mm2:.6g}, volume_ml={self.volume_ml:.6g})")
+
+
+def _mesh_kind(x, iso, select, groups):
+    """mask | labels | scalar from what was given: iso= makes any volume a scalar one; a bool volume is always a mask; without iso a uint8 volume is a mask, any other
+    integer one (and a file, when select= or groups= asks for labels) a label volume, and a float one is refused"""
+    torch = _torch()
+    if isinstance(x, torch.Tensor):
+        kind_of = "b" if x.dtype == torch.bool else ("f" if x.dtype.is_floating_point else "i")
+        u8 = x.dtype == torch.uint8
+    elif isinstance(x, (str, os.PathLike, nifti_min.NiftiVolume)):
+        kind_of, u8 = "file", False
+    else:
+        a = np.asarray(x)
+        kind_of, u8 = ("b" if a.dtype.kind == "b" else ("f" if a.dtype.kind not in "iu" else "i")), a.dtype == np.uint8
+    wants_labels = groups or select != 0
+    if kind_of == "b":
+        if iso is not None:
+            raise ValueError("a mask has no iso value: inside is non-zero")
+        if wants_labels:
+            raise ValueError("select= and groups= need a label volume, not a bool mask")
+        return "mask"
+    if iso is not None:
+        if wants_labels:
+            raise ValueError("select= and groups= need a label volume; iso= describes a scalar volume")
+        return "scalar"
+    if kind_of == "f":
+        raise ValueError("a scalar volume needs iso=: inside is value > iso")
+    if kind_of == "file":
+        return "labels" if wants_labels else "mask"
+    if u8 and not wants_labels:
+        return "mask"
+    return "labels"
+
+
+def _check_mesh_args(kind, iso, select, closed, pad_value, groups):
+    """-> (iso, select, pad_value) as the entry points take them"""
+    if isinstance(select, bool) or not isinstance(select, (int, np.integer)) or select < 0 or select >= 2 ** 31:
+        raise ValueError(f"select is a label (0: every non-zero label), not {select!r}")
+    if not isinstance(closed, (bool, np.bool_)) or not isinstance(groups, (bool, np.bool_)):
+        raise ValueError("closed and groups are True or False")
+    if kind != "scalar":
+        if pad_value is not None:
+            raise ValueError("pad_value belongs to a scalar volume: the virtual layer around a mask is simply outside")
+        return 0.5, int(select), 0.0
+    try:
+        iso = float(iso)
+        pad = iso if pad_value is None else float(pad_value)
+    except (TypeError, ValueError):
+        raise ValueError(f"iso and pad_value are finite numbers, not {iso!r}, {pad_value!r}") from None
+    if not np.isfinite(iso) or not np.isfinite(pad):
+        raise ValueError(f"iso and pad_value are finite numbers, not {iso!r}, {pad_value!r}")
+    if pad > iso:
+        raise ValueError(f"pad_value = {pad} > iso = {iso}: the virtual layer around the volume must be outside")
+    return iso, 0, pad
+
+
+def _check_mesh_lattice(shape, closed):
+    p = 2 if closed else 0
+    if (shape[0] + p) * (shape[1] + p) * (shape[2] + p) >= 2 ** 31:
+        raise ValueError(f"the lattice of a {shape[0]} x {shape[1]} x {shape[2]} volume has 2^31 points or more")
+
+
+def mesh_count_device(dev, kind, vargs, iso, select, closed, pad_value):
+    """unet_vol_mesh_count -> (vertices, triangles, workspace): the two totals on the host and the filled workspace unet_vol_mesh_emit reads"""
+    torch = _torch(); lib, ctx = _ctx()
+    code, X, Y, Z, scaled, slope, inter = vargs
+    ws = torch.empty(max(int(lib.unet_vol_mesh_ws_bytes(X, Y, Z, int(closed))), 16), dtype=torch.uint8, device="cuda")
+    totals = torch.zeros(2, dtype=torch.int64, device="cuda")
+    ctx.check(lib.unet_vol_mesh_count(ctx.handle, dev.data_ptr(), MESH_KINDS.index(kind), code, X, Y, Z, scaled, float(slope), float(inter), float(iso), int(select),
+                                      int(closed), float(pad_value), ws.data_ptr(), ws.numel(), totals.data_ptr(), _stream()), "vol_mesh_count")
+    nv, nt = (int(v) for v in totals.cpu().numpy())
+    return nv, nt, ws
+
+
+def mesh_emit_device(dev, kind, vargs, iso, select, closed, pad_value, M, ws, nv, nt, want_groups=True):
+    """unet_vol_mesh_emit after mesh_count_device -> device tensors (vertices float32 [nv, 3], triangles int32 [nt, 3], groups int32 [nt] or None)"""
+    torch = _torch(); lib, ctx = _ctx()
+    if nv >= 2 ** 31 or nt >= 2 ** 31:
+        raise ValueError(f"a mesh of {nv} vertices and {nt} triangles has 2^31 of either or more")
+    code, X, Y, Z, scaled, slope, inter = vargs
+    m = np.ascontiguousarray(np.asarray(M, np.float64)[:3, :4]).reshape(12)
+    v = torch.empty((nv, 3), dtype=torch.float32, device="cuda")
+    t = torch.empty((nt, 3), dtype=torch.int32, device="cuda")
+    g = torch.empty(nt, dtype=torch.int32, device="cuda") if want_groups else None
+    ctx.check(lib.unet_vol_mesh_emit(ctx.handle, dev.data_ptr(), MESH_KINDS.index(kind), code, X, Y, Z, scaled, float(slope), float(inter), float(iso), int(select),
+                                     int(closed), float(pad_value), m.ctypes.data, ws.data_ptr(), ws.numel(), v.data_ptr() if nv else None, nv,
+                                     t.data_ptr() if nt else None, _ptr(g) if nt else None, nt, _stream()), "vol_mesh_emit")
+    return v, t, g
+
+
+def mesh_measure_device(vertices, triangles):
+    """unet_vol_mesh_measure -> device float64 (area [nt], signed volume [nt]) of the triangles, in the units of the vertices (mm^2, mm^3)"""
+    torch = _torch(); lib, ctx = _ctx()
+    nv, nt = int(vertices.shape[0]), int(triangles.shape[0])
+    area = torch.empty(nt, dtype=torch.float64, device="cuda")
+    vol = torch.empty(nt, dtype=torch.float64, device="cuda")
+    if nt:
+        ctx.check(lib.unet_vol_mesh_measure(ctx.handle, vertices.data_ptr() if nv else None, nv, triangles.data_ptr(), nt, area.data_ptr(), vol.data_ptr(), _stream()),
+                  "vol_mesh_measure")
+    return area, vol
+
+
+def mesh_group_sums(per_triangle, groups):
+    """The two-level sums of unet_vol_group_moments (the same bits on every run) of device float64 [k, nt] quantities: over all triangles, and per group after a stable
+    device sort of the triangle groups -> (totals float64 [k], ids int64 [G], triangles per group int64 [G], sums float64 [k, G]); groups None: one group, 1."""
+    torch = _torch()
+    k, nt = int(per_triangle.shape[0]), int(per_triangle.shape[1])
+    if nt == 0:
+        return np.zeros(k), np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros((k, 0))
+    whole = np.array([0, nt], np.int64)
+    totals = np.array([group_moments_device(per_triangle[i], whole, 1)[0, 0] for i in range(k)], np.float64)
+    if groups is None:
+        return totals, np.array([1], np.int64), np.array([nt], np.int64), totals.reshape(k, 1).copy()
+    sg, perm = torch.sort(groups, stable=True)
+    ids, counts = torch.unique_consecutive(sg, return_counts=True)
+    ids, counts = ids.cpu().numpy().astype(np.int64), counts.cpu().numpy().astype(np.int64)
+    offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    sums = np.stack([group_moments_device(per_triangle[i][perm], offsets, len(ids))[:, 0] for i in range(k)])
+    return totals, ids, counts, sums
+
+
+def extract_surface(x, iso=None, select=0, closed=True, pad_value=None, pixdim=None, affine=None, groups=False, return_device=False, shape=None):
+    """The surface of a volume as a SurfaceMesh, extracted and measured on the device.  x: a mask (bool or uint8: inside = non-zero), a label volume (any other integer
+    dtype: inside = label == select, or every non-zero label with select=0; groups=True keeps the label of every triangle), a scalar volume (iso= required, which makes a
+    volume of ANY dtype a scalar one: inside = value > iso, a NaN is outside, a value equal to iso is outside), a path or a NiftiVolume (a mask, or with select= / groups=
+    a label volume, or with iso= the decoded scalar volume), or a flat Fortran-order device tensor together with shape=(X, Y, Z).  closed=True surrounds the volume with one
+    layer of outside samples (of value pad_value <= iso for a scalar volume, default iso: the cap then lies on the virtual layer), so that a surface that touches the border
+    is closed; closed=False meshes the real cells only.  The frame is the grid's: affine=, else the file's own, else diag(pixdim or the file's pixdim) -- "scaled voxel",
+    and the mesh says so: left and right are never guessed.  Vertex normals, decimation and smoothing are out of scope."""
+    torch = _torch()
+    t0 = time.perf_counter()
+    kind = _mesh_kind(x, iso, select, groups)
+    iso_v, select_v, pad_v = _check_mesh_args(kind, iso, select, closed, pad_value, groups)
+    if kind == "mask" and not isinstance(x, (torch.Tensor, str, os.PathLike, nifti_min.NiftiVolume)):
+        x = np.asarray(x)
+        if x.dtype.kind == "b":
+            x = x.astype(np.uint8)
+    src = _resample_source(x, pixdim, affine, shape, {"mask": "mask", "labels": "labels", "scalar": "volume"}[kind])
+    _check_mesh_lattice(src.shape, closed)
+    dev = src.tensor if src.tensor is not None else upload(src.vol)
+    M = src.grid.affine[:3]
+    nv, nt, ws = mesh_count_device(dev, kind, src.vargs, iso_v, select_v, closed, pad_v)
+    v, t, g = mesh_emit_device(dev, kind, src.vargs, iso_v, select_v, closed, pad_v, M, ws, nv, nt, want_groups=bool(groups))
+    del ws
+    area, vol = mesh_measure_device(v, t)
+    totals, ids, counts, sums = mesh_group_sums(torch.stack([area, vol]), g)
+    launches = ["vol_mesh_count", "vol_mesh_emit"] + (["vol_mesh_measure", "vol_group_moments"] if nt else [])
+    if not return_device:
+        torch.cuda.synchronize()
+        v, t, g = v.cpu().numpy(), t.cpu().numpy(), (None if g is None else g.cpu().numpy())
+    return SurfaceMesh(vertices=v, triangles=t, groups=g, frame="world" if src.grid.oriented else "scaled voxel", closed=bool(closed),
+                       euler=(nv - nt // 2) if closed else None, area_mm2=float(totals[0]), volume_ml=float(totals[1]) / 1000.0, group_ids=ids, group_triangles=counts,
+                       group_area_mm2=sums[0], group_volume_mm3=sums[1], group_volume_ml=sums[1] / 1000.0, volume_mm3=float(totals[1]), kind=kind, iso=(iso_v if kind == "scalar" else None), matrix=np.array(M, np.float64),
+                       grid=src.grid, launches=launches, seconds=time.perf_counter() - t0)
+
+
+def lesion_shapes(labels, n, pixdim=None, affine=None, shape=None, return_mesh=False):
+    """One extract_surface(labels, groups=True) call over a label volume (what label_volume returned: numpy [X, Y, Z], or the device tensor with shape=) -> SHAPE_DTYPE
+    rows keyed like component_table, label 1..n: triangles, area_mm2, mesh_ml (the volume the closed surface encloses), sphericity, surface_to_volume.  Two lesions that
+    touch along a diagonal of the lattice's 14-neighbourhood share one surface: every triangle still belongs to the label on its inside, but each label's patch is then
+    open -- its area stays right, its mesh_ml and sphericity are those of an open patch and depend on the frame's origin.  Labels of label_volume(connectivity=3) never
+    touch that way: every lesion's surface is closed.  A label outside 1..n is an error; a label without voxels has zeros and nan.  return_mesh=True: (table, SurfaceMesh)."""
+    torch = _torch()
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 0:
+        raise ValueError(f"n is the number of labels, not {n!r}")
+    if not isinstance(labels, torch.Tensor):
+        a = np.asarray(labels) if not isinstance(labels, (str, os.PathLike, nifti_min.NiftiVolume)) else None
+        if a is not None and (a.ndim != 3 or a.dtype.kind not in "iu"):
+            raise ValueError(f"labels are an integer [X, Y, Z] volume, not {a.dtype} with {a.ndim} dimensions")
+        if a is not None and a.dtype == np.uint8:
+            labels = a.astype(np.int32)
+    elif labels.dtype != torch.int32:
+        raise ValueError("device labels are an int32 tensor")
+    mesh = extract_surface(labels, groups=True, pixdim=pixdim, affine=affine, shape=shape)
+    if len(mesh.group_ids) and (mesh.group_ids.min() < 1 or mesh.group_ids.max() > n):
+        raise ValueError(f"the volume holds labels outside 1..{int(n)}")
+    table = np.zeros(int(n), SHAPE_DTYPE)
+    table["label"] = np.arange(1, int(n) + 1)
+    table["sphericity"] = table["surface_to_volume"] = np.nan
+    if len(mesh.group_ids):
+        table[mesh.group_ids - 1] = mesh.measure()
+    return (table, mesh) if return_mesh else table
+
+
+def _check_mesh(mesh, lung_mask):
+    """segment_volume's mesh= -> None (off) or the checked dict {what, out_path, lesions}"""
+    if mesh is None or mesh is False:
+        return None
+    kw = {} if mesh is True else (dict(mesh) if isinstance(mesh, dict) else None)
+    if kw is None:
+        raise ValueError(f"mesh is True or a dict with {sorted(_MESH_KEYS)}, not {mesh!r}")
+    if set(kw) - _MESH_KEYS:
+        raise ValueError(f"mesh takes {sorted(_MESH_KEYS)}, not {sorted(set(kw) - _MESH_KEYS)}")
+    kw.setdefault("what", "infection"); kw.setdefault("out_path", None); kw.setdefault("lesions", False)
+    if kw["what"] not in MESH_WHAT:
+        raise ValueError(f"mesh: what is one of {list(MESH_WHAT)}, not {kw['what']!r}")
+    if kw["what"] != "infection" and lung_mask is None:
+        raise ValueError(f"mesh: what={kw['what']!r} needs lung_mask")
+    if not isinstance(kw["lesions"], (bool, np.bool_)):
+        raise ValueError("mesh: lesions is True or False")
+    if kw["out_path"] is not None:
+        mesh_min.format_of(kw["out_path"])
+    return kw
+
+
+def _lung_mesh_path(path):
+    root, ext = os.path.splitext(os.fspath(path))
+    return root + "_lung" + ext
+
+
+def _segmentation_meshes(kw, vol, lv, mask_dev, shape, connectivity):
+    """the mesh= step of _finish_segmentation -> (mesh of the final mask or None, lung mesh or None); the frame is the CT's affine, else its pixdim"""
+    where = dict(affine=vol.affine) if vol.affine is not None else dict(pixdim=vol.pixdim)
+    mesh, lung = None, None
+    if kw["what"] in ("infection", "both"):
+        if kw["lesions"]:
+            own, n_own = label_device(mask_dev, shape, connectivity)
+            table, mesh = lesion_shapes(own, n_own, shape=shape, return_mesh=True, **where)
+            mesh.lesions = table
+            del own
+        else:
+            mesh = extract_surface(mask_dev, shape=shape, **where)
+        if kw["out_path"] is not None:
+            mesh.write(kw["out_path"])
+    if kw["what"] in ("lung", "both"):
+        lung = extract_surface((lv.get_fdata() != 0).astype(np.uint8), **where)
+        if kw["out_path"] is not None:
+            lung.write(kw["out_path"] if kw["what"] == "lung" else _lung_mesh_path(kw["out_path"]))
+    return mesh, lung
