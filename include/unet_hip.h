@@ -968,6 +968,44 @@ int32_t unet_vol_mesh_emit(unet_ctx*, const void* src, int32_t kind, int32_t dty
                            int32_t* triangles, int32_t* groups, int64_t capacity_t, void* stream);
 int32_t unet_vol_mesh_measure(unet_ctx*, const float* vertices, int64_t nv, const int32_t* triangles, int64_t nt, double* area, double* signed_volume, void* stream);
 
+/* ---- every lesion from a baseline to its follow-up (csrc/kernels_track.hip; exact against tests/track_oracle.py; tracking.py) ----
+ * labels_a, labels_b: two int32 label volumes [X, Y, Z] in Fortran order on ONE grid, 4-byte aligned, with lesions 1..n_a and 1..n_b (unet_vol_label); a label outside 0..n
+ * counts as 0 and is never an address.  UNET_E_ARG before any launch, the outputs untouched: n_a or n_b negative, a negative extent or 2^31 voxels or more, a null or
+ * misaligned buffer, and what each entry adds below.  A volume with a zero dimension is UNET_OK with the outputs in their empty state.  Integer arithmetic only; no
+ * workgroup waits for another one; every sum is an integer that leaves as an integer atomic: the same bits on every run.  A lane takes four voxels with one 16-byte load per
+ * volume when both label pointers are 16-byte aligned, voxel by voxel otherwise and in the last N % 4 voxels.
+ *
+ * unet_vol_label_pairs: the sparse contingency table.  The key of a voxel is ((uint64)a << 32) | (uint32)b; the pair (0, 0) is not counted (its key, 0, marks an empty slot),
+ * (a, 0) and (0, b) are: the row and column sums of the table are the lesion sizes.  keys (uint64) and counts (int64) are an open-addressing table of `capacity` slots,
+ * a power of two in 16 .. 2^30 (anything else: UNET_E_ARG), 8-byte aligned; keys, counts and info are cleared on the stream first.  A pair claims a slot with a 64-bit
+ * compare-and-swap on keys and adds to counts[slot] with a 64-bit atomic; a slot's key is written once and never changes.  Probing is linear from the top bits of
+ * key * 0x9E3779B97F4A7C15, at most `capacity` probes: a table loaded to exactly 1.0 completes, a full one never spins.
+ *   info: device int64 [3] = occupied slots, voxels that found no slot (0: the table is complete), voxels with either label non-zero;
+ *         sum(counts) + info[1] == info[2] always.
+ * WHICH slot a pair lands in is unspecified (it depends on who claims first), and so is which pairs got in when the table overflows: callers sort by key, and call again
+ * with a larger table when info[1] != 0.  A workgroup walks a contiguous range of chunks of UNET_VOL_PAIRS_CHUNK voxels and counts in an LDS table of
+ * UNET_VOL_PAIRS_LDS_SLOTS slots first (64-bit key, 32-bit count, 16 probes; a pair that finds no slot there goes straight to the global table), flushed when its range ends.
+ * The lanes of a wave that share the leading lane's pair are summed with shuffles and sent as one add (two rounds), the rest per lane.
+ *
+ * unet_vol_track_map: lut_a / lut_b (int32) and cls_a / cls_b (uint8) are DEVICE tables of n + 1 entries; entry 0 is read as 0 whatever it holds.  Per voxel
+ *   track_a = lut_a[a], track_b = lut_b[b], cls = 3 where a > 0 and b > 0, cls_a[a] where only a > 0, cls_b[b] where only b > 0, 0 elsewhere.
+ * cls (uint8, not a label volume's own buffer), track_a, track_b (int32) and per_slice may each be null -- a null output is not written -- but not all four (UNET_E_ARG); a
+ * table may be null when no output reads it or its n is 0.  per_slice: int64 [Z][6], overwritten: the voxels of every class 0..5 per axial slice, summed per lane, per wave
+ * (shuffles) and per workgroup in LDS, leaving as 64-bit atomics when the workgroup's slice changes.  A class value above 5 in entries 1..n of a class table is UNET_E_ARG:
+ * when cls or per_slice is asked for, the entry point copies both class tables to the host and synchronises the stream before it writes anything. */
+#define UNET_VOL_PAIRS_CHUNK 4096
+#define UNET_VOL_PAIRS_LDS_SLOTS 1024
+#define UNET_TRACK_CLS_NONE 0
+#define UNET_TRACK_CLS_RESOLVED 1      /* a lesion of a alone that has no partner */
+#define UNET_TRACK_CLS_SHRINKAGE 2     /* a alone, inside a lesion that persists */
+#define UNET_TRACK_CLS_BOTH 3          /* present in both */
+#define UNET_TRACK_CLS_GROWTH 4        /* b alone, inside a lesion that persists */
+#define UNET_TRACK_CLS_NEW 5           /* a lesion of b alone that has no partner */
+int32_t unet_vol_label_pairs(unet_ctx*, const int32_t* labels_a, int32_t n_a, const int32_t* labels_b, int32_t n_b, int32_t X, int32_t Y, int32_t Z, uint64_t* keys,
+                             int64_t* counts, int64_t capacity, int64_t* info, void* stream);
+int32_t unet_vol_track_map(unet_ctx*, const int32_t* labels_a, int32_t n_a, const int32_t* labels_b, int32_t n_b, int32_t X, int32_t Y, int32_t Z, const int32_t* lut_a,
+                           const int32_t* lut_b, const uint8_t* cls_a, const uint8_t* cls_b, uint8_t* cls, int32_t* track_a, int32_t* track_b, int64_t* per_slice, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Model level. Replaces the Keras Model built at T1:853-916 and driven by
  * compile/fit/evaluate/predict (T1:1053-1061, 1101, 1137).  A model is a fixed-shape plan:

@@ -10,20 +10,27 @@ Public surface:
                             also reachable from the package itself
   extract_surface / lesion_shapes (SurfaceMesh) -- volume's triangle meshes of a mask, a label volume or a scalar volume, also reachable from the package itself;
                             mesh_min writes them as STL / PLY / OBJ
+  track_lesions / track_series / label_pairs / match_lesions (LesionTracking, LesionSeries, LesionMatch, PALETTE_CHANGE) -- tracking's per-lesion follow-up: every lesion
+                            of a baseline matched to the follow-up's (persistent / merged / split / complex / new / resolved), also reachable from the package itself
   engine.HipUNet         -- the HIP backend (libunet_hip.so through the C ABI of include/unet_hip.h)
 Importing this package has no side effects and does not need a GPU; constructing the
 backend does (there is no CPU fallback).
 """
 __all__ = ["runners", "keras_like", "engine", "weights", "data", "volume", "nifti_min", "png_min", "mesh_min", "split_lungs", "lung_burden", "LungSides", "LungBurden", "LungSplitError",
            "render_planes", "project_volume", "key_slices", "Layer", "RenderedSheet", "resample_volume", "resample_mask", "resample_labels", "reorient_volume", "change_between",
-           "Grid", "ResampledVolume", "VolumeChange", "extract_surface", "lesion_shapes", "SurfaceMesh"]
+           "Grid", "ResampledVolume", "VolumeChange", "extract_surface", "lesion_shapes", "SurfaceMesh", "tracking", "track_lesions", "track_series", "label_pairs", "match_lesions",
+           "LesionTracking", "LesionSeries", "LesionMatch", "PALETTE_CHANGE"]
 _FROM_VOLUME = ("split_lungs", "lung_burden", "LungSides", "LungBurden", "LungSplitError", "render_planes", "project_volume", "key_slices", "Layer", "RenderedSheet",
                 "resample_volume", "resample_mask", "resample_labels", "reorient_volume", "change_between", "Grid", "ResampledVolume", "VolumeChange",
                 "extract_surface", "lesion_shapes", "SurfaceMesh")
+_FROM_TRACKING = ("track_lesions", "track_series", "label_pairs", "match_lesions", "LesionTracking", "LesionSeries", "LesionMatch", "PALETTE_CHANGE")
 
 
 def __getattr__(name):                                              # resolved on first use: importing the package stays free of side effects
     if name in _FROM_VOLUME:
         import importlib
         return getattr(importlib.import_module(__name__ + ".volume"), name)
+    if name in _FROM_TRACKING:
+        import importlib
+        return getattr(importlib.import_module(__name__ + ".tracking"), name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

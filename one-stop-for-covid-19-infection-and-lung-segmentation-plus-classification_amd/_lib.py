@@ -27,6 +27,9 @@ MORPH_MAX_ITERATIONS = 64
 INTENSITY_MAX_EDGES = 63                                              # include/unet_hip.h UNET_VOL_INTENSITY_MAX_EDGES
 JOINT_HIST_MAX_K, JOINT_HIST_MAX_BINS = 16, 64                        # UNET_VOL_JOINT_HIST_MAX_K, UNET_VOL_JOINT_HIST_MAX_BINS
 SMOOTH_MAX_RADIUS = 32                                                # UNET_VOL_SMOOTH_MAX_RADIUS
+PAIRS_CHUNK, PAIRS_LDS_SLOTS = 4096, 1024                             # UNET_VOL_PAIRS_CHUNK, UNET_VOL_PAIRS_LDS_SLOTS
+PAIRS_MIN_CAPACITY, PAIRS_MAX_CAPACITY = 16, 2 ** 30                  # unet_vol_label_pairs: capacity is a power of two in this range
+TRACK_CLS_NONE, TRACK_CLS_RESOLVED, TRACK_CLS_SHRINKAGE, TRACK_CLS_BOTH, TRACK_CLS_GROWTH, TRACK_CLS_NEW = 0, 1, 2, 3, 4, 5          # UNET_TRACK_CLS_*
 MASK_NONE, MASK_RELU, MASK_ELU, MASK_ELU_DROP = 0, 1, 2, 3
 PROG_FWD_TRAIN, PROG_BWD, PROG_FWD_INFER = 0, 1, 2
 SYNC_BN_FWD, SYNC_LOSS, SYNC_BN_BWD, SYNC_GRAD_BUCKET = 0, 1, 2, 3
@@ -249,6 +252,9 @@ _PROTOS = {
     "unet_vol_mesh_count": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, f64, f64, f64, i32, i32, f64, vp, sz, vp, vp]),
     "unet_vol_mesh_emit": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, f64, f64, f64, i32, i32, f64, vp, vp, sz, vp, i64, vp, vp, i64, vp]),
     "unet_vol_mesh_measure": (i32, [vp, vp, i64, vp, i64, vp, vp, vp]),
+    # every lesion from a baseline to its follow-up: the label x label contingency table and the per-voxel maps (csrc/kernels_track.hip, tracking.py)
+    "unet_vol_label_pairs": (i32, [vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, i64, vp, vp]),
+    "unet_vol_track_map": (i32, [vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "unet_model_create": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(vp)]),
     "unet_model_dtype": (i32, [vp]),
     "unet_model_tap_elem_bytes": (i32, [vp, C.c_char_p, i32]),
