@@ -1006,6 +1006,40 @@ int32_t unet_vol_label_pairs(unet_ctx*, const int32_t* labels_a, int32_t n_a, co
 int32_t unet_vol_track_map(unet_ctx*, const int32_t* labels_a, int32_t n_a, const int32_t* labels_b, int32_t n_b, int32_t X, int32_t Y, int32_t Z, const int32_t* lut_a,
                            const int32_t* lut_b, const uint8_t* cls_a, const uint8_t* cls_b, uint8_t* cls, int32_t* track_a, int32_t* track_b, int64_t* per_slice, void* stream);
 
+/* ---- second-order texture of the CT under a mask (csrc/kernels_texture.hip; exact against tests/texture_oracle.py; texture.py) ----
+ * All volumes: [X, Y, Z] in Fortran order, X Y Z < 2^31 (otherwise UNET_E_ARG, nothing launched).  Integer counts by integer atomics only: the same bits on every run.
+ * All count outputs are int64, 8-byte aligned and OVERWRITTEN: the caller does not zero them.  A volume with a zero dimension returns UNET_OK with all counts zero.
+ *
+ * unet_vol_texture_quantize: vox / dtype / X, Y, Z / scaled, slope, inter, labels / mask / n / region: the volume, its decode and its groups exactly as for
+ * unet_vol_intensity_bands (exactly one of labels and mask; a voxel takes part when its group lies in 1..n and region, when given, is non-zero there; a label outside 1..n
+ * is ignored, never an address).  For a non-NaN value v, q = floor(fl(fl(v - lo) / width)), every operation rounded on its own.  outside = 0 (clip): the level is
+ * min(max(q, 0), Ng - 1) + 1, so -inf is level 1 and +inf level Ng; outside = 1 (drop): the voxel takes no part when q < 0 or q >= Ng (the test is on q, not on v).  A NaN
+ * value never takes part.  1 <= Ng <= UNET_VOL_TEXTURE_MAX_LEVELS, lo finite, width finite and > 0, outside 0 or 1: anything else is UNET_E_ARG and nothing is launched.
+ *   levels        device uint8 [X Y Z]: 0 = takes no part, 1..Ng the level.  It alone says whether a voxel takes part: the two counting entries read it and `labels`.
+ *   level_counts  device int64 [n][Ng]: the voxels of group g + 1 at every level (the first-order histogram on the same bins)
+ *
+ * unet_vol_texture_glcm / unet_vol_texture_runs: levels as written above (a level above Ng takes no part), labels int32 or null (null: every taking-part voxel is group 1,
+ * the mask case); a label outside 1..n takes no part.  The 13 directions, in this fixed order, are bits 0..12 of `directions`:
+ *   (1,0,0) (0,1,0) (0,0,1) (1,1,0) (1,-1,0) (1,0,1) (1,0,-1) (0,1,1) (0,1,-1) (1,1,1) (1,1,-1) (1,-1,1) (1,-1,-1)
+ * directions = 0 or a bit above bit 12, Ng outside 1..UNET_VOL_TEXTURE_MAX_LEVELS, n < 0: UNET_E_ARG.
+ *   glcm: counts[g - 1][k][a - 1][b - 1] += 1 for every selected direction k, every voxel p and q = p + distance dir_k inside the volume with levels[p] = a > 0,
+ *   levels[q] = b > 0 and group(p) = group(q) = g.  Not symmetrised: the host forms C + C^T.  1 <= distance <= UNET_VOL_TEXTURE_MAX_DISTANCE.  merge != 0 sums all selected
+ *   directions into one matrix (K = 1); otherwise K = popcount(directions), in ascending bit order.  counts: int64 [n][K][Ng][Ng].  While n K Ng^2 <=
+ *   UNET_VOL_TEXTURE_LDS_COUNTERS a workgroup counts in an int32 table in LDS and leaves one 64-bit atomic per non-zero entry; beyond that every add is a 64-bit atomic.
+ *   runs: along direction k with step 1 a run is a maximal sequence of consecutive voxels with one non-zero level a and one group g; counts[g - 1][k][a - 1][min(len,
+ *   max_run) - 1] += 1 per run, and clamped[g - 1][k] += 1 when len > max_run (the last column then holds longer runs too: repeat with a larger max_run).
+ *   1 <= max_run <= 2^15.  counts: int64 [n][K][Ng][max_run], clamped: int64 [n][K], K = popcount(directions). */
+#define UNET_VOL_TEXTURE_MAX_LEVELS 64
+#define UNET_VOL_TEXTURE_MAX_DISTANCE 4
+#define UNET_VOL_TEXTURE_LDS_COUNTERS 8192
+int32_t unet_vol_texture_quantize(unet_ctx*, const void* vox, int32_t dtype, int32_t X, int32_t Y, int32_t Z, int32_t scaled, double slope, double inter,
+                                  const int32_t* labels, const uint8_t* mask, int32_t n, const uint8_t* region, double lo, double width, int32_t Ng, int32_t outside,
+                                  uint8_t* levels, int64_t* level_counts, void* stream);
+int32_t unet_vol_texture_glcm(unet_ctx*, const uint8_t* levels, const int32_t* labels, int32_t n, int32_t X, int32_t Y, int32_t Z, int32_t Ng, int32_t distance,
+                              int32_t directions, int32_t merge, int64_t* counts, void* stream);
+int32_t unet_vol_texture_runs(unet_ctx*, const uint8_t* levels, const int32_t* labels, int32_t n, int32_t X, int32_t Y, int32_t Z, int32_t Ng, int32_t directions,
+                              int32_t max_run, int64_t* counts, int64_t* clamped, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Model level. Replaces the Keras Model built at T1:853-916 and driven by
  * compile/fit/evaluate/predict (T1:1053-1061, 1101, 1137).  A model is a fixed-shape plan:

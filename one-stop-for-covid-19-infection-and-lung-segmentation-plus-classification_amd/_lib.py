@@ -30,6 +30,8 @@ SMOOTH_MAX_RADIUS = 32                                                # UNET_VOL
 PAIRS_CHUNK, PAIRS_LDS_SLOTS = 4096, 1024                             # UNET_VOL_PAIRS_CHUNK, UNET_VOL_PAIRS_LDS_SLOTS
 PAIRS_MIN_CAPACITY, PAIRS_MAX_CAPACITY = 16, 2 ** 30                  # unet_vol_label_pairs: capacity is a power of two in this range
 TRACK_CLS_NONE, TRACK_CLS_RESOLVED, TRACK_CLS_SHRINKAGE, TRACK_CLS_BOTH, TRACK_CLS_GROWTH, TRACK_CLS_NEW = 0, 1, 2, 3, 4, 5          # UNET_TRACK_CLS_*
+TEXTURE_MAX_LEVELS, TEXTURE_MAX_DISTANCE, TEXTURE_LDS_COUNTERS = 64, 4, 8192          # UNET_VOL_TEXTURE_MAX_LEVELS, UNET_VOL_TEXTURE_MAX_DISTANCE, UNET_VOL_TEXTURE_LDS_COUNTERS
+TEXTURE_MAX_RUN = 2 ** 15                                             # unet_vol_texture_runs: 1 <= max_run <= 2^15
 MASK_NONE, MASK_RELU, MASK_ELU, MASK_ELU_DROP = 0, 1, 2, 3
 PROG_FWD_TRAIN, PROG_BWD, PROG_FWD_INFER = 0, 1, 2
 SYNC_BN_FWD, SYNC_LOSS, SYNC_BN_BWD, SYNC_GRAD_BUCKET = 0, 1, 2, 3
@@ -255,6 +257,10 @@ _PROTOS = {
     # every lesion from a baseline to its follow-up: the label x label contingency table and the per-voxel maps (csrc/kernels_track.hip, tracking.py)
     "unet_vol_label_pairs": (i32, [vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, i64, vp, vp]),
     "unet_vol_track_map": (i32, [vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    # second-order texture of the CT under a mask: grey levels, co-occurrence and run-length matrices (csrc/kernels_texture.hip, texture.py)
+    "unet_vol_texture_quantize": (i32, [vp, vp, i32, i32, i32, i32, i32, f64, f64, vp, vp, i32, vp, f64, f64, i32, i32, vp, vp, vp]),
+    "unet_vol_texture_glcm": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
+    "unet_vol_texture_runs": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
     "unet_model_create": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(vp)]),
     "unet_model_dtype": (i32, [vp]),
     "unet_model_tap_elem_bytes": (i32, [vp, C.c_char_p, i32]),
