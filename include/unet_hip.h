@@ -576,7 +576,11 @@ int32_t unet_cls_head_bwd(unet_ctx*, const float* h, const float* w, const float
 /* ---- image steps in front of the path: byte / integer work, bit-exact against oracle/preprocess_oracle.py ----
  * Replaces: `img = (img - xmin)/(xmax - xmin)` T1:336-337 + `np.uint8(test_img*255)` T1:165-166 (float64 arithmetic, truncation);
  *           `cv2.createCLAHE(clipLimit=3.0, tileGridSize=(8,8)).apply(img)` T1:168-169 (OpenCV clahe.cpp restated; cv2 is not in
- *           this image: parity unpinned); `cts/255` T1:520.  Images are dense [n][h][w] (single channel). */
+ *           this image: parity unpinned); `cts/255` T1:520.  Images are dense [n][h][w] (single channel).
+ * Min-max: an image that holds a NaN comes out all 0, as numpy's propagating min / max make it (so does a constant image: 0 / 0); an infinity zeroes the image
+ * by the arithmetic alone (x / inf = 0, inf / inf = NaN -> 0).
+ * Refusals, nothing launched: a null pointer, n / pixels / count / h / w / tiles < 1, clip_limit < 0, ws_bytes below the _ws_bytes function: UNET_E_ARG; CLAHE on an
+ * image whose reflect-101 padding (`tiles - size % tiles` on both axes as soon as one does not divide) reaches its size: UNET_E_SHAPE. */
 size_t unet_pre_minmax_ws_bytes(int32_t n);
 int32_t unet_pre_minmax_to_u8(unet_ctx*, const float* img, uint8_t* out, int32_t n, int64_t pixels_per_image, void* ws, size_t ws_bytes, void* stream);
 int32_t unet_pre_unit_to_u8(unet_ctx*, const float* img, uint8_t* out, int64_t count, void* stream);
@@ -589,7 +593,9 @@ int32_t unet_pre_clahe_u8(unet_ctx*, const uint8_t* src, uint8_t* dst, int32_t n
  *   `cv2.resize(cts[i], dsize=(new_dim,new_dim), interpolation=cv2.INTER_LINEAR)`    T1:486-488                     (interp = 1)
  * src: dense [n][sh][sw]; rects: HOST array [n][4] = (x, y, w, h) per image in cv2.boundingRect order, or NULL for the whole image;
  * image i is written to the dh x dw window at column dst_x0 of dst[i] (rows of dst_ld bytes), so the two lung crops of a slice
- * land side by side without a concatenate (T1:358).  Interpolation values are cv2's (INTER_LINEAR = 1, INTER_AREA = 3). */
+ * land side by side without a concatenate (T1:358).  Interpolation values are cv2's (INTER_LINEAR = 1, INTER_AREA = 3).
+ * Refusals, nothing launched: a null src / dst, a size < 1, dst_x0 < 0, dst_ld < dst_x0 + dw, another interpolation: UNET_E_ARG; dh dw >= 2^31, or a rectangle that is
+ * empty or leaves the image: UNET_E_SHAPE. */
 enum { UNET_RESIZE_LINEAR = 1, UNET_RESIZE_AREA = 3 };
 int32_t unet_pre_resize_u8(unet_ctx*, const uint8_t* src, int32_t n, int32_t sh, int32_t sw, const int32_t* rects, uint8_t* dst, int32_t dh,
                            int32_t dw, int32_t dst_ld, int32_t dst_x0, int32_t interp, void* stream);
@@ -615,7 +621,9 @@ int32_t unet_pre_contours_u8(unet_ctx*, const uint8_t* host_imgs, int32_t n, int
  *   uniform  int32 [n]: 1 where np.unique(slice).size == 1 on the slice BEFORE the resize       T1:333
  *   minmax   double [n][2]: the resized image's min and max
  * A slice whose resized image has max == min gives what numpy gives: NaN in img_f32, 0 in both uint8 forms.
- * ws: unet_vol_slices_ws_bytes(n, S) bytes, 16-byte aligned; it starts with the resized float64 images [n][S][S] (tests read this stage). */
+ * ws: unet_vol_slices_ws_bytes(n, S) bytes, 16-byte aligned; it starts with the resized float64 images [n][S][S] (tests read this stage).
+ * Refusals, nothing launched (the same codes for unet_vol_unslice): a null vox / ws (canvas / mask / counts), X, Y, Z or S < 1, a datatype code outside the eight, a
+ * voxel buffer off its item size, a workspace too small or off 16 bytes: UNET_E_ARG; a slice range that is empty or leaves [0, Z), S S or X Y >= 2^30: UNET_E_SHAPE. */
 size_t unet_vol_slices_ws_bytes(int32_t n, int32_t S);
 int32_t unet_vol_slices_f64(unet_ctx*, const void* vox, int32_t dtype, int32_t X, int32_t Y, int32_t Z, int32_t scaled, double slope, double inter, int32_t z0,
                             int32_t z1, int32_t S, float* img_f32, uint8_t* img_u8, uint8_t* lung_u8, int32_t* uniform, double* minmax, void* ws, size_t ws_bytes,

@@ -18,14 +18,19 @@ __global__ void minmax_init_kernel(unsigned* mm, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) { mm[2 * i] = 0xFFFFFFFFu; mm[2 * i + 1] = 0u; }
 }
-// per-image min / max: blockIdx.y = image, ordered-integer atomics (exact: min / max do not round)
+// per-image min / max: blockIdx.y = image, ordered-integer atomics (exact: min / max do not round).  numpy's min / max propagate a NaN and fminf / fmaxf drop it:
+// a lane that saw one publishes the key of the positive quiet NaN, which sorts above +inf's, through the same atomicMax -- max = NaN makes the whole image NaN -> 0
 __global__ __launch_bounds__(TPB) void minmax_kernel(const float* __restrict__ img, unsigned* __restrict__ mm, long long pixels) {
   const float* p = img + (long long)blockIdx.y * pixels;
-  float mn = INFINITY, mx = -INFINITY;
-  for (long long i = (long long)blockIdx.x * TPB + threadIdx.x; i < pixels; i += (long long)gridDim.x * TPB) { const float v = p[i]; mn = fminf(mn, v); mx = fmaxf(mx, v); }
+  float mn = INFINITY, mx = -INFINITY; bool nan = false;
+  for (long long i = (long long)blockIdx.x * TPB + threadIdx.x; i < pixels; i += (long long)gridDim.x * TPB) {
+    const float v = p[i];
+    nan |= v != v; mn = fminf(mn, v); mx = fmaxf(mx, v);
+  }
+  unsigned kmn = f2ord(mn), kmx = nan ? f2ord(__uint_as_float(0x7FC00000u)) : f2ord(mx);
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { mn = fminf(mn, __shfl_xor(mn, o, 64)); mx = fmaxf(mx, __shfl_xor(mx, o, 64)); }
-  if ((threadIdx.x & 63) == 0) { atomicMin(mm + 2 * blockIdx.y, f2ord(mn)); atomicMax(mm + 2 * blockIdx.y + 1, f2ord(mx)); }
+  for (int o = 32; o > 0; o >>= 1) { kmn = min(kmn, (unsigned)__shfl_xor((int)kmn, o, 64)); kmx = max(kmx, (unsigned)__shfl_xor((int)kmx, o, 64)); }
+  if ((threadIdx.x & 63) == 0) { atomicMin(mm + 2 * blockIdx.y, kmn); atomicMax(mm + 2 * blockIdx.y + 1, kmx); }
 }
 // np.uint8((img - min)/(max - min) * 255): float64 arithmetic as numpy does on the reference's float64 slices, truncation
 __global__ __launch_bounds__(TPB) void norm_to_u8_kernel(const float* __restrict__ img, const unsigned* __restrict__ mm, uint8_t* __restrict__ out, long long pixels) {
