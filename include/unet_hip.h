@@ -1048,6 +1048,53 @@ int32_t unet_vol_texture_glcm(unet_ctx*, const uint8_t* levels, const int32_t* l
 int32_t unet_vol_texture_runs(unet_ctx*, const uint8_t* levels, const int32_t* labels, int32_t n, int32_t X, int32_t Y, int32_t Z, int32_t Ng, int32_t directions,
                               int32_t max_run, int64_t* counts, int64_t* clamped, void* stream);
 
+/* ---- where the infection sits in the lungs (csrc/kernels_zones.hip; exact against tests/zones_oracle.py; zones.py) ----
+ * All volumes: [X, Y, Z] in Fortran order, X Y Z < 2^31 (otherwise UNET_E_ARG, nothing launched); a volume with a zero dimension returns UNET_OK and touches nothing, the
+ * outputs included.  Integer arithmetic only: a distance (the doubles unet_vol_edt_sq writes, 8-byte aligned) is compared as the order-preserving 64-bit key of its bit
+ * pattern, key(u) = ~u when the sign bit is set, else u | 2^63 -- value order for non-negative values and +inf.  Sums are integers per wave (ballots) and per workgroup in
+ * LDS, then 64-bit atomics; minima and maxima per lane, wave and workgroup, then one atomic: the same bits on every run.  All outputs are overwritten (the caller does not
+ * initialise them).  sides: uint8 0 / 1 / 2, a value above 2 counts as 0.  A lane takes four voxels with one 4-byte load of sides when sides / infection / zone_map are
+ * 4-byte and d2 / labels 16-byte aligned, one voxel otherwise.
+ *
+ * unet_vol_side_extents: box device int32 [2][6], per side value 1 and 2 the inclusive bounding box {x0, x1, y0, y1, z0, z1}; an empty side gives x0 = y0 = z0 = INT32_MAX
+ * and x1 = y1 = z1 = -1.  dmax_key device uint64 [2]: with d2, the largest key of d2 under that side; 0 for an empty side or a null d2 (every key of a real distance is
+ * above 0).  The host turns a key back into a double.
+ *
+ * unet_vol_zone_table: infection uint8, non-zero = infected, nullable; labels int32 with n lesions, nullable, a label outside 1..n is ignored, never an address; n < 0:
+ * UNET_E_ARG; d2 nullable -- then every distance counts as +0.0, every voxel lies in shell 0 and spec->shells must be 1.  spec is a HOST pointer, read before the call
+ * returns.  P = parts[0] parts[1] parts[2], S = shells, B = 2 P S <= UNET_VOL_ZONE_MAX_BINS.  For a voxel of side s (1 or 2) at coordinate c on axis a:
+ *     d_a   = c - lo[s-1][a], or lo[s-1][a] + extent[s-1][a] - 1 - c when flip[a] (the coordinate counted from the other end of the range: the same voxels fall into
+ *             the same part whichever way the axis is stored, also where the extent is no multiple of parts[a]);
+ *     q_a   = clamp(floor(d_a parts[a] / extent[s-1][a]), 0, parts[a] - 1), in 64 bits;
+ *     zone  = q_0 + parts[0] (q_1 + parts[1] q_2);      shell = #{k < S - 1 : key(d2) > key(r2[s-1][k])};      bin = ((s - 1) P + zone) S + shell.
+ * UNET_E_ARG, nothing launched: parts outside 1..8, flip not 0 / 1, an extent < 1, shells outside 1..4, B above the maximum, r2[s][0 .. S-2] not finite, negative or
+ * descending, a zone_map with 2 P > 255, a null or misaligned buffer.  Outputs (device, 8-byte aligned, int64 unless said otherwise):
+ *   table           [B][2]   {lung voxels, infected voxels} of every bin
+ *   outside         [1]      infected voxels under side 0
+ *   lesion_zone     [n][2P]  the voxels of lesion i + 1 per (side, zone), in-lung voxels only            } may be null when n == 0
+ *   lesion_shell    [n][S]   the same per shell                                                          }
+ *   lesion_dmin_key [n]      uint64: the smallest key of d2 over the lesion's in-lung voxels, all ones when it has none   }
+ *   zone_map        uint8 [X Y Z], nullable: 0 off the lungs, else 1 + (s - 1) P + zone
+ * The bin table sits in LDS per workgroup and leaves once; the lanes of a wave that share a bin (a (lesion, bin) pair) are found with one ballot whose first lane adds the
+ * popcount -- the per-lesion tables to LDS while n (2 P + S) <= 4096, straight to the outputs beyond that.  A wave with no lung voxel and no infected voxel reads neither
+ * d2 nor the labels.  17 - 21 bytes read per voxel under the lungs, 1 - 2 elsewhere. */
+#define UNET_VOL_ZONE_MAX_PARTS 8
+#define UNET_VOL_ZONE_MAX_SHELLS 4
+#define UNET_VOL_ZONE_MAX_BINS 1024
+typedef struct unet_zone_spec {
+  int32_t parts[3];        /* equal parts of the bounding range along every voxel axis, 1..8 */
+  int32_t flip[3];         /* 1: the numbering runs against the axis */
+  int32_t lo[2][3];        /* per side: the first coordinate of the divided range */
+  int32_t extent[2][3];    /* per side: its length in voxels, >= 1 */
+  int32_t shells;          /* S, 1..4 */
+  int32_t reserved;        /* 0 */
+  double r2[2][3];         /* per side: the squared radii between the shells, r2[s][0 .. S - 2] */
+} unet_zone_spec;
+int32_t unet_vol_side_extents(unet_ctx*, const uint8_t* sides, const double* d2, int32_t X, int32_t Y, int32_t Z, int32_t* box, uint64_t* dmax_key, void* stream);
+int32_t unet_vol_zone_table(unet_ctx*, const uint8_t* sides, const uint8_t* infection, const int32_t* labels, int32_t n, const double* d2, int32_t X, int32_t Y, int32_t Z,
+                            const unet_zone_spec* spec, int64_t* table, int64_t* outside, int64_t* lesion_zone, int64_t* lesion_shell, uint64_t* lesion_dmin_key,
+                            uint8_t* zone_map, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Model level. Replaces the Keras Model built at T1:853-916 and driven by
  * compile/fit/evaluate/predict (T1:1053-1061, 1101, 1137).  A model is a fixed-shape plan:

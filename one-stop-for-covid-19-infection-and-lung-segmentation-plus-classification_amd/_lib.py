@@ -32,6 +32,7 @@ PAIRS_MIN_CAPACITY, PAIRS_MAX_CAPACITY = 16, 2 ** 30                  # unet_vol
 TRACK_CLS_NONE, TRACK_CLS_RESOLVED, TRACK_CLS_SHRINKAGE, TRACK_CLS_BOTH, TRACK_CLS_GROWTH, TRACK_CLS_NEW = 0, 1, 2, 3, 4, 5          # UNET_TRACK_CLS_*
 TEXTURE_MAX_LEVELS, TEXTURE_MAX_DISTANCE, TEXTURE_LDS_COUNTERS = 64, 4, 8192          # UNET_VOL_TEXTURE_MAX_LEVELS, UNET_VOL_TEXTURE_MAX_DISTANCE, UNET_VOL_TEXTURE_LDS_COUNTERS
 TEXTURE_MAX_RUN = 2 ** 15                                             # unet_vol_texture_runs: 1 <= max_run <= 2^15
+ZONE_MAX_PARTS, ZONE_MAX_SHELLS, ZONE_MAX_BINS = 8, 4, 1024           # UNET_VOL_ZONE_MAX_PARTS, UNET_VOL_ZONE_MAX_SHELLS, UNET_VOL_ZONE_MAX_BINS
 MASK_NONE, MASK_RELU, MASK_ELU, MASK_ELU_DROP = 0, 1, 2, 3
 PROG_FWD_TRAIN, PROG_BWD, PROG_FWD_INFER = 0, 1, 2
 SYNC_BN_FWD, SYNC_LOSS, SYNC_BN_BWD, SYNC_GRAD_BUCKET = 0, 1, 2, 3
@@ -55,6 +56,10 @@ class RenderTile(C.Structure):                                        # unet_ren
 
 class RenderLayer(C.Structure):                                       # unet_render_layer
     _fields_ = [("labels", vp), ("palette", vp), ("dtype", i32), ("palette_size", i32), ("fill_alpha", i32), ("outline_alpha", i32)]
+
+
+class ZoneSpec(C.Structure):                                          # unet_zone_spec
+    _fields_ = [("parts", i32 * 3), ("flip", i32 * 3), ("lo", (i32 * 3) * 2), ("extent", (i32 * 3) * 2), ("shells", i32), ("reserved", i32), ("r2", (f64 * 3) * 2)]
 
 
 # name -> (restype, argtypes); pointers to device memory are passed as void* integers
@@ -261,6 +266,9 @@ _PROTOS = {
     "unet_vol_texture_quantize": (i32, [vp, vp, i32, i32, i32, i32, i32, f64, f64, vp, vp, i32, vp, f64, f64, i32, i32, vp, vp, vp]),
     "unet_vol_texture_glcm": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
     "unet_vol_texture_runs": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
+    # where the infection sits in the lungs: side x zone x depth shell (csrc/kernels_zones.hip, zones.py); spec is a host struct
+    "unet_vol_side_extents": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp]),
+    "unet_vol_zone_table": (i32, [vp, vp, vp, vp, i32, vp, i32, i32, i32, C.POINTER(ZoneSpec), vp, vp, vp, vp, vp, vp, vp]),
     "unet_model_create": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(vp)]),
     "unet_model_dtype": (i32, [vp]),
     "unet_model_tap_elem_bytes": (i32, [vp, C.c_char_p, i32]),

@@ -312,6 +312,8 @@ class VolumeSegmentation:
     density / lung_density: the IntensityStats of the CT under the final mask (per lesion when the lesion table was computed) and under the lung mask (None unless
     segment_volume was given density=);
     per_lung / per_lung_error: the LungBurden of the final mask per lung (None unless segment_volume was given per_lung=) and, when the lungs could not be split, why;
+    distribution / distribution_error: the zones.LungDistribution of the final mask -- where in the lungs it sits -- (None unless segment_volume was given distribution=)
+    and, when the lungs could not be split, why;
     sheet: the RenderedSheet of the final mask over the CT (None unless segment_volume was given render=);
     mesh / lung_mesh: the SurfaceMesh of the final mask and of the lung mask (None unless segment_volume was given mesh=)."""
 
@@ -1061,7 +1063,7 @@ def _prepare_segmentation(ct, lung_mask, truth, img_size, trim, input_size):
 
 
 def segment_volume(ct, model, lung_mask=None, threshold=0.547, batch_size=32, out_path=None, img_size=512, trim=(0.2, 0.8), min_lesion_ml=None, connectivity=1,
-                   lesions=False, truth=None, postprocess=None, density=None, per_lung=None, render=None, mesh=None):
+                   lesions=False, truth=None, postprocess=None, density=None, per_lung=None, render=None, mesh=None, distribution=None):
     """CT file (or array) -> VolumeSegmentation.  `model`: a UNetModel or a routed.ClusterRoutedModel (only `predict` is used); lung_mask=None: whole-frame
     boxes (the two halves of the frame); boxes are keyed by slice number (box_indexing="slice"); out_path: the mask as .nii / .nii.gz with the CT's geometry.
     min_lesion_ml: connected components (`connectivity` 1, 2, 3 = 6, 18, 26 neighbours) smaller than that are removed on the device before the mask comes to the
@@ -1091,10 +1093,16 @@ def segment_volume(ct, model, lung_mask=None, threshold=0.547, batch_size=32, ou
     SurfaceMesh (extract_surface, closed) of the final mask, taken from the device, in the CT's world frame (its affine; "scaled voxel" by its pixdim without one);
     lesions=True labels the final mask (`connectivity`) and meshes the labels with groups, res.mesh.lesions = lesion_shapes' table, its rows aligned with res.lesions;
     res.lung_mesh = the mesh of the lung mask for what "lung" / "both" (needs lung_mask: ValueError before any device work).  out_path receives the infection mesh (the
-    lung mesh for what="lung"; with "both" the lung mesh goes to <stem>_lung<suffix>).  seconds["mesh"]: its time.  None: nothing runs, both fields are None."""
+    lung mesh for what="lung"; with "both" the lung mesh goes to <stem>_lung<suffix>).  seconds["mesh"]: its time.  None: nothing runs, both fields are None.
+    distribution: True, or a dict of zones.lung_zones / lung_distribution keyword arguments (zones, ap_parts, extent, depth, fill, severity_edges, predominance); needs
+    per_lung (ValueError before any work without it).  Right after per_lung, on the sides and the lesion labels it left on the device: res.distribution = the
+    LungDistribution of the final mask -- where in the lungs the infection sits: per region, per depth shell, per lesion (rows aligned with res.lesions when the lesion
+    table is computed), a severity score per region and the words of a report; its zone map is on the host.  When the lungs could not be split res.distribution is None
+    and res.distribution_error holds the reason.  seconds["distribution"]: its time.  None: nothing runs and no other field changes."""
     _check_connectivity(connectivity)
     density = _check_density(density)
     per_lung = _check_per_lung(per_lung, lung_mask)
+    distribution = _check_distribution(distribution, per_lung)
     render = _check_render(render)
     mesh = _check_mesh(mesh, lung_mask)
     if postprocess is not None:
@@ -1109,13 +1117,13 @@ def segment_volume(ct, model, lung_mask=None, threshold=0.547, batch_size=32, ou
     canvas = paste_back(prob, R1, R2, S)
     mask_dev, counts_dev = unslice(canvas, threshold, (X, Y, Z), z0, z1)
     return _finish_segmentation(vol, lv, truth_mask, mask_dev, counts_dev, z0, z1, has, info, threshold, sec, t0, postprocess, min_lesion_ml, lesions, connectivity, out_path,
-                                density=density, per_lung=per_lung, render=render, mesh=mesh)
+                                density=density, per_lung=per_lung, render=render, mesh=mesh, distribution=distribution)
 
 
 def _finish_segmentation(vol, lv, truth_mask, mask_dev, counts_dev, z0, z1, has, info, threshold, sec, t0, postprocess, min_lesion_ml, lesions, connectivity, out_path,
-                         density=None, per_lung=None, render=None, mesh=None, **extra):
+                         density=None, per_lung=None, render=None, mesh=None, distribution=None, **extra):
     """What segment_volume and segment_volume_ensemble do with the mask volume once it is formed (mask_dev, counts_dev [z1 - z0], both on the device): postprocess,
-    min_lesion_ml / lesions, density (the checked keyword arguments of intensity_stats, or None), per_lung (those of split_lungs, or None), render (those of the sheet, or None), mesh (the checked dict of _check_mesh, or None), truth, the download, the lung share and out_path -> VolumeSegmentation (+ `extra` fields).  t0: when the paste-back began."""
+    min_lesion_ml / lesions, density (the checked keyword arguments of intensity_stats, or None), per_lung (those of split_lungs, or None), render (those of the sheet, or None), mesh (the checked dict of _check_mesh, or None), distribution (the checked pair of _check_distribution, or None), truth, the download, the lung share and out_path -> VolumeSegmentation (+ `extra` fields).  t0: when the paste-back began."""
     torch = _torch()
     X, Y, Z = vol.raw.shape
     voxel_mm3 = float(np.prod(np.asarray(vol.pixdim, np.float64)))          # count * prod(pixdim) / 1000 = millilitres
@@ -1143,7 +1151,7 @@ def _finish_segmentation(vol, lv, truth_mask, mask_dev, counts_dev, z0, z1, has,
             table = table[keep[1:]]                                  # the kept components keep their order: renumbered, this is the table of the filtered mask
             table["label"] = np.arange(1, len(table) + 1)
             removed_ml = float(before) * voxel_mm3 / 1000.0 - float(counts_dev.sum().item()) * voxel_mm3 / 1000.0
-        if density is None and per_lung is None:
+        if density is None and per_lung is None:                      # (distribution= needs per_lung=)
             labels_dev = None
         torch.cuda.synchronize(); sec["components"] = time.perf_counter() - tc
     dens, lung_dens = None, None
@@ -1159,6 +1167,7 @@ def _finish_segmentation(vol, lv, truth_mask, mask_dev, counts_dev, z0, z1, has,
             lung_dens = intensity_stats(vol, mask=lv.get_fdata() != 0, **density)
         torch.cuda.synchronize(); sec["density"] = time.perf_counter() - td
     burden, burden_error = None, None
+    distr, distr_error = None, None
     if per_lung is not None:
         torch.cuda.synchronize(); tl = time.perf_counter()
         kw = dict(per_lung)
@@ -1181,9 +1190,18 @@ def _finish_segmentation(vol, lv, truth_mask, mask_dev, counts_dev, z0, z1, has,
             burden = burden_from_tables(totals, les, ps, vol.pixdim)
             if density is not None:
                 burden.density = intensity_stats(vol, labels=ls.sides.to(torch.int32), n=2, shape=(X, Y, Z), **density)
+            sides_dev = ls.sides
             ls.sides = ls.sides.cpu().numpy().reshape((X, Y, Z), order="F")
             burden.sides = ls
         torch.cuda.synchronize(); sec["per_lung"] = time.perf_counter() - tl
+        if distribution is not None:
+            td = time.perf_counter()
+            if burden is None:
+                distr_error = burden_error
+            else:
+                distr = _segmentation_distribution(distribution, ls, sides_dev, mask_dev, labels_dev, n_comp if labels_dev is not None else None, keep, (X, Y, Z), connectivity)
+                del sides_dev
+            torch.cuda.synchronize(); sec["distribution"] = time.perf_counter() - td
     labels_dev = None
     sheet = None
     if render is not None:
@@ -1213,7 +1231,8 @@ def _finish_segmentation(vol, lv, truth_mask, mask_dev, counts_dev, z0, z1, has,
                              total_ml=float(counts.sum()) * voxel_mm3 / 1000.0, lung_ml=None,
                              infected_share=None, fell_through=[int(i) for i in np.nonzero(~has)[0]], flat=info["flat"], z0=z0, z1=z1, pixdim=vol.pixdim,
                              threshold=float(threshold), seconds=sec, lesions=table, n_lesions=None if table is None else len(table), removed_ml=removed_ml, score=score,
-                             postprocess_ml=postprocess_ml, density=dens, lung_density=lung_dens, per_lung=burden, per_lung_error=burden_error, sheet=sheet, mesh=surf, lung_mesh=lung_surf, **extra)
+                             postprocess_ml=postprocess_ml, density=dens, lung_density=lung_dens, per_lung=burden, per_lung_error=burden_error, sheet=sheet, mesh=surf, lung_mesh=lung_surf,
+                             distribution=distr, distribution_error=distr_error, **extra)
     if lv is not None:
         lung_vox = int(np.count_nonzero(lv.get_fdata()[:, :, z0:z1]))
         res.lung_ml = lung_vox * voxel_mm3 / 1000.0
@@ -1472,13 +1491,13 @@ def _predict_device(model, x, batch_size):
 
 def segment_volume_ensemble(ct, models, tta=("id",), combine="mean", weights=None, lung_mask=None, threshold=0.547, batch_size=32, out_path=None, img_size=512,
                             trim=(0.2, 0.8), min_lesion_ml=None, connectivity=1, lesions=False, truth=None, postprocess=None, return_prob=False, prob_path=None,
-                            votes_path=None, density=None, per_lung=None, render=None, mesh=None):
+                            votes_path=None, density=None, per_lung=None, render=None, mesh=None, distribution=None):
     """segment_volume with several members: every (model, symmetry) pair of `models` (each anything segment_volume accepts, all of one input size) and `tta` (names of
     TTA, no repeats), in model-major order, at most 32.  A member sees the prepared batch under its symmetry (transformed once, on the device), its probabilities are
     transformed back, pasted onto the canvas and (a) thresholded into the member's mask, which becomes one bit of a vote word per voxel, (b) added into the weighted
     mean canvas: acc = w_0 c_0, acc = acc + w_m c_m in member order, then acc / wsum, every float32 operation rounded on its own (weights: one per model, None: all 1;
     wsum: the float32 sum of the member weights in order).  combine="mean": the final mask is the thresholded mean probability; "majority" / "any" / "all" / int k: the
-    members' masks voted (vote_volume's rules).  Everything after the mask is formed -- postprocess, min_lesion_ml, lesions, density, per_lung, render, mesh, truth, out_path, the lung share -- is
+    members' masks voted (vote_volume's rules).  Everything after the mask is formed -- postprocess, min_lesion_ml, lesions, density, per_lung, distribution, render, mesh, truth, out_path, the lung share -- is
     segment_volume's, and so are the result's fields.  Added: members [(model index, tta name)], votes (uint8 [X, Y, Z]: how many members marked the voxel),
     member_ml, pairwise_dice, vote_hist (voxels with k votes), unanimous_ml (all members), uncertain_ml (some but not all), combine, seconds["members"] (predict time per
     member), and prob (float32 [X, Y, Z], the mean probability in patient space) with return_prob=True or prob_path (None otherwise).  prob_path / votes_path: those two
@@ -1489,6 +1508,7 @@ def segment_volume_ensemble(ct, models, tta=("id",), combine="mean", weights=Non
     models, members, mw, wsum, min_votes, d = _check_ensemble(models, tta, combine, weights)
     density = _check_density(density)
     per_lung = _check_per_lung(per_lung, lung_mask)
+    distribution = _check_distribution(distribution, per_lung)
     render = _check_render(render)
     if postprocess is not None:
         _check_steps(postprocess, (1.0, 1.0, 1.0))
@@ -1536,7 +1556,7 @@ def segment_volume_ensemble(ct, models, tta=("id",), combine="mean", weights=Non
                  vote_hist=st["hist"], unanimous_ml=float(st["unanimous_voxels"]) * voxel_ml, uncertain_ml=float(st["uncertain_voxels"]) * voxel_ml, combine=combine,
                  weights=mw, prob=prob)
     res = _finish_segmentation(vol, lv, truth_mask, mask_dev, counts_dev, z0, z1, has, info, threshold, sec, t0, postprocess, min_lesion_ml, lesions, connectivity, out_path,
-                               density=density, per_lung=per_lung, render=render, mesh=mesh, **extra)
+                               density=density, per_lung=per_lung, render=render, mesh=mesh, distribution=distribution, **extra)
     if prob_path is not None:
         nifti_min.write(prob_path, prob, vol.header)
     if votes_path is not None:
@@ -2117,6 +2137,32 @@ def lung_burden(infection, sides, labels=None, n=None, pixdim=(1, 1, 1), connect
     if ps is None or not int(np.prod(vshape)):
         ps = np.zeros((vshape[2], 6), np.int64)
     return burden_from_tables(totals, les, ps, p)
+
+
+def _check_distribution(distribution, per_lung):
+    """segment_volume's distribution= -> None (off) or the checked keyword arguments (zones._check_distribution)"""
+    if distribution is None or distribution is False:
+        return None
+    from . import zones
+    return zones._check_distribution(distribution, per_lung)
+
+
+def _segmentation_distribution(distribution, ls, sides_dev, mask_dev, labels_dev, n_comp, keep, shape, connectivity):
+    """segment_volume's distribution=: zones.lung_zones on the sides per_lung= left on the device, zones.lung_distribution on the final mask and the labels the lesion table
+    came from (a filtered lesion's rows go with it) -> LungDistribution, its zone map on the host"""
+    from . import zones
+    kw, rep = distribution
+    dev_sides = LungSides(**{**ls.__dict__, "sides": sides_dev})
+    lz = zones.lung_zones(dev_sides, return_device=True, **kw)
+    if labels_dev is None:
+        labels_dev, n_comp = label_device(mask_dev, shape, connectivity)
+    d = zones.lung_distribution(mask_dev, lz, labels=labels_dev, n=n_comp, shape=shape, **rep)
+    if keep is not None:
+        d.lesions = d.lesions[keep[1:]]
+        d.lesions["label"] = np.arange(1, len(d.lesions) + 1)
+    lz.zone_map = lz.zone_map.cpu().numpy().reshape(shape, order="F")
+    lz.sides, lz.d2 = None, None                                    # device buffers of the size of the volume do not outlive the call
+    return d
 
 
 # ---- a picture of the result (csrc/kernels_render.hip, DESIGN.md section 4v) ---------------------------------------------------------------------------------
