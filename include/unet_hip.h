@@ -1095,6 +1095,25 @@ int32_t unet_vol_zone_table(unet_ctx*, const uint8_t* sides, const uint8_t* infe
                             const unet_zone_spec* spec, int64_t* table, int64_t* outside, int64_t* lesion_zone, int64_t* lesion_shell, uint64_t* lesion_dmin_key,
                             uint8_t* zone_map, void* stream);
 
+/* ---- rank filters of a CT: median, minimum, maximum, percentile, flat grey morphology (csrc/kernels_filter.hip; exact against
+ * tests/filter_oracle.py and scipy.ndimage.rank_filter; filters.py) ----
+ * src, dst: [X, Y, Z] in Fortran order, X Y Z < 2^31, the same element type and shape; they must not overlap.  dtype is the NIfTI code of the STORED element: 2 (uint8),
+ * 256 (int8), 4 (int16), 512 (uint16), 8 (int32), 768 (uint32), 16 (float32); 64 is refused.  No slope or intercept enters: the filter orders stored elements.
+ * Footprint: bit b = (dx + R) + (2 R + 1) ((dy + R) + (2 R + 1) (dz + R)) of the 128-bit word fp_hi:fp_lo says that the offset (dx, dy, dz), |d| <= R, belongs to it;
+ * 1 <= R <= UNET_VOL_RANK_MAX_RADIUS, n = popcount in 1 .. (2 R + 1)^3, no bit at or above (2 R + 1)^3.
+ * dst[v] = the element of rank `rank` (0 = the smallest, 0 <= rank < n) among src[v + o], o in the footprint: scipy.ndimage.rank_filter(a, rank, footprint=fp, mode=..)
+ * with fp[dx + R, dy + R, dz + R].  Integers are ordered by value; float32 by the total order of the key bits ^ (sign ? 0xFFFFFFFF : 0x80000000): NaNs with the sign bit
+ * set lowest, then -inf .. -0 < +0 .. +inf, the other NaNs highest.  The stored bits of the selected element are written unchanged; there is no float arithmetic.
+ * Outside the volume, mode UNET_FILTER_NEAREST: the edge voxel repeats; UNET_FILTER_CONSTANT: the element whose stored bytes are the low bytes of cval_bits;
+ * UNET_FILTER_REFLECT: scipy's default "reflect", index i reads p = i mod 2 n, and 2 n - 1 - p where p >= n (also for extents below R).
+ * UNET_E_ARG, nothing launched, dst untouched: a null buffer or one not aligned to its element, src and dst overlapping, a bad dimension, dtype, R, footprint, rank or
+ * mode, cval_bits with a bit above the element's width (in every mode).  A zero dimension touches nothing and returns UNET_OK.
+ * One launch, no atomics, no workgroup waits for another: the same bits on every run. */
+#define UNET_VOL_RANK_MAX_RADIUS 2
+enum { UNET_FILTER_NEAREST = 0, UNET_FILTER_CONSTANT = 1, UNET_FILTER_REFLECT = 2 };
+int32_t unet_vol_rank_filter(unet_ctx*, const void* src, int32_t dtype, int32_t X, int32_t Y, int32_t Z, int32_t R, uint64_t fp_lo, uint64_t fp_hi, int32_t rank,
+                             int32_t mode, uint64_t cval_bits, void* dst, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Model level. Replaces the Keras Model built at T1:853-916 and driven by
  * compile/fit/evaluate/predict (T1:1053-1061, 1101, 1137).  A model is a fixed-shape plan:

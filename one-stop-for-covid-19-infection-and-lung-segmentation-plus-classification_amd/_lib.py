@@ -33,6 +33,8 @@ TRACK_CLS_NONE, TRACK_CLS_RESOLVED, TRACK_CLS_SHRINKAGE, TRACK_CLS_BOTH, TRACK_C
 TEXTURE_MAX_LEVELS, TEXTURE_MAX_DISTANCE, TEXTURE_LDS_COUNTERS = 64, 4, 8192          # UNET_VOL_TEXTURE_MAX_LEVELS, UNET_VOL_TEXTURE_MAX_DISTANCE, UNET_VOL_TEXTURE_LDS_COUNTERS
 TEXTURE_MAX_RUN = 2 ** 15                                             # unet_vol_texture_runs: 1 <= max_run <= 2^15
 ZONE_MAX_PARTS, ZONE_MAX_SHELLS, ZONE_MAX_BINS = 8, 4, 1024           # UNET_VOL_ZONE_MAX_PARTS, UNET_VOL_ZONE_MAX_SHELLS, UNET_VOL_ZONE_MAX_BINS
+RANK_MAX_RADIUS = 2                                                   # UNET_VOL_RANK_MAX_RADIUS
+FILTER_MODES = {"nearest": 0, "constant": 1, "reflect": 2}            # UNET_FILTER_NEAREST, UNET_FILTER_CONSTANT, UNET_FILTER_REFLECT
 MASK_NONE, MASK_RELU, MASK_ELU, MASK_ELU_DROP = 0, 1, 2, 3
 PROG_FWD_TRAIN, PROG_BWD, PROG_FWD_INFER = 0, 1, 2
 SYNC_BN_FWD, SYNC_LOSS, SYNC_BN_BWD, SYNC_GRAD_BUCKET = 0, 1, 2, 3
@@ -269,6 +271,8 @@ _PROTOS = {
     # where the infection sits in the lungs: side x zone x depth shell (csrc/kernels_zones.hip, zones.py); spec is a host struct
     "unet_vol_side_extents": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp]),
     "unet_vol_zone_table": (i32, [vp, vp, vp, vp, i32, vp, i32, i32, i32, C.POINTER(ZoneSpec), vp, vp, vp, vp, vp, vp, vp]),
+    # rank filters of a CT: median, minimum, maximum, percentile, flat grey morphology (csrc/kernels_filter.hip, filters.py)
+    "unet_vol_rank_filter": (i32, [vp, vp, i32, i32, i32, i32, i32, u64, u64, i32, i32, u64, vp, vp]),
     "unet_model_create": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(vp)]),
     "unet_model_dtype": (i32, [vp]),
     "unet_model_tap_elem_bytes": (i32, [vp, C.c_char_p, i32]),

@@ -2925,7 +2925,7 @@ def resample_volume(ct, spacing=None, shape=None, like=None, grid=None, order="l
     STORED value, by default the stored element that decodes to the minimum; with every other dtype cval= is a decoded value, in both orders.  order="nearest" with a
     float dtype moves the stored elements on the device and decodes them on the host (an explicit cval= is written there, where the same kernel finds a volume of ones
     outside), so it cannot be combined with return_device=True.  out_path: the result as .nii / .nii.gz with the new grid as its sform (float32 or uint8 data).
-    Neither order filters before it coarsens: coarsening by more than 2x aliases.  Every argument error is a ValueError raised before any device work."""
+    Neither order filters before it coarsens: coarsening by more than 2x aliases (filters.gaussian_filter is the low-pass to run first).  Every argument error is a ValueError raised before any device work."""
     _check_resample_args(order, mode, cval, dtype)
     if order == "nearest" and dtype != "raw" and return_device:
         raise ValueError("order='nearest' moves stored elements; with return_device=True ask for dtype='raw' (the decode to a float dtype happens on the host)")
