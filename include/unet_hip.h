@@ -1114,6 +1114,39 @@ enum { UNET_FILTER_NEAREST = 0, UNET_FILTER_CONSTANT = 1, UNET_FILTER_REFLECT = 
 int32_t unet_vol_rank_filter(unet_ctx*, const void* src, int32_t dtype, int32_t X, int32_t Y, int32_t Z, int32_t R, uint64_t fp_lo, uint64_t fp_hi, int32_t rank,
                              int32_t mode, uint64_t cval_bits, void* dst, void* stream);
 
+/* ---- a lung mask from the CT itself: the threshold pass and the growth from seeds inside a mask (csrc/kernels_lungmask.hip; exact against
+ * tests/lungmask_oracle.py; lungs.py) ----
+ * Volumes are [X, Y, Z] in Fortran order, X Y Z < 2^31.
+ * unet_vol_threshold: vox, dtype, X, Y, Z, scaled, slope, inter as unet_vol_intensity_bands takes them (the eight NIfTI codes 2, 256, 4, 512, 8, 768, 16, 64).  The value
+ *   of a voxel is v = double(raw), then (v * slope) + inter as two rounded operations when scaled: get_fdata's value.  mask[f] = 1 when lo <= v < hi and region is null or
+ *   region[f] != 0, else 0; a NaN value gives 0.  lo = -inf and hi = +inf are allowed.  slice_counts (nullable): int64 [Z], overwritten with the set voxels of every slice.
+ *   UNET_E_ARG, nothing launched, nothing written: a NaN edge or lo >= hi, NaN scaling, a bad dtype or dimension, a null or misaligned buffer (vox to its element,
+ *   slice_counts to 8 bytes), mask overlapping vox or region.  A zero dimension touches nothing.  One launch over a bounded grid; the counts are integer sums.
+ * unet_vol_geodesic_*: breadth-first growth of `seeds` inside `constraint` (uint8 volumes, set = non-zero).  By definition the result is the GEODESIC STEP DISTANCE
+ *   inside the constraint: arrival[f] = the least number of steps of a path from a voxel of seeds & constraint to f that stays inside the constraint, each step moving to
+ *   a neighbour under generate_binary_structure(3, connectivity) (planar: without its dz != 0 planes, connectivity 1 or 2; outside the volume is background); 0xFFFF
+ *   where no such path exists or none of at most the steps run so far.  It is a count of steps, not millimetres.
+ *   _ws_bytes  the workspace: four volumes of one bit per voxel in unet_vol_morph's packed layout (rows padded to 64-bit words): constraint, reached, two frontiers; 0 for
+ *              a bad or zero dimension.
+ *   _begin     packs constraint and seeds & constraint into the workspace, writes arrival (uint16 [X Y Z]: 0 on seeds & constraint, 0xFFFF elsewhere) and counts[0] =
+ *              their number.  Seeds outside the constraint are ignored.
+ *   _steps     runs the steps first_step .. first_step + n_steps - 1, one launch each: step s reaches the unreached constraint voxels that have a neighbour reached at
+ *              step s - 1, stores s into their arrival and overwrites counts[s] (int64) with their number.  counts holds at least first_step + n_steps entries.  The calls
+ *              after _begin continue each other: first_step is 1 after _begin and the previous call's last step + 1 afterwards, with the same X, Y, Z, connectivity, planar,
+ *              arrival and workspace (the frontier of step s - 1 lives in the workspace).  After a step with counts[s] == 0 every later step finds nothing.  The host reads
+ *              counts only between calls.
+ *   Steps lie in 1 .. UNET_VOL_GEODESIC_MAX_STEP.  UNET_E_ARG, nothing launched: a bad dimension, connectivity, planar or step range, a null or misaligned buffer (arrival 2,
+ *   counts 8, ws 16 bytes), a short workspace, arrival overlapping the workspace (or, in _begin, the seeds or the constraint).  A zero dimension touches nothing.
+ *   No workgroup waits for another: a step boundary is a kernel boundary.  Integer work only: the same bits on every run. */
+#define UNET_VOL_GEODESIC_MAX_STEP 65534
+int32_t unet_vol_threshold(unet_ctx*, const void* vox, int32_t dtype, int32_t X, int32_t Y, int32_t Z, int32_t scaled, double slope, double inter, double lo, double hi,
+                           const uint8_t* region, uint8_t* mask, int64_t* slice_counts, void* stream);
+size_t unet_vol_geodesic_ws_bytes(int32_t X, int32_t Y, int32_t Z);
+int32_t unet_vol_geodesic_begin(unet_ctx*, const uint8_t* seeds, const uint8_t* constraint, int32_t X, int32_t Y, int32_t Z, uint16_t* arrival, int64_t* counts, void* ws,
+                                size_t ws_bytes, void* stream);
+int32_t unet_vol_geodesic_steps(unet_ctx*, int32_t X, int32_t Y, int32_t Z, int32_t first_step, int32_t n_steps, int32_t connectivity, int32_t planar, uint16_t* arrival,
+                                int64_t* counts, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Model level. Replaces the Keras Model built at T1:853-916 and driven by
  * compile/fit/evaluate/predict (T1:1053-1061, 1101, 1137).  A model is a fixed-shape plan:

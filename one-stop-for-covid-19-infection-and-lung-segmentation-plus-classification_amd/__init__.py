@@ -20,6 +20,9 @@ Public surface:
   rank_filter / median_filter / minimum_filter / maximum_filter / percentile_filter / grey_erosion / grey_dilation / grey_opening / grey_closing / gaussian_filter
                             (FilteredVolume, footprint_bits, structure) -- filters' changes to the CT's own voxels: the element of a rank under a footprint of radius
                             <= 2, exact against scipy.ndimage, and the Gaussian low-pass to run before resample_volume coarsens, also reachable from the package itself
+  lung_mask / threshold_volume / geodesic_distance / reconstruct / body_mask / find_trachea / grow_airways (LungMask, AirwayGrowth, TracheaSeed, LungMaskError) -- lungs'
+                            lung mask from the CT itself: the air inside the body, trachea and main bronchi grown from a seed and removed, the two lungs kept; also
+                            reachable from the package itself
   engine.HipUNet         -- the HIP backend (libunet_hip.so through the C ABI of include/unet_hip.h)
 Importing this package has no side effects and does not need a GPU; constructing the
 backend does (there is no CPU fallback).
@@ -29,7 +32,9 @@ __all__ = ["runners", "keras_like", "engine", "weights", "data", "volume", "nift
            "Grid", "ResampledVolume", "VolumeChange", "extract_surface", "lesion_shapes", "SurfaceMesh", "tracking", "track_lesions", "track_series", "label_pairs", "match_lesions",
            "LesionTracking", "LesionSeries", "LesionMatch", "PALETTE_CHANGE", "texture", "texture_stats", "lesion_texture", "glcm", "run_lengths", "quantize_volume", "glcm_features",
            "run_features", "TextureStats", "zones", "lung_zones", "lung_distribution", "LungZones", "LungDistribution", "filters", "rank_filter", "median_filter", "minimum_filter", "maximum_filter", "percentile_filter",
-           "grey_erosion", "grey_dilation", "grey_opening", "grey_closing", "gaussian_filter", "footprint_bits", "structure", "FilteredVolume"]
+           "grey_erosion", "grey_dilation", "grey_opening", "grey_closing", "gaussian_filter", "footprint_bits", "structure", "FilteredVolume",
+           "lungs", "lung_mask", "threshold_volume", "geodesic_distance", "reconstruct", "body_mask", "find_trachea", "grow_airways", "LungMask", "AirwayGrowth", "TracheaSeed",
+           "LungMaskError"]
 _FROM_VOLUME = ("split_lungs", "lung_burden", "LungSides", "LungBurden", "LungSplitError", "render_planes", "project_volume", "key_slices", "Layer", "RenderedSheet",
                 "resample_volume", "resample_mask", "resample_labels", "reorient_volume", "change_between", "Grid", "ResampledVolume", "VolumeChange",
                 "extract_surface", "lesion_shapes", "SurfaceMesh")
@@ -37,6 +42,8 @@ _FROM_TRACKING = ("track_lesions", "track_series", "label_pairs", "match_lesions
 _FROM_ZONES = ("lung_zones", "lung_distribution", "LungZones", "LungDistribution")
 _FROM_FILTERS = ("rank_filter", "median_filter", "minimum_filter", "maximum_filter", "percentile_filter", "grey_erosion", "grey_dilation", "grey_opening", "grey_closing",
                  "gaussian_filter", "footprint_bits", "structure", "FilteredVolume")
+_FROM_LUNGS = ("lung_mask", "threshold_volume", "geodesic_distance", "reconstruct", "body_mask", "find_trachea", "grow_airways", "LungMask", "AirwayGrowth", "TracheaSeed",
+               "LungMaskError")
 _FROM_TEXTURE = ("texture_stats", "lesion_texture", "glcm", "run_lengths", "quantize_volume", "glcm_features", "run_features", "TextureStats")
 
 
@@ -56,4 +63,7 @@ def __getattr__(name):                                              # resolved o
     if name in _FROM_FILTERS:
         import importlib
         return getattr(importlib.import_module(__name__ + ".filters"), name)
+    if name in _FROM_LUNGS:
+        import importlib
+        return getattr(importlib.import_module(__name__ + ".lungs"), name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -35,6 +35,7 @@ TEXTURE_MAX_RUN = 2 ** 15                                             # unet_vol
 ZONE_MAX_PARTS, ZONE_MAX_SHELLS, ZONE_MAX_BINS = 8, 4, 1024           # UNET_VOL_ZONE_MAX_PARTS, UNET_VOL_ZONE_MAX_SHELLS, UNET_VOL_ZONE_MAX_BINS
 RANK_MAX_RADIUS = 2                                                   # UNET_VOL_RANK_MAX_RADIUS
 FILTER_MODES = {"nearest": 0, "constant": 1, "reflect": 2}            # UNET_FILTER_NEAREST, UNET_FILTER_CONSTANT, UNET_FILTER_REFLECT
+GEODESIC_MAX_STEP = 65534                                             # UNET_VOL_GEODESIC_MAX_STEP
 MASK_NONE, MASK_RELU, MASK_ELU, MASK_ELU_DROP = 0, 1, 2, 3
 PROG_FWD_TRAIN, PROG_BWD, PROG_FWD_INFER = 0, 1, 2
 SYNC_BN_FWD, SYNC_LOSS, SYNC_BN_BWD, SYNC_GRAD_BUCKET = 0, 1, 2, 3
@@ -273,6 +274,11 @@ _PROTOS = {
     "unet_vol_zone_table": (i32, [vp, vp, vp, vp, i32, vp, i32, i32, i32, C.POINTER(ZoneSpec), vp, vp, vp, vp, vp, vp, vp]),
     # rank filters of a CT: median, minimum, maximum, percentile, flat grey morphology (csrc/kernels_filter.hip, filters.py)
     "unet_vol_rank_filter": (i32, [vp, vp, i32, i32, i32, i32, i32, u64, u64, i32, i32, u64, vp, vp]),
+    # a lung mask from the CT itself: the threshold pass, and the growth from seeds inside a mask that records its steps (csrc/kernels_lungmask.hip, lungs.py)
+    "unet_vol_threshold": (i32, [vp, vp, i32, i32, i32, i32, i32, f64, f64, f64, f64, vp, vp, vp, vp]),
+    "unet_vol_geodesic_ws_bytes": (sz, [i32, i32, i32]),
+    "unet_vol_geodesic_begin": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, sz, vp]),
+    "unet_vol_geodesic_steps": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
     "unet_model_create": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(vp)]),
     "unet_model_dtype": (i32, [vp]),
     "unet_model_tap_elem_bytes": (i32, [vp, C.c_char_p, i32]),

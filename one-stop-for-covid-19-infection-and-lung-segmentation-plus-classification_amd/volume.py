@@ -1026,6 +1026,32 @@ def postprocess(mask, steps, pixdim=None, return_device=False, shape=None):
     return _result(postprocess_device(dev, shape, steps, pixdim)[0], shape, return_device)
 
 
+def _check_lungs(lungs, lung_mask):
+    """segment_volume's lungs= -> None (off) or the checked keyword arguments of lungs.lung_mask"""
+    if lungs is None or lungs is False:
+        return None
+    if lung_mask is not None:
+        raise ValueError("lungs= computes the lung mask and lung_mask= gives one: pass one of them")
+    if lungs is not True and not isinstance(lungs, dict):
+        raise ValueError(f"lungs is True or a dict of lungs.lung_mask keyword arguments, not {lungs!r}")
+    from . import lungs as L
+    kw = {} if lungs is True else dict(lungs)
+    if set(kw) - L._LUNG_MASK_KEYS:
+        raise ValueError(f"lungs takes {sorted(L._LUNG_MASK_KEYS)}, not {sorted(set(kw) - L._LUNG_MASK_KEYS)}")
+    L._check_lung_mask_args(**kw)
+    return kw
+
+
+def _computed_lungs(ct, lungs, lung_mask):
+    """-> (the lung mask segment_volume goes on with, (extra result fields, extra seconds)): lungs.lung_mask(ct) as a host array when lungs= asks for it"""
+    if lungs is None:
+        return lung_mask, ({}, {})
+    from . import lungs as L
+    t0 = time.perf_counter()
+    lm = L.lung_mask(ct, **lungs)
+    return lm.mask, (dict(lungs=lm), dict(lungs=time.perf_counter() - t0))
+
+
 def _prepare_segmentation(ct, lung_mask, truth, img_size, trim, input_size):
     """The front of segment_volume / segment_volume_ensemble: decode the CT (and the truth and lung masks), the lung rectangles keyed by slice number, the prepared
     batch x [n, d, d, 1] on the device (d = input_size(), asked for once the truth mask has been checked) -> (vol, lv, truth_mask, z0, z1, S, x, info, R1, R2, has, seconds); R1, R2: int32 [n, 4] per kept slice, zeros where has is False."""
@@ -1063,7 +1089,7 @@ def _prepare_segmentation(ct, lung_mask, truth, img_size, trim, input_size):
 
 
 def segment_volume(ct, model, lung_mask=None, threshold=0.547, batch_size=32, out_path=None, img_size=512, trim=(0.2, 0.8), min_lesion_ml=None, connectivity=1,
-                   lesions=False, truth=None, postprocess=None, density=None, per_lung=None, render=None, mesh=None, distribution=None):
+                   lesions=False, truth=None, postprocess=None, density=None, per_lung=None, render=None, mesh=None, distribution=None, lungs=None):
     """CT file (or array) -> VolumeSegmentation.  `model`: a UNetModel or a routed.ClusterRoutedModel (only `predict` is used); lung_mask=None: whole-frame
     boxes (the two halves of the frame); boxes are keyed by slice number (box_indexing="slice"); out_path: the mask as .nii / .nii.gz with the CT's geometry.
     min_lesion_ml: connected components (`connectivity` 1, 2, 3 = 6, 18, 26 neighbours) smaller than that are removed on the device before the mask comes to the
@@ -1098,8 +1124,13 @@ def segment_volume(ct, model, lung_mask=None, threshold=0.547, batch_size=32, ou
     per_lung (ValueError before any work without it).  Right after per_lung, on the sides and the lesion labels it left on the device: res.distribution = the
     LungDistribution of the final mask -- where in the lungs the infection sits: per region, per depth shell, per lesion (rows aligned with res.lesions when the lesion
     table is computed), a severity score per region and the words of a report; its zone map is on the host.  When the lungs could not be split res.distribution is None
-    and res.distribution_error holds the reason.  seconds["distribution"]: its time.  None: nothing runs and no other field changes."""
+    and res.distribution_error holds the reason.  seconds["distribution"]: its time.  None: nothing runs and no other field changes.
+    lungs: True, or a dict of lungs.lung_mask keyword arguments: the lung mask is computed from the CT first (lungs.lung_mask; a lung U-Net under its model= key) and used
+    exactly as a lung_mask= array in the CT's orientation would be; res.lungs is the LungMask and seconds["lungs"] its time.  Giving both lungs= and lung_mask= is a
+    ValueError.  None: nothing runs and nothing changes."""
     _check_connectivity(connectivity)
+    lungs = _check_lungs(lungs, lung_mask)
+    lung_mask = True if lungs is not None else lung_mask          # (the checks below ask only whether there is one)
     density = _check_density(density)
     per_lung = _check_per_lung(per_lung, lung_mask)
     distribution = _check_distribution(distribution, per_lung)
@@ -1108,7 +1139,9 @@ def segment_volume(ct, model, lung_mask=None, threshold=0.547, batch_size=32, ou
     if postprocess is not None:
         _check_steps(postprocess, (1.0, 1.0, 1.0))                   # the steps' own arguments, before any work (the CT's pixdim takes this one's place below)
     torch = _torch()
+    lung_mask, found = _computed_lungs(ct, lungs, lung_mask)
     vol, lv, truth_mask, z0, z1, S, x, info, R1, R2, has, sec = _prepare_segmentation(ct, lung_mask, truth, img_size, trim, lambda: int(getattr(model, "h", None) or model.base.h))
+    sec.update(found[1])
     X, Y, Z = vol.raw.shape
     t0 = time.perf_counter()
     prob = torch.from_numpy(np.ascontiguousarray(model.predict(x, batch_size=batch_size), np.float32)).cuda()
@@ -1117,7 +1150,7 @@ def segment_volume(ct, model, lung_mask=None, threshold=0.547, batch_size=32, ou
     canvas = paste_back(prob, R1, R2, S)
     mask_dev, counts_dev = unslice(canvas, threshold, (X, Y, Z), z0, z1)
     return _finish_segmentation(vol, lv, truth_mask, mask_dev, counts_dev, z0, z1, has, info, threshold, sec, t0, postprocess, min_lesion_ml, lesions, connectivity, out_path,
-                                density=density, per_lung=per_lung, render=render, mesh=mesh, distribution=distribution)
+                                density=density, per_lung=per_lung, render=render, mesh=mesh, distribution=distribution, **found[0])
 
 
 def _finish_segmentation(vol, lv, truth_mask, mask_dev, counts_dev, z0, z1, has, info, threshold, sec, t0, postprocess, min_lesion_ml, lesions, connectivity, out_path,
@@ -1491,7 +1524,7 @@ def _predict_device(model, x, batch_size):
 
 def segment_volume_ensemble(ct, models, tta=("id",), combine="mean", weights=None, lung_mask=None, threshold=0.547, batch_size=32, out_path=None, img_size=512,
                             trim=(0.2, 0.8), min_lesion_ml=None, connectivity=1, lesions=False, truth=None, postprocess=None, return_prob=False, prob_path=None,
-                            votes_path=None, density=None, per_lung=None, render=None, mesh=None, distribution=None):
+                            votes_path=None, density=None, per_lung=None, render=None, mesh=None, distribution=None, lungs=None):
     """segment_volume with several members: every (model, symmetry) pair of `models` (each anything segment_volume accepts, all of one input size) and `tta` (names of
     TTA, no repeats), in model-major order, at most 32.  A member sees the prepared batch under its symmetry (transformed once, on the device), its probabilities are
     transformed back, pasted onto the canvas and (a) thresholded into the member's mask, which becomes one bit of a vote word per voxel, (b) added into the weighted
@@ -1504,6 +1537,8 @@ def segment_volume_ensemble(ct, models, tta=("id",), combine="mean", weights=Non
     volumes as .nii / .nii.gz with the CT's header.  The vote statistics describe the members' masks at `threshold` in both modes (combine="mean" counts them under the
     majority rule).  One member ("id",) with combine="mean" and weight 1 is segment_volume bit for bit.  Under data parallelism every rank runs every member."""
     _check_connectivity(connectivity)
+    lungs = _check_lungs(lungs, lung_mask)
+    lung_mask = True if lungs is not None else lung_mask
     mesh = _check_mesh(mesh, lung_mask)
     models, members, mw, wsum, min_votes, d = _check_ensemble(models, tta, combine, weights)
     density = _check_density(density)
@@ -1514,7 +1549,9 @@ def segment_volume_ensemble(ct, models, tta=("id",), combine="mean", weights=Non
         _check_steps(postprocess, (1.0, 1.0, 1.0))
     torch = _torch()
     M = len(members)
+    lung_mask, found = _computed_lungs(ct, lungs, lung_mask)
     vol, lv, truth_mask, z0, z1, S, x, info, R1, R2, has, sec = _prepare_segmentation(ct, lung_mask, truth, img_size, trim, lambda: d)
+    sec.update(found[1])
     X, Y, Z = vol.raw.shape
     _check_volume_dims((X, Y, Z))
     sec["members"] = []
@@ -1554,7 +1591,7 @@ def segment_volume_ensemble(ct, models, tta=("id",), combine="mean", weights=Non
     del r, prob_dev
     extra = dict(members=members, votes=votes, member_ml=st["member_voxels"].astype(np.float64) * voxel_ml, pairwise_dice=st["pairwise_dice"], vote_pair=st["pair"],
                  vote_hist=st["hist"], unanimous_ml=float(st["unanimous_voxels"]) * voxel_ml, uncertain_ml=float(st["uncertain_voxels"]) * voxel_ml, combine=combine,
-                 weights=mw, prob=prob)
+                 weights=mw, prob=prob, **found[0])
     res = _finish_segmentation(vol, lv, truth_mask, mask_dev, counts_dev, z0, z1, has, info, threshold, sec, t0, postprocess, min_lesion_ml, lesions, connectivity, out_path,
                                density=density, per_lung=per_lung, render=render, mesh=mesh, distribution=distribution, **extra)
     if prob_path is not None:
