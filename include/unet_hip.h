@@ -95,10 +95,16 @@ int32_t unet_ctx_set_profiling(unet_ctx* ctx, int32_t on);
  *                          (the split then computes bit for bit what the two launches computed) and whose two half launches each fill the resident workgroup slots at least
  *                          twice (at 512 x 512 x 16 on 256 CUs: the 512 and 256 pixel levels); 0 = the two launches of before everywhere;
  *                          2 = every level, whatever its size (tests)
+ *   WGRAD_EARLY_SPLIT (15; default 0) h2 conv3x3 weight gradient (unet_conv3x3_bwd_weights and the entry behind the head stream), 1: a step of the kernel's pixel loop scales and splits
+ *                          the NEXT step's fetched rows into their two fp16 planes in the gaps of its own MFMAs, at the block exponents it holds, and confirms the exponents
+ *                          behind the barrier; when a block's maximum moves one (rare) the rows are fetched again and split between the barriers as with 0.  Same MFMA order,
+ *                          same scales: 1 and 0 give the same bits (tests/test_gpu_wgrad_early_split.py).  Off: on one box 1 was 0.3 - 1.8 % slower per op, the loop waits for
+ *                          the rows, not for the split (profiles/wgrad_early_split_ab.txt)
  *   (options 11 / 12 of ABI v13-v14 -- WGRAD_ATOMIC, C1A_RECOMPUTE -- were same-box A/B losers and left the library in v15; DESIGN.md keeps the measurements)
  */
 enum { UNET_OPT_RELU_BITS = 1, UNET_OPT_BN_FOLD = 2, UNET_OPT_ENC_BN_FUSED = 3, UNET_OPT_BN_CONCAT_ANALYTIC = 4, UNET_OPT_BN_FUSE_STATS = 5, UNET_OPT_DETERMINISTIC = 6,
-       UNET_OPT_HEAD_FUSED = 7, UNET_OPT_SKIP_RAW = 8, UNET_OPT_POOL_SUMS_FUSED = 9, UNET_OPT_HEAD_BWD_FUSED = 10, UNET_OPT_CONV_PP = 13, UNET_OPT_ENC_TAIL_DGRAD = 14 };
+       UNET_OPT_HEAD_FUSED = 7, UNET_OPT_SKIP_RAW = 8, UNET_OPT_POOL_SUMS_FUSED = 9, UNET_OPT_HEAD_BWD_FUSED = 10, UNET_OPT_CONV_PP = 13, UNET_OPT_ENC_TAIL_DGRAD = 14,
+       UNET_OPT_WGRAD_EARLY_SPLIT = 15 };
 int32_t unet_ctx_set_option(unet_ctx* ctx, int32_t option, int32_t value);
 int32_t unet_ctx_get_option(unet_ctx* ctx, int32_t option);   /* >= 0: the value; < 0: error */
 

@@ -16,7 +16,7 @@ COMM_HANDLE_BYTES, COMM_MAX_WORLD, COMM_MAX_DOUBLES = 64, 8, 2048          # inc
 
 ALGO_AUTO, ALGO_NAIVE, ALGO_MFMA = 0, 1, 2          # fp16-split h2 kernels where the shape allows / VALU kernels / strict fp32 MFMA kernels
 # unet_ctx_set_option (include/unet_hip.h UNET_OPT_*)
-OPTIONS = {"relu_bits": 1, "bn_fold": 2, "enc_bn_fused": 3, "bn_concat_analytic": 4, "bn_fuse_stats": 5, "deterministic": 6, "head_fused": 7, "skip_raw": 8, "pool_sums_fused": 9, "head_bwd_fused": 10, "conv_pp": 13, "enc_tail_dgrad": 14}
+OPTIONS = {"relu_bits": 1, "bn_fold": 2, "enc_bn_fused": 3, "bn_concat_analytic": 4, "bn_fuse_stats": 5, "deterministic": 6, "head_fused": 7, "skip_raw": 8, "pool_sums_fused": 9, "head_bwd_fused": 10, "conv_pp": 13, "enc_tail_dgrad": 14, "wgrad_early_split": 15}
 ARCH_UNET, ARCH_UNETPP, ARCH_CLASSIFIER = 0, 1, 2
 # include/unet_hip.h UNET_LOSS_*: the segmentation losses a U-Net / U-Net++ trains on (unet_model_set_loss), by their Keras names
 LOSSES = {"bce_dice_loss": 0, "binary_crossentropy": 1, "dice_loss": 2, "tversky_loss": 3, "weighted_bce_dice_loss": 4}

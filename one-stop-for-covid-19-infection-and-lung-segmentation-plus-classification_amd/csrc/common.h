@@ -41,6 +41,7 @@ struct unet_ctx {
   int opt_head_fused = 1;           // the 1x1 sigmoid head + loss sums + the head's weight-gradient sums in the epilogue of the last conv3x3 (fp32 h2 kernels)
   int opt_head_bwd_fused = 1;       // the head's backward as an 8-byte-per-pixel {dz, mask} stream that the last conv's two gradients expand (no fp32 dY tensor)
   int opt_enc_tail_dgrad = 1;       // fp32 U-Net: the skip half of a folded decoder BatchNorm's data gradient deferred into the encoder tail's backward (no gskip tensor); 2: also levels whose half launches do not fill the device (tests)
+  int opt_wgrad_early_split = 0;    // h2 conv3x3 weight gradient, 1: the next step's pieces are scaled and split under the current step's MFMAs at the exponents held, confirmed behind the barrier (same bits; measured no faster: off)
   int opt_conv_pp = 1;              // shallow conv3x3 forward / data-gradient launches on the persistent two-half schedule (kernels_conv_pp.hip)
   int opt_deterministic = 0;        // fixed-order reductions everywhere (no floating-point atomics): bit-identical reruns
   double* bn_slots = nullptr;       // device, UNET_BN_SLOTS_DET x UNET_BN_SLOT_DOUBLES (16 MB), all zero between launches

@@ -49,7 +49,15 @@ constexpr int APX = 34;                                       // X pixels per st
 // VDY: the dY operand is VIRTUAL -- the gradient of the network's last conv3x3 output, dy[p][c] = dz_p w_c [y_pc > 0] (T1:911-913 backwards), staged from the
 // 8-byte-per-pixel stream {dz_p, 32 mask bits} of head_dzm_kernel (B = that stream, CB = 32): one value is scaled and split per staged piece, the mask bits pick the
 // channels; w_c (colscale) multiplies the finished columns.
-template <int WA, int WB, int WR, int R, bool VDY = false>
+// ES (UNET_OPT_WGRAD_EARLY_SPLIT): a step's VALU work used to sit between its two barriers, where none of it overlaps the wave's own MFMAs.  With ES a step after the
+// workgroup's first scales and splits the NEXT step's landed pieces in place (four fp32 words -> h0, h1, m0, m1) in front of its last ES_BACK groups of nine MFMAs, at
+// the exponents it holds -- the maxima are taken from the fp32 values first --, and behind the barrier only confirms them: neither exponent moves (the workgroup-uniform
+// common case) -> the ds_writes are all that is left between the barriers; one moves -> the step's rows are fetched again and store_lds runs as without ES.  Same bits.
+// Measured no faster (the second resident workgroup already covers the split; the earlier wait exposes more of the loads' latency: DESIGN.md section 4g), so the option is off.
+#ifndef WGRAD_ES_BACK
+#define WGRAD_ES_BACK 3
+#endif
+template <int WA, int WB, int WR, int R, bool VDY = false, bool ES = false>
 __global__ __launch_bounds__(256, (R == 4 && WA * WB > 1) ? 1 : 2) void wgrad_h2_kernel(const float* __restrict__ A, const float* __restrict__ B, float* __restrict__ part, int N, int H, int W,
                                                           int CA, int CB, int tiles_b, int strips, int rows_per_chunk, int chunks_per_strip, int nsplit,
                                                           int npairs, long long pstride, int units, int upb, const float* __restrict__ colscale) {
@@ -101,17 +109,28 @@ __global__ __launch_bounds__(256, (R == 4 && WA * WB > 1) ? 1 : 2) void wgrad_h2
     // operand (and per 32-channel sub-plane: its validity differs) is all it keeps; rows and sub-planes are wave-uniform immediates.  The X rows have
     // 34 pixels: columns 0..31 (image column x0 - 1 + pc) go with the main pieces, columns 32 / 33 with one extra piece of the first 16 * WA * AROWS threads.
     const int q8 = tid & 7, pc = tid >> 3;
-    int abase_t[WA], bbase_t[WB];
+    // ES: ONE base per operand, in plain scalars (the form lives at the register limit; arrays of one spilled a register in <2,2,1,2>).  Two sub-planes exist only
+    // where the channel count is a multiple of 64 (plan_wgrad_h2), so the second one is as valid as the first: its 128 bytes ride on the wave-uniform offset, and an
+    // invalid base stays past the end of the buffer with them.
+    constexpr int SUBOFF = ES ? 32 * 4 : 0;
+    int abase_t[WA], bbase_t[WB], abase_1 = UNET_OOB, bbase_1 = UNET_OOB;
+    if (ES) {
+      const int gxa = x0 - 1 + pc, gxb = x0 + pc;
+      abase_1 = (gxa >= 0 && gxa < W && a0 + q8 * 4 < CA) ? (gxa * CA + a0 + q8 * 4) * 4 : UNET_OOB;
+      if (VDY) bbase_1 = gxb < W ? gxb * 8 : UNET_OOB;
+      else bbase_1 = (gxb < W && b0 + q8 * 4 < CB) ? (gxb * CB + b0 + q8 * 4) * 4 : UNET_OOB;
+    } else {
 #pragma unroll
-    for (int sub = 0; sub < WA; ++sub) {
-      const int gx = x0 - 1 + pc, ch = a0 + sub * 32 + q8 * 4;
-      abase_t[sub] = (gx >= 0 && gx < W && ch < CA) ? (gx * CA + ch) * 4 : UNET_OOB;
-    }
+      for (int sub = 0; sub < WA; ++sub) {
+        const int gx = x0 - 1 + pc, ch = a0 + sub * 32 + q8 * 4;
+        abase_t[sub] = (gx >= 0 && gx < W && ch < CA) ? (gx * CA + ch) * 4 : UNET_OOB;
+      }
 #pragma unroll
-    for (int sub = 0; sub < WB; ++sub) {
-      const int gx = x0 + pc, ch = b0 + sub * 32 + q8 * 4;
-      if (VDY) bbase_t[sub] = gx < W ? gx * 8 : UNET_OOB;          // (the eight quads of a pixel read the same 8 bytes)
-      else bbase_t[sub] = (gx < W && ch < CB) ? (gx * CB + ch) * 4 : UNET_OOB;
+      for (int sub = 0; sub < WB; ++sub) {
+        const int gx = x0 + pc, ch = b0 + sub * 32 + q8 * 4;
+        if (VDY) bbase_t[sub] = gx < W ? gx * 8 : UNET_OOB;          // (the eight quads of a pixel read the same 8 bytes)
+        else bbase_t[sub] = (gx < W && ch < CB) ? (gx * CB + ch) * 4 : UNET_OOB;
+      }
     }
     // halo piece: thread t < 16 * WA * AROWS -> column 32 + ((t >> 3) & 1), (sub, row) = t >> 4
     constexpr int HALO_T = 16 * WA * AROWS;
@@ -130,7 +149,7 @@ __global__ __launch_bounds__(256, (R == 4 && WA * WB > 1) ? 1 : 2) void wgrad_h2
         for (int row = 0; row < 2; ++row) {
           const int gy = ys - 1 + row;
           const bool ok = gy >= 0 && gy < H;
-          areg[sub * AROWS + row] = __builtin_amdgcn_raw_buffer_load_b128(rs_a, ok ? abase_t[sub] : UNET_OOB, ok ? gy * W * CA * 4 : 0, 0);
+          areg[sub * AROWS + row] = __builtin_amdgcn_raw_buffer_load_b128(rs_a, ok ? (ES ? abase_1 : abase_t[sub]) : UNET_OOB, ok ? gy * W * CA * 4 + sub * SUBOFF : 0, 0);
         }
       const int gy = ys - 1 + h_row;
       areg[NA] = __builtin_amdgcn_raw_buffer_load_b128(rs_a, (h_row < 2 && gy >= 0 && gy < H) ? hbase_t + gy * W * CA * 4 : UNET_OOB, 0, 0);
@@ -144,7 +163,7 @@ __global__ __launch_bounds__(256, (R == 4 && WA * WB > 1) ? 1 : 2) void wgrad_h2
           if (row < j0) continue;
           const int gy = ysa + row;                                      // wave-uniform
           const bool ok = gy >= 0 && gy < H;
-          areg[sub * AROWS + row] = __builtin_amdgcn_raw_buffer_load_b128(rs_a, ok ? abase_t[sub] : UNET_OOB, ok ? gy * W * CA * 4 : 0, 0);
+          areg[sub * AROWS + row] = __builtin_amdgcn_raw_buffer_load_b128(rs_a, ok ? (ES ? abase_1 : abase_t[sub]) : UNET_OOB, ok ? gy * W * CA * 4 + sub * SUBOFF : 0, 0);
         }
       {
         const int gy = ysa + h_row;
@@ -156,12 +175,13 @@ __global__ __launch_bounds__(256, (R == 4 && WA * WB > 1) ? 1 : 2) void wgrad_h2
         for (int row = 0; row < R; ++row) {
           const int gy = ys + row;
           const bool ok = gy < yb;                                       // rows past the chunk contribute 0
-          if (VDY) { const unet_u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rs_b, ok ? bbase_t[sub] : UNET_OOB, ok ? gy * W * 8 : 0, 0); breg[sub * R + row][0] = v[0]; breg[sub * R + row][1] = v[1]; }
-          else breg[sub * R + row] = __builtin_amdgcn_raw_buffer_load_b128(rs_b, ok ? bbase_t[sub] : UNET_OOB, ok ? gy * W * CB * 4 : 0, 0);
+          if (VDY) { const unet_u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rs_b, ok ? (ES ? bbase_1 : bbase_t[sub]) : UNET_OOB, ok ? gy * W * 8 : 0, 0); breg[sub * R + row][0] = v[0]; breg[sub * R + row][1] = v[1]; }
+          else breg[sub * R + row] = __builtin_amdgcn_raw_buffer_load_b128(rs_b, ok ? (ES ? bbase_1 : bbase_t[sub]) : UNET_OOB, ok ? gy * W * CB * 4 + sub * SUBOFF : 0, 0);
         }
     };
-    auto post_amax = [&]() __attribute__((always_inline)) {
-      float ma = 0.f, mb = 0.f;
+    float ma = 0.f, mb = 0.f;                                     // (wave-uniform) the maxima of the pieces in flight
+    auto take_amax = [&]() __attribute__((always_inline)) {
+      ma = 0.f; mb = 0.f;
 #pragma unroll
       for (int k = 0; k < NA + 1; ++k)
 #pragma unroll
@@ -173,8 +193,9 @@ __global__ __launch_bounds__(256, (R == 4 && WA * WB > 1) ? 1 : 2) void wgrad_h2
         for (int j = 0; j < 4; ++j) mb = fmaxf(mb, fabsf(__uint_as_float(breg[k][j])));
       }
       ma = wave_max_nonneg(ma); mb = wave_max_nonneg(mb);
-      if (lane == 0) { s_amax[0][wave] = ma; s_amax[1][wave] = mb; }
     };
+    auto publish_amax = [&]() __attribute__((always_inline)) { if (lane == 0) { s_amax[0][wave] = ma; s_amax[1][wave] = mb; } };
+    auto post_amax = [&]() __attribute__((always_inline)) { take_amax(); publish_amax(); };
     auto store_lds = [&](int ys, int base, int j0) __attribute__((always_inline)) {
       const float ma = fmaxf(fmaxf(s_amax[0][0], s_amax[0][1]), fmaxf(s_amax[0][2], s_amax[0][3]));
       const float mb = fmaxf(fmaxf(s_amax[1][0], s_amax[1][1]), fmaxf(s_amax[1][2], s_amax[1][3]));
@@ -234,12 +255,70 @@ __global__ __launch_bounds__(256, (R == 4 && WA * WB > 1) ? 1 : 2) void wgrad_h2
         }
     };
 
+    // ES: scale and split the new pieces of the next step where they are, at the exponents held now (rows < 2 of areg: the kept rows, not fetched)
+    auto split_piece = [&](unet_u32x4& v, float sc) __attribute__((always_inline)) {
+      unsigned h0, m0, h1, m1;
+      split2_scaled(__uint_as_float(v[0]), __uint_as_float(v[1]), sc, h0, m0);
+      split2_scaled(__uint_as_float(v[2]), __uint_as_float(v[3]), sc, h1, m1);
+      v[0] = h0; v[1] = h1; v[2] = m0; v[3] = m1;
+    };
+    auto early_split = [&]() __attribute__((always_inline)) {
+      const float sa = pow2f(e_a), sb = pow2f(e_b);
+#pragma unroll
+      for (int sub = 0; sub < WA; ++sub)
+#pragma unroll
+        for (int row = 2; row < AROWS; ++row) split_piece(areg[sub * AROWS + row], sa);
+      split_piece(areg[NA], sa);
+#pragma unroll
+      for (int k = 0; k < NB_; ++k) {
+        if (VDY) {
+          const float x = __uint_as_float(breg[k][0]) * sb;
+          unsigned hh, mm;
+          split2(x, x, hh, mm);
+          breg[k][0] = hh; breg[k][2] = mm;
+        } else split_piece(breg[k], sb);
+      }
+    };
+    auto exponents_hold = [&]() __attribute__((always_inline)) {          // what store_lds would decide from s_amax: does neither running exponent move?  (workgroup-uniform)
+      const float ma = fmaxf(fmaxf(s_amax[0][0], s_amax[0][1]), fmaxf(s_amax[0][2], s_amax[0][3]));
+      const float mb = fmaxf(fmaxf(s_amax[1][0], s_amax[1][1]), fmaxf(s_amax[1][2], s_amax[1][3]));
+      const int eba = __builtin_amdgcn_readfirstlane((int)((__float_as_uint(ma) >> 23) & 0xFF));
+      const int ebb = __builtin_amdgcn_readfirstlane((int)((__float_as_uint(mb) >> 23) & 0xFF));
+      return !(eba >= 11 && eba - 127 + e_a >= 15) && !(ebb >= 11 && ebb - 127 + e_b >= 15);
+    };
+    auto store_split = [&](int base) __attribute__((always_inline)) {      // the ds_writes of store_lds(., base, 2) for pieces that early_split has split
+      auto put2 = [&](char* dst, const unet_u32x4& v) __attribute__((always_inline)) {
+        *reinterpret_cast<uint2*>(dst) = make_uint2(v[0], v[1]);
+        *reinterpret_cast<uint2*>(dst + STAGE1) = make_uint2(v[2], v[3]);
+      };
+#pragma unroll
+      for (int sub = 0; sub < WA; ++sub)
+#pragma unroll
+        for (int row = 2; row < AROWS; ++row) { int sl = base + row; sl = sl >= AROWS ? sl - AROWS : sl; put2(s_a + ((sub * AROWS + sl) * APX + pc) * 64 + q8 * 8, areg[sub * AROWS + row]); }
+      if (tid < HALO_T && h_row >= 2) { int sl = base + h_row; sl = sl >= AROWS ? sl - AROWS : sl; put2(s_a + ((h_sub * AROWS + sl) * APX + h_px) * 64 + q8 * 8, areg[NA]); }
+#pragma unroll
+      for (int sub = 0; sub < WB; ++sub)
+#pragma unroll
+        for (int row = 0; row < R; ++row) {
+          char* dst = s_b + ((sub * R + row) * 32 + pc) * 64 + q8 * 8;
+          const unet_u32x4& v = breg[sub * R + row];
+          if (VDY) {
+            const unsigned nib = v[1] >> (q8 * 4);
+            const unsigned k01 = h2_pair_mask(nib, 0), k23 = h2_pair_mask(nib, 2);
+            *reinterpret_cast<uint2*>(dst) = make_uint2(v[0] & k01, v[0] & k23);
+            *reinterpret_cast<uint2*>(dst + STAGE1) = make_uint2(v[2] & k01, v[2] & k23);
+          } else put2(dst, v);
+        }
+    };
+
     issue_loads(ya, 0);
     post_amax();
     __syncthreads();
     store_lds(ya, 0, 0);
     __syncthreads();
     int base = 0;
+    constexpr int GROUPS = (R / WR) * 2 * 3;                       // groups of nine MFMAs per wave and step
+    constexpr int ES_AT = GROUPS > WGRAD_ES_BACK ? GROUPS - WGRAD_ES_BACK : 0;
     for (int ys = ya; ys < yb; ys += R) {
       const bool more = ys + R < yb;
       int nbase = base + R; nbase = nbase >= AROWS ? nbase - AROWS : nbase;
@@ -247,6 +326,7 @@ __global__ __launch_bounds__(256, (R == 4 && WA * WB > 1) ? 1 : 2) void wgrad_h2
 #pragma unroll
       for (int j = 0; j < AROWS; ++j) { int sl = base + j; sl = sl >= AROWS ? sl - AROWS : sl; roff[j] = sl * APX * 64; }
       if (more) issue_loads(ys + R, 2);
+      int grp = 0;                                                 // (a constant in every unrolled copy)
 #pragma unroll
       for (int r = wr; r < R; r += WR) {
 #pragma unroll
@@ -258,7 +338,10 @@ __global__ __launch_bounds__(256, (R == 4 && WA * WB > 1) ? 1 : 2) void wgrad_h2
             for (int j = 0; j < 8; ++j) bsum += (float)bh[j] + (float)bm[j];
           }
 #pragma unroll
-          for (int ky = 0; ky < 3; ++ky) {
+          for (int ky = 0; ky < 3; ++ky, ++grp) {
+            // ES: without a branch, so that it shares the basic block of the MFMAs behind it and its VALU work issues in their gaps (the last step of a chunk, which
+            // has fetched nothing, splits the registers' old contents again: nobody reads the result)
+            if (ES && grp == ES_AT) { take_amax(); early_split(); }
             // the three taps of a kernel row together: 3 products x 3 taps, consecutive MFMAs on different accumulators (a dependent 32x32x16 MFMA right
             // behind its producer stalls the matrix pipe)
             f16x8 ah[3], am[3];
@@ -276,9 +359,14 @@ __global__ __launch_bounds__(256, (R == 4 && WA * WB > 1) ? 1 : 2) void wgrad_h2
           }
         }
       }
-      if (more) post_amax();
+      if (more) { if (ES) publish_amax(); else post_amax(); }          // (ES: the lane-0 write is a branch, so it stays behind the MFMAs' block)
       __syncthreads();
-      if (more) { store_lds(ys + R, nbase, 2); __syncthreads(); }
+      if (more) {
+        if (!ES) store_lds(ys + R, nbase, 2);
+        else if (exponents_hold()) store_split(nbase);
+        else { issue_loads(ys + R, 2); store_lds(ys + R, nbase, 2); }          // (workgroup-uniform, rare) the pieces were split at a scale that no longer holds: fetch them again
+        __syncthreads();
+      }
       base = nbase;
     }
   }
@@ -644,13 +732,15 @@ int32_t k_conv3x3_h2_wgrad(unet_ctx* ctx, const float* x, const float* dy, float
   const long long S = 9LL * cin * cout + cout;
   const int npairs = p.tiles_a * p.tiles_b;
   const dim3 grid((unsigned)(8 * ((p.nsplit + 7) / 8) * npairs));
-#define UNET_WG(WA_, WB_, WR_) hipLaunchKernelGGL((wgrad_h2_kernel<WA_, WB_, WR_, 2>), grid, dim3(256), 0, s, x, dy, part, n, h, wd, cin, cout, p.tiles_b, p.strips, \
-                                                  p.rows_per_chunk, p.chunks_per_strip, p.nsplit, npairs, S, p.units, p.upb, (const float*)nullptr)
-  if (p.WA == 2 && p.WB == 2) UNET_WG(2, 2, 1);
-  else if (p.WA == 2) UNET_WG(2, 1, 2);
-  else if (p.WB == 2) UNET_WG(1, 2, 2);
-  else hipLaunchKernelGGL((wgrad_h2_kernel<1, 1, 4, 4>), grid, dim3(256), 0, s, x, dy, part, n, h, wd, cin, cout, p.tiles_b, p.strips, p.rows_per_chunk, p.chunks_per_strip, p.nsplit, npairs, S,
-                          p.units, p.upb, (const float*)nullptr);
+#define UNET_WG(WA_, WB_, WR_, R_, ES_) do { auto kern = wgrad_h2_kernel<WA_, WB_, WR_, R_, false, ES_>; unet_note_kernel(ctx, reinterpret_cast<const void*>(kern)); \
+    hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, x, dy, part, n, h, wd, cin, cout, p.tiles_b, p.strips, p.rows_per_chunk, p.chunks_per_strip, p.nsplit, npairs, S, p.units, p.upb, \
+                       (const float*)nullptr); } while (0)
+#define UNET_WG_ES(WA_, WB_, WR_, R_) do { if (ctx->opt_wgrad_early_split) UNET_WG(WA_, WB_, WR_, R_, true); else UNET_WG(WA_, WB_, WR_, R_, false); } while (0)
+  if (p.WA == 2 && p.WB == 2) UNET_WG_ES(2, 2, 1, 2);
+  else if (p.WA == 2) UNET_WG_ES(2, 1, 2, 2);
+  else if (p.WB == 2) UNET_WG_ES(1, 2, 2, 2);
+  else UNET_WG_ES(1, 1, 4, 4);          // one 32 x 32 channel tile: four row phases
+#undef UNET_WG_ES
 #undef UNET_WG
   UNET_CHECK_LAUNCH(ctx, "wgrad_h2");
   return k_wgrad_reduce(ctx, part, p.nslabs, 9, cin, cout, cout, dw, db, s);
@@ -669,8 +759,10 @@ int32_t k_conv3x3_h2_wgrad_dzm(unet_ctx* ctx, const float* x, const void* dzm, c
   const long long S = 9LL * cin * cout + cout;
   const int npairs = p.tiles_a * p.tiles_b;
   const dim3 grid((unsigned)(8 * ((p.nsplit + 7) / 8) * npairs));
-  hipLaunchKernelGGL((wgrad_h2_kernel<1, 1, 4, 4, true>), grid, dim3(256), 0, s, x, static_cast<const float*>(dzm), part, n, h, wd, cin, cout, p.tiles_b, p.strips, p.rows_per_chunk,
-                     p.chunks_per_strip, p.nsplit, npairs, S, p.units, p.upb, w_head);
+  auto kern = ctx->opt_wgrad_early_split ? wgrad_h2_kernel<1, 1, 4, 4, true, true> : wgrad_h2_kernel<1, 1, 4, 4, true, false>;
+  unet_note_kernel(ctx, reinterpret_cast<const void*>(kern));
+  hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, x, static_cast<const float*>(dzm), part, n, h, wd, cin, cout, p.tiles_b, p.strips, p.rows_per_chunk, p.chunks_per_strip, p.nsplit, npairs, S,
+                     p.units, p.upb, w_head);
   UNET_CHECK_LAUNCH(ctx, "wgrad_h2_dzm");
   return k_wgrad_reduce(ctx, part, p.nslabs, 9, cin, cout, cout, dw, db, s);
 }

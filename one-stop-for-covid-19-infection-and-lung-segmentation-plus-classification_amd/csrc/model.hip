@@ -73,6 +73,7 @@ static int* ctx_option(unet_ctx* ctx, int32_t option) {
     case UNET_OPT_HEAD_BWD_FUSED: return &ctx->opt_head_bwd_fused;
     case UNET_OPT_CONV_PP: return &ctx->opt_conv_pp;
     case UNET_OPT_ENC_TAIL_DGRAD: return &ctx->opt_enc_tail_dgrad;
+    case UNET_OPT_WGRAD_EARLY_SPLIT: return &ctx->opt_wgrad_early_split;
     default: return nullptr;
   }
 }
