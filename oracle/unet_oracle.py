@@ -230,6 +230,80 @@ def store_bf16(t):
     return _StoreBF16.apply(t)
 
 
+class _FanOut(torch.autograd.Function):
+    """A stored tensor with several consumers, as the bf16-storage engine accumulates its gradient: one copy per consumer going forward; going back the
+    consumers' gradients are added in `groups` (the sizes of the launches that accumulate into the gradient buffer, in program order) and the buffer is
+    rounded by `store` after every launch, not once after the float64 total.  Test infrastructure for the mixed-precision path only."""
+
+    @staticmethod
+    def forward(ctx, t, groups, store):
+        ctx.groups, ctx.store = groups, store
+        return tuple(t.clone() for _ in range(sum(groups)))
+
+    @staticmethod
+    def backward(ctx, *gs):
+        r, i = None, 0
+        for size in ctx.groups:
+            part = [g for g in gs[i:i + size] if g is not None]
+            i += size
+            if not part:
+                continue
+            tot = sum(part[1:], part[0]) if r is None else sum(part, r)
+            r = ctx.store(tot.detach())
+        return r, None, None
+
+
+class _EluDropStore(torch.autograd.Function):
+    """ELU -> Dropout -> store, as the storage-mode engine runs it: y = store(keep / (1 - rate) * elu(z)); going back the producer's derivative is taken from the
+    STORED y (a = y (1 - rate) is elu(z) again: 1 where a > 0, a + 1 elsewhere), times the keep factor, and the pre-activation gradient is stored once -- the
+    convention of the engine's gradient taps of a conv output."""
+
+    @staticmethod
+    def forward(ctx, z, keep, rate, store):
+        y = F.elu(z)
+        if keep is not None:
+            y = dropout(y, keep, rate)
+        y = store(y)
+        ctx.save_for_backward(y, keep)
+        ctx.rate, ctx.store = rate, store
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        y, keep = ctx.saved_tensors
+        a = y * (1.0 - ctx.rate) if keep is not None else y
+        f = torch.where(a > 0, torch.ones_like(a), a + 1.0)
+        if keep is not None:
+            f = f * keep * (1.0 / (1.0 - ctx.rate))
+        return ctx.store((g * f).detach()), None, None, None
+
+
+def pp_grad_stages():
+    """U-Net++: tensor -> the launches that write its gradient buffer in the backward program's order (build_programs_pp: reverse creation order; the first
+    launch overwrites, the later ones accumulate), each a list of consumers ("pool",) / ("convT", node) / ("skip", node).  The skip slices of a tensor are only
+    noted while their nodes run and summed by ONE launch right before the tensor's own backward starts."""
+    stages, pend = {}, {}
+    nodes = {n[0]: n for n in PP_NODES}
+
+    def flush(t):
+        if pend.get(t):
+            stages.setdefault(t, []).append(pend.pop(t))
+
+    for it in reversed(["e1", "e2", "x1_2", "e3", "x2_2", "x1_3", "e4", "x3_2", "x2_3", "x1_4"]):
+        if it[0] == "e":
+            k = int(it[1])
+            flush(f"c{k}")
+            if k > 1:
+                stages.setdefault(f"c{k - 1}", []).append([("pool",)])
+        else:
+            flush(it)
+            _, _, src, skips = nodes[it]
+            stages.setdefault(src, []).append([("convT", it)])
+            for sk in skips:
+                pend.setdefault(sk, []).append(("skip", it))
+    return stages
+
+
 def forward(weights, x, training=False, keep_masks=None, dtype=torch.float32, want_acts=False, store=None, ckpt=False, relu_masks=None, pool_sel=None):
     """Whole graph T1:853-916.  weights: dict name->array/tensor.  x: [N,H,W,Cin].
     keep_masks: None (dropout off / inference) or dict 'p1'..'p4' -> {0,1} arrays of the
@@ -515,13 +589,30 @@ def pp_init_weights(seed: int = 0, in_ch: int = 1, dtype=np.float32):
     return w
 
 
-def pp_forward(weights, x, training=False, keep_masks=None, dtype=torch.float32, want_acts=False, ckpt=False):
+def pp_forward(weights, x, training=False, keep_masks=None, dtype=torch.float32, want_acts=False, ckpt=False, store=None, pool_sel=None, fold=()):
     """U-Net++ graph.  keep_masks: None or dict conv-name -> {0,1} array of that conv's output shape (the
     Dropout that follows it); ckpt: recompute each encoder block / node in backward (see forward()); returns
-    (p, acts, bn_batch_stats)."""
+    (p, acts, bn_batch_stats).
+    store: None, or store_bf16 to emulate bf16 storage at exactly the tensors plan_workspace_pp materialises: every conv output (after its ELU and dropout), the
+    encoder BatchNorm outputs c1..c4, the pooled p1..p3, the ConvT output inside its concat (the skip slices are copies of stored tensors), every node BatchNorm
+    output, and the gradient twin of each; the staging tensor of a ConvT's data gradient; a gradient buffer that several launches accumulate into is rounded
+    after each of them (pp_grad_stages).  The probabilities and the parameter gradients stay full precision.  A folded BatchNorm (`fold`) is never stored.
+    pool_sel: None or dict 'p1'..'p3' -> {0,1} array: the element every 2 x 2 window takes (see maxpool2x2).
+    fold: names of second convs ('x1_2b', ...) whose BatchNorm in front is folded into them the way the engine does it (needs training=True): the conv runs on
+    the raw tensor with the kernel scale[c] * w stored through `store` and a bias per border class from shift[c]; only the VALUE uses the stored kernel, every
+    gradient is that of the unfolded expression (the engine's backward runs on w itself)."""
     W = {k: _t(v, dtype) for k, v in weights.items()}
     a, stats, T = OrderedDict(), OrderedDict(), {}
     keep = want_acts and not ckpt
+    st = store if store is not None else (lambda t: t)
+    stages = pp_grad_stages() if store is not None else {}
+
+    def fan(name, t):
+        """consumer tag -> the copy of stored tensor t that consumer reads"""
+        if name not in stages:
+            return {}
+        tags = [c for g in stages[name] for c in g]
+        return dict(zip(tags, _FanOut.apply(t, tuple(len(g) for g in stages[name]), store)))
 
     def run(fn, *args):
         if ckpt:
@@ -529,19 +620,37 @@ def pp_forward(weights, x, training=False, keep_masks=None, dtype=torch.float32,
             return checkpoint(fn, *args, use_reentrant=False)
         return fn(*args)
 
-    def conv(name, h, rate):
-        z = conv3x3_bias_relu(h, W[name + "/kernel"], W[name + "/bias"], relu=False)
-        y = F.elu(z)
-        if training and keep_masks is not None and rate > 0:
-            y = dropout(y, _t(keep_masks[name], dtype), rate)
+    def conv(name, h, rate, z=None):
+        if z is None:
+            z = conv3x3_bias_relu(h, W[name + "/kernel"], W[name + "/bias"], relu=False)
+        km = _t(keep_masks[name], dtype) if (training and keep_masks is not None and rate > 0) else None
+        if store is not None:
+            y = _EluDropStore.apply(z, km, rate, store)
+        else:
+            y = F.elu(z)
+            if km is not None:
+                y = dropout(y, km, rate)
         if keep: a[name] = y
         return y
 
-    def bn(name, h):
+    def bn(name, h, stored=True):
         y, mu, va = batchnorm(h, W[name + "/gamma"], W[name + "/beta"], W[name + "/mean"], W[name + "/var"], training)
         stats[name] = (mu.detach(), va.detach(), h.shape[0] * h.shape[1] * h.shape[2])
+        if stored:
+            y = st(y)
         if keep: a[name] = y
         return y
+
+    def conv_folded(name, bnn, h, rate):
+        mu = h.mean(dim=(0, 1, 2)); va = ((h - mu) ** 2).mean(dim=(0, 1, 2))
+        stats[bnn] = (mu.detach(), va.detach(), h.shape[0] * h.shape[1] * h.shape[2])
+        sc = W[bnn + "/gamma"] / torch.sqrt(va + BN_EPS); sh = W[bnn + "/beta"] - mu * sc
+        k = W[name + "/kernel"]
+        ks = k * sc[None, None, :, None]
+        z = conv3x3_bias_relu(h, ks, None, relu=False)
+        z = z + (conv3x3_bias_relu(h, st(ks), None, relu=False) - z).detach()
+        z = z + conv3x3_bias_relu(sh.expand(1, h.shape[1], h.shape[2], -1), k, W[name + "/bias"], relu=False)      # zero padding of the NORMALISED tensor: per border class
+        return conv(name, None, rate, z=z)
 
     def enc(k, h):
         h = conv(f"c{k}a", h, PP_ENC_DROP)
@@ -549,33 +658,41 @@ def pp_forward(weights, x, training=False, keep_masks=None, dtype=torch.float32,
         return bn(f"bn{k}", h)
 
     def node(nm, c, tsrc, *tskips):
-        u = convT2x2s2_bias(tsrc, W[f"u{nm[1:]}/kernel"], W[f"u{nm[1:]}/bias"])
+        u = st(convT2x2s2_bias(st(tsrc), W[f"u{nm[1:]}/kernel"], W[f"u{nm[1:]}/bias"]))          # (st on the input: identity forward, the staging tensor of the data gradient backward)
         if keep: a[f"u{nm[1:]}"] = u
-        hh = torch.cat([u] + list(tskips), dim=3)
-        hh = bn(nm + "abn", conv(nm + "a", hh, PP_BLOCK_DROP))
-        return bn(nm + "bbn", conv(nm + "b", hh, PP_BLOCK_DROP))
+        hh = st(torch.cat([u] + list(tskips), dim=3))                       # (all bf16 already: only the concat's gradient buffer is rounded)
+        if keep and store is not None: a["cat_" + nm] = hh
+        ha = conv(nm + "a", hh, PP_BLOCK_DROP)
+        if nm + "b" in fold:
+            hb = conv_folded(nm + "b", nm + "abn", ha, PP_BLOCK_DROP)
+        else:
+            hb = conv(nm + "b", bn(nm + "abn", ha), PP_BLOCK_DROP)
+        return bn(nm + "bbn", hb)
 
     h = _t(x, dtype)
     todo = {1: [], 2: ["x1_2"], 3: ["x2_2", "x1_3"], 4: ["x3_2", "x2_3", "x1_4"]}
     nodes = {n[0]: n for n in PP_NODES}
+    use = {}
     for k in (1, 2, 3, 4):
         T[f"c{k}"] = run(lambda t, k=k: enc(k, t), h)
+        use[f"c{k}"] = fan(f"c{k}", T[f"c{k}"])
         for nm in todo[k]:
             _, c, src, skips = nodes[nm]
-            T[nm] = run(lambda ts, *sk, nm=nm, c=c: node(nm, c, ts, *sk), T[src], *[T[s] for s in skips])
-        h = maxpool2x2(T[f"c{k}"])
+            T[nm] = run(lambda ts, *sk, nm=nm, c=c: node(nm, c, ts, *sk), use[src].get(("convT", nm), T[src]), *[use[s].get(("skip", nm), T[s]) for s in skips])
+            use[nm] = fan(nm, T[nm])
+        h = st(maxpool2x2(use[f"c{k}"].get(("pool",), T[f"c{k}"]), _t(pool_sel[f"p{k}"], dtype) if (pool_sel is not None and f"p{k}" in pool_sel) else None))
         if keep: a[f"p{k}"] = h
     p = conv1x1_sigmoid(T["x1_4"], W["out/kernel"], W["out/bias"])
     if keep: a["out"] = p
     return (p, a, stats) if keep else (p, None, stats)
 
 
-def pp_loss_and_grads(weights, x, y, keep_masks=None, dtype=torch.float32, want_acts=False, ckpt=False):
+def pp_loss_and_grads(weights, x, y, keep_masks=None, dtype=torch.float32, want_acts=False, ckpt=False, store=None, pool_sel=None, fold=()):
     names = pp_trainable_names(np.asarray(x).shape[-1])
     W = {k: _t(v, dtype).clone() for k, v in weights.items()}
     for k in names:
         W[k].requires_grad_(True)
-    p, acts, stats = pp_forward(W, x, training=True, keep_masks=keep_masks, dtype=dtype, want_acts=want_acts, ckpt=ckpt)
+    p, acts, stats = pp_forward(W, x, training=True, keep_masks=keep_masks, dtype=dtype, want_acts=want_acts, ckpt=ckpt, store=store, pool_sel=pool_sel, fold=fold)
     t = _t(y, dtype)
     loss = bce_dice_loss(t, p); dice = dice_coeff(t, p)
     if want_acts:
@@ -656,23 +773,47 @@ def cls_init_weights(seed: int = 0, in_ch: int = 1, hw=(224, 224), dtype=np.floa
     return w
 
 
-def cls_forward(weights, x, training=False, keep_mask=None, dtype=torch.float32, want_acts=False, ckpt=False, relu_masks=None, pool_sel=None):
+def cls_forward(weights, x, training=False, keep_mask=None, dtype=torch.float32, want_acts=False, ckpt=False, relu_masks=None, pool_sel=None, store=None, fold=()):
     """keep_mask: None or {0,1} array [n, 32] of the Dropout(0.4) after Dense(32).  ckpt: recompute each conv block in
-    backward (see forward()).  Returns (p [n], acts, bn stats)."""
+    backward (see forward()).  Returns (p [n], acts, bn stats).
+    store: None, or store_bf16 to emulate bf16 storage at exactly the tensors plan_workspace_cls materialises (every conv, BatchNorm and pool output and its
+    gradient twin; the 32 hidden units, the probabilities and the parameter gradients stay full precision).  fold: names of second convs ('c2b', ...) whose
+    BatchNorm in front is folded into them (see pp_forward; that BatchNorm's output is never stored)."""
     W = {k: _t(v, dtype) for k, v in weights.items()}
     a, stats = OrderedDict(), OrderedDict()
     keep = want_acts and not ckpt
 
+    st = store if store is not None else (lambda t: t)
+
     def block(k, h):
         for ab in "ab":
-            h = conv3x3_bias_relu(h, W[f"c{k}{ab}/kernel"], W[f"c{k}{ab}/bias"], relu_mask=(_t(relu_masks[f"c{k}{ab}"], dtype) if relu_masks is not None else None))
-            if keep: a[f"c{k}{ab}"] = h
-            nm = f"bn{k}{ab}"
+            cn, nm = f"c{k}{ab}", f"bn{k}{ab}"
+            rmask = _t(relu_masks[cn], dtype) if relu_masks is not None else None
+            if ab == "b" and cn in fold:
+                # BatchNorm bn{k}a folded into conv c{k}b the way the engine does it (see pp_forward): `h` is the raw c{k}a
+                pn = f"bn{k}a"
+                sc = W[pn + "/gamma"] / torch.sqrt(stats[pn][1] + BN_EPS); sh = W[pn + "/beta"] - stats[pn][0] * sc
+                ks = W[cn + "/kernel"] * sc[None, None, :, None]
+                z = conv3x3_bias_relu(h, ks, None, relu=False)
+                z = z + (conv3x3_bias_relu(h, st(ks), None, relu=False) - z).detach()
+                z = z + conv3x3_bias_relu(sh.expand(1, h.shape[1], h.shape[2], -1), W[cn + "/kernel"], W[cn + "/bias"], relu=False)
+                h = st(z * rmask if rmask is not None else torch.relu(z))
+            else:
+                h = st(conv3x3_bias_relu(h, W[cn + "/kernel"], W[cn + "/bias"], relu_mask=rmask))
+            if keep: a[cn] = h
             src = h
+            if ab == "a" and f"c{k}b" in fold:
+                mu = src.mean(dim=(0, 1, 2)); va = ((src - mu) ** 2).mean(dim=(0, 1, 2))
+                stats[nm] = (mu, va, src.shape[0] * src.shape[1] * src.shape[2])          # (attached: the folded conv's gradient runs through them; detached below)
+                continue
             h, mu, va = batchnorm(h, W[nm + "/gamma"], W[nm + "/beta"], W[nm + "/mean"], W[nm + "/var"], training)
+            h = st(h)
             stats[nm] = (mu.detach(), va.detach(), src.shape[0] * src.shape[1] * src.shape[2])
             if keep: a[nm] = h
-        h = maxpool2x2(h, _t(pool_sel[f"p{k}"], dtype) if pool_sel is not None else None)
+        if f"c{k}b" in fold:
+            pn = f"bn{k}a"
+            stats[pn] = (stats[pn][0].detach(), stats[pn][1].detach(), stats[pn][2])
+        h = st(maxpool2x2(h, _t(pool_sel[f"p{k}"], dtype) if pool_sel is not None else None))
         if keep: a[f"p{k}"] = h
         return h
 
@@ -710,13 +851,13 @@ def cls_loss(y_true, y_pred, class_weights=(1.0, 1.0)):
     return (l * w).mean()
 
 
-def cls_loss_and_grads(weights, x, y, keep_mask=None, class_weights=(1.0, 1.0), dtype=torch.float32, want_acts=False, ckpt=False, relu_masks=None, pool_sel=None):
+def cls_loss_and_grads(weights, x, y, keep_mask=None, class_weights=(1.0, 1.0), dtype=torch.float32, want_acts=False, ckpt=False, relu_masks=None, pool_sel=None, store=None, fold=()):
     xs = np.asarray(x)
     names = cls_trainable_names(xs.shape[-1], xs.shape[1:3])
     W = {k: _t(v, dtype).clone() for k, v in weights.items()}
     for k in names:
         W[k].requires_grad_(True)
-    p, acts, stats = cls_forward(W, x, training=True, keep_mask=keep_mask, dtype=dtype, want_acts=want_acts, ckpt=ckpt, relu_masks=relu_masks, pool_sel=pool_sel)
+    p, acts, stats = cls_forward(W, x, training=True, keep_mask=keep_mask, dtype=dtype, want_acts=want_acts, ckpt=ckpt, relu_masks=relu_masks, pool_sel=pool_sel, store=store, fold=fold)
     t = _t(np.asarray(y, np.float64).reshape(-1), dtype)
     loss = cls_loss(t, p, class_weights); f1 = cls_f1(t, p)
     if want_acts:
