@@ -496,6 +496,15 @@ struct Layer { std::string name; int kind; int cin, cout; };   // kind 0 conv3, 
 struct TInfo { int is_state; int64_t off, count; };
 struct Buf { size_t off = 0; int ld = 0, n = 0, h = 0, w = 0, c = 0; size_t chan_off = 0; int f32 = 0; };   // offsets in 4-byte units into the workspace; f32: stays fp32 in bf16-storage mode
 
+// An activation / gradient address in the model's storage type: converts to the pointer type of whichever storage twin (X / X_bf16) takes it -- TWIN below
+struct TPtr {
+  void* p;
+  operator const float*() const { return static_cast<const float*>(p); }
+  operator float*() const { return static_cast<float*>(p); }
+  operator const unet_bf16*() const { return static_cast<const unet_bf16*>(p); }
+  operator unet_bf16*() const { return static_cast<unet_bf16*>(p); }
+};
+
 struct Op {
   std::string name;
   std::function<int32_t(hipStream_t)> run;
@@ -566,6 +575,8 @@ struct unet_model {
   void* bufptr(const Buf& b) const { return ws + b.off * 4 + b.chan_off * elem_bytes(b); }
   void* Av(const std::string& n) const { return bufptr(act.at(n)); }
   void* Dv(const std::string& n) const { return bufptr(grad.at(n)); }
+  TPtr At(const std::string& n) const { return {Av(n)}; }
+  TPtr Dt(const std::string& n) const { return {Dv(n)}; }
 };
 
 namespace {
@@ -831,18 +842,273 @@ static int32_t first_conv_wgrad_bf16(unet_ctx* ctx, unet_model* m, const std::st
   return k_conv3x3_naive_wgrad(ctx, m->x, tmp, m->G(name + "/kernel"), m->G(name + "/bias"), ob.n, ob.h, ob.w, m->in_ch, cout, s);
 }
 
+#define CBF(p) static_cast<const unet_bf16*>(p)
+#define WBF(p) static_cast<unet_bf16*>(p)
+// An fp32 entry point and its bf16-storage twin that take the same argument list apart from the element type behind the activation pointers: one spelling, the activation
+// arguments as TPtr (m->At / m->Dt).  Launches whose two storage types take different arguments (the first conv, prepared images, an algorithm selector) stay spelled out
+#define TWIN(dt, f32_fn, bf16_fn, ...) ((dt) ? bf16_fn(__VA_ARGS__) : f32_fn(__VA_ARGS__))
+
+// =========================================================================================
+// Op emitters: the launches the three graphs have in common, each defined once.  An emitter appends its ops to the program `F` / `BW` it is given and, where the group has a
+// cross-rank reduction, the sync point to `SY`; the builders below hold the topology and the ops only one graph has.  A new kind of op goes here, not into a builder.
+// eb: bytes per stored activation element (roofline accounting); gcount: multiplies per-rank element counts into global counts.
+// Dropout arguments are (rate, salt): the launch gets the seed m->drop_seed + salt, and the rate only while dropout is on (m->drop_rate > 0).
+// =========================================================================================
+using Ops = std::vector<Op>;
+using Syncs = std::vector<unet_model::SyncRef>;
+
+// ---- head and loss
+// lazy: the U-Net's inference program skips the launch when there are no labels (no statistics, no loss sums -- nothing adds into them)
+void emit_zero_sums(unet_model* m, Ops& F, bool lazy) {
+  unet_ctx* ctx = m->ctx;
+  const size_t sums_bytes = (m->bn_sums_doubles + 5 + UNET_HEAD_SUMS) * sizeof(double);
+  ADD_OP(F, "zero_sums", 0, 0, {
+    if (lazy && !m->yt) return UNET_OK;
+    return unet_zero(ctx, m->wsf(m->off_bn_sums), sums_bytes, s);
+  });
+}
+void emit_loss_weight_map(unet_model* m, Ops& F) {          // weighted_bce_dice_loss (T1:837-845): its map of this batch's labels
+  if (!m->weighted()) return;
+  unet_ctx* ctx = m->ctx;
+  ADD_OP(F, "loss_weight_map", 0, 8.0 * m->N * m->H * m->W, {
+    if (!m->yt) return UNET_OK;
+    return k_loss_weight_map(ctx, m->yt, m->wsf(m->off_wmap), m->N, m->H, m->W, s);
+  });
+}
+void emit_head_fwd(unet_model* m, Ops& F, const std::string& src) {          // 1x1 sigmoid head on `src` + the loss sums
+  unet_ctx* ctx = m->ctx; const int dt = m->dt; const double eb = dt ? 2.0 : 4.0;
+  const Buf hb = m->act.at(src);
+  const int64_t hp = (int64_t)hb.n * hb.h * hb.w;
+  ADD_OP(F, "head_fwd", 2.0 * 32 * hp, hp * (eb * 32 + 8.0), {
+    if (!m->pout) UNET_FAIL(ctx, UNET_E_STATE, "head_fwd: p_out not set (unet_model_set_io)");
+    return TWIN(dt, unet_head_fwd_ex, unet_head_fwd_bf16_ex, ctx, m->At(src), m->P("out/kernel"), m->P("out/bias"), m->pout, m->yt, m->yt ? m->wmap() : nullptr,
+                m->yt ? m->wsd(m->off_loss_sums) : nullptr, hp, hb.c, s);
+  });
+}
+// the sync point of the loss sums on the op in front (head_fwd, or the U-Net's head_fold), then the loss over the pixels of `src`
+void emit_loss_finalize(unet_model* m, Ops& F, Syncs& SY, const std::string& src) {
+  unet_ctx* ctx = m->ctx; const double gcount = (double)m->world;
+  const Buf hb = m->act.at(src);
+  const int64_t hp = (int64_t)hb.n * hb.h * hb.w;
+  SY.push_back({(int)F.size() - 1, 1, true, m->off_loss_sums * 4, m->weighted() ? 5 : 4});
+  ADD_OP(F, "loss_finalize", 0, 0, {
+    if (!m->yt) return UNET_OK;
+    return k_loss_finalize(ctx, m->wsd(m->off_loss_sums), (double)hp * gcount, m->wsf(m->off_loss_out), m->loss_out2, s, m->loss);
+  });
+}
+void emit_zero_bwd_sums(unet_model* m, Ops& BW) {          // the BatchNorm backward sums and the head's weight gradient (head_bwd adds into it)
+  unet_ctx* ctx = m->ctx;
+  size_t bs_bytes = 0;
+  for (auto& l : m->layers) if (l.kind == 2) bs_bytes += 2 * (size_t)l.cout * sizeof(double);
+  ADD_OP(BW, "zero_bwd_sums", 0, 0, {
+    int32_t r = unet_zero(ctx, m->wsf(m->off_bn_bsums), bs_bytes, s);
+    if (r) return r;
+    return unet_zero(ctx, m->G("out/kernel"), (size_t)(m->tinfo.at("out/kernel").count + 1) * sizeof(float), s);
+  });
+}
+void emit_head_bwd(unet_model* m, Ops& BW, const std::string& src, int relu_mask) {          // relu_mask: `src` came out of a ReLU, whose derivative goes into its gradient
+  unet_ctx* ctx = m->ctx; const int dt = m->dt; const double eb = dt ? 2.0 : 4.0, gcount = (double)m->world;
+  const Buf hb = m->act.at(src);
+  const int64_t hp = (int64_t)hb.n * hb.h * hb.w;
+  ADD_OP(BW, "head_bwd", 4.0 * 32 * hp, hp * (eb * 64 + 8.0), {
+    if (!m->yt || !m->pout) UNET_FAIL(ctx, UNET_E_STATE, "head_bwd: io not set");
+    const unet_loss_sel& L = m->loss;
+    return TWIN(dt, unet_head_bwd_ex, unet_head_bwd_bf16_ex, ctx, m->At(src), m->P("out/kernel"), m->pout, m->yt, m->wsd(m->off_loss_sums), (double)hp * gcount, L.kind, L.alpha, L.beta,
+                m->wmap(), m->Dt(src), m->G("out/kernel"), m->G("out/bias"), hp, hb.c, relu_mask, s);
+  });
+}
+
+// ---- gradient buckets and ConvT
+void emit_bucket(unet_model* m, const Ops& BW, Syncs& SY, const std::string& first, const std::string& last_tensor) {          // gradients [first, last_tensor] are final behind the last op
+  const TInfo a = m->tinfo.at(first), b = m->tinfo.at(last_tensor);
+  SY.push_back({(int)BW.size() - 1, 3, false, (size_t)a.off * 4, b.off + b.count - a.off});
+}
+void emit_convT_wgrad(unet_model* m, Ops& BW, const std::string& un, const std::string& src, int cin, int c) {
+  unet_ctx* ctx = m->ctx; const int dt = m->dt, algo = m->algo; const double eb = dt ? 2.0 : 4.0;
+  const Buf ib = m->act.at(src), ug = m->grad.at(un);
+  ADD_OP(BW, "convT_wgrad:" + un, 2.0 * 4 * cin * c * nel(ib) / ib.c, eb * (nel(ib) + nel(ug)), {
+    if (dt) return k_convT_bf16_wgrad(ctx, m->At(src), m->Dt(un), ug.ld, m->G(un + "/kernel"), m->G(un + "/bias"), m->wsf(m->off_wgrad_ws), m->wgrad_ws_bytes, ib.n, ib.h, ib.w, cin, c, s);
+    return unet_convT2x2_bwd_weights(ctx, m->At(src), m->Dt(un), ug.ld, m->G(un + "/kernel"), m->G(un + "/bias"), m->wsf(m->off_wgrad_ws), m->wgrad_ws_bytes, ib.n, ib.h, ib.w, cin, c, algo, s);
+  });
+}
+
+// ---- BatchNorm forward: stats -> [sync] -> finalize -> apply.  The pieces (the U-Net puts its analytic-concat statistics and composed finalize between them) ...
+void emit_bn_stats(unet_model* m, Ops& F, const std::string& name, const std::string& in, int c) {
+  unet_ctx* ctx = m->ctx; const int dt = m->dt; const double eb = dt ? 2.0 : 4.0;
+  const Buf ib = m->act.at(in);
+  const int64_t pixels = (int64_t)ib.n * ib.h * ib.w;
+  const size_t so = m->bn_sum_off.at(name);
+  ADD_OP(F, "bn_stats:" + name, 0, eb * pixels * c, {
+    return TWIN(dt, unet_bn_stats, unet_bn_stats_bf16, ctx, m->At(in), ib.ld, m->wsd(m->off_bn_sums) + so, pixels, c, s);
+  });
+}
+void emit_bn_stats_sync(unet_model* m, const Ops& F, Syncs& SY, const std::string& name, int c) {          // on the statistics op in front
+  SY.push_back({(int)F.size() - 1, 0, true, (m->off_bn_sums * 4) + m->bn_sum_off.at(name) * 8, 2 * (int64_t)c});
+}
+void emit_bn_finalize(unet_model* m, Ops& F, const std::string& name, const std::string& in, int c, bool training) {
+  unet_ctx* ctx = m->ctx; const double gcount = (double)m->world;
+  const Buf ib = m->act.at(in);
+  const int64_t pixels = (int64_t)ib.n * ib.h * ib.w;
+  const size_t so = m->bn_sum_off.at(name), bo = m->bnp_off.at(name);
+  if (training) ADD_OP(F, "bn_finalize:" + name, 0, 0, {
+    return unet_bn_finalize_train(ctx, m->wsd(m->off_bn_sums) + so, (double)pixels * gcount, m->P(name + "/gamma"), m->P(name + "/beta"), m->P(name + "/mean"), m->P(name + "/var"), m->wsf(bo), c, s);
+  });
+  else ADD_OP(F, "bn_finalize_infer:" + name, 0, 0, {
+    return unet_bn_finalize_infer(ctx, m->P(name + "/gamma"), m->P(name + "/beta"), m->P(name + "/mean"), m->P(name + "/var"), m->wsf(bo), c, s);
+  });
+}
+void emit_bn_apply(unet_model* m, Ops& F, const std::string& name, const std::string& in, const std::string& out, int c) {
+  unet_ctx* ctx = m->ctx; const int dt = m->dt; const double eb = dt ? 2.0 : 4.0;
+  const Buf ib = m->act.at(in), ob = m->act.at(out);
+  const int64_t pixels = (int64_t)ib.n * ib.h * ib.w;
+  const size_t bo = m->bnp_off.at(name);
+  ADD_OP(F, "bn_apply:" + name, 0, 2 * eb * pixels * c, {
+    return TWIN(dt, unet_bn_apply, unet_bn_apply_bf16, ctx, m->At(in), ib.ld, m->wsf(bo), m->At(out), ob.ld, pixels, c, s);
+  });
+}
+// ... and the whole site: apply fused with the 2x2 pool when `pool` names the pooled output, none at all when the BatchNorm is folded into the conv behind it (folded_bn)
+void emit_bn_fwd(unet_model* m, Ops& F, Syncs& SY, const std::string& name, const std::string& in, const std::string& out, int c, const std::string& pool, bool training) {
+  if (training) { emit_bn_stats(m, F, name, in, c); emit_bn_stats_sync(m, F, SY, name, c); }
+  emit_bn_finalize(m, F, name, in, c, training);
+  if (pool.empty()) { if (!m->folded_bn.count(name)) emit_bn_apply(m, F, name, in, out, c); return; }
+  unet_ctx* ctx = m->ctx; const int dt = m->dt; const double eb = dt ? 2.0 : 4.0;
+  const Buf ib = m->act.at(in), ob = m->act.at(out);
+  const int64_t pixels = (int64_t)ib.n * ib.h * ib.w;
+  const size_t bo = m->bnp_off.at(name);
+  ADD_OP(F, "bn_apply_pool:" + pool, 0, eb * 2.25 * pixels * c, {
+    return TWIN(dt, unet_bn_apply_maxpool_dropout_fwd, unet_bn_apply_maxpool_dropout_fwd_bf16, ctx, m->At(in), ib.ld, m->wsf(bo), m->At(out), ob.ld, m->At(pool), ib.n, ib.h, ib.w, c, 0.0f, 0, s);
+  });
+}
+
+// ---- conv3x3 forward.  Plain: `in` empty = the network input
+void emit_conv_fwd(unet_model* m, Ops& F, const std::string& name, const std::string& in, int cin, int cout, int act, float rate, uint64_t salt, bool training) {
+  unet_ctx* ctx = m->ctx; const int dt = m->dt, algo = m->algo; const double eb = dt ? 2.0 : 4.0;
+  const Buf ob = m->act.at(name);
+  const double px = (double)ob.n * ob.h * ob.w;
+  ADD_OP(F, "conv3x3_fwd:" + name, 2.0 * 9 * cin * cout * px, eb * px * (cin + cout) + 4.0 * 9.0 * cin * cout, {
+    const float r = (training && m->drop_rate > 0.0f) ? rate : 0.0f;
+    if (dt) {
+      if (in.empty()) return first_conv_fwd_bf16(ctx, m, name, ob, cout, act, r, m->drop_seed + salt, s);
+      return k_conv3x3_bf16_fwd(ctx, m->At(in), m->P(name + "/kernel"), m->P(name + "/bias"), nullptr, MASK_NONE, m->At(name), ob.n, ob.h, ob.w, cin, cout, act, r, m->drop_seed + salt,
+                                WBF(static_cast<void*>(m->wsf(m->off_wt))), 0, s);
+    }
+    return conv3x3_fwd_dispatch(ctx, in.empty() ? m->x : m->A(in), m->P(name + "/kernel"), m->P(name + "/bias"), nullptr, MASK_NONE, m->Aw(name), ob.n, ob.h, ob.w, cin, cout, act, r,
+                                m->drop_seed + salt, algo, s, m->wsf(m->off_wt), 0);
+  });
+}
+// Folded: the BatchNorm `bnn` in front of conv `cn` (c -> c channels) lives in the conv's scaled weights and border-class bias table, the conv reads the raw `xn`
+void emit_conv_fwd_folded(unet_model* m, Ops& F, const std::string& cn, const std::string& xn, const std::string& bnn, int c, int act, float rate, uint64_t salt, bool training) {
+  unet_ctx* ctx = m->ctx; const int dt = m->dt; const double eb = dt ? 2.0 : 4.0;
+  const Buf ob = m->act.at(cn);
+  const double px = (double)ob.n * ob.h * ob.w;
+  const size_t fo = m->fold_off.at(cn), bo = m->bnp_off.at(bnn);
+  ADD_OP(F, "bn_fold_prepare:" + cn, 2.0 * 9 * c * c * 2, 4.0 * 9 * c * c * 4, {
+    return k_bn_fold_prepare(ctx, m->P(cn + "/kernel"), m->P(cn + "/bias"), m->wsf(bo), m->wsf(bo) + c, c, c, m->wsf(fo), s, dt != 0);
+  });
+  ADD_OP(F, "conv3x3_fwd:" + cn, 2.0 * 9 * c * c * px, eb * px * 2 * c + 4.0 * 9.0 * c * c, {
+    const float r = (training && m->drop_rate > 0.0f) ? rate : 0.0f;
+    const float* tab = m->wsf(fo) + (size_t)9 * c * c;
+    if (dt) return k_conv3x3_bf16_fwd(ctx, m->At(xn), m->wsf(fo), tab, reinterpret_cast<const unet_bf16*>(tab), MASK_BIAS_TAB, m->At(cn), ob.n, ob.h, ob.w, c, c, act, r, m->drop_seed + salt,
+                                      WBF(static_cast<void*>(m->wsf(m->off_wt))), 0, s);
+    int32_t e = k_h2_weights(ctx, m->P(cn + "/kernel"), m->wsf(m->off_wt), c, c, 0, s, m->wsf(bo));
+    if (e) return e;
+    return k_conv3x3_h2_fwd(ctx, m->A(xn), m->wsf(m->off_wt), tab, tab, MASK_BIAS_TAB, m->Aw(cn), ob.n, ob.h, ob.w, c, c, act, r, m->drop_seed + salt, s);
+  });
+}
+
+// ---- BatchNorm backward: dy = grad[dyname], x = act[xname], dx = grad[dxname] with the derivative `mask_mode` of what produced x: backward statistics + parameter
+// gradients -> [sync] -> apply.  stats_done: the sums (sum dy, sum dy * xhat) are already there (the U-Net's pool backward, its folded weight gradient): parameter gradients only
+void emit_bn_bwd(unet_model* m, Ops& BW, Syncs& SY, const std::string& name, const std::string& dyname, const std::string& xname, const std::string& dxname, int c, int mask_mode, float rate,
+                 uint64_t salt, bool stats_done) {
+  unet_ctx* ctx = m->ctx; const int dt = m->dt; const double eb = dt ? 2.0 : 4.0, gcount = (double)m->world;
+  const Buf gb = m->grad.at(dyname), xb = m->act.at(xname), db = m->grad.at(dxname);
+  const int64_t pixels = (int64_t)xb.n * xb.h * xb.w;
+  const size_t so = m->bn_bsum_off.at(name), bo = m->bnp_off.at(name);
+  if (stats_done) ADD_OP(BW, "bn_bwd_param_grads:" + name, 0, 0, {
+    return unet_bn_bwd_param_grads(ctx, m->wsd(m->off_bn_bsums) + so, m->G(name + "/gamma"), m->G(name + "/beta"), c, s);
+  });
+  else ADD_OP(BW, "bn_bwd_stats:" + name, 0, 2 * eb * pixels * c, {
+    int32_t r = TWIN(dt, unet_bn_bwd_stats, unet_bn_bwd_stats_bf16, ctx, m->Dt(dyname), gb.ld, m->At(xname), xb.ld, m->wsf(bo), m->wsd(m->off_bn_bsums) + so, pixels, c, s);
+    if (r) return r;
+    return unet_bn_bwd_param_grads(ctx, m->wsd(m->off_bn_bsums) + so, m->G(name + "/gamma"), m->G(name + "/beta"), c, s);
+  });
+  SY.push_back({(int)BW.size() - 1, 2, true, m->off_bn_bsums * 4 + so * 8, 2 * (int64_t)c});
+  ADD_OP(BW, "bn_bwd_apply:" + name, 0, 3 * eb * pixels * c, {
+    const bool drop = m->drop_rate > 0.0f && rate > 0.0f;
+    return TWIN(dt, unet_bn_bwd_apply, unet_bn_bwd_apply_bf16, ctx, m->Dt(dyname), gb.ld, m->At(xname), xb.ld, m->wsf(bo), m->wsd(m->off_bn_bsums) + so, (double)pixels * gcount,
+                (mask_mode == MASK_ELU_DROP && !drop) ? MASK_ELU : mask_mode, drop ? rate : 0.0f, m->drop_seed + salt, m->Dt(dxname), db.ld, pixels, c, s);
+  });
+}
+
+// ---- conv3x3 backward.  The weight gradient: x = act[in] or the network input, dy = grad[name] ...
+void emit_conv_wgrad(unet_model* m, Ops& BW, const std::string& name, const std::string& in, int cin, int cout) {
+  unet_ctx* ctx = m->ctx; const int dt = m->dt, algo = m->algo; const double eb = dt ? 2.0 : 4.0;
+  const Buf ob = m->act.at(name);
+  const double px = (double)ob.n * ob.h * ob.w;
+  ADD_OP(BW, "conv3x3_wgrad:" + name, 2.0 * 9 * cin * cout * px, eb * px * (cin + cout) + 4.0 * 9.0 * cin * cout, {
+    if (dt) {
+      if (in.empty()) return first_conv_wgrad_bf16(ctx, m, name, ob, cout, s);
+      return k_conv3x3_bf16_wgrad(ctx, m->At(in), m->Dt(name), m->G(name + "/kernel"), m->G(name + "/bias"), m->wsf(m->off_wgrad_ws), m->wgrad_ws_bytes, ob.n, ob.h, ob.w, cin, cout, s);
+    }
+    return conv3x3_wgrad_dispatch(ctx, in.empty() ? m->x : m->A(in), m->D(name), m->G(name + "/kernel"), m->G(name + "/bias"), m->wsf(m->off_wgrad_ws), m->wgrad_ws_bytes, ob.n, ob.h, ob.w, cin,
+                                  cout, algo, s);
+  });
+}
+// ... then, if wanted, the data gradient into grad[in] with the derivative `mask_mode` (mask = act[in])
+void emit_conv_bwd(unet_model* m, Ops& BW, const std::string& name, const std::string& in, int cin, int cout, bool want_dx, int mask_mode, float rate, uint64_t salt) {
+  emit_conv_wgrad(m, BW, name, in, cin, cout);
+  if (!want_dx) return;
+  unet_ctx* ctx = m->ctx; const int dt = m->dt, algo = m->algo; const double eb = dt ? 2.0 : 4.0;
+  const Buf ob = m->act.at(name);
+  const double px = (double)ob.n * ob.h * ob.w;
+  ADD_OP(BW, "conv3x3_dgrad:" + name, 2.0 * 9 * cin * cout * px, eb * px * (cout + cin + (mask_mode ? cin : 0)) + 4.0 * 9.0 * cin * cout, {
+    const bool drop = m->drop_rate > 0.0f && rate > 0.0f;
+    const int mm = (mask_mode == MASK_ELU_DROP && !drop) ? MASK_ELU : mask_mode;
+    if (dt) return k_conv3x3_bf16_fwd(ctx, m->Dt(name), m->P(name + "/kernel"), nullptr, mm ? CBF(m->Av(in)) : nullptr, mm, m->Dt(in), ob.n, ob.h, ob.w, cout, cin, ACT_NONE, drop ? rate : 0.0f,
+                                      m->drop_seed + salt, WBF(static_cast<void*>(m->wsf(m->off_wt))), 1, s);
+    return unet_conv3x3_bwd_data(ctx, m->D(name), m->P(name + "/kernel"), mm ? m->A(in) : nullptr, mm, drop ? rate : 0.0f, m->drop_seed + salt, m->D(in), m->wsf(m->off_wt), ob.n, ob.h, ob.w, cin, cout,
+                                 algo, s);
+  });
+}
+// Folded (emit_conv_fwd_folded): the weight gradient on the raw x, corrected; the BatchNorm's backward sums out of W . dW_raw and S [sync]; its backward apply and the
+// derivative `mask_mode` of what produced x (MASK_BN_BWD_RELU, or MASK_BN_BWD_ELU_DROP with its dropout) in the data gradient's epilogue, which writes grad[xn] directly
+void emit_conv_bwd_folded(unet_model* m, Ops& BW, Syncs& SY, const std::string& cn, const std::string& xn, const std::string& bnn, int c, int mask_mode, float rate, uint64_t salt) {
+  unet_ctx* ctx = m->ctx; const int dt = m->dt; const double eb = dt ? 2.0 : 4.0, gcount = (double)m->world;
+  const Buf ob = m->act.at(cn);
+  const double px = (double)ob.n * ob.h * ob.w;
+  const size_t go = m->fold_g_off.at(cn), co = m->fold_c_off.at(cn), bo = m->bnp_off.at(bnn), so = m->bn_bsum_off.at(bnn);
+  emit_conv_wgrad(m, BW, cn, xn, c, c);
+  ADD_OP(BW, "wgrad_bn_fold_fix:" + cn, 2.0 * 9 * c * c, 8.0 * 9 * c * c, {
+    int32_t r = dt ? k_wgrad_bn_fold_fix_bf16(ctx, m->Dt(cn), ob.n, ob.h, ob.w, c, c, m->wsf(bo), m->wsf(bo) + c, m->G(cn + "/kernel"), m->G(cn + "/bias"), m->wsf(go), s, m->P(cn + "/kernel"),
+                                              m->wsf(bo) + 2 * c, m->wsf(bo) + 3 * c, m->wsd(m->off_bn_bsums) + so)
+                   : k_wgrad_bn_fold_fix(ctx, m->D(cn), ob.n, ob.h, ob.w, c, c, m->wsf(bo), m->wsf(bo) + c, m->G(cn + "/kernel"), m->G(cn + "/bias"), m->wsf(go), s, m->P(cn + "/kernel"),
+                                         m->wsf(bo) + 2 * c, m->wsf(bo) + 3 * c, m->wsd(m->off_bn_bsums) + so);
+    if (r) return r;
+    return unet_bn_bwd_param_grads(ctx, m->wsd(m->off_bn_bsums) + so, m->G(bnn + "/gamma"), m->G(bnn + "/beta"), c, s);
+  });
+  SY.push_back({(int)BW.size() - 1, 2, true, m->off_bn_bsums * 4 + so * 8, 2 * (int64_t)c});
+  ADD_OP(BW, "conv3x3_dgrad_bn_bwd:" + cn, 2.0 * 9 * c * c * px, eb * px * 3 * c + 4.0 * 9.0 * c * c, {
+    const bool drop = m->drop_rate > 0.0f && rate > 0.0f;
+    const int mm = (mask_mode == MASK_BN_BWD_ELU_DROP && !drop) ? MASK_BN_BWD_ELU : mask_mode;
+    int32_t r = k_bn_bwd_coef(ctx, m->wsf(bo), m->wsd(m->off_bn_bsums) + so, px * gcount, m->wsf(co), c, s);
+    if (r) return r;
+    if (dt) return k_conv3x3_bf16_fwd(ctx, m->Dt(cn), m->P(cn + "/kernel"), m->wsf(co), m->At(xn), mm, m->Dt(xn), ob.n, ob.h, ob.w, c, c, ACT_NONE, drop ? rate : 0.0f, m->drop_seed + salt,
+                                      WBF(static_cast<void*>(m->wsf(m->off_wt))), 1, s);
+    r = k_h2_weights(ctx, m->P(cn + "/kernel"), m->wsf(m->off_wt), c, c, 1, s);
+    if (r) return r;
+    return k_conv3x3_h2_fwd(ctx, m->D(cn), m->wsf(m->off_wt), m->wsf(co), m->A(xn), mm, m->D(xn), ob.n, ob.h, ob.w, c, c, ACT_NONE, drop ? rate : 0.0f, m->drop_seed + salt, s);
+  });
+}
+
 void build_programs(unet_model* m) {
   unet_ctx* ctx = m->ctx;
   const int algo = m->algo;
   const double gcount = (double)m->world;     // multiplies per-rank element counts into global counts
   const int dt = m->dt;
   const double eb = dt ? 2.0 : 4.0;           // bytes per stored activation element (roofline accounting)
-#define CBF(p) static_cast<const unet_bf16*>(p)
-#define WBF(p) static_cast<unet_bf16*>(p)
   auto& FT = m->prog[UNET_PROG_FWD_TRAIN];
   auto& FI = m->prog[UNET_PROG_FWD_INFER];
   auto& BW = m->prog[UNET_PROG_BWD];
-  const size_t sums_bytes = (m->bn_sums_doubles + 5 + UNET_HEAD_SUMS) * sizeof(double);
   // layers whose 3x3 weights are consumed as a prepared image (decided per layer exactly as the conv dispatch does)
   struct PrepItem { std::string name; int cin, cout, h, w; };
   std::vector<PrepItem> prep_items;
@@ -883,15 +1149,8 @@ void build_programs(unet_model* m) {
   for (int training = 1; training >= 0; --training) {
     auto& F = training ? FT : FI;
     auto& SY = m->syncref[training ? UNET_PROG_FWD_TRAIN : UNET_PROG_FWD_INFER];
-    const int tr_ = training;
-    ADD_OP(F, "zero_sums", 0, 0, {
-      if (!tr_ && !m->yt) return UNET_OK;          // (inference without labels: no statistics, no loss sums -- nothing adds into them)
-      return unet_zero(ctx, m->wsf(m->off_bn_sums), sums_bytes, s);
-    });
-    if (m->weighted()) ADD_OP(F, "loss_weight_map", 0, 8.0 * m->N * m->H * m->W, {          // weighted_bce_dice_loss (T1:837-845): its map of this batch's labels
-      if (!m->yt) return UNET_OK;
-      return k_loss_weight_map(ctx, m->yt, m->wsf(m->off_wmap), m->N, m->H, m->W, s);
-    });
+    emit_zero_sums(m, F, !training);
+    emit_loss_weight_map(m, F);
     if (!dt) ADD_OP(F, "weight_images:fwd", 0, 0, { return prep_weights(0, s); });       // all split weight images of the program in one batch of launches
     else ADD_OP(F, "weight_images:fwd", 0, 0, { return prep_weights_bf16(0, s); });
     auto conv = [&](const std::string& name, const std::string& in, int cin, int cout) {
@@ -919,44 +1178,29 @@ void build_programs(unet_model* m) {
     };
     // skip_src: the encoder BatchNorm whose output is the second half of the concat `in` -- its statistics are analytic (unet_bn_stats_concat)
     auto bn = [&](const std::string& name, const std::string& in, const std::string& out, int c, bool fuse_pool, const std::string& skip_src = "") {
-      const Buf ib = m->act.at(in), ob = m->act.at(out);
+      const Buf ib = m->act.at(in);
       const int64_t pixels = (int64_t)ib.n * ib.h * ib.w;
       const size_t so = m->bn_sum_off.at(name), bo = m->bnp_off.at(name);
-      const bool composed = m->skip_raw && !skip_src.empty() && m->bn_comp_off.count(name) != 0;          // decoder BatchNorm over [up | RAW encoder output]: finalize + k_bn_compose in one launch
       if (training) {
         if (!skip_src.empty() && ctx->opt_bn_concat_analytic) {
           const size_t sso = m->bn_sum_off.at(skip_src);
           const int cu = c / 2, cs = c - c / 2;
           ADD_OP(F, "bn_stats:" + name, 0, eb * pixels * cu, {
-            if (dt) return unet_bn_stats_concat_bf16(ctx, CBF(m->Av(in)), ib.ld, m->wsd(m->off_bn_sums) + sso, (double)pixels * gcount, m->P(skip_src + "/gamma"),
-                                                     m->P(skip_src + "/beta"), m->wsd(m->off_bn_sums) + so, pixels, cu, cs, s);
-            return unet_bn_stats_concat(ctx, m->A(in), ib.ld, m->wsd(m->off_bn_sums) + sso, (double)pixels * gcount, m->P(skip_src + "/gamma"), m->P(skip_src + "/beta"),
-                                        m->wsd(m->off_bn_sums) + so, pixels, cu, cs, s);
+            return TWIN(dt, unet_bn_stats_concat, unet_bn_stats_concat_bf16, ctx, m->At(in), ib.ld, m->wsd(m->off_bn_sums) + sso, (double)pixels * gcount, m->P(skip_src + "/gamma"),
+                        m->P(skip_src + "/beta"), m->wsd(m->off_bn_sums) + so, pixels, cu, cs, s);
           });
-        } else {
-          ADD_OP(F, "bn_stats:" + name, 0, eb * pixels * c, {
-            if (dt) return unet_bn_stats_bf16(ctx, CBF(m->Av(in)), ib.ld, m->wsd(m->off_bn_sums) + so, pixels, c, s);
-            return unet_bn_stats(ctx, m->A(in), ib.ld, m->wsd(m->off_bn_sums) + so, pixels, c, s);
-          });
-        }
-        SY.push_back({(int)F.size() - 1, 0, true, (m->off_bn_sums * 4) + so * 8, 2 * (int64_t)c});
-        ADD_OP(F, "bn_finalize:" + name, 0, 0, {
-          if (composed) return k_bn_finalize_compose(ctx, 1, m->wsd(m->off_bn_sums) + so, (double)pixels * gcount, m->P(name + "/gamma"), m->P(name + "/beta"), m->P(name + "/mean"),
-                                                     m->P(name + "/var"), m->wsf(bo), c, m->wsf(m->bnp_off.at(skip_src)), m->wsf(m->bn_comp_off.at(name)), s);
-          return unet_bn_finalize_train(ctx, m->wsd(m->off_bn_sums) + so, (double)pixels * gcount, m->P(name + "/gamma"), m->P(name + "/beta"),
-                                        m->P(name + "/mean"), m->P(name + "/var"), m->wsf(bo), c, s);
-        });
-      } else {
-        ADD_OP(F, "bn_finalize_infer:" + name, 0, 0, {
-          if (composed) return k_bn_finalize_compose(ctx, 0, nullptr, 0.0, m->P(name + "/gamma"), m->P(name + "/beta"), m->P(name + "/mean"), m->P(name + "/var"), m->wsf(bo), c,
-                                                     m->wsf(m->bnp_off.at(skip_src)), m->wsf(m->bn_comp_off.at(name)), s);
-          return unet_bn_finalize_infer(ctx, m->P(name + "/gamma"), m->P(name + "/beta"), m->P(name + "/mean"), m->P(name + "/var"), m->wsf(bo), c, s);
-        });
+        } else
+        emit_bn_stats(m, F, name, in, c);
+        emit_bn_stats_sync(m, F, SY, name, c);
       }
-      if (!fuse_pool && !m->folded_bn.count(name)) ADD_OP(F, "bn_apply:" + name, 0, 2 * eb * pixels * c, {
-        if (dt) return unet_bn_apply_bf16(ctx, CBF(m->Av(in)), ib.ld, m->wsf(bo), WBF(m->Av(out)), ob.ld, pixels, c, s);
-        return unet_bn_apply(ctx, m->A(in), ib.ld, m->wsf(bo), m->Aw(out), ob.ld, pixels, c, s);
-      });
+      if (m->skip_raw && !skip_src.empty() && m->bn_comp_off.count(name) != 0)          // decoder BatchNorm over [up | RAW encoder output]: finalize + k_bn_compose in one launch
+        ADD_OP(F, (training ? "bn_finalize:" : "bn_finalize_infer:") + name, 0, 0, {
+          return k_bn_finalize_compose(ctx, training, training ? m->wsd(m->off_bn_sums) + so : nullptr, training ? (double)pixels * gcount : 0.0, m->P(name + "/gamma"), m->P(name + "/beta"),
+                                       m->P(name + "/mean"), m->P(name + "/var"), m->wsf(bo), c, m->wsf(m->bnp_off.at(skip_src)), m->wsf(m->bn_comp_off.at(name)), s);
+        });
+      else
+      emit_bn_finalize(m, F, name, in, c, training != 0);
+      if (!fuse_pool && !m->folded_bn.count(name)) emit_bn_apply(m, F, name, in, out, c);
     };
     std::string prev = "";
     int cprev = m->in_ch;
@@ -998,11 +1242,10 @@ void build_programs(unet_model* m) {
         const std::string cn = "c" + ks + "a", xn = "cat" + ks, bnn = "bn" + ks;
         const Buf ob = m->act.at(cn); const int cin = 2 * c, cout = c;
         const size_t fo = m->fold_off.at(cn), bo = m->bnp_off.at(bnn), uo = m->wprep_f.at(cn);
-        const size_t co_ = m->skip_raw ? m->bn_comp_off.at(bnn) : 0, boe = m->skip_raw ? m->bnp_off.at("bn" + std::to_string(10 - k)) : 0;
+        const size_t co_ = m->skip_raw ? m->bn_comp_off.at(bnn) : 0;
         ADD_OP(F, "bn_fold_prepare:" + cn, 2.0 * 9 * cin * cout * 2, 4.0 * 9 * cin * cout * 4, {
           const float* sc_ = m->wsf(bo);                        // [scale 2C][shift 2C] of the folded map
           if (m->skip_raw) sc_ = m->wsf(co_);                  // the skip half of the concat is the RAW encoder output: the composite map bn_finalize left (k_bn_finalize_compose)
-          (void)boe;
           int32_t r = k_bn_fold_prepare(ctx, m->P(cn + "/kernel"), m->P(cn + "/bias"), sc_, sc_ + cin, cin, cout, m->wsf(fo), s, dt != 0);
           if (r || dt) return r;                                // bf16 storage: the conv below builds its weight image from the scaled fp32 weights
           return k_h2_weights_bound(ctx, m->P(cn + "/kernel"), sc_, m->wsf(uo), cin, cout, s);          // fp32: the image kernel applies the scale per input channel (exponent from max |w| max |scale|)
@@ -1042,38 +1285,19 @@ void build_programs(unet_model* m) {
       conv("c" + ks + "b", "c" + ks + "a", c, c);
       prev = "c" + ks + "b"; cprev = c;
     }
-    const Buf hb = m->act.at("c9b");
-    const int64_t hp = (int64_t)hb.n * hb.h * hb.w;
     if (m->head_fused) ADD_OP(F, "head_fold", 0, 0, {
       if (!m->yt) return UNET_OK;
       return k_head_fold(ctx, m->wsd(m->off_loss_sums), m->wsd(m->off_head_sums), s, m->weighted());
     });
     else
-    ADD_OP(F, "head_fwd", 2.0 * 32 * hp, hp * (eb * 32 + 8.0), {
-      if (!m->pout) UNET_FAIL(ctx, UNET_E_STATE, "head_fwd: p_out not set (unet_model_set_io)");
-      if (dt) return unet_head_fwd_bf16_ex(ctx, CBF(m->Av("c9b")), m->P("out/kernel"), m->P("out/bias"), m->pout, m->yt, m->yt ? m->wmap() : nullptr, m->yt ? m->wsd(m->off_loss_sums) : nullptr,
-                                           hp, hb.c, s);
-      return unet_head_fwd_ex(ctx, m->A("c9b"), m->P("out/kernel"), m->P("out/bias"), m->pout, m->yt, m->yt ? m->wmap() : nullptr, m->yt ? m->wsd(m->off_loss_sums) : nullptr, hp, hb.c, s);
-    });
-    SY.push_back({(int)F.size() - 1, 1, true, m->off_loss_sums * 4, m->weighted() ? 5 : 4});
-    ADD_OP(F, "loss_finalize", 0, 0, {
-      if (!m->yt) return UNET_OK;
-      return k_loss_finalize(ctx, m->wsd(m->off_loss_sums), (double)hp * gcount, m->wsf(m->off_loss_out), m->loss_out2, s, m->loss);
-    });
+    emit_head_fwd(m, F, "c9b");
+    emit_loss_finalize(m, F, SY, "c9b");
   }
 
   // ------------------------------------------------------------------ backward
   {
     auto& SY = m->syncref[UNET_PROG_BWD];
-    size_t nb = 0;
-    for (auto& kv : m->bn_bsum_off) nb = std::max(nb, kv.second);
-    size_t bs_bytes = 0;
-    for (auto& l : m->layers) if (l.kind == 2) bs_bytes += 2 * (size_t)l.cout * sizeof(double);
-    ADD_OP(BW, "zero_bwd_sums", 0, 0, {
-      int32_t r = unet_zero(ctx, m->wsf(m->off_bn_bsums), bs_bytes, s);
-      if (r) return r;
-      return unet_zero(ctx, m->G("out/kernel"), (size_t)(m->tinfo.at("out/kernel").count + 1) * sizeof(float), s);
-    });
+    emit_zero_bwd_sums(m, BW);
     const Buf hb = m->act.at("c9b");
     const int64_t hp = (int64_t)hb.n * hb.h * hb.w;
     if (!dt) ADD_OP(BW, "weight_images:bwd", 0, 0, { return prep_weights(1, s); });
@@ -1094,14 +1318,7 @@ void build_programs(unet_model* m) {
                        m->G("out/kernel"), m->G("out/bias"), hb.n, hb.h, hb.w, s, m->loss, m->wmap());
     });
     else
-    ADD_OP(BW, "head_bwd", 4.0 * 32 * hp, hp * (eb * 64 + 8.0), {
-      if (!m->yt || !m->pout) UNET_FAIL(ctx, UNET_E_STATE, "head_bwd: io not set");
-      const unet_loss_sel& L = m->loss;
-      if (dt) return unet_head_bwd_bf16_ex(ctx, CBF(m->Av("c9b")), m->P("out/kernel"), m->pout, m->yt, m->wsd(m->off_loss_sums), (double)hp * gcount, L.kind, L.alpha, L.beta, m->wmap(), WBF(m->Dv("c9b")),
-                                        m->G("out/kernel"), m->G("out/bias"), hp, hb.c, 1, s);
-      return unet_head_bwd_ex(ctx, m->A("c9b"), m->P("out/kernel"), m->pout, m->yt, m->wsd(m->off_loss_sums), (double)hp * gcount, L.kind, L.alpha, L.beta, m->wmap(), m->D("c9b"),
-                           m->G("out/kernel"), m->G("out/bias"), hp, hb.c, 1, s);
-    });
+    emit_head_bwd(m, BW, "c9b", 1);
     // conv backward: wgrad (x, dy) then dgrad (dy -> dx, optional relu mask = activation that produced x)
     // xraw: the conv's input BatchNorm is folded (fold_off): the weight gradient runs on the raw tensor `xraw` and is corrected afterwards
     // Data parallelism: a batch-global reduction (BatchNorm backward sums) sits between the op that produces the local sums and the op that consumes the
@@ -1116,18 +1333,10 @@ void build_programs(unet_model* m) {
       const std::string xsrc = xraw.empty() ? in : xraw;
       auto& WV = (defer_wgrad && xraw.empty()) ? DEF : BW;
       const bool hstream = name == "c9b" && m->head_bwd_fused;          // dy = the head's 8-byte-per-pixel stream
-      ADD_OP(WV, "conv3x3_wgrad:" + name, 2.0 * 9 * cin * cout * px, (hstream ? eb * px * cin + 8.0 * px : eb * px * (cin + cout)) + 4.0 * 9.0 * cin * cout, {
-        if (dt) {
-          if (in.empty()) return first_conv_wgrad_bf16(ctx, m, name, ob, cout, s);
-          return k_conv3x3_bf16_wgrad(ctx, CBF(m->Av(xsrc)), CBF(m->Dv(name)), m->G(name + "/kernel"), m->G(name + "/bias"), m->wsf(m->off_wgrad_ws), m->wgrad_ws_bytes, ob.n, ob.h, ob.w,
-                                      cin, cout, s);
-        }
-        const float* xin = xsrc.empty() ? m->x : m->A(xsrc);
-        if (name == "c9b" && m->head_bwd_fused)               // dy = the head's {dz, mask} stream (head_dzm above)
-          return k_conv3x3_h2_wgrad_dzm(ctx, xin, m->D(name), m->P("out/kernel"), m->G(name + "/kernel"), m->G(name + "/bias"), m->wsf(m->off_wgrad_ws), m->wgrad_ws_bytes, ob.n, ob.h, ob.w, cin, s);
-        return conv3x3_wgrad_dispatch(ctx, xin, m->D(name), m->G(name + "/kernel"), m->G(name + "/bias"), m->wsf(m->off_wgrad_ws), m->wgrad_ws_bytes,
-                                      ob.n, ob.h, ob.w, cin, cout, algo, s);
+      if (hstream) ADD_OP(WV, "conv3x3_wgrad:" + name, 2.0 * 9 * cin * cout * px, eb * px * cin + 8.0 * px + 4.0 * 9.0 * cin * cout, {          // (fp32 only: head_dzm above)
+        return k_conv3x3_h2_wgrad_dzm(ctx, m->A(xsrc), m->D(name), m->P("out/kernel"), m->G(name + "/kernel"), m->G(name + "/bias"), m->wsf(m->off_wgrad_ws), m->wgrad_ws_bytes, ob.n, ob.h, ob.w, cin, s);
       });
+      else emit_conv_wgrad(m, WV, name, xsrc, cin, cout);
       if (!xraw.empty()) {
         const size_t go = m->fold_g_off.at(name), bo = m->bnp_off.at(in);
         const bool pg = !dt && m->fold_c_off.count(name) != 0;          // the BatchNorm's parameter gradients ride in the same launch (the op below stays as the carrier of the sync point)
@@ -1179,11 +1388,9 @@ void build_programs(unet_model* m) {
         // the gradient of a pooled tensor p<k>: the pooled-path sums of the encoder tail's BatchNorm backward ride in this launch's epilogue (MASK_POOL_SUMS) --
         // the pool_bwd_sums op below then only adds the closed-form skip term
         const std::string bnn = "bn" + in.substr(1);
-        const size_t so = m->bn_bsum_off.at(bnn);
         m->pool_sums_fused.insert(in);
         ADD_OP(BW, "conv3x3_dgrad_pool_sums:" + name, 2.0 * 9 * cin * cout * px, eb * px * (cout + 2 * cin) + 4.0 * 9.0 * cin * cout, {
           // (the sums stay in the slot copies: the pool_bwd_skip_term op right below folds them out together with the skip term -- nothing between the two uses the slots)
-          (void)so;
           return k_conv3x3_h2_dgrad_pool_sums(ctx, m->D(name), m->wsf(m->wprep_b.at(name)), m->A(in), m->P(bnn + "/gamma"), m->P(bnn + "/beta"), m->drop_rate, m->D(in),
                                               nullptr, ob.n, ob.h, ob.w, cout, cin, s);
         });
@@ -1206,37 +1413,7 @@ void build_programs(unet_model* m) {
         });
       }
     };
-    // bn backward: dy tensor `dyname` (grad buffer), x tensor `xname` (act), output grad `dxname`
-    // stats_done: the (sum dy, sum dy*xhat) sums were already accumulated by the fused pool backward
-    auto bn_bwd = [&](const std::string& name, const std::string& dyname, const std::string& xname, const std::string& dxname, int c, int mask,
-                      bool stats_done) {
-      const Buf gb = m->grad.at(dyname), xb = m->act.at(xname), db = m->grad.at(dxname);
-      const int64_t pixels = (int64_t)xb.n * xb.h * xb.w;
-      const size_t so = m->bn_bsum_off.at(name), bo = m->bnp_off.at(name);
-      if (stats_done) {
-        ADD_OP(BW, "bn_bwd_param_grads:" + name, 0, 0, {
-          return unet_bn_bwd_param_grads(ctx, m->wsd(m->off_bn_bsums) + so, m->G(name + "/gamma"), m->G(name + "/beta"), c, s);
-        });
-      } else {
-        ADD_OP(BW, "bn_bwd_stats:" + name, 0, 2 * eb * pixels * c, {
-          int32_t r = dt ? unet_bn_bwd_stats_bf16(ctx, CBF(m->Dv(dyname)), gb.ld, CBF(m->Av(xname)), xb.ld, m->wsf(bo), m->wsd(m->off_bn_bsums) + so, pixels, c, s)
-                         : unet_bn_bwd_stats(ctx, m->D(dyname), gb.ld, m->A(xname), xb.ld, m->wsf(bo), m->wsd(m->off_bn_bsums) + so, pixels, c, s);
-          if (r) return r;
-          return unet_bn_bwd_param_grads(ctx, m->wsd(m->off_bn_bsums) + so, m->G(name + "/gamma"), m->G(name + "/beta"), c, s);
-        });
-      }
-      SY.push_back({(int)BW.size() - 1, 2, true, m->off_bn_bsums * 4 + so * 8, 2 * (int64_t)c});
-      ADD_OP(BW, "bn_bwd_apply:" + name, 0, 3 * eb * pixels * c, {
-        if (dt) return unet_bn_bwd_apply_bf16(ctx, CBF(m->Dv(dyname)), gb.ld, CBF(m->Av(xname)), xb.ld, m->wsf(bo), m->wsd(m->off_bn_bsums) + so, (double)pixels * gcount,
-                                              mask ? MASK_RELU : MASK_NONE, 0.0f, 0, WBF(m->Dv(dxname)), db.ld, pixels, c, s);
-        return unet_bn_bwd_apply(ctx, m->D(dyname), gb.ld, m->A(xname), xb.ld, m->wsf(bo), m->wsd(m->off_bn_bsums) + so, (double)pixels * gcount, mask ? MASK_RELU : MASK_NONE, 0.0f, 0,
-                                 m->D(dxname), db.ld, pixels, c, s);
-      });
-    };
-    auto bucket = [&](const std::string& first, const std::string& last_tensor) {
-      const TInfo a = m->tinfo.at(first), b = m->tinfo.at(last_tensor);
-      SY.push_back({(int)BW.size() - 1, 3, false, (size_t)a.off * 4, b.off + b.count - a.off});
-    };
+    auto bucket = [&](const std::string& first, const std::string& last_tensor) { emit_bucket(m, BW, SY, first, last_tensor); };
     // ENC_TAIL_DGRAD: which levels split the decoder's folded data gradient (kernels_conv_h2.hip: h2_enc_tail_dgrad_selected -- a rule on the launch shapes and the CU count)
     if (!dt && m->skip_raw && ctx->opt_enc_bn_fused && ctx->opt_enc_tail_dgrad)
       for (int k = 1; k <= 4; ++k) {
@@ -1255,15 +1432,11 @@ void build_programs(unet_model* m) {
       conv_bwd("c" + ks + "b", "c" + ks + "a", c, c, true, true, "", m->fold_c_off.count("c" + ks + "a") != 0);          // (its weight gradient: behind c<k>a's sums)
       conv_bwd("c" + ks + "a", "bn" + ks, 2 * c, c, true, false, m->fold_off.count("c" + ks + "a") ? "cat" + ks : "");
       flush_def();
-      if (!m->fold_c_off.count("c" + ks + "a")) bn_bwd("bn" + ks, "bn" + ks, "cat" + ks, "cat" + ks, 2 * c, 0, m->fold_off.count("c" + ks + "a") != 0);
+      // (the sums of a BatchNorm folded forward only came out of wgrad_bn_fold_fix: stats_done)
+      if (!m->fold_c_off.count("c" + ks + "a")) emit_bn_bwd(m, BW, SY, "bn" + ks, "bn" + ks, "cat" + ks, "cat" + ks, 2 * c, MASK_NONE, 0.0f, 0, m->fold_off.count("c" + ks + "a") != 0);
       const Buf ib = m->act.at(prev), ug = m->grad.at("u" + ks);
       const std::string un = "u" + ks;
-      ADD_OP(BW, "convT_wgrad:" + un, 2.0 * 4 * cprev * c * nel(ib) / ib.c, eb * (nel(ib) + nel(ug)), {
-        if (dt) return k_convT_bf16_wgrad(ctx, CBF(m->Av(prev)), CBF(m->Dv(un)), ug.ld, m->G(un + "/kernel"), m->G(un + "/bias"), m->wsf(m->off_wgrad_ws), m->wgrad_ws_bytes, ib.n, ib.h,
-                                          ib.w, cprev, c, s);
-        return unet_convT2x2_bwd_weights(ctx, m->A(prev), m->D(un), ug.ld, m->G(un + "/kernel"), m->G(un + "/bias"), m->wsf(m->off_wgrad_ws), m->wgrad_ws_bytes,
-                                         ib.n, ib.h, ib.w, cprev, c, algo, s);
-      });
+      emit_convT_wgrad(m, BW, un, prev, cprev, c);
       ADD_OP(BW, "convT_dgrad:" + un, 2.0 * 4 * cprev * c * nel(ib) / ib.c, eb * (2 * nel(ib) + nel(ug)), {
         if (dt) return k_convT_bf16_dgrad(ctx, CBF(m->Dv(un)), ug.ld, m->P(un + "/kernel"), CBF(m->Av(prev)), WBF(m->Dv(prev)), ib.n, ib.h, ib.w, cprev, c, WBF(static_cast<void*>(m->wsf(m->off_wt))), s);
         const auto so = m->sign_off.find(prev);
@@ -1340,7 +1513,7 @@ void build_programs(unet_model* m) {
                                                    m->wsd(m->off_bn_bsums) + so, xb.n, xb.h, xb.w, xb.c, m->drop_rate,
                                                    m->drop_seed + (uint64_t)k * 0x9E3779B97F4A7C15ull, s);
       });
-      bn_bwd(bnn, bnn, "c" + ks + "b", "c" + ks + "b", c, 1, true);
+      emit_bn_bwd(m, BW, SY, bnn, bnn, "c" + ks + "b", "c" + ks + "b", c, MASK_RELU, 0.0f, 0, true);          // (the sums: out of the pool backward above)
       }
       conv_bwd("c" + ks + "b", "c" + ks + "a", c, c, true, true);
       int cprev = (k == 1) ? m->in_ch : ENC[k - 2];
@@ -1349,8 +1522,6 @@ void build_programs(unet_model* m) {
     flush_def();
     bucket("c1a/kernel", enc_split ? "bn2/beta" : "bn4/beta");
   }
-#undef CBF
-#undef WBF
 }
 
 // =========================================================================================
@@ -1475,14 +1646,9 @@ void plan_workspace_pp(unet_model* m) {
 void build_programs_pp(unet_model* m) {
   unet_ctx* ctx = m->ctx;
   const int algo = m->algo;
-  const double gcount = (double)m->world;
   const int dt = m->dt;
   const double eb = dt ? 2.0 : 4.0;           // bytes per stored activation element (roofline accounting)
-  const size_t esz = dt ? 2 : 4;
-#define CBF(p) static_cast<const unet_bf16*>(p)
-#define WBF(p) static_cast<unet_bf16*>(p)
   auto& BW = m->prog[UNET_PROG_BWD];
-  const size_t sums_bytes = (m->bn_sums_doubles + 5 + UNET_HEAD_SUMS) * sizeof(double);
   std::map<std::string, int> lidx;
   for (size_t i = 0; i < m->layers.size(); ++i) lidx[m->layers[i].name] = (int)i;
   auto seed_of = [=](const std::string& conv) { return (uint64_t)(lidx.at(conv) + 1) * 0x9E3779B97F4A7C15ull; };
@@ -1491,70 +1657,17 @@ void build_programs_pp(unet_model* m) {
   for (int training = 1; training >= 0; --training) {
     auto& F = m->prog[training ? UNET_PROG_FWD_TRAIN : UNET_PROG_FWD_INFER];
     auto& SY = m->syncref[training ? UNET_PROG_FWD_TRAIN : UNET_PROG_FWD_INFER];
-    const int tr = training;
-    ADD_OP(F, "zero_sums", 0, 0, { return unet_zero(ctx, m->wsf(m->off_bn_sums), sums_bytes, s); });
-    if (m->weighted()) ADD_OP(F, "loss_weight_map", 0, 8.0 * m->N * m->H * m->W, {          // weighted_bce_dice_loss (T1:837-845): its map of this batch's labels
-      if (!m->yt) return UNET_OK;
-      return k_loss_weight_map(ctx, m->yt, m->wsf(m->off_wmap), m->N, m->H, m->W, s);
-    });
-    auto conv = [&](const std::string& name, const std::string& in, int cin, int cout, float rate) {
-      const Buf ob = m->act.at(name);
-      const uint64_t sd = seed_of(name);
-      double px = (double)ob.n * ob.h * ob.w;
-      ADD_OP(F, "conv3x3_fwd:" + name, 2.0 * 9 * cin * cout * px, eb * px * (cin + cout) + 4.0 * 9.0 * cin * cout, {
-        const float r = (tr && m->drop_rate > 0.0f) ? rate : 0.0f;
-        if (dt) {
-          if (in.empty()) return first_conv_fwd_bf16(ctx, m, name, ob, cout, ACT_ELU, r, m->drop_seed + sd, s);
-          return k_conv3x3_bf16_fwd(ctx, CBF(m->Av(in)), m->P(name + "/kernel"), m->P(name + "/bias"), nullptr, MASK_NONE, WBF(m->Av(name)), ob.n, ob.h, ob.w, cin, cout, ACT_ELU, r,
-                                    m->drop_seed + sd, WBF(static_cast<void*>(m->wsf(m->off_wt))), 0, s);
-        }
-        const float* xin = in.empty() ? m->x : m->A(in);
-        return conv3x3_fwd_dispatch(ctx, xin, m->P(name + "/kernel"), m->P(name + "/bias"), nullptr, MASK_NONE, m->Aw(name), ob.n, ob.h, ob.w, cin, cout,
-                                    ACT_ELU, r, m->drop_seed + sd, algo, s, m->wsf(m->off_wt), 0);
-      });
-    };
-    // BN: stats -> [sync] -> finalize -> apply (or apply fused with the 2x2 pool when `pool` names the pooled output)
-    auto bn = [&](const std::string& name, const std::string& in, const std::string& out, int c, const std::string& pool) {
-      const Buf ib = m->act.at(in), ob = m->act.at(out);
-      const int64_t pixels = (int64_t)ib.n * ib.h * ib.w;
-      const size_t so = m->bn_sum_off.at(name), bo = m->bnp_off.at(name);
-      if (training) {
-        ADD_OP(F, "bn_stats:" + name, 0, eb * pixels * c, {
-          if (dt) return unet_bn_stats_bf16(ctx, CBF(m->Av(in)), ib.ld, m->wsd(m->off_bn_sums) + so, pixels, c, s);
-          return unet_bn_stats(ctx, m->A(in), ib.ld, m->wsd(m->off_bn_sums) + so, pixels, c, s);
-        });
-        SY.push_back({(int)F.size() - 1, 0, true, (m->off_bn_sums * 4) + so * 8, 2 * (int64_t)c});
-        ADD_OP(F, "bn_finalize:" + name, 0, 0, {
-          return unet_bn_finalize_train(ctx, m->wsd(m->off_bn_sums) + so, (double)pixels * gcount, m->P(name + "/gamma"), m->P(name + "/beta"),
-                                        m->P(name + "/mean"), m->P(name + "/var"), m->wsf(bo), c, s);
-        });
-      } else {
-        ADD_OP(F, "bn_finalize_infer:" + name, 0, 0, {
-          return unet_bn_finalize_infer(ctx, m->P(name + "/gamma"), m->P(name + "/beta"), m->P(name + "/mean"), m->P(name + "/var"), m->wsf(bo), c, s);
-        });
-      }
-      if (pool.empty() && m->folded_bn.count(name)) {
-        // folded into the conv behind it: no normalised tensor
-      } else if (pool.empty()) {
-        ADD_OP(F, "bn_apply:" + name, 0, 2 * eb * pixels * c, {
-          if (dt) return unet_bn_apply_bf16(ctx, CBF(m->Av(in)), ib.ld, m->wsf(bo), WBF(m->Av(out)), ob.ld, pixels, c, s);
-          return unet_bn_apply(ctx, m->A(in), ib.ld, m->wsf(bo), m->Aw(out), ob.ld, pixels, c, s);
-        });
-      } else {
-        ADD_OP(F, "bn_apply_pool:" + pool, 0, eb * 2.25 * pixels * c, {
-          if (dt) return unet_bn_apply_maxpool_dropout_fwd_bf16(ctx, CBF(m->Av(in)), ib.ld, m->wsf(bo), WBF(m->Av(out)), ob.ld, WBF(m->Av(pool)), ib.n, ib.h, ib.w, c, 0.0f, 0, s);
-          return unet_bn_apply_maxpool_dropout_fwd(ctx, m->A(in), ib.ld, m->wsf(bo), m->Aw(out), ob.ld, m->Aw(pool), ib.n, ib.h, ib.w, c, 0.0f, 0, s);
-        });
-      }
-    };
+    const bool tr = training != 0;
+    emit_zero_sums(m, F, false);
+    emit_loss_weight_map(m, F);
     for (const char* item : PP_ORDER) {
       std::string it = item;
       if (it[0] == 'e') {
         int k = it[1] - '0', c = ENC[k - 1], cin = k == 1 ? m->in_ch : ENC[k - 2];
         std::string ks = std::to_string(k);
-        conv("c" + ks + "a", k == 1 ? "" : "p" + std::to_string(k - 1), cin, c, PP_ENC_DROP);
-        conv("c" + ks + "b", "c" + ks + "a", c, c, 0.0f);
-        bn("bn" + ks, "c" + ks + "b", "c" + ks, c, k <= 3 ? "p" + ks : "");
+        emit_conv_fwd(m, F, "c" + ks + "a", k == 1 ? "" : "p" + std::to_string(k - 1), cin, c, ACT_ELU, PP_ENC_DROP, seed_of("c" + ks + "a"), tr);
+        emit_conv_fwd(m, F, "c" + ks + "b", "c" + ks + "a", c, c, ACT_ELU, 0.0f, seed_of("c" + ks + "b"), tr);
+        emit_bn_fwd(m, F, SY, "bn" + ks, "c" + ks + "b", "c" + ks, c, k <= 3 ? "p" + ks : "", tr);
       } else {
         const PPNode* nd = nullptr;
         for (auto& n : pp_nodes()) if (it == n.name) nd = &n;
@@ -1575,118 +1688,27 @@ void build_programs_pp(unet_model* m) {
           });
           off += cw;
         }
-        conv(it + "a", cat, cb.c, c, PP_BLOCK_DROP);
-        bn(it + "abn", it + "a", it + "abn", c, "");
-        if (m->fold_off.count(it + "b")) {
-          const std::string cn = it + "b", xn = it + "a", bnn = it + "abn";
-          const Buf ob = m->act.at(cn);
-          const size_t fo = m->fold_off.at(cn), bo = m->bnp_off.at(bnn);
-          const uint64_t sd = seed_of(cn);
-          ADD_OP(F, "bn_fold_prepare:" + cn, 2.0 * 9 * c * c * 2, 4.0 * 9 * c * c * 4, {
-            return k_bn_fold_prepare(ctx, m->P(cn + "/kernel"), m->P(cn + "/bias"), m->wsf(bo), m->wsf(bo) + c, c, c, m->wsf(fo), s, dt != 0);
-          });
-          ADD_OP(F, "conv3x3_fwd:" + cn, 2.0 * 9 * c * c * (double)ob.n * ob.h * ob.w, eb * (double)ob.n * ob.h * ob.w * 2 * c + 4.0 * 9.0 * c * c, {
-            const float r = (tr && m->drop_rate > 0.0f) ? PP_BLOCK_DROP : 0.0f;
-            const float* tab = m->wsf(fo) + (size_t)9 * c * c;
-            if (dt) return k_conv3x3_bf16_fwd(ctx, CBF(m->Av(xn)), m->wsf(fo), tab, reinterpret_cast<const unet_bf16*>(tab), MASK_BIAS_TAB, WBF(m->Av(cn)), ob.n, ob.h, ob.w, c, c, ACT_ELU, r,
-                                              m->drop_seed + sd, WBF(static_cast<void*>(m->wsf(m->off_wt))), 0, s);
-            int32_t e = k_h2_weights(ctx, m->P(cn + "/kernel"), m->wsf(m->off_wt), c, c, 0, s, m->wsf(bo));
-            if (e) return e;
-            return k_conv3x3_h2_fwd(ctx, m->A(xn), m->wsf(m->off_wt), tab, tab, MASK_BIAS_TAB, m->Aw(cn), ob.n, ob.h, ob.w, c, c, ACT_ELU, r, m->drop_seed + sd, s);
-          });
-        } else
-        conv(it + "b", it + "abn", c, c, PP_BLOCK_DROP);
-        bn(it + "bbn", it + "b", it, c, "");
+        emit_conv_fwd(m, F, it + "a", cat, cb.c, c, ACT_ELU, PP_BLOCK_DROP, seed_of(it + "a"), tr);
+        emit_bn_fwd(m, F, SY, it + "abn", it + "a", it + "abn", c, "", tr);
+        if (m->fold_off.count(it + "b")) emit_conv_fwd_folded(m, F, it + "b", it + "a", it + "abn", c, ACT_ELU, PP_BLOCK_DROP, seed_of(it + "b"), tr);
+        else emit_conv_fwd(m, F, it + "b", it + "abn", c, c, ACT_ELU, PP_BLOCK_DROP, seed_of(it + "b"), tr);
+        emit_bn_fwd(m, F, SY, it + "bbn", it + "b", it, c, "", tr);
       }
     }
-    const Buf hb = m->act.at("x1_4");
-    const int64_t hp = (int64_t)hb.n * hb.h * hb.w;
-    ADD_OP(F, "head_fwd", 2.0 * 32 * hp, hp * (eb * 32 + 8.0), {
-      if (!m->pout) UNET_FAIL(ctx, UNET_E_STATE, "head_fwd: p_out not set (unet_model_set_io)");
-      if (dt) return unet_head_fwd_bf16_ex(ctx, CBF(m->Av("x1_4")), m->P("out/kernel"), m->P("out/bias"), m->pout, m->yt, m->yt ? m->wmap() : nullptr, m->yt ? m->wsd(m->off_loss_sums) : nullptr,
-                                           hp, hb.c, s);
-      return unet_head_fwd_ex(ctx, m->A("x1_4"), m->P("out/kernel"), m->P("out/bias"), m->pout, m->yt, m->yt ? m->wmap() : nullptr, m->yt ? m->wsd(m->off_loss_sums) : nullptr, hp, hb.c, s);
-    });
-    SY.push_back({(int)F.size() - 1, 1, true, m->off_loss_sums * 4, m->weighted() ? 5 : 4});
-    ADD_OP(F, "loss_finalize", 0, 0, {
-      if (!m->yt) return UNET_OK;
-      return k_loss_finalize(ctx, m->wsd(m->off_loss_sums), (double)hp * gcount, m->wsf(m->off_loss_out), m->loss_out2, s, m->loss);
-    });
+    emit_head_fwd(m, F, "x1_4");
+    emit_loss_finalize(m, F, SY, "x1_4");
   }
 
   // ------------------------------------------------------------------ backward (reverse creation order)
   auto& SY = m->syncref[UNET_PROG_BWD];
-  size_t bs_bytes = 0;
-  for (auto& l : m->layers) if (l.kind == 2) bs_bytes += 2 * (size_t)l.cout * sizeof(double);
   // Gradients summed from several consumers (c1..c4, x1_2, x2_2, x1_3, x3_2, x2_3): every contribution is an accumulate-capable op (accum_slices, the ConvT data
   // gradient's accum, pool backward), so the FIRST one in program order overwrites and the rest accumulate -- no memset of 9 activation-sized buffers per step
   // (0.3 ms) and no read of zeros by the first writer.  first_touch(name) returns the accumulate flag to use and remembers the tensor.
   std::set<std::string> touched;
   auto first_touch = [&](const std::string& t) -> int { return touched.insert(t).second ? 0 : 1; };
-  (void)esz;
-  ADD_OP(BW, "zero_bwd_sums", 0, 0, {
-    int32_t r = unet_zero(ctx, m->wsf(m->off_bn_bsums), bs_bytes, s); if (r) return r;
-    return unet_zero(ctx, m->G("out/kernel"), (size_t)(m->tinfo.at("out/kernel").count + 1) * sizeof(float), s);
-  });
-  const Buf hb = m->act.at("x1_4");
-  const int64_t hp = (int64_t)hb.n * hb.h * hb.w;
-  ADD_OP(BW, "head_bwd", 4.0 * 32 * hp, hp * (eb * 64 + 8.0), {
-    if (!m->yt || !m->pout) UNET_FAIL(ctx, UNET_E_STATE, "head_bwd: io not set");
-    const unet_loss_sel& L = m->loss;
-    if (dt) return unet_head_bwd_bf16_ex(ctx, CBF(m->Av("x1_4")), m->P("out/kernel"), m->pout, m->yt, m->wsd(m->off_loss_sums), (double)hp * gcount, L.kind, L.alpha, L.beta, m->wmap(), WBF(m->Dv("x1_4")),
-                                      m->G("out/kernel"), m->G("out/bias"), hp, hb.c, 0, s);
-    return unet_head_bwd_ex(ctx, m->A("x1_4"), m->P("out/kernel"), m->pout, m->yt, m->wsd(m->off_loss_sums), (double)hp * gcount, L.kind, L.alpha, L.beta, m->wmap(), m->D("x1_4"),
-                         m->G("out/kernel"), m->G("out/bias"), hp, hb.c, 0, s);
-  });
-  // BN backward: dy = grad[dyname] (dense), x = act[xname] = dropout(elu(conv)) or elu(conv); dx = grad[xname] (pre-activation gradient)
-  auto bn_bwd = [&](const std::string& name, const std::string& dyname, const std::string& xname, int c, int mask_mode, float rate, uint64_t sd) {
-    const Buf gb = m->grad.at(dyname), xb = m->act.at(xname), db = m->grad.at(xname);
-    const int64_t pixels = (int64_t)xb.n * xb.h * xb.w;
-    const size_t so = m->bn_bsum_off.at(name), bo = m->bnp_off.at(name);
-    ADD_OP(BW, "bn_bwd_stats:" + name, 0, 2 * eb * pixels * c, {
-      int32_t r = dt ? unet_bn_bwd_stats_bf16(ctx, CBF(m->Dv(dyname)), gb.ld, CBF(m->Av(xname)), xb.ld, m->wsf(bo), m->wsd(m->off_bn_bsums) + so, pixels, c, s)
-                     : unet_bn_bwd_stats(ctx, m->D(dyname), gb.ld, m->A(xname), xb.ld, m->wsf(bo), m->wsd(m->off_bn_bsums) + so, pixels, c, s);
-      if (r) return r;
-      return unet_bn_bwd_param_grads(ctx, m->wsd(m->off_bn_bsums) + so, m->G(name + "/gamma"), m->G(name + "/beta"), c, s);
-    });
-    SY.push_back({(int)BW.size() - 1, 2, true, m->off_bn_bsums * 4 + so * 8, 2 * (int64_t)c});
-    ADD_OP(BW, "bn_bwd_apply:" + name, 0, 3 * eb * pixels * c, {
-      const bool drop = m->drop_rate > 0.0f && rate > 0.0f;
-      if (dt) return unet_bn_bwd_apply_bf16(ctx, CBF(m->Dv(dyname)), gb.ld, CBF(m->Av(xname)), xb.ld, m->wsf(bo), m->wsd(m->off_bn_bsums) + so, (double)pixels * gcount,
-                                            (mask_mode == MASK_ELU_DROP && !drop) ? MASK_ELU : mask_mode, drop ? rate : 0.0f, m->drop_seed + sd, WBF(m->Dv(xname)), db.ld, pixels, c, s);
-      return unet_bn_bwd_apply(ctx, m->D(dyname), gb.ld, m->A(xname), xb.ld, m->wsf(bo), m->wsd(m->off_bn_bsums) + so, (double)pixels * gcount,
-                               (mask_mode == MASK_ELU_DROP && !drop) ? MASK_ELU : mask_mode, drop ? rate : 0.0f, m->drop_seed + sd, m->D(xname), db.ld,
-                               pixels, c, s);
-    });
-  };
-  // conv backward: wgrad (x = act[in] or the network input, dy = grad[name]) + optional dgrad into grad[in] with the mask of act[in]
-  auto conv_bwd = [&](const std::string& name, const std::string& in, int cin, int cout, bool want_dx, int mask_mode, float rate, uint64_t sd) {
-    const Buf ob = m->act.at(name);
-    const double px = (double)ob.n * ob.h * ob.w;
-    ADD_OP(BW, "conv3x3_wgrad:" + name, 2.0 * 9 * cin * cout * px, eb * px * (cin + cout) + 4.0 * 9.0 * cin * cout, {
-      if (dt) {
-        if (in.empty()) return first_conv_wgrad_bf16(ctx, m, name, ob, cout, s);
-        return k_conv3x3_bf16_wgrad(ctx, CBF(m->Av(in)), CBF(m->Dv(name)), m->G(name + "/kernel"), m->G(name + "/bias"), m->wsf(m->off_wgrad_ws), m->wgrad_ws_bytes, ob.n, ob.h, ob.w, cin, cout, s);
-      }
-      const float* xin = in.empty() ? m->x : m->A(in);
-      return conv3x3_wgrad_dispatch(ctx, xin, m->D(name), m->G(name + "/kernel"), m->G(name + "/bias"), m->wsf(m->off_wgrad_ws), m->wgrad_ws_bytes,
-                                    ob.n, ob.h, ob.w, cin, cout, algo, s);
-    });
-    if (want_dx) {
-      ADD_OP(BW, "conv3x3_dgrad:" + name, 2.0 * 9 * cin * cout * px, eb * px * (cout + cin + (mask_mode ? cin : 0)) + 4.0 * 9.0 * cin * cout, {
-        const bool drop = m->drop_rate > 0.0f && rate > 0.0f;
-        const int mm = (mask_mode == MASK_ELU_DROP && !drop) ? MASK_ELU : mask_mode;
-        if (dt) return k_conv3x3_bf16_fwd(ctx, CBF(m->Dv(name)), m->P(name + "/kernel"), nullptr, mm ? CBF(m->Av(in)) : nullptr, mm, WBF(m->Dv(in)), ob.n, ob.h, ob.w, cout, cin, ACT_NONE,
-                                          drop ? rate : 0.0f, m->drop_seed + sd, WBF(static_cast<void*>(m->wsf(m->off_wt))), 1, s);
-        return unet_conv3x3_bwd_data(ctx, m->D(name), m->P(name + "/kernel"), mm ? m->A(in) : nullptr, mm, drop ? rate : 0.0f, m->drop_seed + sd, m->D(in),
-                                     m->wsf(m->off_wt), ob.n, ob.h, ob.w, cin, cout, algo, s);
-      });
-    }
-  };
-  auto bucket = [&](const std::string& first, const std::string& last_tensor) {
-    const TInfo a = m->tinfo.at(first), b = m->tinfo.at(last_tensor);
-    SY.push_back({(int)BW.size() - 1, 3, false, (size_t)a.off * 4, b.off + b.count - a.off});
-  };
+  emit_zero_bwd_sums(m, BW);
+  emit_head_bwd(m, BW, "x1_4", 0);
+  auto bucket = [&](const std::string& first, const std::string& last_tensor) { emit_bucket(m, BW, SY, first, last_tensor); };
   // The gradient of a tensor that went into several concats is the sum of those concats' gradient slices (each concat keeps its own gradient buffer): the slices
   // are only NOTED as the consumers finish and summed by ONE launch (up to 4 sources) right before the tensor's own backward starts -- x1_4, x1_3, x1_2 -> c1
   // as one read-modify-write of 268 MB instead of three
@@ -1717,9 +1739,10 @@ void build_programs_pp(unet_model* m) {
       int k = it[1] - '0', c = ENC[k - 1], cin = k == 1 ? m->in_ch : ENC[k - 2];
       std::string ks = std::to_string(k), ca = "c" + ks + "a", cb = "c" + ks + "b";
       flush_pending("c" + ks);
-      bn_bwd("bn" + ks, "c" + ks, cb, c, MASK_ELU, 0.0f, 0);
-      conv_bwd(cb, ca, c, c, true, MASK_ELU_DROP, PP_ENC_DROP, seed_of(ca));
-      conv_bwd(ca, k == 1 ? "" : "p" + std::to_string(k - 1), cin, c, k > 1, MASK_NONE, 0.0f, 0);
+      // BatchNorm backward: x = dropout(elu(conv)) or elu(conv), dx the conv's pre-activation gradient; a conv's data gradient carries the mask of ITS input
+      emit_bn_bwd(m, BW, SY, "bn" + ks, "c" + ks, cb, cb, c, MASK_ELU, 0.0f, 0, false);
+      emit_conv_bwd(m, BW, cb, ca, c, c, true, MASK_ELU_DROP, PP_ENC_DROP, seed_of(ca));
+      emit_conv_bwd(m, BW, ca, k == 1 ? "" : "p" + std::to_string(k - 1), cin, c, k > 1, MASK_NONE, 0.0f, 0);
       if (k > 1) {
         const std::string pk = "p" + std::to_string(k - 1), ck = "c" + std::to_string(k - 1);
         const Buf xb = m->act.at(ck);
@@ -1740,50 +1763,15 @@ void build_programs_pp(unet_model* m) {
       const Buf sb = m->act.at(src), cb = m->act.at(cat);
       const int c = nd->c, csrc = pp_width(src);
       flush_pending(it);
-      bn_bwd(it + "bbn", it, it + "b", c, MASK_ELU_DROP, PP_BLOCK_DROP, seed_of(it + "b"));
-      if (m->fold_off.count(it + "b")) {
-        // folded BatchNorm (abn -> conv b): weight gradient on the raw x, corrected; the BatchNorm's backward sums from W . dW_raw and S; its backward apply and the
-        // ELU / dropout derivative of conv a in the data-gradient epilogue, which writes conv a's pre-activation gradient directly
-        const std::string cn = it + "b", xn = it + "a", bnn = it + "abn";
-        const Buf ob = m->act.at(cn);
-        const double px = (double)ob.n * ob.h * ob.w;
-        const size_t go = m->fold_g_off.at(cn), co = m->fold_c_off.at(cn), bo = m->bnp_off.at(bnn), so = m->bn_bsum_off.at(bnn);
-        const uint64_t sda = seed_of(xn);
-        ADD_OP(BW, "conv3x3_wgrad:" + cn, 2.0 * 9 * c * c * px, eb * px * 2 * c + 4.0 * 9.0 * c * c, {
-          if (dt) return k_conv3x3_bf16_wgrad(ctx, CBF(m->Av(xn)), CBF(m->Dv(cn)), m->G(cn + "/kernel"), m->G(cn + "/bias"), m->wsf(m->off_wgrad_ws), m->wgrad_ws_bytes, ob.n, ob.h, ob.w, c, c, s);
-          return conv3x3_wgrad_dispatch(ctx, m->A(xn), m->D(cn), m->G(cn + "/kernel"), m->G(cn + "/bias"), m->wsf(m->off_wgrad_ws), m->wgrad_ws_bytes, ob.n, ob.h, ob.w, c, c, algo, s);
-        });
-        ADD_OP(BW, "wgrad_bn_fold_fix:" + cn, 2.0 * 9 * c * c, 8.0 * 9 * c * c, {
-          int32_t r = dt ? k_wgrad_bn_fold_fix_bf16(ctx, CBF(m->Dv(cn)), ob.n, ob.h, ob.w, c, c, m->wsf(bo), m->wsf(bo) + c, m->G(cn + "/kernel"), m->G(cn + "/bias"), m->wsf(go), s,
-                                                    m->P(cn + "/kernel"), m->wsf(bo) + 2 * c, m->wsf(bo) + 3 * c, m->wsd(m->off_bn_bsums) + so)
-                         : k_wgrad_bn_fold_fix(ctx, m->D(cn), ob.n, ob.h, ob.w, c, c, m->wsf(bo), m->wsf(bo) + c, m->G(cn + "/kernel"), m->G(cn + "/bias"), m->wsf(go), s, m->P(cn + "/kernel"),
-                                               m->wsf(bo) + 2 * c, m->wsf(bo) + 3 * c, m->wsd(m->off_bn_bsums) + so);
-          if (r) return r;
-          return unet_bn_bwd_param_grads(ctx, m->wsd(m->off_bn_bsums) + so, m->G(bnn + "/gamma"), m->G(bnn + "/beta"), c, s);
-        });
-        SY.push_back({(int)BW.size() - 1, 2, true, m->off_bn_bsums * 4 + so * 8, 2 * (int64_t)c});
-        ADD_OP(BW, "conv3x3_dgrad_bn_bwd:" + cn, 2.0 * 9 * c * c * px, eb * px * 3 * c + 4.0 * 9.0 * c * c, {
-          const bool drop = m->drop_rate > 0.0f;
-          int32_t r = k_bn_bwd_coef(ctx, m->wsf(bo), m->wsd(m->off_bn_bsums) + so, px * gcount, m->wsf(co), c, s);
-          if (r) return r;
-          if (dt) return k_conv3x3_bf16_fwd(ctx, CBF(m->Dv(cn)), m->P(cn + "/kernel"), m->wsf(co), CBF(m->Av(xn)), drop ? MASK_BN_BWD_ELU_DROP : MASK_BN_BWD_ELU, WBF(m->Dv(xn)), ob.n, ob.h, ob.w, c, c,
-                                            ACT_NONE, drop ? PP_BLOCK_DROP : 0.0f, m->drop_seed + sda, WBF(static_cast<void*>(m->wsf(m->off_wt))), 1, s);
-          r = k_h2_weights(ctx, m->P(cn + "/kernel"), m->wsf(m->off_wt), c, c, 1, s);
-          if (r) return r;
-          return k_conv3x3_h2_fwd(ctx, m->D(cn), m->wsf(m->off_wt), m->wsf(co), m->A(xn), drop ? MASK_BN_BWD_ELU_DROP : MASK_BN_BWD_ELU, m->D(xn), ob.n, ob.h, ob.w, c, c, ACT_NONE,
-                                    drop ? PP_BLOCK_DROP : 0.0f, m->drop_seed + sda, s);
-        });
-      } else {
-      conv_bwd(it + "b", it + "abn", c, c, true, MASK_NONE, 0.0f, 0);
-      bn_bwd(it + "abn", it + "abn", it + "a", c, MASK_ELU_DROP, PP_BLOCK_DROP, seed_of(it + "a"));
+      emit_bn_bwd(m, BW, SY, it + "bbn", it, it + "b", it + "b", c, MASK_ELU_DROP, PP_BLOCK_DROP, seed_of(it + "b"), false);
+      if (m->fold_off.count(it + "b")) emit_conv_bwd_folded(m, BW, SY, it + "b", it + "a", it + "abn", c, MASK_BN_BWD_ELU_DROP, PP_BLOCK_DROP, seed_of(it + "a"));
+      else {
+        emit_conv_bwd(m, BW, it + "b", it + "abn", c, c, true, MASK_NONE, 0.0f, 0);
+        emit_bn_bwd(m, BW, SY, it + "abn", it + "abn", it + "a", it + "a", c, MASK_ELU_DROP, PP_BLOCK_DROP, seed_of(it + "a"), false);
       }
-      conv_bwd(it + "a", cat, cb.c, c, true, MASK_NONE, 0.0f, 0);
+      emit_conv_bwd(m, BW, it + "a", cat, cb.c, c, true, MASK_NONE, 0.0f, 0);
+      emit_convT_wgrad(m, BW, un, src, csrc, c);
       const Buf ug = m->grad.at(un);
-      ADD_OP(BW, "convT_wgrad:" + un, 2.0 * 4 * csrc * c * nel(sb) / sb.c, eb * (nel(sb) + 4.0 * nel(sb) / sb.c * c), {
-        if (dt) return k_convT_bf16_wgrad(ctx, CBF(m->Av(src)), CBF(m->Dv(un)), ug.ld, m->G(un + "/kernel"), m->G(un + "/bias"), m->wsf(m->off_wgrad_ws), m->wgrad_ws_bytes, sb.n, sb.h, sb.w, csrc, c, s);
-        return unet_convT2x2_bwd_weights(ctx, m->A(src), m->D(un), ug.ld, m->G(un + "/kernel"), m->G(un + "/bias"), m->wsf(m->off_wgrad_ws), m->wgrad_ws_bytes,
-                                         sb.n, sb.h, sb.w, csrc, c, algo, s);
-      });
       const int accu = first_touch(src);
       ADD_OP(BW, "convT_dgrad:" + un, 2.0 * 4 * csrc * c * nel(sb) / sb.c, eb * (2 * nel(sb) + 4.0 * nel(sb) / sb.c * c), {
         float* tmp = m->wsf(m->act.at("tmp_up").off);
@@ -1804,8 +1792,6 @@ void build_programs_pp(unet_model* m) {
       if (it == "x1_4") bucket("u1_4/kernel", "out/bias");
     }
   }
-#undef CBF
-#undef WBF
 }
 
 // =========================================================================================
@@ -1884,13 +1870,9 @@ void plan_workspace_cls(unet_model* m) {
 
 void build_programs_cls(unet_model* m) {
   unet_ctx* ctx = m->ctx;
-  const int algo = m->algo;
   const double gcount = (double)m->world;
   const int dt = m->dt;
   const double eb = dt ? 2.0 : 4.0;
-#define CBF(p) static_cast<const unet_bf16*>(p)
-#define WBF(p) static_cast<unet_bf16*>(p)
-  const size_t sums_bytes = (m->bn_sums_doubles + 5 + UNET_HEAD_SUMS) * sizeof(double);
   const Buf fb = m->act.at("p3");
   const int N = m->N, K = fb.h * fb.w * fb.c;
   const uint64_t fc_seed = 0xC2B2AE3D27D4EB4Full;
@@ -1898,82 +1880,17 @@ void build_programs_cls(unet_model* m) {
   for (int training = 1; training >= 0; --training) {
     auto& F = m->prog[training ? UNET_PROG_FWD_TRAIN : UNET_PROG_FWD_INFER];
     auto& SY = m->syncref[training ? UNET_PROG_FWD_TRAIN : UNET_PROG_FWD_INFER];
-    const int tr = training;
-    ADD_OP(F, "zero_sums", 0, 0, { return unet_zero(ctx, m->wsf(m->off_bn_sums), sums_bytes, s); });
-    if (m->weighted()) ADD_OP(F, "loss_weight_map", 0, 8.0 * m->N * m->H * m->W, {          // weighted_bce_dice_loss (T1:837-845): its map of this batch's labels
-      if (!m->yt) return UNET_OK;
-      return k_loss_weight_map(ctx, m->yt, m->wsf(m->off_wmap), m->N, m->H, m->W, s);
-    });
-    auto conv = [&](const std::string& name, const std::string& in, int cin, int cout) {
-      const Buf ob = m->act.at(name);
-      double px = (double)ob.n * ob.h * ob.w;
-      ADD_OP(F, "conv3x3_fwd:" + name, 2.0 * 9 * cin * cout * px, eb * px * (cin + cout) + 4.0 * 9.0 * cin * cout, {
-        if (dt) {
-          if (in.empty()) return first_conv_fwd_bf16(ctx, m, name, ob, cout, ACT_RELU, 0.0f, 0, s);
-          return k_conv3x3_bf16_fwd(ctx, CBF(m->Av(in)), m->P(name + "/kernel"), m->P(name + "/bias"), nullptr, MASK_NONE, WBF(m->Av(name)), ob.n, ob.h, ob.w, cin, cout, ACT_RELU, 0.0f, 0,
-                                    WBF(static_cast<void*>(m->wsf(m->off_wt))), 0, s);
-        }
-        const float* xin = in.empty() ? m->x : m->A(in);
-        return conv3x3_fwd_dispatch(ctx, xin, m->P(name + "/kernel"), m->P(name + "/bias"), nullptr, MASK_NONE, m->Aw(name), ob.n, ob.h, ob.w, cin, cout,
-                                    ACT_RELU, 0.0f, 0, algo, s, m->wsf(m->off_wt), 0);
-      });
-    };
-    auto bn = [&](const std::string& name, const std::string& in, int c, const std::string& pool) {
-      const Buf ib = m->act.at(in), ob = m->act.at(name);
-      const int64_t pixels = (int64_t)ib.n * ib.h * ib.w;
-      const size_t so = m->bn_sum_off.at(name), bo = m->bnp_off.at(name);
-      if (training) {
-        ADD_OP(F, "bn_stats:" + name, 0, eb * pixels * c, {
-          if (dt) return unet_bn_stats_bf16(ctx, CBF(m->Av(in)), ib.ld, m->wsd(m->off_bn_sums) + so, pixels, c, s);
-          return unet_bn_stats(ctx, m->A(in), ib.ld, m->wsd(m->off_bn_sums) + so, pixels, c, s);
-        });
-        SY.push_back({(int)F.size() - 1, 0, true, (m->off_bn_sums * 4) + so * 8, 2 * (int64_t)c});
-        ADD_OP(F, "bn_finalize:" + name, 0, 0, {
-          return unet_bn_finalize_train(ctx, m->wsd(m->off_bn_sums) + so, (double)pixels * gcount, m->P(name + "/gamma"), m->P(name + "/beta"),
-                                        m->P(name + "/mean"), m->P(name + "/var"), m->wsf(bo), c, s);
-        });
-      } else {
-        ADD_OP(F, "bn_finalize_infer:" + name, 0, 0, {
-          return unet_bn_finalize_infer(ctx, m->P(name + "/gamma"), m->P(name + "/beta"), m->P(name + "/mean"), m->P(name + "/var"), m->wsf(bo), c, s);
-        });
-      }
-      if (pool.empty() && m->folded_bn.count(name)) {
-        // folded into the conv behind it: no normalised tensor
-      } else if (pool.empty()) {
-        ADD_OP(F, "bn_apply:" + name, 0, 2 * eb * pixels * c, {
-          if (dt) return unet_bn_apply_bf16(ctx, CBF(m->Av(in)), ib.ld, m->wsf(bo), WBF(m->Av(name)), ob.ld, pixels, c, s);
-          return unet_bn_apply(ctx, m->A(in), ib.ld, m->wsf(bo), m->Aw(name), ob.ld, pixels, c, s);
-        });
-      } else {
-        ADD_OP(F, "bn_apply_pool:" + pool, 0, eb * 2.25 * pixels * c, {
-          if (dt) return unet_bn_apply_maxpool_dropout_fwd_bf16(ctx, CBF(m->Av(in)), ib.ld, m->wsf(bo), WBF(m->Av(name)), ob.ld, WBF(m->Av(pool)), ib.n, ib.h, ib.w, c, 0.0f, 0, s);
-          return unet_bn_apply_maxpool_dropout_fwd(ctx, m->A(in), ib.ld, m->wsf(bo), m->Aw(name), ob.ld, m->Aw(pool), ib.n, ib.h, ib.w, c, 0.0f, 0, s);
-        });
-      }
-    };
+    const bool tr = training != 0;
+    emit_zero_sums(m, F, false);
+    emit_loss_weight_map(m, F);
     int cprev = m->in_ch;
     for (int k = 1; k <= 3; ++k) {
       const int c = CLS_C[k - 1]; const std::string ks = std::to_string(k);
-      conv("c" + ks + "a", k == 1 ? "" : "p" + std::to_string(k - 1), cprev, c);
-      bn("bn" + ks + "a", "c" + ks + "a", c, "");
-      if (m->fold_off.count("c" + ks + "b")) {
-        const std::string cn = "c" + ks + "b", xn = "c" + ks + "a", bnn = "bn" + ks + "a";
-        const Buf ob = m->act.at(cn);
-        const size_t fo = m->fold_off.at(cn), bo = m->bnp_off.at(bnn);
-        ADD_OP(F, "bn_fold_prepare:" + cn, 2.0 * 9 * c * c * 2, 4.0 * 9 * c * c * 4, {
-          return k_bn_fold_prepare(ctx, m->P(cn + "/kernel"), m->P(cn + "/bias"), m->wsf(bo), m->wsf(bo) + c, c, c, m->wsf(fo), s, dt != 0);
-        });
-        ADD_OP(F, "conv3x3_fwd:" + cn, 2.0 * 9 * c * c * (double)ob.n * ob.h * ob.w, eb * (double)ob.n * ob.h * ob.w * 2 * c + 4.0 * 9.0 * c * c, {
-          const float* tab = m->wsf(fo) + (size_t)9 * c * c;
-          if (dt) return k_conv3x3_bf16_fwd(ctx, CBF(m->Av(xn)), m->wsf(fo), tab, reinterpret_cast<const unet_bf16*>(tab), MASK_BIAS_TAB, WBF(m->Av(cn)), ob.n, ob.h, ob.w, c, c, ACT_RELU, 0.0f, 0,
-                                            WBF(static_cast<void*>(m->wsf(m->off_wt))), 0, s);
-          int32_t e = k_h2_weights(ctx, m->P(cn + "/kernel"), m->wsf(m->off_wt), c, c, 0, s, m->wsf(bo));
-          if (e) return e;
-          return k_conv3x3_h2_fwd(ctx, m->A(xn), m->wsf(m->off_wt), tab, tab, MASK_BIAS_TAB, m->Aw(cn), ob.n, ob.h, ob.w, c, c, ACT_RELU, 0.0f, 0, s);
-        });
-      } else
-      conv("c" + ks + "b", "bn" + ks + "a", c, c);
-      bn("bn" + ks + "b", "c" + ks + "b", c, "p" + ks);
+      emit_conv_fwd(m, F, "c" + ks + "a", k == 1 ? "" : "p" + std::to_string(k - 1), cprev, c, ACT_RELU, 0.0f, 0, tr);
+      emit_bn_fwd(m, F, SY, "bn" + ks + "a", "c" + ks + "a", "bn" + ks + "a", c, "", tr);
+      if (m->fold_off.count("c" + ks + "b")) emit_conv_fwd_folded(m, F, "c" + ks + "b", "c" + ks + "a", "bn" + ks + "a", c, ACT_RELU, 0.0f, 0, tr);
+      else emit_conv_fwd(m, F, "c" + ks + "b", "bn" + ks + "a", c, c, ACT_RELU, 0.0f, 0, tr);
+      emit_bn_fwd(m, F, SY, "bn" + ks + "b", "c" + ks + "b", "bn" + ks + "b", c, "p" + ks, tr);
       cprev = c;
     }
     ADD_OP(F, "dense_fwd:fc1", 2.0 * N * K * CLS_HIDDEN, eb * (double)N * K + 4.0 * (double)K * CLS_HIDDEN, {
@@ -2010,46 +1927,7 @@ void build_programs_cls(unet_model* m) {
     if (dt) return unet_dense_bwd_bf16(ctx, CBF(m->Av("p3")), m->P("fc1/kernel"), m->D("h1"), WBF(m->Dv("p3")), m->G("fc1/kernel"), N, K, CLS_HIDDEN, s);
     return unet_dense_bwd(ctx, m->A("p3"), m->P("fc1/kernel"), m->D("h1"), m->D("p3"), m->G("fc1/kernel"), N, K, CLS_HIDDEN, s);
   });
-  { const TInfo a = m->tinfo.at("fc1/kernel"), b = m->tinfo.at("fc2/bias"); SY.push_back({(int)BW.size() - 1, 3, false, (size_t)a.off * 4, b.off + b.count - a.off}); }
-  auto bn_bwd = [&](const std::string& name, const std::string& xname, int c) {      // dy = grad[name], x = act[xname] (ReLU conv), dx = grad[xname]
-    const Buf gb = m->grad.at(name), xb = m->act.at(xname), db = m->grad.at(xname);
-    const int64_t pixels = (int64_t)xb.n * xb.h * xb.w;
-    const size_t so = m->bn_bsum_off.at(name), bo = m->bnp_off.at(name);
-    ADD_OP(BW, "bn_bwd_stats:" + name, 0, 2 * eb * pixels * c, {
-      int32_t r = dt ? unet_bn_bwd_stats_bf16(ctx, CBF(m->Dv(name)), gb.ld, CBF(m->Av(xname)), xb.ld, m->wsf(bo), m->wsd(m->off_bn_bsums) + so, pixels, c, s)
-                     : unet_bn_bwd_stats(ctx, m->D(name), gb.ld, m->A(xname), xb.ld, m->wsf(bo), m->wsd(m->off_bn_bsums) + so, pixels, c, s);
-      if (r) return r;
-      return unet_bn_bwd_param_grads(ctx, m->wsd(m->off_bn_bsums) + so, m->G(name + "/gamma"), m->G(name + "/beta"), c, s);
-    });
-    SY.push_back({(int)BW.size() - 1, 2, true, m->off_bn_bsums * 4 + so * 8, 2 * (int64_t)c});
-    ADD_OP(BW, "bn_bwd_apply:" + name, 0, 3 * eb * pixels * c, {
-      if (dt) return unet_bn_bwd_apply_bf16(ctx, CBF(m->Dv(name)), gb.ld, CBF(m->Av(xname)), xb.ld, m->wsf(bo), m->wsd(m->off_bn_bsums) + so, (double)pixels * gcount, MASK_RELU, 0.0f, 0,
-                                            WBF(m->Dv(xname)), db.ld, pixels, c, s);
-      return unet_bn_bwd_apply(ctx, m->D(name), gb.ld, m->A(xname), xb.ld, m->wsf(bo), m->wsd(m->off_bn_bsums) + so, (double)pixels * gcount, MASK_RELU, 0.0f, 0,
-                               m->D(xname), db.ld, pixels, c, s);
-    });
-  };
-  auto conv_bwd = [&](const std::string& name, const std::string& in, int cin, int cout, bool want_dx) {
-    const Buf ob = m->act.at(name);
-    const double px = (double)ob.n * ob.h * ob.w;
-    ADD_OP(BW, "conv3x3_wgrad:" + name, 2.0 * 9 * cin * cout * px, eb * px * (cin + cout) + 4.0 * 9.0 * cin * cout, {
-      if (dt) {
-        if (in.empty()) return first_conv_wgrad_bf16(ctx, m, name, ob, cout, s);
-        return k_conv3x3_bf16_wgrad(ctx, CBF(m->Av(in)), CBF(m->Dv(name)), m->G(name + "/kernel"), m->G(name + "/bias"), m->wsf(m->off_wgrad_ws), m->wgrad_ws_bytes, ob.n, ob.h, ob.w, cin, cout, s);
-      }
-      const float* xin = in.empty() ? m->x : m->A(in);
-      return conv3x3_wgrad_dispatch(ctx, xin, m->D(name), m->G(name + "/kernel"), m->G(name + "/bias"), m->wsf(m->off_wgrad_ws), m->wgrad_ws_bytes,
-                                    ob.n, ob.h, ob.w, cin, cout, algo, s);
-    });
-    if (want_dx) {
-      ADD_OP(BW, "conv3x3_dgrad:" + name, 2.0 * 9 * cin * cout * px, eb * px * (cout + cin) + 4.0 * 9.0 * cin * cout, {
-        if (dt) return k_conv3x3_bf16_fwd(ctx, CBF(m->Dv(name)), m->P(name + "/kernel"), nullptr, nullptr, MASK_NONE, WBF(m->Dv(in)), ob.n, ob.h, ob.w, cout, cin, ACT_NONE, 0.0f, 0,
-                                          WBF(static_cast<void*>(m->wsf(m->off_wt))), 1, s);
-        return unet_conv3x3_bwd_data(ctx, m->D(name), m->P(name + "/kernel"), nullptr, MASK_NONE, 0.0f, 0, m->D(in), m->wsf(m->off_wt), ob.n, ob.h, ob.w, cin,
-                                     cout, algo, s);
-      });
-    }
-  };
+  emit_bucket(m, BW, SY, "fc1/kernel", "fc2/bias");
   for (int k = 3; k >= 1; --k) {
     const int c = CLS_C[k - 1], cin = k == 1 ? m->in_ch : CLS_C[k - 2];
     const std::string ks = std::to_string(k), ca = "c" + ks + "a", cb = "c" + ks + "b", ba = "bn" + ks + "a", bb = "bn" + ks + "b", pk = "p" + ks;
@@ -2078,45 +1956,17 @@ void build_programs_cls(unet_model* m) {
       if (dt) return unet_maxpool2x2_dropout_bwd_bf16(ctx, CBF(m->Av(bb)), xb.ld, CBF(m->Dv(pk)), WBF(m->Dv(bb)), xb.ld, xb.n, xb.h, xb.w, xb.c, 0.0f, 0, 0, s);
       return unet_maxpool2x2_dropout_bwd(ctx, m->A(bb), xb.ld, m->D(pk), m->D(bb), xb.ld, xb.n, xb.h, xb.w, xb.c, 0.0f, 0, 0, s);
     });
-    bn_bwd(bb, cb, c);
+    emit_bn_bwd(m, BW, SY, bb, bb, cb, cb, c, MASK_RELU, 0.0f, 0, false);
     }
-    if (m->fold_off.count(cb)) {
-      // folded BatchNorm (bn_ka -> conv kb): weight gradient on the raw x, corrected; backward sums from W . dW_raw and S; backward apply + ReLU mask of conv ka in the
-      // data-gradient epilogue, which writes conv ka's output gradient directly
-      const Buf ob = m->act.at(cb);
-      const double px = (double)ob.n * ob.h * ob.w;
-      const size_t go = m->fold_g_off.at(cb), co = m->fold_c_off.at(cb), bo = m->bnp_off.at(ba), so = m->bn_bsum_off.at(ba);
-      ADD_OP(BW, "conv3x3_wgrad:" + cb, 2.0 * 9 * c * c * px, eb * px * 2 * c + 4.0 * 9.0 * c * c, {
-        if (dt) return k_conv3x3_bf16_wgrad(ctx, CBF(m->Av(ca)), CBF(m->Dv(cb)), m->G(cb + "/kernel"), m->G(cb + "/bias"), m->wsf(m->off_wgrad_ws), m->wgrad_ws_bytes, ob.n, ob.h, ob.w, c, c, s);
-        return conv3x3_wgrad_dispatch(ctx, m->A(ca), m->D(cb), m->G(cb + "/kernel"), m->G(cb + "/bias"), m->wsf(m->off_wgrad_ws), m->wgrad_ws_bytes, ob.n, ob.h, ob.w, c, c, algo, s);
-      });
-      ADD_OP(BW, "wgrad_bn_fold_fix:" + cb, 2.0 * 9 * c * c, 8.0 * 9 * c * c, {
-        int32_t r = dt ? k_wgrad_bn_fold_fix_bf16(ctx, CBF(m->Dv(cb)), ob.n, ob.h, ob.w, c, c, m->wsf(bo), m->wsf(bo) + c, m->G(cb + "/kernel"), m->G(cb + "/bias"), m->wsf(go), s,
-                                                  m->P(cb + "/kernel"), m->wsf(bo) + 2 * c, m->wsf(bo) + 3 * c, m->wsd(m->off_bn_bsums) + so)
-                       : k_wgrad_bn_fold_fix(ctx, m->D(cb), ob.n, ob.h, ob.w, c, c, m->wsf(bo), m->wsf(bo) + c, m->G(cb + "/kernel"), m->G(cb + "/bias"), m->wsf(go), s, m->P(cb + "/kernel"),
-                                             m->wsf(bo) + 2 * c, m->wsf(bo) + 3 * c, m->wsd(m->off_bn_bsums) + so);
-        if (r) return r;
-        return unet_bn_bwd_param_grads(ctx, m->wsd(m->off_bn_bsums) + so, m->G(ba + "/gamma"), m->G(ba + "/beta"), c, s);
-      });
-      SY.push_back({(int)BW.size() - 1, 2, true, m->off_bn_bsums * 4 + so * 8, 2 * (int64_t)c});
-      ADD_OP(BW, "conv3x3_dgrad_bn_bwd:" + cb, 2.0 * 9 * c * c * px, eb * px * 3 * c + 4.0 * 9.0 * c * c, {
-        int32_t r = k_bn_bwd_coef(ctx, m->wsf(bo), m->wsd(m->off_bn_bsums) + so, px * gcount, m->wsf(co), c, s);
-        if (r) return r;
-        if (dt) return k_conv3x3_bf16_fwd(ctx, CBF(m->Dv(cb)), m->P(cb + "/kernel"), m->wsf(co), CBF(m->Av(ca)), MASK_BN_BWD_RELU, WBF(m->Dv(ca)), ob.n, ob.h, ob.w, c, c, ACT_NONE, 0.0f, 0,
-                                          WBF(static_cast<void*>(m->wsf(m->off_wt))), 1, s);
-        r = k_h2_weights(ctx, m->P(cb + "/kernel"), m->wsf(m->off_wt), c, c, 1, s);
-        if (r) return r;
-        return k_conv3x3_h2_fwd(ctx, m->D(cb), m->wsf(m->off_wt), m->wsf(co), m->A(ca), MASK_BN_BWD_RELU, m->D(ca), ob.n, ob.h, ob.w, c, c, ACT_NONE, 0.0f, 0, s);
-      });
-    } else {
-    conv_bwd(cb, ba, c, c, true);
-    bn_bwd(ba, ca, c);
+    // (every BatchNorm backward carries the ReLU mask of the conv in front of it, every data gradient lands on a BatchNorm output: no mask)
+    if (m->fold_off.count(cb)) emit_conv_bwd_folded(m, BW, SY, cb, ca, ba, c, MASK_BN_BWD_RELU, 0.0f, 0);
+    else {
+      emit_conv_bwd(m, BW, cb, ba, c, c, true, MASK_NONE, 0.0f, 0);
+      emit_bn_bwd(m, BW, SY, ba, ba, ca, ca, c, MASK_RELU, 0.0f, 0, false);
     }
-    conv_bwd(ca, k == 1 ? "" : "p" + std::to_string(k - 1), cin, c, k > 1);
+    emit_conv_bwd(m, BW, ca, k == 1 ? "" : "p" + std::to_string(k - 1), cin, c, k > 1, MASK_NONE, 0.0f, 0);
   }
-  { const TInfo a = m->tinfo.at("c1a/kernel"), b = m->tinfo.at("bn3b/beta"); SY.push_back({(int)BW.size() - 1, 3, false, (size_t)a.off * 4, b.off + b.count - a.off}); }
-#undef CBF
-#undef WBF
+  emit_bucket(m, BW, SY, "c1a/kernel", "bn3b/beta");
 }
 
 void resolve_sync(unet_model* m) {
