@@ -1153,6 +1153,40 @@ int32_t unet_vol_geodesic_begin(unet_ctx*, const uint8_t* seeds, const uint8_t* 
 int32_t unet_vol_geodesic_steps(unet_ctx*, int32_t X, int32_t Y, int32_t Z, int32_t first_step, int32_t n_steps, int32_t connectivity, int32_t planar, uint16_t* arrival,
                                 int64_t* counts, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- vesselness of a CT: Hessian eigenvalues and Frangi's tube measure (csrc/kernels_vessel.hip; exact against tests/vessel_oracle.py;
+ * vessels.py) ----
+ * L: a float32 volume [X, Y, Z] in Fortran order, X Y Z < 2^31, already smoothed at the scale sigma (millimetres) by unet_vol_smooth_axis.  Outside the volume the edge
+ * voxel repeats (the Gaussian's only mode).  All arithmetic is float64, every operation rounded on its own (fl); the float32 samples convert exactly.
+ * k: SIX HOST doubles, the scale-normalised (gamma = 1) factors computed once by the caller from sigma and the voxel size h:
+ *   k[0..2] = kxx, kyy, kzz = sigma^2 / h_a^2;   k[3..5] = kxy, kxz, kyz = sigma^2 / (4 h_a h_b).
+ * Hessian, 19 samples:  Hxx = fl(fl(fl(L[x+1] + L[x-1]) - fl(2 L[x])) kxx), likewise yy, zz;
+ *   Hxy = fl(fl(fl(L[x+1,y+1] - L[x+1,y-1]) - fl(L[x-1,y+1] - L[x-1,y-1])) kxy), likewise xz, yz.
+ * If any of the six entries is not finite, the three eigenvalues are the quiet NaN 0x7FC00000, the response is 0 and the voxel never becomes a best scale.
+ * Eigenvalues: cyclic Jacobi on (a00, a11, a22, a01, a02, a12), pairs (0,1), (0,2), (1,2), five sweeps.  A rotation of (p, q), r the third index, is skipped when
+ *   apq == 0 (so ending once all three off-diagonals are exactly 0 gives the same bits); otherwise theta = (aqq - app) / (2 apq), t = sgn(theta) / (|theta| +
+ *   sqrt(theta^2 + 1)) with sgn(+-0) = +1, c = 1 / sqrt(t^2 + 1), s = t c, tau = s / (1 + c); app -= t apq, aqq += t apq; arp' = arp - s (arq + tau arp),
+ *   arq' = arq + s (arp - tau arq), both from the old arp, arq; apq = 0.  An overflowing theta^2 needs no special case: IEEE gives sqrt = +inf and t = +-0.  The square
+ *   root is the correctly rounded one, the division plain.
+ * Order: the diagonal (a00, a11, a22) sorted by magnitude, |l1| <= |l2| <= |l3|, stable: exchange (1,2), (2,3), (1,2), each on strictly greater magnitude only.
+ * Measure (Frangi): bright != 0 looks for tubes brighter than their surroundings, 0 for darker ones.  V = 0 unless l2 < 0 and l3 < 0 (dark: l2 > 0 and l3 > 0); else
+ *   RA = |l2| / |l3|, RB = |l1| / sqrt(|l2| |l3|), S2 = (l1^2 + l2^2) + l3^2,
+ *   V = float32(((1 - E(RA^2 / den_a)) E(RB^2 / den_b)) (1 - E(S2 / den_c))),   den_a = 2 alpha^2, den_b = 2 beta^2, den_c = 2 c^2 (from the host).
+ * E(u) = exp(-u), the library's own: u = (u < 745 ? u : 745); k = rint(u INV_LN2); r = -((u - k LN2_HI) - k LN2_LO); p = the Taylor polynomial of degree 13 of e^r in
+ *   Horner form, p = C13, p = p r + Cn for n = 12 .. 0, Cn = the double nearest 1 / n!; E = ldexp(p, -k).  INV_LN2 = 0x1.71547652b82fep+0, LN2_HI = 0x1.62e42fee00000p-1,
+ *   LN2_LO = 0x1.a39ef35793c76p-33.
+ * region (nullable, uint8 [X Y Z], non-zero = takes part): a voxel outside keeps eigenvalues +0.0, response 0, scale 0.
+ * unet_vol_hessian_eig  writes eig = l1 | l2 | l3, three float32 volumes one after the other (3 X Y Z floats).
+ * unet_vol_vesselness   reads and updates best (float32) and scale (uint8) in place for the scale of index `index`, 0 <= index < UNET_VOL_VESSEL_MAX_SCALES: index 0
+ *   initialises them (best = V, scale = V > 0 ? 1 : 0); a later one replaces only where V > best, with scale = index + 1.  So over the scales of a call best is the maximum
+ *   response and scale is 0 where best == 0, else 1 + the index of the first scale that reached the maximum.
+ * UNET_E_ARG before any launch, nothing written: a null pointer (region aside), an extent <= 0 or X Y Z >= 2^31, a factor or denominator that is not finite and positive,
+ *   bright outside 0 / 1, an index outside its range, a misaligned float buffer, an output overlapping L, the region or the other output.
+ * One launch over a bounded grid of persistent workgroups, no atomics, every output element written by one lane: the same bits on every run. */
+#define UNET_VOL_VESSEL_MAX_SCALES 254
+int32_t unet_vol_hessian_eig(unet_ctx*, const float* L, int32_t X, int32_t Y, int32_t Z, const double* k, const uint8_t* region, float* eig, void* stream);
+int32_t unet_vol_vesselness(unet_ctx*, const float* L, int32_t X, int32_t Y, int32_t Z, const double* k, const uint8_t* region, double den_a, double den_b, double den_c,
+                            int32_t bright, int32_t index, float* best, uint8_t* scale, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Model level. Replaces the Keras Model built at T1:853-916 and driven by
  * compile/fit/evaluate/predict (T1:1053-1061, 1101, 1137).  A model is a fixed-shape plan:

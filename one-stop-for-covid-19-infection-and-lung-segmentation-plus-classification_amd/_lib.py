@@ -36,6 +36,7 @@ ZONE_MAX_PARTS, ZONE_MAX_SHELLS, ZONE_MAX_BINS = 8, 4, 1024           # UNET_VOL
 RANK_MAX_RADIUS = 2                                                   # UNET_VOL_RANK_MAX_RADIUS
 FILTER_MODES = {"nearest": 0, "constant": 1, "reflect": 2}            # UNET_FILTER_NEAREST, UNET_FILTER_CONSTANT, UNET_FILTER_REFLECT
 GEODESIC_MAX_STEP = 65534                                             # UNET_VOL_GEODESIC_MAX_STEP
+VESSEL_MAX_SCALES = 254                                               # UNET_VOL_VESSEL_MAX_SCALES
 MASK_NONE, MASK_RELU, MASK_ELU, MASK_ELU_DROP = 0, 1, 2, 3
 PROG_FWD_TRAIN, PROG_BWD, PROG_FWD_INFER = 0, 1, 2
 SYNC_BN_FWD, SYNC_LOSS, SYNC_BN_BWD, SYNC_GRAD_BUCKET = 0, 1, 2, 3
@@ -279,6 +280,9 @@ _PROTOS = {
     "unet_vol_geodesic_ws_bytes": (sz, [i32, i32, i32]),
     "unet_vol_geodesic_begin": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, sz, vp]),
     "unet_vol_geodesic_steps": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
+    # vesselness of a CT: Hessian eigenvalues and Frangi's tube measure (csrc/kernels_vessel.hip, vessels.py); k is a host array of 6 doubles
+    "unet_vol_hessian_eig": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp]),
+    "unet_vol_vesselness": (i32, [vp, vp, i32, i32, i32, vp, vp, f64, f64, f64, i32, i32, vp, vp, vp]),
     "unet_model_create": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(vp)]),
     "unet_model_dtype": (i32, [vp]),
     "unet_model_tap_elem_bytes": (i32, [vp, C.c_char_p, i32]),

@@ -14,8 +14,9 @@ Sources are what filters / resample_volume take: a path, a NiftiVolume, an [X, Y
 result equals tests/lungmask_oracle.py element for element.  Every argument error is a ValueError raised before any device work; there is no CPU fallback for the device
 steps.  The geodesic distance is a count of steps inside the constraint, not millimetres.  The airway growth is explosion-controlled region growing with a front-count
 criterion: its thresholds (airway_hu, leak_ratio, min_front, ref_steps), like air_hu, body_hu, min_lung_ml and min_ratio, are conventional defaults, configurable and
-NOT clinically validated here.  Lobes and fissures, vessel exclusion, dense consolidation at the pleura (a threshold misses it unless close_mm bridges it), per-branch
-leak control (the front count is global), airway walls and sharding across ranks are out of scope (section 4ae).
+NOT clinically validated here.  Lobes and fissures, vessel exclusion inside the mask itself (vessels.vessel_mask finds the vessels afterwards, section 4af), dense
+consolidation at the pleura (a threshold misses it unless close_mm bridges it), per-branch leak control (the front count is global), airway walls and sharding across
+ranks are out of scope (section 4ae).
 """
 from __future__ import annotations
 

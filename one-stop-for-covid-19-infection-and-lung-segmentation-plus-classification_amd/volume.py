@@ -1042,6 +1042,38 @@ def _check_lungs(lungs, lung_mask):
     return kw
 
 
+def _check_vessels(vessels, lung_mask):
+    """segment_volume's vessels= -> None (off) or the checked keyword arguments of vessels.vessel_mask"""
+    if vessels is None or vessels is False:
+        return None
+    if vessels is not True and not isinstance(vessels, dict):
+        raise ValueError(f"vessels is True or a dict of vessels.vessel_mask keyword arguments, not {vessels!r}")
+    from . import vessels as VS
+    kw = {} if vessels is True else dict(vessels)
+    if set(kw) - VS._VESSEL_MASK_KEYS:
+        raise ValueError(f"vessels takes {sorted(VS._VESSEL_MASK_KEYS)}, not {sorted(set(kw) - VS._VESSEL_MASK_KEYS)}")
+    VS._check_vessel_mask_args(**kw)
+    if lung_mask is None:
+        raise ValueError("vessels needs lung_mask (or lungs=): the vessels are searched inside the lungs")
+    return kw
+
+
+def _segmentation_vessels(vessels, vol, lv, mask_dev, shape, density):
+    """the vessel mask inside the lung mask, the infection's volume on it and, with density=, the infection's density without it -> the extra result fields"""
+    from . import lungs as L
+    from . import vessels as VS
+    torch = _torch()
+    lungs_dev = _mask_to_device(lv.get_fdata() != 0, None)[0]
+    vm = VS.vessel_mask(vol, lungs_dev, pixdim=vol.pixdim, return_device=True, **vessels)
+    on = int(torch.count_nonzero((mask_dev != 0) & (vm.mask != 0)).item())
+    out = dict(vessels=vm, infected_ml_on_vessels=float(on) * float(np.prod(np.asarray(vol.pixdim, np.float64))) / 1000.0)
+    if density is not None:
+        out["vessel_free_density"] = intensity_stats(vol, mask=mask_dev, region=L._and_not(lungs_dev, vm.mask, shape), shape=shape, **density)
+    vm.mask = _host_of(vm.mask, np.uint8, shape)
+    vm.vesselness.response, vm.vesselness.scale = _host_of(vm.vesselness.response, np.float32, shape), _host_of(vm.vesselness.scale, np.uint8, shape)
+    return out
+
+
 def _computed_lungs(ct, lungs, lung_mask):
     """-> (the lung mask segment_volume goes on with, (extra result fields, extra seconds)): lungs.lung_mask(ct) as a host array when lungs= asks for it"""
     if lungs is None:
@@ -1089,7 +1121,7 @@ def _prepare_segmentation(ct, lung_mask, truth, img_size, trim, input_size):
 
 
 def segment_volume(ct, model, lung_mask=None, threshold=0.547, batch_size=32, out_path=None, img_size=512, trim=(0.2, 0.8), min_lesion_ml=None, connectivity=1,
-                   lesions=False, truth=None, postprocess=None, density=None, per_lung=None, render=None, mesh=None, distribution=None, lungs=None):
+                   lesions=False, truth=None, postprocess=None, density=None, per_lung=None, render=None, mesh=None, distribution=None, lungs=None, vessels=None):
     """CT file (or array) -> VolumeSegmentation.  `model`: a UNetModel or a routed.ClusterRoutedModel (only `predict` is used); lung_mask=None: whole-frame
     boxes (the two halves of the frame); boxes are keyed by slice number (box_indexing="slice"); out_path: the mask as .nii / .nii.gz with the CT's geometry.
     min_lesion_ml: connected components (`connectivity` 1, 2, 3 = 6, 18, 26 neighbours) smaller than that are removed on the device before the mask comes to the
@@ -1127,10 +1159,16 @@ def segment_volume(ct, model, lung_mask=None, threshold=0.547, batch_size=32, ou
     and res.distribution_error holds the reason.  seconds["distribution"]: its time.  None: nothing runs and no other field changes.
     lungs: True, or a dict of lungs.lung_mask keyword arguments: the lung mask is computed from the CT first (lungs.lung_mask; a lung U-Net under its model= key) and used
     exactly as a lung_mask= array in the CT's orientation would be; res.lungs is the LungMask and seconds["lungs"] its time.  Giving both lungs= and lung_mask= is a
-    ValueError.  None: nothing runs and nothing changes."""
+    ValueError.  None: nothing runs and nothing changes.
+    vessels: True, or a dict of vessels.vessel_mask keyword arguments (threshold, dense_hu, max_radius_mm, min_ml, connectivity, erode_mm, sigmas_mm, alpha, beta, c,
+    bright); needs a lung mask (lung_mask= or lungs=; ValueError before any work without one).  After density, on the final mask: res.vessels = the VesselMask inside the
+    lung mask (host arrays; the CT's pixdim), res.infected_ml_on_vessels the volume of infection AND vessels -- the infection U-Net's false positives sit there -- and,
+    with density= as well, res.vessel_free_density = intensity_stats(ct, mask=infection, region=lungs & ~vessels) beside the unchanged res.density.  The infection mask
+    itself is never altered.  A float64 CT is refused as filters refuse it.  seconds["vessels"]: its time.  None: nothing runs and no field is added."""
     _check_connectivity(connectivity)
     lungs = _check_lungs(lungs, lung_mask)
     lung_mask = True if lungs is not None else lung_mask          # (the checks below ask only whether there is one)
+    vessels = _check_vessels(vessels, lung_mask)
     density = _check_density(density)
     per_lung = _check_per_lung(per_lung, lung_mask)
     distribution = _check_distribution(distribution, per_lung)
@@ -1150,11 +1188,11 @@ def segment_volume(ct, model, lung_mask=None, threshold=0.547, batch_size=32, ou
     canvas = paste_back(prob, R1, R2, S)
     mask_dev, counts_dev = unslice(canvas, threshold, (X, Y, Z), z0, z1)
     return _finish_segmentation(vol, lv, truth_mask, mask_dev, counts_dev, z0, z1, has, info, threshold, sec, t0, postprocess, min_lesion_ml, lesions, connectivity, out_path,
-                                density=density, per_lung=per_lung, render=render, mesh=mesh, distribution=distribution, **found[0])
+                                density=density, per_lung=per_lung, render=render, mesh=mesh, distribution=distribution, vessels=vessels, **found[0])
 
 
 def _finish_segmentation(vol, lv, truth_mask, mask_dev, counts_dev, z0, z1, has, info, threshold, sec, t0, postprocess, min_lesion_ml, lesions, connectivity, out_path,
-                         density=None, per_lung=None, render=None, mesh=None, distribution=None, **extra):
+                         density=None, per_lung=None, render=None, mesh=None, distribution=None, vessels=None, **extra):
     """What segment_volume and segment_volume_ensemble do with the mask volume once it is formed (mask_dev, counts_dev [z1 - z0], both on the device): postprocess,
     min_lesion_ml / lesions, density (the checked keyword arguments of intensity_stats, or None), per_lung (those of split_lungs, or None), render (those of the sheet, or None), mesh (the checked dict of _check_mesh, or None), distribution (the checked pair of _check_distribution, or None), truth, the download, the lung share and out_path -> VolumeSegmentation (+ `extra` fields).  t0: when the paste-back began."""
     torch = _torch()
@@ -1199,6 +1237,10 @@ def _finish_segmentation(vol, lv, truth_mask, mask_dev, counts_dev, z0, z1, has,
         if lv is not None:
             lung_dens = intensity_stats(vol, mask=lv.get_fdata() != 0, **density)
         torch.cuda.synchronize(); sec["density"] = time.perf_counter() - td
+    if vessels is not None:                                         # (the checked keyword arguments of vessels.vessel_mask; the fields exist only when it is asked for)
+        torch.cuda.synchronize(); tv = time.perf_counter()
+        extra.update(_segmentation_vessels(vessels, vol, lv, mask_dev, (X, Y, Z), density))
+        torch.cuda.synchronize(); sec["vessels"] = time.perf_counter() - tv
     burden, burden_error = None, None
     distr, distr_error = None, None
     if per_lung is not None:
