@@ -1187,6 +1187,49 @@ int32_t unet_vol_hessian_eig(unet_ctx*, const float* L, int32_t X, int32_t Y, in
 int32_t unet_vol_vesselness(unet_ctx*, const float* L, int32_t X, int32_t Y, int32_t Z, const double* k, const uint8_t* region, double den_a, double den_b, double den_c,
                             int32_t bright, int32_t index, float* best, uint8_t* scale, void* stream);
 
+/* ---- centerlines of a mask volume: thinning, the table of a thin mask, label spread (csrc/kernels_skeleton.hip; exact against
+ * tests/skeleton_oracle.py; skeleton.py) ----
+ * Volumes are [X, Y, Z] in Fortran order, X Y Z < 2^31; set = non-zero; outside the volume is background; extents of 1 are legal (a 2-D image is Z = 1).
+ * NEIGHBOUR MASK: the 26 neighbours of a voxel are numbered i = (dx + 1) + 3 (dy + 1) + 9 (dz + 1), i = 0 .. 26 without the centre 13; neighbour i is bit i (i < 13) or
+ *   bit i - 1 (i > 13) of a uint32.  n26 = its popcount.
+ * simple(v) (Bertrand and Malandain): the set neighbours form exactly one 26-connected component, and the clear voxels of the 18-neighbourhood that are 6-adjacent to v are
+ *   not empty and lie in one 6-connected component of the clear voxels of the 18-neighbourhood.  25 985 144 of the 2^26 neighbourhoods are simple.
+ * Thinning: an iteration is six direction passes +z, -z, +y, -y, +x, -x.  Pass d: the candidates, all judged on the image as the pass finds it, are the set voxels v with
+ *   v + d clear or outside, n26(v) >= 2 (endpoints != 0) or >= 1 (endpoints == 0), and simple(v); then eight sub-passes k = 0 .. 7 clear, all at once, the candidates with
+ *   (x & 1) | (y & 1) << 1 | (z & 1) << 2 == k that are still simple in the current image (only simplicity is tested again).  The result does not depend on the order lanes
+ *   run in: two voxels of a subfield are never 26-neighbours.
+ *   _ws_bytes     two volumes of one bit per voxel in unet_vol_morph's packed layout (rows padded to 64-bit words): the image and the candidates; 0 for a bad or zero
+ *                 dimension.
+ *   _begin        packs mask (bytes, any alignment) into the workspace.
+ *   _iterations   runs the iterations first .. first + n - 1 (6 x 9 launches each) and overwrites removed[it] (int64, 8-byte aligned, at least first + n entries) with the
+ *                 voxels iteration it cleared.  The host reads removed only between calls and stops after the first iteration that cleared nothing.
+ *   _end          unpacks the image into out (bytes 0 / 1, any alignment).
+ *   UNET_E_ARG, nothing launched: a bad dimension, first < 0, n < 0, endpoints outside 0 / 1, a null or misaligned buffer (removed 8, ws 16 bytes), a workspace below
+ *   _ws_bytes, a buffer overlapping the workspace.  A zero dimension, or n == 0, launches nothing.
+ * Table: the set voxels of a mask sorted by flat index, by count -> scan -> emit.
+ *   unet_vol_skeleton_count   *total (device int64) = the set voxels; ws (unet_vol_skeleton_ws_bytes) keeps the offsets for _emit.
+ *   unet_vol_skeleton_emit    the same mask and ws after the host has read the total and passes it back with the capacity of the outputs: index int32 [capacity] the flat
+ *                             index, nbr uint32 [capacity] the neighbour mask, and, when d2 (float64 [X Y Z], e.g. of unet_vol_edt_sq) and vals (float64 [capacity]) are
+ *                             both given, vals[i] = d2[index[i]].  capacity < total is UNET_E_ARG; no row at or past capacity is ever written.
+ *   UNET_E_ARG, nothing launched: a bad dimension, a null or misaligned buffer (index, nbr 4, d2, vals, total 8, ws 16 bytes), a short workspace, total or capacity out of
+ *   range, only one of d2 / vals, an output overlapping an input or another output.
+ * unet_vol_label_spread: arrival is what unet_vol_geodesic_* wrote (uint16), labels int32 [X Y Z], non-zero on the voxels of arrival 0 that carry a label.  One launch per
+ *   step s = first .. first + n - 1: a voxel with arrival == s takes the smallest non-zero label among its neighbours under generate_binary_structure(3, connectivity) whose
+ *   arrival == s - 1, and keeps its label when there is none.  A launch writes only step-s voxels and reads only step-(s - 1) voxels.  UNET_E_ARG, nothing launched: a bad
+ *   dimension or connectivity, first < 1, n < 0, a step beyond UNET_VOL_GEODESIC_MAX_STEP, a null or misaligned buffer, labels overlapping arrival.
+ * Integer work only, no workgroup waits for another, every grid is sized to its work: the same bits on every run. */
+size_t unet_vol_thin_ws_bytes(int32_t X, int32_t Y, int32_t Z);
+int32_t unet_vol_thin_begin(unet_ctx*, const uint8_t* mask, int32_t X, int32_t Y, int32_t Z, void* ws, size_t ws_bytes, void* stream);
+int32_t unet_vol_thin_iterations(unet_ctx*, int32_t X, int32_t Y, int32_t Z, int32_t first, int32_t n, int32_t endpoints, int64_t* removed, void* ws, size_t ws_bytes,
+                                 void* stream);
+int32_t unet_vol_thin_end(unet_ctx*, int32_t X, int32_t Y, int32_t Z, uint8_t* out, const void* ws, size_t ws_bytes, void* stream);
+size_t unet_vol_skeleton_ws_bytes(int32_t X, int32_t Y, int32_t Z);
+int32_t unet_vol_skeleton_count(unet_ctx*, const uint8_t* mask, int32_t X, int32_t Y, int32_t Z, int64_t* total, void* ws, size_t ws_bytes, void* stream);
+int32_t unet_vol_skeleton_emit(unet_ctx*, const uint8_t* mask, int32_t X, int32_t Y, int32_t Z, const double* d2, int64_t total, int64_t capacity, int32_t* index,
+                               uint32_t* nbr, double* vals, const void* ws, size_t ws_bytes, void* stream);
+int32_t unet_vol_label_spread(unet_ctx*, const uint16_t* arrival, int32_t* labels, int32_t X, int32_t Y, int32_t Z, int32_t first, int32_t n, int32_t connectivity,
+                              void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Model level. Replaces the Keras Model built at T1:853-916 and driven by
  * compile/fit/evaluate/predict (T1:1053-1061, 1101, 1137).  A model is a fixed-shape plan:

@@ -26,6 +26,9 @@ Public surface:
   hessian_eigenvalues / vesselness / vessel_mask (Vesselness, VesselMask) -- vessels' tube measure of the CT: the eigenvalues of the scale-normalised Hessian, Frangi's
                             vesselness over a few scales and the vessel mask inside the lungs that segment_volume(vessels=) reports the infection against; also
                             reachable from the package itself
+  thin_volume / skeleton_table / skeleton_graph / prune / root_tree / branch_territories / airway_tree / vessel_tree (Skeleton, SkeletonGraph, RootedTree,
+                            BranchTerritories, CenterlineTree) -- skeleton's centerlines of the airway and vessel masks: topology-preserving thinning on the device, the
+                            branch graph with lengths and calibres, generations from a root and the mask voxels of every branch; also reachable from the package itself
   engine.HipUNet         -- the HIP backend (libunet_hip.so through the C ABI of include/unet_hip.h)
 Importing this package has no side effects and does not need a GPU; constructing the
 backend does (there is no CPU fallback).
@@ -37,7 +40,9 @@ __all__ = ["runners", "keras_like", "engine", "weights", "data", "volume", "nift
            "run_features", "TextureStats", "zones", "lung_zones", "lung_distribution", "LungZones", "LungDistribution", "filters", "rank_filter", "median_filter", "minimum_filter", "maximum_filter", "percentile_filter",
            "grey_erosion", "grey_dilation", "grey_opening", "grey_closing", "gaussian_filter", "footprint_bits", "structure", "FilteredVolume",
            "lungs", "lung_mask", "threshold_volume", "geodesic_distance", "reconstruct", "body_mask", "find_trachea", "grow_airways", "LungMask", "AirwayGrowth", "TracheaSeed",
-           "LungMaskError", "vessels", "hessian_eigenvalues", "vesselness", "vessel_mask", "Vesselness", "VesselMask"]
+           "LungMaskError", "vessels", "hessian_eigenvalues", "vesselness", "vessel_mask", "Vesselness", "VesselMask",
+           "skeleton", "thin_volume", "skeleton_table", "skeleton_graph", "prune", "root_tree", "branch_territories", "airway_tree", "vessel_tree", "Skeleton", "SkeletonGraph",
+           "RootedTree", "BranchTerritories", "CenterlineTree"]
 _FROM_VOLUME = ("split_lungs", "lung_burden", "LungSides", "LungBurden", "LungSplitError", "render_planes", "project_volume", "key_slices", "Layer", "RenderedSheet",
                 "resample_volume", "resample_mask", "resample_labels", "reorient_volume", "change_between", "Grid", "ResampledVolume", "VolumeChange",
                 "extract_surface", "lesion_shapes", "SurfaceMesh")
@@ -48,6 +53,8 @@ _FROM_FILTERS = ("rank_filter", "median_filter", "minimum_filter", "maximum_filt
 _FROM_LUNGS = ("lung_mask", "threshold_volume", "geodesic_distance", "reconstruct", "body_mask", "find_trachea", "grow_airways", "LungMask", "AirwayGrowth", "TracheaSeed",
                "LungMaskError")
 _FROM_VESSELS = ("hessian_eigenvalues", "vesselness", "vessel_mask", "Vesselness", "VesselMask")
+_FROM_SKELETON = ("thin_volume", "skeleton_table", "skeleton_graph", "prune", "root_tree", "branch_territories", "airway_tree", "vessel_tree", "Skeleton", "SkeletonGraph",
+                  "RootedTree", "BranchTerritories", "CenterlineTree")
 _FROM_TEXTURE = ("texture_stats", "lesion_texture", "glcm", "run_lengths", "quantize_volume", "glcm_features", "run_features", "TextureStats")
 
 
@@ -73,4 +80,7 @@ def __getattr__(name):                                              # resolved o
     if name in _FROM_VESSELS:
         import importlib
         return getattr(importlib.import_module(__name__ + ".vessels"), name)
+    if name in _FROM_SKELETON:
+        import importlib
+        return getattr(importlib.import_module(__name__ + ".skeleton"), name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

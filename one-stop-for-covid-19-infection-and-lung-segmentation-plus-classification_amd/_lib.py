@@ -283,6 +283,15 @@ _PROTOS = {
     # vesselness of a CT: Hessian eigenvalues and Frangi's tube measure (csrc/kernels_vessel.hip, vessels.py); k is a host array of 6 doubles
     "unet_vol_hessian_eig": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp]),
     "unet_vol_vesselness": (i32, [vp, vp, i32, i32, i32, vp, vp, f64, f64, f64, i32, i32, vp, vp, vp]),
+    # centerlines of a mask volume: thinning, the table of a thin mask's voxels, the spread of labels along arrival steps (csrc/kernels_skeleton.hip, skeleton.py)
+    "unet_vol_thin_ws_bytes": (sz, [i32, i32, i32]),
+    "unet_vol_thin_begin": (i32, [vp, vp, i32, i32, i32, vp, sz, vp]),
+    "unet_vol_thin_iterations": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp, sz, vp]),
+    "unet_vol_thin_end": (i32, [vp, i32, i32, i32, vp, vp, sz, vp]),
+    "unet_vol_skeleton_ws_bytes": (sz, [i32, i32, i32]),
+    "unet_vol_skeleton_count": (i32, [vp, vp, i32, i32, i32, vp, vp, sz, vp]),
+    "unet_vol_skeleton_emit": (i32, [vp, vp, i32, i32, i32, vp, i64, i64, vp, vp, vp, vp, sz, vp]),
+    "unet_vol_label_spread": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "unet_model_create": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(vp)]),
     "unet_model_dtype": (i32, [vp]),
     "unet_model_tap_elem_bytes": (i32, [vp, C.c_char_p, i32]),

@@ -1058,6 +1058,38 @@ def _check_vessels(vessels, lung_mask):
     return kw
 
 
+def _check_airway_tree(airway_tree, lungs):
+    """segment_volume's airway_tree= -> None (off) or the checked keyword arguments of skeleton.airway_tree; lungs: the checked lungs= (or None)"""
+    if airway_tree is None or airway_tree is False:
+        return None
+    if airway_tree is not True and not isinstance(airway_tree, dict):
+        raise ValueError(f"airway_tree is True or a dict of skeleton.airway_tree keyword arguments, not {airway_tree!r}")
+    from . import skeleton as SK
+    kw = {} if airway_tree is True else dict(airway_tree)
+    SK._check_tree_args(kw, "airway_tree")
+    if lungs is None or lungs.get("airways", "auto") is False:
+        raise ValueError("airway_tree needs lungs= with its airway step: the airway it thins is the one lungs.lung_mask grows")
+    return kw
+
+
+def _segmentation_airway_tree(kw, lm, ct, lungs):
+    """the airway tree of the airway lungs.lung_mask grew, from the device buffers it left -> the extra result fields; the superior end: airway_tree's own orientation /
+    affine, else lungs=' orientation, else the axis codes of the CT (a NiftiVolume by now: a path is decoded once, in front).  An airway step that did not run leaves
+    res.airway_tree None and the reason in res.airway_tree_error."""
+    from . import skeleton as SK
+    if lm.airways is None:
+        return dict(airway_tree=None, airway_tree_error=lm.airway_error)
+    kw = dict(kw)
+    if kw.get("orientation") is None and kw.get("affine") is None:
+        kw["orientation"] = lungs.get("orientation")
+        if kw["orientation"] is None and isinstance(ct, nifti_min.NiftiVolume) and ct.affine is not None:
+            try:
+                kw["orientation"] = ct.axcodes
+            except nifti_min.NiftiFormatError:
+                kw["orientation"] = None
+    return dict(airway_tree=SK.airway_tree(lm, **kw), airway_tree_error=None)
+
+
 def _segmentation_vessels(vessels, vol, lv, mask_dev, shape, density):
     """the vessel mask inside the lung mask, the infection's volume on it and, with density=, the infection's density without it -> the extra result fields"""
     from . import lungs as L
@@ -1074,14 +1106,24 @@ def _segmentation_vessels(vessels, vol, lv, mask_dev, shape, density):
     return out
 
 
-def _computed_lungs(ct, lungs, lung_mask):
-    """-> (the lung mask segment_volume goes on with, (extra result fields, extra seconds)): lungs.lung_mask(ct) as a host array when lungs= asks for it"""
+def _computed_lungs(ct, lungs, lung_mask, airway_tree=None):
+    """-> (the lung mask segment_volume goes on with, (extra result fields, extra seconds)): lungs.lung_mask(ct) as a host array when lungs= asks for it.  airway_tree
+    (the checked keyword arguments, or None): the lung mask then stays on the device until the airway it grew has been thinned, and comes to the host after that."""
     if lungs is None:
         return lung_mask, ({}, {})
     from . import lungs as L
     t0 = time.perf_counter()
-    lm = L.lung_mask(ct, **lungs)
-    return lm.mask, (dict(lungs=lm), dict(lungs=time.perf_counter() - t0))
+    if airway_tree is None:
+        lm = L.lung_mask(ct, **lungs)
+        return lm.mask, (dict(lungs=lm), dict(lungs=time.perf_counter() - t0))
+    lm = L.lung_mask(ct, return_device=True, **lungs)
+    _torch().cuda.synchronize(); t1 = time.perf_counter()
+    extra = _segmentation_airway_tree(airway_tree, lm, ct, lungs)
+    _torch().cuda.synchronize(); t2 = time.perf_counter()
+    lm.mask = _host_of(lm.mask, np.uint8, lm.shape)
+    if lm.airways is not None:
+        lm.airways.mask = _host_of(lm.airways.mask, np.uint8, lm.shape)
+    return lm.mask, (dict(lungs=lm, **extra), dict(lungs=t1 - t0 + time.perf_counter() - t2, airway_tree=t2 - t1))
 
 
 def _prepare_segmentation(ct, lung_mask, truth, img_size, trim, input_size):
@@ -1121,7 +1163,7 @@ def _prepare_segmentation(ct, lung_mask, truth, img_size, trim, input_size):
 
 
 def segment_volume(ct, model, lung_mask=None, threshold=0.547, batch_size=32, out_path=None, img_size=512, trim=(0.2, 0.8), min_lesion_ml=None, connectivity=1,
-                   lesions=False, truth=None, postprocess=None, density=None, per_lung=None, render=None, mesh=None, distribution=None, lungs=None, vessels=None):
+                   lesions=False, truth=None, postprocess=None, density=None, per_lung=None, render=None, mesh=None, distribution=None, lungs=None, vessels=None, airway_tree=None):
     """CT file (or array) -> VolumeSegmentation.  `model`: a UNetModel or a routed.ClusterRoutedModel (only `predict` is used); lung_mask=None: whole-frame
     boxes (the two halves of the frame); boxes are keyed by slice number (box_indexing="slice"); out_path: the mask as .nii / .nii.gz with the CT's geometry.
     min_lesion_ml: connected components (`connectivity` 1, 2, 3 = 6, 18, 26 neighbours) smaller than that are removed on the device before the mask comes to the
@@ -1164,9 +1206,15 @@ def segment_volume(ct, model, lung_mask=None, threshold=0.547, batch_size=32, ou
     bright); needs a lung mask (lung_mask= or lungs=; ValueError before any work without one).  After density, on the final mask: res.vessels = the VesselMask inside the
     lung mask (host arrays; the CT's pixdim), res.infected_ml_on_vessels the volume of infection AND vessels -- the infection U-Net's false positives sit there -- and,
     with density= as well, res.vessel_free_density = intensity_stats(ct, mask=infection, region=lungs & ~vessels) beside the unchanged res.density.  The infection mask
-    itself is never altered.  A float64 CT is refused as filters refuse it.  seconds["vessels"]: its time.  None: nothing runs and no field is added."""
+    itself is never altered.  A float64 CT is refused as filters refuse it.  seconds["vessels"]: its time.  None: nothing runs and no field is added.
+    airway_tree: True, or a dict of skeleton.airway_tree keyword arguments; needs lungs= with its airway step (ValueError before any work otherwise).  Right after the
+    lung mask: res.airway_tree = the CenterlineTree of the airway lungs.lung_mask grew -- centerline, branch graph, generations from the superior end, the airway voxels
+    of every branch; a cycle marks a leak.  The superior end comes from the keyword's own orientation / affine, else from lungs=' orientation, else from the CT file's
+    axis codes; it is never guessed.  When the airway step did not run res.airway_tree is None and res.airway_tree_error says why.  seconds["airway_tree"]: its time.
+    None: nothing runs and no field is added."""
     _check_connectivity(connectivity)
     lungs = _check_lungs(lungs, lung_mask)
+    airway_tree = _check_airway_tree(airway_tree, lungs)
     lung_mask = True if lungs is not None else lung_mask          # (the checks below ask only whether there is one)
     vessels = _check_vessels(vessels, lung_mask)
     density = _check_density(density)
@@ -1177,7 +1225,9 @@ def segment_volume(ct, model, lung_mask=None, threshold=0.547, batch_size=32, ou
     if postprocess is not None:
         _check_steps(postprocess, (1.0, 1.0, 1.0))                   # the steps' own arguments, before any work (the CT's pixdim takes this one's place below)
     torch = _torch()
-    lung_mask, found = _computed_lungs(ct, lungs, lung_mask)
+    if airway_tree is not None and isinstance(ct, (str, os.PathLike)):
+        ct = nifti_min.read(ct)                                      # once: the lung mask, the airway tree's axis codes and the slices below all take the decoded volume
+    lung_mask, found = _computed_lungs(ct, lungs, lung_mask, airway_tree)
     vol, lv, truth_mask, z0, z1, S, x, info, R1, R2, has, sec = _prepare_segmentation(ct, lung_mask, truth, img_size, trim, lambda: int(getattr(model, "h", None) or model.base.h))
     sec.update(found[1])
     X, Y, Z = vol.raw.shape
