@@ -14,6 +14,7 @@
 //   cc_final_kernel    every voxel takes its root's number; background -> 0
 // Everything is integer arithmetic: the result is the same on every run.
 #include "common.h"
+#include "vol_common.h"
 
 #include <climits>
 
@@ -203,16 +204,6 @@ __global__ __launch_bounds__(TPB) void cc_flatten_kernel(int32_t* labels, cc_dim
 
 // ---- (d) number the roots: prefix sum over the key-indexed flags (bytes 0 / 1; the array is padded with zeros to a multiple of 16) ------------------
 __device__ __forceinline__ int bytesum(unsigned w) { return (int)((w * 0x01010101u) >> 24); }
-__device__ __forceinline__ int block_sum_int(int v, int* s_w) {      // -> the sum in every lane; s_w: TPB / 64 words
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
-  __syncthreads();
-  int t = 0;
-#pragma unroll
-  for (int w = 0; w < TPB / 64; ++w) t += s_w[w];
-  return t;
-}
 __device__ __forceinline__ int lane_flags(const uint8_t* flags, long long base, long long npad, uint4* w) {
   int c = 0;
 #pragma unroll
@@ -227,7 +218,7 @@ __global__ __launch_bounds__(TPB) void cc_count_kernel(const uint8_t* __restrict
   __shared__ int s_w[TPB / 64];
   uint4 w[4];
   const int c = lane_flags(flags, (long long)blockIdx.x * CHUNK + threadIdx.x * 64, npad, w);
-  const int t = block_sum_int(c, s_w);
+  const int t = vol_block_sum<int, TPB>(c, s_w);
   if (threadIdx.x == 0) bsum[blockIdx.x] = t;
 }
 // one workgroup: chunk sums -> exclusive offsets in place, the total -> n_out
@@ -395,12 +386,10 @@ __global__ __launch_bounds__(TPB) void cc_filter_kernel(const int32_t* __restric
       *reinterpret_cast<uint4*>(mask + base + i) = make_uint4(w[0], w[1], w[2], w[3]);
     } else mask[base + i] = b[0];
   }
-  const int t = block_sum_int(cnt, s_w);
+  const int t = vol_block_sum<int, TPB>(cnt, s_w);
   if (threadIdx.x == 0 && t && z >= z0 && z < z1) atomicAdd(counts + (z - z0), (unsigned long long)t);          // integer sums: exact in any order
 }
 
-inline unsigned cc_blocks(long long items, long long cap) { long long b = (items + TPB - 1) / TPB; return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b)); }
-inline bool cc_dims_ok(int X, int Y, int Z) { return X >= 0 && Y >= 0 && Z >= 0 && (long long)X * Y * Z < 0x80000000LL && (X == 0 || Y == 0 || (long long)X * Y < 0x80000000LL); }
 inline cc_dims cc_make(int X, int Y, int Z) { return {X, Y, Z, (int)((long long)Y * Z), (long long)X * Y, (long long)X * Y * Z}; }
 inline size_t cc_flag_bytes(long long N) { return (size_t)((N + 15) / 16 * 16); }
 inline long long cc_chunks(long long N) { return (N + CHUNK - 1) / CHUNK; }
@@ -410,7 +399,7 @@ constexpr long long GRID_CAP = 256 * 32;                             // grid-str
 // the launches behind unet_vol_label / unet_vol_label_planar / unet_vol_fill_holes (invert: the components of the mask's ZERO voxels); connectivity is the caller's to check
 int32_t k_vol_label(unet_ctx* ctx, const uint8_t* mask, int X, int Y, int Z, int connectivity, int planar, int invert, int32_t* labels, int32_t* n_out, void* ws, size_t ws_bytes,
                     hipStream_t s) {
-  if (!cc_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_label: %d x %d x %d is negative or has 2^31 voxels or more", X, Y, Z);
+  if (!vol_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_label: %d x %d x %d is negative or has 2^31 voxels or more", X, Y, Z);
   const cc_dims d = cc_make(X, Y, Z);
   if (d.N == 0) { UNET_HIP(ctx, hipMemsetAsync(n_out, 0, sizeof(int32_t), s)); return UNET_OK; }
   if (!mask || !labels || !ws) UNET_FAIL(ctx, UNET_E_ARG, "vol_label: bad args");
@@ -429,20 +418,20 @@ int32_t k_vol_label(unet_ctx* ctx, const uint8_t* mask, int X, int Y, int Z, int
   else
     hipLaunchKernelGGL(cc_local_kernel<false>, dim3((unsigned)bricks), dim3(TPB), 0, s, mask, d, connectivity, planar, invert, nbx, nby, labels);
   const long long PX = (long long)(nbx - 1) * Y * Z, PY = (long long)(nby - 1) * X * Z, PZ = (long long)(nbz - 1) * X * Y;
-  if (PX + PY + PZ > 0) hipLaunchKernelGGL(cc_merge_kernel, dim3(cc_blocks(PX + PY + PZ, GRID_CAP)), dim3(TPB), 0, s, labels, d, connectivity, planar, PX, PY, PZ);
+  if (PX + PY + PZ > 0) hipLaunchKernelGGL(cc_merge_kernel, dim3(vol_blocks(PX + PY + PZ, GRID_CAP, TPB)), dim3(TPB), 0, s, labels, d, connectivity, planar, PX, PY, PZ);
   const long long quads = (d.N + 3) / 4;
-  hipLaunchKernelGGL(cc_flatten_kernel, dim3(cc_blocks(quads, GRID_CAP)), dim3(TPB), 0, s, labels, d, flags);
+  hipLaunchKernelGGL(cc_flatten_kernel, dim3(vol_blocks(quads, GRID_CAP, TPB)), dim3(TPB), 0, s, labels, d, flags);
   hipLaunchKernelGGL(cc_count_kernel, dim3((unsigned)nb), dim3(TPB), 0, s, flags, (long long)npad, bsum);
   hipLaunchKernelGGL(cc_scan_kernel, dim3(1), dim3(1024), 0, s, bsum, nb, n_out);
   hipLaunchKernelGGL(cc_number_kernel, dim3((unsigned)nb), dim3(TPB), 0, s, flags, (long long)npad, bsum, d, labels);
-  hipLaunchKernelGGL(cc_final_kernel, dim3(cc_blocks(quads, GRID_CAP)), dim3(TPB), 0, s, labels, d);
+  hipLaunchKernelGGL(cc_final_kernel, dim3(vol_blocks(quads, GRID_CAP, TPB)), dim3(TPB), 0, s, labels, d);
   UNET_CHECK_LAUNCH(ctx, "vol_label"); return UNET_OK;
 }
 
 extern "C" {
 
 size_t unet_vol_label_ws_bytes(int32_t X, int32_t Y, int32_t Z) {
-  if (!cc_dims_ok(X, Y, Z)) return 0;
+  if (!vol_dims_ok(X, Y, Z)) return 0;
   const long long N = (long long)X * Y * Z;
   if (N == 0) return 0;
   return cc_flag_bytes(N) + (size_t)((cc_chunks(N) * sizeof(int32_t) + 15) / 16 * 16);
@@ -463,7 +452,7 @@ int32_t unet_vol_label_planar(unet_ctx* ctx, const uint8_t* mask, int32_t X, int
 }
 
 int32_t unet_vol_component_stats(unet_ctx* ctx, const int32_t* labels, int32_t X, int32_t Y, int32_t Z, int32_t n, void* stats, void* stream) {
-  if (!ctx || n < 0 || !cc_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_component_stats: bad args");
+  if (!ctx || n < 0 || !vol_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_component_stats: bad args");
   const cc_dims d = cc_make(X, Y, Z);
   if (n == 0 || d.N == 0) return UNET_OK;
   if (!labels || !stats || (reinterpret_cast<uintptr_t>(labels) % 16) != 0 || (reinterpret_cast<uintptr_t>(stats) % 8) != 0)
@@ -471,13 +460,13 @@ int32_t unet_vol_component_stats(unet_ctx* ctx, const int32_t* labels, int32_t X
   hipStream_t s = as_stream(stream);
   comp_stat* st = static_cast<comp_stat*>(stats);
   hipLaunchKernelGGL(stat_init_kernel, dim3((unsigned)((n + TPB - 1) / TPB)), dim3(TPB), 0, s, st, n);
-  hipLaunchKernelGGL(cc_stats_kernel, dim3(cc_blocks((d.N + 3) / 4, GRID_CAP)), dim3(TPB), 0, s, labels, d, n, st);
+  hipLaunchKernelGGL(cc_stats_kernel, dim3(vol_blocks((d.N + 3) / 4, GRID_CAP, TPB)), dim3(TPB), 0, s, labels, d, n, st);
   UNET_CHECK_LAUNCH(ctx, "vol_component_stats"); return UNET_OK;
 }
 
 int32_t unet_vol_filter_components(unet_ctx* ctx, const int32_t* labels, const uint8_t* keep, int32_t n, int32_t X, int32_t Y, int32_t Z, int32_t z0, int32_t z1, uint8_t* mask,
                                    int64_t* counts, void* stream) {
-  if (!ctx || n < 0 || !keep || !cc_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_filter_components: bad args");
+  if (!ctx || n < 0 || !keep || !vol_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_filter_components: bad args");
   if (z0 < 0 || z1 > Z || z1 < z0 || (z1 > z0 && !counts)) UNET_FAIL(ctx, UNET_E_ARG, "vol_filter_components: slice range [%d, %d) leaves the %d slices", z0, z1, Z);
   hipStream_t s = as_stream(stream);
   if (z1 > z0) UNET_HIP(ctx, hipMemsetAsync(counts, 0, (size_t)(z1 - z0) * sizeof(int64_t), s));

@@ -28,13 +28,12 @@ constexpr int MAX_C = 1024;
 constexpr long long GRID_CAP = 256 * 32;
 constexpr double DEN_MIN = 1e-9;                                      // a demons denominator (HU^2 / mm^2) at or below this moves nothing: no gradient and no difference
 
-inline unsigned df_blocks(long long items) { long long b = (items + TPB - 1) / TPB; return (unsigned)(b < 1 ? 1 : (b > GRID_CAP ? GRID_CAP : b)); }
 inline bool df_finite(const double* p, int n) {
   if (!p) return false;
   for (int i = 0; i < n; ++i) if (!std::isfinite(p[i])) return false;
   return true;
 }
-inline bool df_aligned(const void* p, size_t a) { return p && (reinterpret_cast<uintptr_t>(p) % a) == 0; }
+inline bool df_aligned(const void* p, size_t a) { return p && vol_aligned(p, a); }          // (a null pointer is refused too: every buffer of these entries is required)
 
 // ---- the Gaussian pass: out = fl32(sum_t w[t] src[clamp(p + t - R)]), t ascending, acc = acc + fl(w v) from acc = 0 ---------------------------------------------------
 struct sm_weights { double w[2 * MAX_R + 1]; };                       // 520 bytes of kernel arguments
@@ -90,16 +89,16 @@ __device__ __forceinline__ double df_displace(double c, const df_mat3& L, int r,
 // ---- the demons step ---------------------------------------------------------------------------------------------------------------------------------------------
 struct dm_geom { rs_mat W; df_mat3 L, G; double delta2; };
 
-__global__ __launch_bounds__(TPB) void dm_kernel(rs_src fix, const uint8_t* __restrict__ mask, int X, int Y, int Z, rs_src mov, int Xm, int Ym, int Zm, dm_geom g,
+__global__ __launch_bounds__(TPB) void dm_kernel(vol_voxels fix, const uint8_t* __restrict__ mask, int X, int Y, int Z, vol_voxels mov, int Xm, int Ym, int Zm, dm_geom g,
                                                  const float* __restrict__ uin, float* __restrict__ uout) {
   const long long N = (long long)X * Y * Z;
   const double top[3] = {(double)(Xm - 1), (double)(Ym - 1), (double)(Zm - 1)};
-  const auto get = [&](long long f) { return rs_dec(fix, f); };
+  const auto get = [&](long long f) { return vol_dec(fix, f); };
   for (long long o = (long long)blockIdx.x * TPB + threadIdx.x; o < N; o += (long long)gridDim.x * TPB) {
     const double u[3] = {(double)uin[o], (double)uin[N + o], (double)uin[2 * N + o]};
     double v[3] = {0.0, 0.0, 0.0};
     if (!mask || mask[o] != 0) {
-      const double fv = rs_dec(fix, o);
+      const double fv = vol_dec(fix, o);
       const long long c = o / X;
       const int i = (int)(o - c * X), k = (int)(c / Y), j = (int)(c - (long long)k * Y);
       double s[3];
@@ -146,7 +145,7 @@ __device__ __forceinline__ void wf_coord(const wf_geom& g, int i, int j, int k, 
       q[r] = !(v >= 0.0) ? 0.0 : (v > top ? top : v);                 // mode 0: clamped into the field (a NaN goes to 0)
     }
 #pragma unroll
-    for (int c = 0; c < 3; ++c) u[c] = rs_blend_inside(rs_src{g.field + c * Nf, 16, 0, 1.0, 0.0}, g.Xf, g.Yf, g.Zf, q);
+    for (int c = 0; c < 3; ++c) u[c] = rs_blend_inside(vol_voxels{g.field + c * Nf, 16, 0, 1.0, 0.0}, g.Xf, g.Yf, g.Zf, q);
   }
 #pragma unroll
   for (int r = 0; r < 3; ++r) s[r] = df_displace(rs_coord(g.W, r, i, j, k), g.L, r, u);
@@ -154,7 +153,7 @@ __device__ __forceinline__ void wf_coord(const wf_geom& g, int i, int j, int k, 
 
 template <typename D>
 struct wf_lin {
-  wf_geom g; rs_src src; double cval;
+  wf_geom g; vol_voxels src; double cval;
   __device__ __forceinline__ D operator()(int i, int j, int k, long long o) const {
     double s[3];
     wf_coord(g, i, j, k, o, s);
@@ -182,7 +181,7 @@ __global__ __launch_bounds__(TPB) void wf_kernel(Op op, T* __restrict__ dst, int
 }
 template <typename T, typename Op>
 void wf_launch(const Op& op, void* dst, int X2, int Y2, int Z2, hipStream_t s) {
-  hipLaunchKernelGGL((wf_kernel<T, Op>), dim3(df_blocks((long long)X2 * Y2 * Z2)), dim3(TPB), 0, s, op, static_cast<T*>(dst), X2, Y2, Z2);
+  hipLaunchKernelGGL((wf_kernel<T, Op>), dim3(vol_blocks((long long)X2 * Y2 * Z2, GRID_CAP, TPB)), dim3(TPB), 0, s, op, static_cast<T*>(dst), X2, Y2, Z2);
 }
 
 // ---- the Jacobian determinant: J = I + D inv(A), D[c][a] the index-space difference of u_c along axis a; det by the first row --------------------------------------------
@@ -242,7 +241,7 @@ int32_t unet_vol_smooth_axis(unet_ctx* ctx, const float* src, int32_t C, int32_t
     const long long tiles = ((rows + ROWS - 1) / ROWS) * segs;
     hipLaunchKernelGGL(sm_x_kernel, dim3((unsigned)(tiles > GRID_CAP ? GRID_CAP : tiles)), dim3(TPB), 0, s, src, dst, X, rows, segs, tiles, R, wt);
   } else {
-    hipLaunchKernelGGL(sm_yz_kernel, dim3(df_blocks(C * N)), dim3(TPB), 0, s, src, dst, X, Y, Z, C * N, axis, R, wt);
+    hipLaunchKernelGGL(sm_yz_kernel, dim3(vol_blocks(C * N, GRID_CAP, TPB)), dim3(TPB), 0, s, src, dst, X, Y, Z, C * N, axis, R, wt);
   }
   UNET_CHECK_LAUNCH(ctx, "vol_smooth_axis"); return UNET_OK;
 }
@@ -252,19 +251,19 @@ int32_t unet_vol_demons_step(unet_ctx* ctx, const void* fixed, int32_t f_dtype, 
                              const double* W, const double* L, const double* Ginv, double delta, const float* field_in, float* field_out, void* stream) {
   if (!ctx) return UNET_E_ARG;
   if (!rs_out_ok(X, Y, Z) || !rs_out_ok(Xm, Ym, Zm)) UNET_FAIL(ctx, UNET_E_ARG, "vol_demons_step: a volume of %d x %d x %d and one of %d x %d x %d (every extent is at least 1, fewer than 2^31 voxels)", X, Y, Z, Xm, Ym, Zm);
-  if (rs_itemsize(f_dtype) == 0 || rs_itemsize(m_dtype) == 0) UNET_FAIL(ctx, UNET_E_ARG, "vol_demons_step: a NIfTI datatype code is not one of 2, 256, 4, 512, 8, 768, 16, 64");
+  if (vol_itemsize(f_dtype) == 0 || vol_itemsize(m_dtype) == 0) UNET_FAIL(ctx, UNET_E_ARG, "vol_demons_step: a NIfTI datatype code is not one of 2, 256, 4, 512, 8, 768, 16, 64");
   if (!df_finite(W, 12) || !df_finite(L, 9) || !df_finite(Ginv, 9)) UNET_FAIL(ctx, UNET_E_ARG, "vol_demons_step: W is 12, L and Ginv are 9 finite doubles");
   if (!std::isfinite(delta) || !(delta > 0.0) || !std::isfinite(delta * delta) || !(delta * delta > 0.0))
     UNET_FAIL(ctx, UNET_E_ARG, "vol_demons_step: the step bound is a finite positive number of millimetres whose square is one too");
-  if (!df_aligned(fixed, rs_itemsize(f_dtype)) || !df_aligned(moving, rs_itemsize(m_dtype)) || !df_aligned(field_in, sizeof(float)) || !df_aligned(field_out, sizeof(float)) ||
+  if (!df_aligned(fixed, vol_itemsize(f_dtype)) || !df_aligned(moving, vol_itemsize(m_dtype)) || !df_aligned(field_in, sizeof(float)) || !df_aligned(field_out, sizeof(float)) ||
       field_in == field_out)
     UNET_FAIL(ctx, UNET_E_ARG, "vol_demons_step: a null buffer, one not aligned to its element size, or field_in = field_out");
   dm_geom g{};
   for (int i = 0; i < 12; ++i) g.W.m[i] = W[i];
   for (int i = 0; i < 9; ++i) { g.L.m[i] = L[i]; g.G.m[i] = Ginv[i]; }
   g.delta2 = delta * delta;
-  const rs_src fs{fixed, f_dtype, f_scaled ? 1 : 0, f_slope, f_inter}, ms{moving, m_dtype, m_scaled ? 1 : 0, m_slope, m_inter};
-  hipLaunchKernelGGL(dm_kernel, dim3(df_blocks((long long)X * Y * Z)), dim3(TPB), 0, as_stream(stream), fs, mask, X, Y, Z, ms, Xm, Ym, Zm, g, field_in, field_out);
+  const vol_voxels fs{fixed, f_dtype, f_scaled ? 1 : 0, f_slope, f_inter}, ms{moving, m_dtype, m_scaled ? 1 : 0, m_slope, m_inter};
+  hipLaunchKernelGGL(dm_kernel, dim3(vol_blocks((long long)X * Y * Z, GRID_CAP, TPB)), dim3(TPB), 0, as_stream(stream), fs, mask, X, Y, Z, ms, Xm, Ym, Zm, g, field_in, field_out);
   UNET_CHECK_LAUNCH(ctx, "vol_demons_step"); return UNET_OK;
 }
 
@@ -272,9 +271,9 @@ int32_t unet_vol_warp_field(unet_ctx* ctx, const void* src, int32_t dtype, int32
                             const double* L, const float* field, int32_t Xf, int32_t Yf, int32_t Zf, const double* F, int32_t order, int32_t mode, double cval,
                             uint64_t cval_bits, void* dst, int32_t dst_dtype, int32_t X2, int32_t Y2, int32_t Z2, void* stream) {
   if (!ctx) return UNET_E_ARG;
-  if (!rs_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_warp_field: a source dimension is negative or the source has 2^31 voxels or more");
+  if (!vol_dims_ok_or_empty(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_warp_field: a source dimension is negative or the source has 2^31 voxels or more");
   if (!rs_out_ok(X2, Y2, Z2) || !rs_out_ok(Xf, Yf, Zf)) UNET_FAIL(ctx, UNET_E_ARG, "vol_warp_field: an output of %d x %d x %d and a field of %d x %d x %d (every extent is at least 1, fewer than 2^31 voxels)", X2, Y2, Z2, Xf, Yf, Zf);
-  if (rs_itemsize(dtype) == 0) UNET_FAIL(ctx, UNET_E_ARG, "vol_warp_field: the NIfTI datatype code is not one of 2, 256, 4, 512, 8, 768, 16, 64");
+  if (vol_itemsize(dtype) == 0) UNET_FAIL(ctx, UNET_E_ARG, "vol_warp_field: the NIfTI datatype code is not one of 2, 256, 4, 512, 8, 768, 16, 64");
   if (order < 0 || order > 1) UNET_FAIL(ctx, UNET_E_ARG, "vol_warp_field: order %d is not 0 (nearest) or 1 (linear)", order);
   if (order == 1 && dst_dtype != 64 && dst_dtype != 16 && dst_dtype != 2) UNET_FAIL(ctx, UNET_E_ARG, "vol_warp_field: dst_dtype %d is not 64 (float64), 16 (float32) or 2 (uint8 mask)", dst_dtype);
   if (order == 0 && dst_dtype != dtype) UNET_FAIL(ctx, UNET_E_ARG, "vol_warp_field: order 0 moves the stored elements: dst_dtype %d is not the source's %d", dst_dtype, dtype);
@@ -283,8 +282,8 @@ int32_t unet_vol_warp_field(unet_ctx* ctx, const void* src, int32_t dtype, int32
   if (empty && mode == 0) UNET_FAIL(ctx, UNET_E_ARG, "vol_warp_field: the source has no voxels and mode 0 has no edge to repeat");
   if (!df_finite(W, 12) || !df_finite(L, 9) || (F && !df_finite(F, 12))) UNET_FAIL(ctx, UNET_E_ARG, "vol_warp_field: W and F are 12, L is 9 finite doubles");
   if (!F && (Xf != X2 || Yf != Y2 || Zf != Z2)) UNET_FAIL(ctx, UNET_E_ARG, "vol_warp_field: without F the field lies on the output grid, and %d x %d x %d is not %d x %d x %d", Xf, Yf, Zf, X2, Y2, Z2);
-  const size_t out_size = order == 0 ? rs_itemsize(dtype) : rs_itemsize(dst_dtype);
-  if ((!empty && !df_aligned(src, rs_itemsize(dtype))) || !df_aligned(field, sizeof(float)) || !df_aligned(dst, out_size))
+  const size_t out_size = order == 0 ? vol_itemsize(dtype) : vol_itemsize(dst_dtype);
+  if ((!empty && !df_aligned(src, vol_itemsize(dtype))) || !df_aligned(field, sizeof(float)) || !df_aligned(dst, out_size))
     UNET_FAIL(ctx, UNET_E_ARG, "vol_warp_field: a null buffer, or one not aligned to its element size");
   wf_geom g{};
   for (int i = 0; i < 12; ++i) { g.W.m[i] = W[i]; g.F.m[i] = F ? F[i] : 0.0; }
@@ -293,14 +292,14 @@ int32_t unet_vol_warp_field(unet_ctx* ctx, const void* src, int32_t dtype, int32
   g.X = X; g.Y = Y; g.Z = Z; g.mode = mode;
   hipStream_t s = as_stream(stream);
   if (order == 1) {
-    const rs_src sv{src, dtype, scaled ? 1 : 0, slope, inter};
+    const vol_voxels sv{src, dtype, scaled ? 1 : 0, slope, inter};
     switch (dst_dtype) {
       case 64: wf_launch<double>(wf_lin<double>{g, sv, cval}, dst, X2, Y2, Z2, s); break;
       case 16: wf_launch<float>(wf_lin<float>{g, sv, cval}, dst, X2, Y2, Z2, s); break;
       default: wf_launch<uint8_t>(wf_lin<uint8_t>{g, sv, cval}, dst, X2, Y2, Z2, s); break;
     }
   } else {
-    switch (rs_itemsize(dtype)) {
+    switch (vol_itemsize(dtype)) {
       case 1: wf_launch<uint8_t>(wf_near<uint8_t>{g, static_cast<const uint8_t*>(src), (uint8_t)cval_bits}, dst, X2, Y2, Z2, s); break;
       case 2: wf_launch<uint16_t>(wf_near<uint16_t>{g, static_cast<const uint16_t*>(src), (uint16_t)cval_bits}, dst, X2, Y2, Z2, s); break;
       case 4: wf_launch<uint32_t>(wf_near<uint32_t>{g, static_cast<const uint32_t*>(src), (uint32_t)cval_bits}, dst, X2, Y2, Z2, s); break;
@@ -320,7 +319,7 @@ int32_t unet_vol_jacobian(unet_ctx* ctx, const float* field, int32_t X, int32_t 
   for (int i = 0; i < 9; ++i) Ai.m[i] = Ainv[i];
   hipStream_t s = as_stream(stream);
   UNET_HIP(ctx, hipMemsetAsync(folded, 0, sizeof(uint32_t), s));
-  hipLaunchKernelGGL(jc_kernel, dim3(df_blocks((long long)X * Y * Z)), dim3(TPB), 0, s, field, X, Y, Z, Ai, det, folded);
+  hipLaunchKernelGGL(jc_kernel, dim3(vol_blocks((long long)X * Y * Z, GRID_CAP, TPB)), dim3(TPB), 0, s, field, X, Y, Z, Ai, det, folded);
   UNET_CHECK_LAUNCH(ctx, "vol_jacobian"); return UNET_OK;
 }
 

@@ -7,23 +7,12 @@
 // Copies, integer sums and float32 operations that numpy performs one at a time: bit-exact against tests/ensemble_oracle.py, the same on every run.
 // Compiled with -ffp-contract=off (csrc/Makefile), and the mean spells its roundings out (__fmul_rn, __fadd_rn, __fdiv_rn): no product is fused into a sum.
 #include "common.h"
+#include "vol_common.h"
 #include "vol_sample.h"
 
 namespace {
 constexpr int TPB = 256;
 typedef unsigned long long u64;
-
-inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
-inline bool overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-  return x < y + nb && y < x + na;
-}
-inline unsigned ens_blocks(long long items, int cap) { long long b = (items + TPB - 1) / TPB; return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b)); }
-inline bool ens_dims_ok(int X, int Y, int Z) {                     // X Y Z < 2^31, without overflowing on the way: X Y < 2^62 always, and it is compared before Z multiplies it
-  if (X < 0 || Y < 0 || Z < 0) return false;
-  const long long xy = (long long)X * Y;
-  return xy == 0 || Z == 0 || (xy < 0x80000000LL && xy * Z < 0x80000000LL);
-}
 
 // ---- the eight symmetries of the square: dst[i][j] = src[si][sj] ---------------------------------------------------------------------------------
 // codes 0, 2, 4, 5 keep rows as rows: si = (flip_i ? d - 1 - i : i), sj = (flip_j ? d - 1 - j : j): both sides run along a row (backwards at worst)
@@ -229,14 +218,14 @@ int32_t unet_vol_dihedral(unet_ctx* ctx, const float* src, int32_t n, int32_t d,
   if (n < 0 || d < 0 || (long long)d * d > 0x3FFFFFFFLL) UNET_FAIL(ctx, UNET_E_ARG, "vol_dihedral: %d slices of %d x %d are negative or too large", n, d, d);
   const long long total = (long long)n * d * d;
   if (total == 0) return UNET_OK;
-  if (!src || !dst || !aligned(src, 4) || !aligned(dst, 4)) UNET_FAIL(ctx, UNET_E_ARG, "vol_dihedral: null or misaligned buffer");
-  if (overlap(src, (size_t)total * 4, dst, (size_t)total * 4)) UNET_FAIL(ctx, UNET_E_ARG, "vol_dihedral: dst must not be (or overlap) src");
+  if (!src || !dst || !vol_aligned(src, 4) || !vol_aligned(dst, 4)) UNET_FAIL(ctx, UNET_E_ARG, "vol_dihedral: null or misaligned buffer");
+  if (vol_overlap(src, (size_t)total * 4, dst, (size_t)total * 4)) UNET_FAIL(ctx, UNET_E_ARG, "vol_dihedral: dst must not be (or overlap) src");
   hipStream_t s = as_stream(stream);
   const dih_map m = dih_code(code);
   const uint32_t* in = reinterpret_cast<const uint32_t*>(src);
   uint32_t* out = reinterpret_cast<uint32_t*>(dst);
   if (!m.transposed) {
-    hipLaunchKernelGGL(dih_rows_kernel, dim3(ens_blocks(total, 2048)), dim3(TPB), 0, s, in, total, d, m.flip_a, m.flip_b, out);
+    hipLaunchKernelGGL(dih_rows_kernel, dim3(vol_blocks(total, 2048, TPB)), dim3(TPB), 0, s, in, total, d, m.flip_a, m.flip_b, out);
   } else {
     const unsigned tiles = (unsigned)((d + DIH_TILE - 1) / DIH_TILE);
     if (tiles > 65535u) UNET_FAIL(ctx, UNET_E_ARG, "vol_dihedral: %d x %d is too large for the transposing codes", d, d);
@@ -248,37 +237,37 @@ int32_t unet_vol_dihedral(unet_ctx* ctx, const float* src, int32_t n, int32_t d,
 int32_t unet_vol_canvas_axpy(unet_ctx* ctx, const float* canvas, float w, float* acc, int64_t count, int32_t first, void* stream) {
   if (!ctx || count < 0) UNET_FAIL(ctx, UNET_E_ARG, "vol_canvas_axpy: bad args");
   if (count == 0) return UNET_OK;
-  if (!canvas || !acc || !aligned(canvas, 4) || !aligned(acc, 4)) UNET_FAIL(ctx, UNET_E_ARG, "vol_canvas_axpy: null or misaligned buffer");
-  if (overlap(canvas, (size_t)count * 4, acc, (size_t)count * 4)) UNET_FAIL(ctx, UNET_E_ARG, "vol_canvas_axpy: acc must not be (or overlap) the canvas");
+  if (!canvas || !acc || !vol_aligned(canvas, 4) || !vol_aligned(acc, 4)) UNET_FAIL(ctx, UNET_E_ARG, "vol_canvas_axpy: null or misaligned buffer");
+  if (vol_overlap(canvas, (size_t)count * 4, acc, (size_t)count * 4)) UNET_FAIL(ctx, UNET_E_ARG, "vol_canvas_axpy: acc must not be (or overlap) the canvas");
   hipStream_t s = as_stream(stream);
-  if ((count % 4) == 0 && aligned(canvas, 16) && aligned(acc, 16))
-    hipLaunchKernelGGL(canvas_axpy_kernel<4>, dim3(ens_blocks(count / 4, 2048)), dim3(TPB), 0, s, canvas, w, acc, (long long)count, first ? 1 : 0);
+  if ((count % 4) == 0 && vol_aligned(canvas, 16) && vol_aligned(acc, 16))
+    hipLaunchKernelGGL(canvas_axpy_kernel<4>, dim3(vol_blocks(count / 4, 2048, TPB)), dim3(TPB), 0, s, canvas, w, acc, (long long)count, first ? 1 : 0);
   else
-    hipLaunchKernelGGL(canvas_axpy_kernel<1>, dim3(ens_blocks(count, 2048)), dim3(TPB), 0, s, canvas, w, acc, (long long)count, first ? 1 : 0);
+    hipLaunchKernelGGL(canvas_axpy_kernel<1>, dim3(vol_blocks(count, 2048, TPB)), dim3(TPB), 0, s, canvas, w, acc, (long long)count, first ? 1 : 0);
   UNET_CHECK_LAUNCH(ctx, "vol_canvas_axpy"); return UNET_OK;
 }
 
 int32_t unet_vol_canvas_div(unet_ctx* ctx, float* acc, float denom, int64_t count, void* stream) {
   if (!ctx || count < 0) UNET_FAIL(ctx, UNET_E_ARG, "vol_canvas_div: bad args");
   if (count == 0) return UNET_OK;
-  if (!acc || !aligned(acc, 4)) UNET_FAIL(ctx, UNET_E_ARG, "vol_canvas_div: null or misaligned buffer");
+  if (!acc || !vol_aligned(acc, 4)) UNET_FAIL(ctx, UNET_E_ARG, "vol_canvas_div: null or misaligned buffer");
   hipStream_t s = as_stream(stream);
-  if ((count % 4) == 0 && aligned(acc, 16)) hipLaunchKernelGGL(canvas_div_kernel<4>, dim3(ens_blocks(count / 4, 2048)), dim3(TPB), 0, s, acc, denom, (long long)count);
-  else hipLaunchKernelGGL(canvas_div_kernel<1>, dim3(ens_blocks(count, 2048)), dim3(TPB), 0, s, acc, denom, (long long)count);
+  if ((count % 4) == 0 && vol_aligned(acc, 16)) hipLaunchKernelGGL(canvas_div_kernel<4>, dim3(vol_blocks(count / 4, 2048, TPB)), dim3(TPB), 0, s, acc, denom, (long long)count);
+  else hipLaunchKernelGGL(canvas_div_kernel<1>, dim3(vol_blocks(count, 2048, TPB)), dim3(TPB), 0, s, acc, denom, (long long)count);
   UNET_CHECK_LAUNCH(ctx, "vol_canvas_div"); return UNET_OK;
 }
 
 int32_t unet_vol_unslice_prob(unet_ctx* ctx, const float* canvas, int32_t S, int32_t X, int32_t Y, int32_t Z, int32_t z0, int32_t z1, float* prob, void* stream) {
   if (!ctx) UNET_FAIL(ctx, UNET_E_ARG, "vol_unslice_prob: bad args");
-  if (!ens_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_unslice_prob: %d x %d x %d is negative or has 2^31 voxels or more", X, Y, Z);
+  if (!vol_dims_ok_or_empty(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_unslice_prob: %d x %d x %d is negative or has 2^31 voxels or more", X, Y, Z);
   if (X == 0 || Y == 0 || Z == 0) return UNET_OK;
-  if (!canvas || !prob || !aligned(canvas, 4) || !aligned(prob, 4) || S < 1 || (long long)S * S > 0x3FFFFFFFLL) UNET_FAIL(ctx, UNET_E_ARG, "vol_unslice_prob: bad args");
+  if (!canvas || !prob || !vol_aligned(canvas, 4) || !vol_aligned(prob, 4) || S < 1 || (long long)S * S > 0x3FFFFFFFLL) UNET_FAIL(ctx, UNET_E_ARG, "vol_unslice_prob: bad args");
   if (z0 < 0 || z1 > Z || z1 <= z0) UNET_FAIL(ctx, UNET_E_ARG, "vol_unslice_prob: slice range [%d, %d) is empty or leaves the %d slices", z0, z1, Z);
   const int n = z1 - z0;
   hipStream_t s = as_stream(stream);
   UNET_HIP(ctx, hipMemsetAsync(prob, 0, (size_t)X * Y * Z * sizeof(float), s));                   // the trimmed slices stay 0
-  if ((X % 4) == 0 && aligned(prob, 16)) hipLaunchKernelGGL(vol_unslice_prob_kernel<4>, dim3(ens_blocks((long long)(X / 4) * Y, 256), n), dim3(TPB), 0, s, canvas, S, X, Y, z0, prob);
-  else hipLaunchKernelGGL(vol_unslice_prob_kernel<1>, dim3(ens_blocks((long long)X * Y, 1024), n), dim3(TPB), 0, s, canvas, S, X, Y, z0, prob);
+  if ((X % 4) == 0 && vol_aligned(prob, 16)) hipLaunchKernelGGL(vol_unslice_prob_kernel<4>, dim3(vol_blocks((long long)(X / 4) * Y, 256, TPB), n), dim3(TPB), 0, s, canvas, S, X, Y, z0, prob);
+  else hipLaunchKernelGGL(vol_unslice_prob_kernel<1>, dim3(vol_blocks((long long)X * Y, 1024, TPB), n), dim3(TPB), 0, s, canvas, S, X, Y, z0, prob);
   UNET_CHECK_LAUNCH(ctx, "vol_unslice_prob"); return UNET_OK;
 }
 
@@ -286,13 +275,13 @@ int32_t unet_vol_vote_pack(unet_ctx* ctx, const uint8_t* mask, int32_t member, i
   if (!ctx || nvox < 0) UNET_FAIL(ctx, UNET_E_ARG, "vol_vote_pack: bad args");
   if (member < 0 || member > 31) UNET_FAIL(ctx, UNET_E_ARG, "vol_vote_pack: member %d is not one of 0..31", member);
   if (nvox == 0) return UNET_OK;
-  if (!mask || !words || !aligned(words, 4)) UNET_FAIL(ctx, UNET_E_ARG, "vol_vote_pack: null or misaligned buffer");
-  if (overlap(mask, (size_t)nvox, words, (size_t)nvox * 4)) UNET_FAIL(ctx, UNET_E_ARG, "vol_vote_pack: the words must not overlap the mask");
+  if (!mask || !words || !vol_aligned(words, 4)) UNET_FAIL(ctx, UNET_E_ARG, "vol_vote_pack: null or misaligned buffer");
+  if (vol_overlap(mask, (size_t)nvox, words, (size_t)nvox * 4)) UNET_FAIL(ctx, UNET_E_ARG, "vol_vote_pack: the words must not overlap the mask");
   hipStream_t s = as_stream(stream);
-  if ((nvox % 4) == 0 && aligned(mask, 4) && aligned(words, 16))
-    hipLaunchKernelGGL(vote_pack_kernel<4>, dim3(ens_blocks(nvox / 4, 2048)), dim3(TPB), 0, s, mask, member, first ? 1 : 0, words, (long long)nvox);
+  if ((nvox % 4) == 0 && vol_aligned(mask, 4) && vol_aligned(words, 16))
+    hipLaunchKernelGGL(vote_pack_kernel<4>, dim3(vol_blocks(nvox / 4, 2048, TPB)), dim3(TPB), 0, s, mask, member, first ? 1 : 0, words, (long long)nvox);
   else
-    hipLaunchKernelGGL(vote_pack_kernel<1>, dim3(ens_blocks(nvox, 2048)), dim3(TPB), 0, s, mask, member, first ? 1 : 0, words, (long long)nvox);
+    hipLaunchKernelGGL(vote_pack_kernel<1>, dim3(vol_blocks(nvox, 2048, TPB)), dim3(TPB), 0, s, mask, member, first ? 1 : 0, words, (long long)nvox);
   UNET_CHECK_LAUNCH(ctx, "vol_vote_pack"); return UNET_OK;
 }
 
@@ -301,20 +290,20 @@ int32_t unet_vol_vote_reduce(unet_ctx* ctx, const uint32_t* words, int32_t M, in
   if (!ctx) UNET_FAIL(ctx, UNET_E_ARG, "vol_vote_reduce: bad args");
   if (M < 1 || M > 32) UNET_FAIL(ctx, UNET_E_ARG, "vol_vote_reduce: %d members are outside 1..32", M);
   if (min_votes < 1 || min_votes > M) UNET_FAIL(ctx, UNET_E_ARG, "vol_vote_reduce: min_votes %d is outside 1..%d", min_votes, M);
-  if (!ens_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_vote_reduce: %d x %d x %d is negative or has 2^31 voxels or more", X, Y, Z);
+  if (!vol_dims_ok_or_empty(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_vote_reduce: %d x %d x %d is negative or has 2^31 voxels or more", X, Y, Z);
   const long long N = (long long)X * Y * Z;                         // (< 2^31: checked above)
   if (N == 0) return UNET_OK;
   if (!words || !mask || !counts || !member_voxels || !pair || !hist) UNET_FAIL(ctx, UNET_E_ARG, "vol_vote_reduce: null buffer");
-  if (!aligned(words, 4) || !aligned(counts, 8) || !aligned(member_voxels, 8) || !aligned(pair, 8) || !aligned(hist, 8))
+  if (!vol_aligned(words, 4) || !vol_aligned(counts, 8) || !vol_aligned(member_voxels, 8) || !vol_aligned(pair, 8) || !vol_aligned(hist, 8))
     UNET_FAIL(ctx, UNET_E_ARG, "vol_vote_reduce: misaligned buffer (words 4 bytes, the int64 outputs 8)");
-  if (overlap(words, (size_t)N * 4, mask, (size_t)N) || (votes && (overlap(words, (size_t)N * 4, votes, (size_t)N) || overlap(mask, (size_t)N, votes, (size_t)N))))
+  if (vol_overlap(words, (size_t)N * 4, mask, (size_t)N) || (votes && (vol_overlap(words, (size_t)N * 4, votes, (size_t)N) || vol_overlap(mask, (size_t)N, votes, (size_t)N))))
     UNET_FAIL(ctx, UNET_E_ARG, "vol_vote_reduce: words, mask and votes must not overlap");
   hipStream_t s = as_stream(stream);
   UNET_HIP(ctx, hipMemsetAsync(counts, 0, (size_t)Z * sizeof(int64_t), s));
   UNET_HIP(ctx, hipMemsetAsync(pair, 0, (size_t)M * M * sizeof(int64_t), s));
   UNET_HIP(ctx, hipMemsetAsync(hist, 0, (size_t)(M + 1) * sizeof(int64_t), s));
   const int XY = X * Y;
-  const unsigned gx = ens_blocks(XY, 256);
+  const unsigned gx = vol_blocks(XY, 256, TPB);
   const unsigned gy_cap = 2048u / gx;                                 // at most 2048 workgroups: 8 per CU
   const unsigned gy = (unsigned)Z < gy_cap ? (unsigned)Z : gy_cap;
   hipLaunchKernelGGL(vote_reduce_kernel, dim3(gx, gy), dim3(TPB), 0, s, words, M, XY, Z, min_votes, mask, votes, reinterpret_cast<u64*>(counts), reinterpret_cast<u64*>(pair),

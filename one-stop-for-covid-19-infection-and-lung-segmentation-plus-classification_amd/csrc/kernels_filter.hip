@@ -13,6 +13,7 @@
 // fast at the 27-box median as re-reading the brick every round); larger footprints, and the end ranks, which read every key once anyway, count from the staged brick.
 // One launch, no atomics, no workgroup waits for another, every voxel written by one lane: the same bits on every run.
 #include "common.h"
+#include "vol_common.h"
 
 namespace {
 constexpr int TPB = 256;
@@ -31,9 +32,7 @@ template <> struct rf_elem<1> { using type = uint8_t; };
 template <> struct rf_elem<2> { using type = uint16_t; };
 template <> struct rf_elem<4> { using type = uint32_t; };
 
-inline int rf_itemsize(int dt) {
-  switch (dt) { case 2: case 256: return 1; case 4: case 512: return 2; case 8: case 768: case 16: return 4; default: return 0; }          // (64 is refused)
-}
+inline int rf_itemsize(int dt) { return dt == 64 ? 0 : vol_itemsize(dt); }          // (float64 is refused: the keys are 32 bits)
 inline uint32_t rf_flip(int dt) { return dt == 256 ? 0x80u : dt == 4 ? 0x8000u : dt == 8 ? 0x80000000u : 0u; }
 // stored bits <-> key (flip: the sign bit of a signed integer type, 0 for an unsigned one)
 __host__ __device__ __forceinline__ uint32_t rf_key(uint32_t raw, uint32_t flip, int is_float) {
@@ -161,7 +160,7 @@ extern "C" {
 int32_t unet_vol_rank_filter(unet_ctx* ctx, const void* src, int32_t dtype, int32_t X, int32_t Y, int32_t Z, int32_t R, uint64_t fp_lo, uint64_t fp_hi, int32_t rank,
                              int32_t mode, uint64_t cval_bits, void* dst, void* stream) {
   if (!ctx) return UNET_E_ARG;
-  if (X < 0 || Y < 0 || Z < 0 || (long long)X * Y * Z >= 0x80000000LL || (X != 0 && Y != 0 && (long long)X * Y >= 0x80000000LL))
+  if (!vol_dims_ok(X, Y, Z))
     UNET_FAIL(ctx, UNET_E_ARG, "vol_rank_filter: a dimension is negative or the volume has 2^31 voxels or more");
   const int eb = rf_itemsize(dtype);
   if (eb == 0) UNET_FAIL(ctx, UNET_E_ARG, "vol_rank_filter: the NIfTI datatype code is not one of 2, 256, 4, 512, 8, 768, 16 (64 is not taken: ask for float32)");

@@ -12,6 +12,7 @@
 // The moments are a fixed tree over a canonical order (see include/unet_hip.h): 256-element chunks summed left to right by one lane each, the chunk sums left to right by
 // one lane per group; no floating-point atomics.  Compiled with -ffp-contract=off: d d + acc must round twice.
 #include "common.h"
+#include "vol_common.h"
 
 #include <cmath>
 
@@ -25,43 +26,6 @@ constexpr int IB_GRID = 256 * 4;                                     // workgrou
 constexpr long long GRID_CAP = 256 * 32;
 constexpr int MOM_CHUNK = 256;                                       // elements per partial sum of unet_vol_group_moments
 
-inline bool iv_dims_ok(int X, int Y, int Z) { return X >= 0 && Y >= 0 && Z >= 0 && (long long)X * Y * Z < 0x80000000LL && (X == 0 || Y == 0 || (long long)X * Y < 0x80000000LL); }
-inline unsigned iv_blocks(long long items, long long cap) { long long b = (items + TPB - 1) / TPB; return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b)); }
-inline int iv_itemsize(int dt) {
-  switch (dt) { case 2: case 256: return 1; case 4: case 512: return 2; case 8: case 768: case 16: return 4; case 64: return 8; default: return 0; }
-}
-
-// ---- typed voxel access: kernels_volume.hip's vol_raw / vol_dec (NIfTI-1 datatype codes; (float64(v) * slope) + inter, two rounded operations) ----------------
-struct iv_src { const void* p; int dt; int scaled; double slope, inter; };
-__device__ __forceinline__ double iv_dec(const iv_src& s, long long i) {
-  double v;
-  switch (s.dt) {                                                     // (wave-uniform: one datatype per launch)
-    case 2: v = (double)static_cast<const uint8_t*>(s.p)[i]; break;
-    case 256: v = (double)static_cast<const int8_t*>(s.p)[i]; break;
-    case 4: v = (double)static_cast<const int16_t*>(s.p)[i]; break;
-    case 512: v = (double)static_cast<const uint16_t*>(s.p)[i]; break;
-    case 8: v = (double)static_cast<const int32_t*>(s.p)[i]; break;
-    case 768: v = (double)static_cast<const uint32_t*>(s.p)[i]; break;
-    case 16: v = (double)static_cast<const float*>(s.p)[i]; break;
-    default: v = static_cast<const double*>(s.p)[i]; break;           // 64
-  }
-  return s.scaled ? __dadd_rn(__dmul_rn(v, s.slope), s.inter) : v;
-}
-// the group of voxel i: 1..n, or 0 when it takes no part.  A label outside 1..n is ignored, never an address.
-struct iv_groups { const int32_t* labels; const uint8_t* mask; const uint8_t* region; int n; };
-__device__ __forceinline__ int iv_group(const iv_groups& g, long long i) {
-  if (g.region && g.region[i] == 0) return 0;
-  const int l = g.labels ? g.labels[i] : (g.mask[i] ? 1 : 0);
-  return (unsigned)(l - 1) < (unsigned)g.n ? l : 0;
-}
-
-// order-preserving keys of the doubles (-0.0 below +0.0); no non-NaN value maps to ~0 or to 0, the two "nothing seen" marks
-__device__ __forceinline__ unsigned long long iv_d2ord(double d) {
-  const unsigned long long u = (unsigned long long)__double_as_longlong(d);
-  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double iv_ord2d(unsigned long long o) { return __longlong_as_double((long long)((o >> 63) ? (o & 0x7FFFFFFFFFFFFFFFull) : ~o)); }
-
 struct iv_edges { double e[MAX_EDGES]; int n; };
 
 // ---- (a) bands ------------------------------------------------------------------------------------------------------------------------------------
@@ -74,15 +38,15 @@ __global__ void ib_minmax_final_kernel(unsigned long long* __restrict__ keys, in
   if (i >= n) return;
   const unsigned long long a = keys[2 * i], b = keys[2 * i + 1];
   double* out = reinterpret_cast<double*>(keys);
-  out[2 * i] = a == ~0ull ? __longlong_as_double(0x7FF0000000000000ll) : iv_ord2d(a);
-  out[2 * i + 1] = b == 0ull ? __longlong_as_double((long long)0xFFF0000000000000ull) : iv_ord2d(b);
+  out[2 * i] = a == ~0ull ? __longlong_as_double(0x7FF0000000000000ll) : vol_ord2d(a);
+  out[2 * i + 1] = b == 0ull ? __longlong_as_double((long long)0xFFF0000000000000ull) : vol_ord2d(b);
 }
 
 // LDS_TABLE: the (group, band) counters and the min / max keys of this workgroup live in LDS and leave it once, at the end; otherwise every add goes to the output.
 // Chunk c of the launch = IB_CHUNK voxels of one slice (cps chunks per slice); workgroup b walks chunks [b per, (b + 1) per): the slice changes rarely, and the per-slice
 // counters leave LDS when it does.  Every loop bound and every barrier below is uniform over the workgroup.
 template <bool LDS_TABLE>
-__global__ __launch_bounds__(TPB) void ib_bands_kernel(iv_src src, iv_groups grp, iv_edges ed, long long XY, int Z, int cps, long long per,
+__global__ __launch_bounds__(TPB) void ib_bands_kernel(vol_voxels src, vol_groups grp, iv_edges ed, long long XY, int Z, int cps, long long per,
                                                       unsigned long long* __restrict__ band_counts, unsigned long long* __restrict__ slice_counts,
                                                       unsigned long long* __restrict__ minmax) {
   __shared__ int s_tab[LDS_TABLE ? IB_TABLE : 1];
@@ -104,18 +68,18 @@ __global__ __launch_bounds__(TPB) void ib_bands_kernel(iv_src src, iv_groups grp
     const long long i0 = (c - (long long)z * cps) * IB_CHUNK, base = (long long)z * XY;
     for (int k = 0; k < IB_CHUNK / TPB; ++k) {
       const long long i = i0 + (long long)k * TPB + tid;
-      const int g = i < XY ? iv_group(grp, base + i) : 0;
+      const int g = i < XY ? vol_group(grp, base + i) : 0;
       unsigned long long pending = __ballot(g != 0);
       if (!pending) continue;                                         // wave-uniform: most waves of a CT lie outside every lesion and never read a voxel
       long long key = -1;                                             // (g - 1) W + band: n W may pass 2^31 beyond the LDS table
       if (g) {
-        const double v = iv_dec(src, base + i);
+        const double v = vol_dec(src, base + i);
         int band = ed.n + 1;                                          // NaN
         if (v == v) {
           band = 0;
           for (int e = 0; e < ed.n; ++e) band += ed.e[e] <= v ? 1 : 0;          // the number of edges <= v
           if (want_mm) {
-            const unsigned long long o = iv_d2ord(v);
+            const unsigned long long o = vol_d2ord(v);
             if constexpr (LDS_TABLE) {
               unsigned long long* q = s_mm + 2 * (g - 1);
               if (o < __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) atomicMin(q, o);
@@ -164,16 +128,16 @@ __global__ __launch_bounds__(TPB) void ib_bands_kernel(iv_src src, iv_groups grp
 }
 
 // ---- (b) gather: one slot range per wave from a ballot, one atomic by its first taking-part lane -----------------------------------------------------------
-__global__ __launch_bounds__(TPB) void ig_gather_kernel(iv_src src, iv_groups grp, long long N, long long cap, double* __restrict__ values, int32_t* __restrict__ groups,
+__global__ __launch_bounds__(TPB) void ig_gather_kernel(vol_voxels src, vol_groups grp, long long N, long long cap, double* __restrict__ values, int32_t* __restrict__ groups,
                                                        unsigned long long* __restrict__ count) {
   const int lane = threadIdx.x & 63;
   for (long long i0 = (long long)blockIdx.x * TPB + (threadIdx.x - lane); i0 < N; i0 += (long long)gridDim.x * TPB) {          // wave-uniform trip count
     const long long i = i0 + lane;
-    const int g = i < N ? iv_group(grp, i) : 0;
+    const int g = i < N ? vol_group(grp, i) : 0;
     if (!__ballot(g != 0)) continue;
     double v = 0.0;
     bool take = false;
-    if (g) { v = iv_dec(src, i); take = v == v; }
+    if (g) { v = vol_dec(src, i); take = v == v; }
     const unsigned long long m = __ballot(take);
     if (!m) continue;
     const int leader = __ffsll((long long)m) - 1;
@@ -227,8 +191,8 @@ __global__ __launch_bounds__(TPB) void mom_fold_kernel(const long long* __restri
 
 // the checks the two volume entry points share -> 0, or the message of the refusal
 const char* iv_refusal(int dtype, int X, int Y, int Z, const void* labels, const void* mask, int n) {
-  if (!iv_dims_ok(X, Y, Z)) return "a dimension is negative or the volume has 2^31 voxels or more";
-  if (iv_itemsize(dtype) == 0) return "the NIfTI datatype code is not one of 2, 256, 4, 512, 8, 768, 16, 64";
+  if (!vol_dims_ok(X, Y, Z)) return "a dimension is negative or the volume has 2^31 voxels or more";
+  if (vol_itemsize(dtype) == 0) return "the NIfTI datatype code is not one of 2, 256, 4, 512, 8, 768, 16, 64";
   if ((labels != nullptr) == (mask != nullptr)) return "exactly one of labels and mask is given";
   if (n < 0) return "n is negative";
   return nullptr;
@@ -252,7 +216,7 @@ int32_t unet_vol_intensity_bands(unet_ctx* ctx, const void* vox, int32_t dtype, 
       (reinterpret_cast<uintptr_t>(minmax) % 8) != 0)
     UNET_FAIL(ctx, UNET_E_ARG, "vol_intensity_bands: null or misaligned output");
   const long long XY = (long long)X * Y, N = XY * Z;
-  if (N > 0 && (!vox || (reinterpret_cast<uintptr_t>(vox) % iv_itemsize(dtype)) != 0 || (labels && (reinterpret_cast<uintptr_t>(labels) % 4) != 0)))
+  if (N > 0 && (!vox || (reinterpret_cast<uintptr_t>(vox) % vol_itemsize(dtype)) != 0 || (labels && (reinterpret_cast<uintptr_t>(labels) % 4) != 0)))
     UNET_FAIL(ctx, UNET_E_ARG, "vol_intensity_bands: null voxel buffer, or a buffer not aligned to its item size");
   hipStream_t s = as_stream(stream);
   const int W = n_edges + 2;
@@ -261,8 +225,8 @@ int32_t unet_vol_intensity_bands(unet_ctx* ctx, const void* vox, int32_t dtype, 
   unsigned long long* keys = reinterpret_cast<unsigned long long*>(minmax);
   if (minmax && n > 0) hipLaunchKernelGGL(ib_minmax_init_kernel, dim3((n + TPB - 1) / TPB), dim3(TPB), 0, s, keys, n);
   if (N > 0 && n > 0) {
-    const iv_src src{vox, dtype, scaled ? 1 : 0, slope, inter};
-    const iv_groups grp{labels, mask, region, n};
+    const vol_voxels src{vox, dtype, scaled ? 1 : 0, slope, inter};
+    const vol_groups grp{labels, mask, region, n};
     const int cps = (int)((XY + IB_CHUNK - 1) / IB_CHUNK);
     const long long chunks = (long long)cps * Z;
     const long long per = (chunks + IB_GRID - 1) / IB_GRID;
@@ -287,14 +251,14 @@ int32_t unet_vol_intensity_gather(unet_ctx* ctx, const void* vox, int32_t dtype,
       (reinterpret_cast<uintptr_t>(groups) % 4) != 0)
     UNET_FAIL(ctx, UNET_E_ARG, "vol_intensity_gather: null or misaligned output, or a negative capacity");
   const long long N = (long long)X * Y * Z;
-  if (N > 0 && (!vox || (reinterpret_cast<uintptr_t>(vox) % iv_itemsize(dtype)) != 0 || (labels && (reinterpret_cast<uintptr_t>(labels) % 4) != 0)))
+  if (N > 0 && (!vox || (reinterpret_cast<uintptr_t>(vox) % vol_itemsize(dtype)) != 0 || (labels && (reinterpret_cast<uintptr_t>(labels) % 4) != 0)))
     UNET_FAIL(ctx, UNET_E_ARG, "vol_intensity_gather: null voxel buffer, or a buffer not aligned to its item size");
   hipStream_t s = as_stream(stream);
   UNET_HIP(ctx, hipMemsetAsync(count, 0, sizeof(int64_t), s));
   if (N == 0 || n == 0) return UNET_OK;
-  const iv_src src{vox, dtype, scaled ? 1 : 0, slope, inter};
-  const iv_groups grp{labels, mask, region, n};
-  hipLaunchKernelGGL(ig_gather_kernel, dim3(iv_blocks(N, GRID_CAP)), dim3(TPB), 0, s, src, grp, N, (long long)capacity, values, groups,
+  const vol_voxels src{vox, dtype, scaled ? 1 : 0, slope, inter};
+  const vol_groups grp{labels, mask, region, n};
+  hipLaunchKernelGGL(ig_gather_kernel, dim3(vol_blocks(N, GRID_CAP, TPB)), dim3(TPB), 0, s, src, grp, N, (long long)capacity, values, groups,
                      reinterpret_cast<unsigned long long*>(count));
   UNET_CHECK_LAUNCH(ctx, "vol_intensity_gather"); return UNET_OK;
 }
@@ -316,7 +280,7 @@ int32_t unet_vol_group_moments(unet_ctx* ctx, const double* values, const int64_
   double* partial = mean + n;
   const long long slot_cap = (long long)(ws_bytes / sizeof(double)) - n;          // nothing is written past the workspace whatever the offsets say
   const long long* off = reinterpret_cast<const long long*>(offsets);
-  const unsigned gc = iv_blocks(slot_cap, GRID_CAP), gf = (unsigned)((n + TPB - 1) / TPB);
+  const unsigned gc = vol_blocks(slot_cap, GRID_CAP, TPB), gf = (unsigned)((n + TPB - 1) / TPB);
   hipLaunchKernelGGL(mom_chunk_kernel<false>, dim3(gc), dim3(TPB), 0, s, values, off, n, mean, partial, slot_cap);
   hipLaunchKernelGGL(mom_fold_kernel<false>, dim3(gf), dim3(TPB), 0, s, off, n, partial, slot_cap, mean, out);
   hipLaunchKernelGGL(mom_chunk_kernel<true>, dim3(gc), dim3(TPB), 0, s, values, off, n, mean, partial, slot_cap);

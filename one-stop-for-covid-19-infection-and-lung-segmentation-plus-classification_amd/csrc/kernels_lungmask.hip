@@ -8,7 +8,7 @@
 // (double(raw) * slope) + inter as two rounded operations (-ffp-contract=off); a NaN satisfies neither edge and gives 0.  The slice counts: popcounts (a ballot in the
 // one-voxel form), summed per wave by butterflies and per workgroup in LDS, leave as one 64-bit integer atomic per workgroup and trip while the workgroup's voxels lie
 // in one slice, and voxel by voxel where a workgroup straddles slices (slices smaller than a trip).  Integer sums: the same bits on every run.
-// Growth: kernels_morph.hip's packed layout -- word wi of row (y, z) holds the voxels x = 64 wi .. 64 wi + 63, bit b voxel 64 wi + b, rows padded to words.  The
+// Growth: vol_common.h's packed layout (vol_bits: one bit per voxel along x, rows padded to 64-bit words; a set holds no bit at or beyond X).  The
 // workspace holds four packed volumes: the constraint C, the reached set R and two frontiers F[0], F[1]; step s reads F[(s - 1) & 1] and writes F[s & 1].
 //   gd_begin_kernel   bytes -> bits of C and of S = seeds & C (16 voxels per lane, four lanes make a word), R = F[0] = S, arrival = 0 on S and 0xFFFF elsewhere, counts[0]
 //   gd_step_kernel    one word per lane: new = dilate(F[(s - 1) & 1]) & C & ~R under the structure of section 4r (x neighbours: a shift with the edge bit of the
@@ -16,6 +16,7 @@
 // A word with no unreached constraint voxel reads no neighbour.  A lane reads and writes only its own word of R; the frontier it reads is the one the previous launch
 // wrote.  No workgroup waits for another: a step boundary is a kernel boundary.  Integer work only: the same bits on every run.
 #include "common.h"
+#include "vol_common.h"
 
 #include <cmath>
 
@@ -24,33 +25,6 @@ constexpr int TPB = 256;
 constexpr long long GRID_CAP = 256 * 32;                             // grid-stride launches: 32 workgroups per CU
 constexpr int TH_VEC = 8;                                            // voxels of a lane in the vector form of the threshold
 typedef unsigned long long u64;
-
-inline bool lm_dims_ok(int X, int Y, int Z) { return X >= 0 && Y >= 0 && Z >= 0 && (long long)X * Y * Z < 0x80000000LL && (X == 0 || Y == 0 || (long long)X * Y < 0x80000000LL); }
-inline bool lm_aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
-inline bool lm_overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t p = reinterpret_cast<uintptr_t>(a), q = reinterpret_cast<uintptr_t>(b);
-  return p < q + nb && q < p + na;
-}
-inline unsigned lm_blocks(long long items) { long long b = (items + TPB - 1) / TPB; return (unsigned)(b < 1 ? 1 : (b > GRID_CAP ? GRID_CAP : b)); }
-inline size_t pad16(size_t b) { return (b + 15) / 16 * 16; }
-inline int lm_itemsize(int dt) {
-  switch (dt) { case 2: case 256: return 1; case 4: case 512: return 2; case 8: case 768: case 16: return 4; case 64: return 8; default: return 0; }
-}
-
-__device__ __forceinline__ int lm_wave_sum(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ int lm_block_sum(int v, int* s_w) {       // -> the sum in every lane; s_w: TPB / 64 words; a barrier separates two uses
-  v = lm_wave_sum(v);
-  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
-  __syncthreads();
-  int t = 0;
-#pragma unroll
-  for (int w = 0; w < TPB / 64; ++w) t += s_w[w];
-  return t;
-}
 
 // ---- threshold ----------------------------------------------------------------------------------------------------------------------------------
 struct th_args { int scaled; double slope, inter, lo, hi; };
@@ -121,7 +95,7 @@ __global__ __launch_bounds__(TPB) void th_threshold_kernel(const T* __restrict__
         int c;
         if constexpr (VEC) c = __popc(bits);
         else { const u64 set = __ballot(bits != 0); c = (tid & 63) == 0 ? (int)__popcll(set) : 0; }
-        const int t = lm_block_sum(c, s_w);
+        const int t = vol_block_sum<int, TPB>(c, s_w);
         if (tid == 0 && t) atomicAdd(slice_counts + zb, (u64)t);
         __syncthreads();                                              // s_w is written again on the next trip
       } else {
@@ -134,29 +108,15 @@ __global__ __launch_bounds__(TPB) void th_threshold_kernel(const T* __restrict__
 template <typename T>
 void th_launch(hipStream_t s, const void* vox, const th_args& a, const uint8_t* region, long long N, long long XY, uint8_t* mask, u64* sc) {
   const T* p = static_cast<const T*>(vox);
-  const bool vec = lm_aligned(vox, sizeof(T) == 1 ? 8 : 16) && lm_aligned(mask, 8) && lm_aligned(region, 8);
-  if (vec) hipLaunchKernelGGL((th_threshold_kernel<T, true>), dim3(lm_blocks((N + TH_VEC - 1) / TH_VEC)), dim3(TPB), 0, s, p, a, region, N, XY, mask, sc);
-  else hipLaunchKernelGGL((th_threshold_kernel<T, false>), dim3(lm_blocks(N)), dim3(TPB), 0, s, p, a, region, N, XY, mask, sc);
+  const bool vec = vol_aligned(vox, sizeof(T) == 1 ? 8 : 16) && vol_aligned(mask, 8) && vol_aligned(region, 8);
+  if (vec) hipLaunchKernelGGL((th_threshold_kernel<T, true>), dim3(vol_blocks((N + TH_VEC - 1) / TH_VEC, GRID_CAP, TPB)), dim3(TPB), 0, s, p, a, region, N, XY, mask, sc);
+  else hipLaunchKernelGGL((th_threshold_kernel<T, false>), dim3(vol_blocks(N, GRID_CAP, TPB)), dim3(TPB), 0, s, p, a, region, N, XY, mask, sc);
 }
 
-// ---- growth -------------------------------------------------------------------------------------------------------------------------------------
-struct gd_dims { int X, Y, Z, WX; long long N, words; };              // WX words per row, words = WX Y Z
-inline gd_dims gd_make(int X, int Y, int Z) { const int WX = (X + 63) / 64; return {X, Y, Z, WX, (long long)X * Y * Z, (long long)WX * Y * Z}; }
-// the workspace: C | R | F[0] | F[1], `words` 64-bit words each
-struct gd_layout { size_t plane, total; };
-inline gd_layout gd_layout_of(const gd_dims& d) { const size_t p = pad16((size_t)d.words * sizeof(u64)); return {p, 4 * p}; }
-
-__device__ __forceinline__ unsigned gd_bytes_to_bits(uint4 w) {       // 16 bytes -> 16 bits (byte != 0)
-  const unsigned ws[4] = {w.x, w.y, w.z, w.w};
-  unsigned bits = 0;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) bits |= ((ws[i >> 2] >> (8 * (i & 3))) & 0xFFu) ? (1u << i) : 0u;
-  return bits;
-}
-
+// ---- growth: the workspace is C | R | F[0] | F[1], `words` 64-bit words each ----------------------------------------------------------------------
 // one 16-voxel segment per lane (VEC: X % 16 == 0, so a segment is inside or outside as a whole, and 16-byte accesses); the four lanes of a word join by shuffles
 template <bool VEC>
-__global__ __launch_bounds__(TPB) void gd_begin_kernel(const uint8_t* __restrict__ seeds, const uint8_t* __restrict__ constraint, gd_dims d, u64* __restrict__ C,
+__global__ __launch_bounds__(TPB) void gd_begin_kernel(const uint8_t* __restrict__ seeds, const uint8_t* __restrict__ constraint, vol_bits d, u64* __restrict__ C,
                                                       u64* __restrict__ R, u64* __restrict__ F0, uint16_t* __restrict__ arrival, u64* __restrict__ count0) {
   __shared__ int s_w[TPB / 64];
   const long long segs = d.words * 4;                                 // a multiple of 4: the four lanes of a word are all inside or all outside
@@ -171,8 +131,8 @@ __global__ __launch_bounds__(TPB) void gd_begin_kernel(const uint8_t* __restrict
       if (x0 < d.X) {
         const long long f = row * d.X + x0;
         if (VEC) {
-          cb = gd_bytes_to_bits(*reinterpret_cast<const uint4*>(constraint + f));
-          sb = gd_bytes_to_bits(*reinterpret_cast<const uint4*>(seeds + f)) & cb;
+          cb = vol_bytes_to_bits(*reinterpret_cast<const uint4*>(constraint + f));
+          sb = vol_bytes_to_bits(*reinterpret_cast<const uint4*>(seeds + f)) & cb;
           unsigned h[8];
 #pragma unroll
           for (int i = 0; i < 8; ++i) h[i] = (((sb >> (2 * i)) & 1u) ? 0u : 0xFFFFu) | (((sb >> (2 * i + 1)) & 1u) ? 0u : 0xFFFF0000u);
@@ -196,18 +156,13 @@ __global__ __launch_bounds__(TPB) void gd_begin_kernel(const uint8_t* __restrict
     sv |= __shfl_xor(sv, 1, 64); sv |= __shfl_xor(sv, 2, 64);
     if (t < segs && (lane & 3) == 0) { C[t >> 2] = cv; R[t >> 2] = sv; F0[t >> 2] = sv; }
   }
-  const int tot = lm_block_sum(cnt, s_w);
+  const int tot = vol_block_sum<int, TPB>(cnt, s_w);
   if (threadIdx.x == 0 && tot) atomicAdd(count0, (u64)tot);           // integer sums: exact in any order
 }
 
-// the packed sets hold no bit at or beyond X, and every word outside the volume reads as 0
-__device__ __forceinline__ u64 gd_load(const u64* __restrict__ P, const gd_dims& d, int wi, int y, int z) {
-  if (wi < 0 || wi >= d.WX || y < 0 || y >= d.Y || z < 0 || z >= d.Z) return 0ull;
-  return P[wi + (long long)d.WX * (y + (long long)d.Y * z)];
-}
 // generate_binary_structure(3, conn) holds (dx, dy, dz) when it moves along at most conn axes: a row (dy, dz) with n = (dy != 0) + (dz != 0) <= conn takes part, with its
 // x neighbours when n < conn.  planar: only dz = 0.
-__global__ __launch_bounds__(TPB) void gd_step_kernel(const u64* __restrict__ C, u64* __restrict__ R, const u64* __restrict__ Fp, u64* __restrict__ Fn, gd_dims d, int conn,
+__global__ __launch_bounds__(TPB) void gd_step_kernel(const u64* __restrict__ C, u64* __restrict__ R, const u64* __restrict__ Fp, u64* __restrict__ Fn, vol_bits d, int conn,
                                                      int planar, unsigned step, uint16_t* __restrict__ arrival, u64* __restrict__ count) {
   __shared__ int s_w[TPB / 64];
   const int zr = planar ? 0 : 1;
@@ -223,10 +178,10 @@ __global__ __launch_bounds__(TPB) void gd_step_kernel(const u64* __restrict__ C,
         for (int dy = -1; dy <= 1; ++dy) {
           const int n = (dy != 0) + (dz != 0);
           if (n > conn) continue;
-          const u64 c = gd_load(Fp, d, wi, y + dy, z + dz);
+          const u64 c = vol_bits_load(Fp, d, wi, y + dy, z + dz);
           u64 t = c;
           if (n < conn) {
-            const u64 lo = gd_load(Fp, d, wi - 1, y + dy, z + dz), hi = gd_load(Fp, d, wi + 1, y + dy, z + dz);
+            const u64 lo = vol_bits_load(Fp, d, wi - 1, y + dy, z + dz), hi = vol_bits_load(Fp, d, wi + 1, y + dy, z + dz);
             t |= (c << 1) | (lo >> 63) | (c >> 1) | (hi << 63);       // bit x takes voxel x - 1 / voxel x + 1
           }
           acc |= t;
@@ -241,7 +196,7 @@ __global__ __launch_bounds__(TPB) void gd_step_kernel(const u64* __restrict__ C,
     }
     Fn[w] = got;
   }
-  const int tot = lm_block_sum(cnt, s_w);
+  const int tot = vol_block_sum<int, TPB>(cnt, s_w);
   if (threadIdx.x == 0 && tot) atomicAdd(count, (u64)tot);
 }
 }  // namespace
@@ -251,15 +206,15 @@ extern "C" {
 int32_t unet_vol_threshold(unet_ctx* ctx, const void* vox, int32_t dtype, int32_t X, int32_t Y, int32_t Z, int32_t scaled, double slope, double inter, double lo, double hi,
                            const uint8_t* region, uint8_t* mask, int64_t* slice_counts, void* stream) {
   if (!ctx) return UNET_E_ARG;
-  const int isz = lm_itemsize(dtype);
+  const int isz = vol_itemsize(dtype);
   if (!isz) UNET_FAIL(ctx, UNET_E_ARG, "vol_threshold: dtype %d is not a NIfTI element type (2, 256, 4, 512, 8, 768, 16, 64)", dtype);
-  if (!lm_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_threshold: a dimension is negative or the volume has 2^31 voxels or more");
+  if (!vol_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_threshold: a dimension is negative or the volume has 2^31 voxels or more");
   if (std::isnan(lo) || std::isnan(hi) || !(lo < hi)) UNET_FAIL(ctx, UNET_E_ARG, "vol_threshold: the edges must satisfy lo < hi and neither is NaN (-inf and +inf are allowed)");
   if (scaled && (std::isnan(slope) || std::isnan(inter))) UNET_FAIL(ctx, UNET_E_ARG, "vol_threshold: NaN scaling");
   const long long XY = (long long)X * Y, N = XY * Z;
   if (N == 0) return UNET_OK;
-  if (!vox || !mask || !lm_aligned(vox, (uintptr_t)isz) || !lm_aligned(slice_counts, 8)) UNET_FAIL(ctx, UNET_E_ARG, "vol_threshold: null or misaligned buffer");
-  if (lm_overlap(vox, (size_t)N * isz, mask, (size_t)N) || (region && lm_overlap(region, (size_t)N, mask, (size_t)N)))
+  if (!vox || !mask || !vol_aligned(vox, (uintptr_t)isz) || !vol_aligned(slice_counts, 8)) UNET_FAIL(ctx, UNET_E_ARG, "vol_threshold: null or misaligned buffer");
+  if (vol_overlap(vox, (size_t)N * isz, mask, (size_t)N) || (region && vol_overlap(region, (size_t)N, mask, (size_t)N)))
     UNET_FAIL(ctx, UNET_E_ARG, "vol_threshold: mask must not overlap the voxels or the region");
   hipStream_t s = as_stream(stream);
   if (slice_counts) UNET_HIP(ctx, hipMemsetAsync(slice_counts, 0, (size_t)Z * sizeof(int64_t), s));
@@ -279,28 +234,28 @@ int32_t unet_vol_threshold(unet_ctx* ctx, const void* vox, int32_t dtype, int32_
 }
 
 size_t unet_vol_geodesic_ws_bytes(int32_t X, int32_t Y, int32_t Z) {
-  if (!lm_dims_ok(X, Y, Z) || (long long)X * Y * Z == 0) return 0;
-  return gd_layout_of(gd_make(X, Y, Z)).total;
+  if (!vol_dims_ok(X, Y, Z) || (long long)X * Y * Z == 0) return 0;
+  return vol_bits_layout_of(vol_bits_make(X, Y, Z), 4).total;
 }
 
 int32_t unet_vol_geodesic_begin(unet_ctx* ctx, const uint8_t* seeds, const uint8_t* constraint, int32_t X, int32_t Y, int32_t Z, uint16_t* arrival, int64_t* counts, void* ws,
                                 size_t ws_bytes, void* stream) {
   if (!ctx) return UNET_E_ARG;
-  if (!lm_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_geodesic_begin: a dimension is negative or the volume has 2^31 voxels or more");
-  const gd_dims d = gd_make(X, Y, Z);
+  if (!vol_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_geodesic_begin: a dimension is negative or the volume has 2^31 voxels or more");
+  const vol_bits d = vol_bits_make(X, Y, Z);
   if (d.N == 0) return UNET_OK;
-  if (!seeds || !constraint || !arrival || !counts || !ws || !lm_aligned(arrival, 2) || !lm_aligned(counts, 8))
+  if (!seeds || !constraint || !arrival || !counts || !ws || !vol_aligned(arrival, 2) || !vol_aligned(counts, 8))
     UNET_FAIL(ctx, UNET_E_ARG, "vol_geodesic_begin: null or misaligned buffer");
-  if (ws_bytes < unet_vol_geodesic_ws_bytes(X, Y, Z) || !lm_aligned(ws, 16)) UNET_FAIL(ctx, UNET_E_ARG, "vol_geodesic_begin: workspace too small or not 16-byte aligned");
-  const gd_layout L = gd_layout_of(d);
-  if (lm_overlap(arrival, (size_t)d.N * 2, ws, L.total) || lm_overlap(arrival, (size_t)d.N * 2, seeds, (size_t)d.N) || lm_overlap(arrival, (size_t)d.N * 2, constraint, (size_t)d.N))
+  if (ws_bytes < unet_vol_geodesic_ws_bytes(X, Y, Z) || !vol_aligned(ws, 16)) UNET_FAIL(ctx, UNET_E_ARG, "vol_geodesic_begin: workspace too small or not 16-byte aligned");
+  const vol_bits_layout L = vol_bits_layout_of(d, 4);
+  if (vol_overlap(arrival, (size_t)d.N * 2, ws, L.total) || vol_overlap(arrival, (size_t)d.N * 2, seeds, (size_t)d.N) || vol_overlap(arrival, (size_t)d.N * 2, constraint, (size_t)d.N))
     UNET_FAIL(ctx, UNET_E_ARG, "vol_geodesic_begin: arrival must not overlap the workspace, the seeds or the constraint");
   hipStream_t s = as_stream(stream);
   uint8_t* base = static_cast<uint8_t*>(ws);
   u64 *C = reinterpret_cast<u64*>(base), *R = reinterpret_cast<u64*>(base + L.plane), *F0 = reinterpret_cast<u64*>(base + 2 * L.plane);
   UNET_HIP(ctx, hipMemsetAsync(counts, 0, sizeof(int64_t), s));
-  const unsigned blocks = lm_blocks(d.words * 4);
-  if ((X % 16) == 0 && lm_aligned(seeds, 16) && lm_aligned(constraint, 16) && lm_aligned(arrival, 16))
+  const unsigned blocks = vol_blocks(d.words * 4, GRID_CAP, TPB);
+  if ((X % 16) == 0 && vol_aligned(seeds, 16) && vol_aligned(constraint, 16) && vol_aligned(arrival, 16))
     hipLaunchKernelGGL(gd_begin_kernel<true>, dim3(blocks), dim3(TPB), 0, s, seeds, constraint, d, C, R, F0, arrival, reinterpret_cast<u64*>(counts));
   else
     hipLaunchKernelGGL(gd_begin_kernel<false>, dim3(blocks), dim3(TPB), 0, s, seeds, constraint, d, C, R, F0, arrival, reinterpret_cast<u64*>(counts));
@@ -310,24 +265,24 @@ int32_t unet_vol_geodesic_begin(unet_ctx* ctx, const uint8_t* seeds, const uint8
 int32_t unet_vol_geodesic_steps(unet_ctx* ctx, int32_t X, int32_t Y, int32_t Z, int32_t first_step, int32_t n_steps, int32_t connectivity, int32_t planar, uint16_t* arrival,
                                 int64_t* counts, void* ws, size_t ws_bytes, void* stream) {
   if (!ctx) return UNET_E_ARG;
-  if (!lm_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_geodesic_steps: a dimension is negative or the volume has 2^31 voxels or more");
+  if (!vol_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_geodesic_steps: a dimension is negative or the volume has 2^31 voxels or more");
   if (planar != 0 && planar != 1) UNET_FAIL(ctx, UNET_E_ARG, "vol_geodesic_steps: planar %d is not 0 or 1", planar);
   if (connectivity < 1 || connectivity > (planar ? 2 : 3))
     UNET_FAIL(ctx, UNET_E_ARG, "vol_geodesic_steps: connectivity %d is not 1, 2%s", connectivity, planar ? " (a planar structure has no third axis)" : " or 3");
   if (first_step < 1 || n_steps < 1 || (long long)first_step + n_steps - 1 > UNET_VOL_GEODESIC_MAX_STEP)
     UNET_FAIL(ctx, UNET_E_ARG, "vol_geodesic_steps: steps %d .. %lld are not inside 1 .. %d", first_step, (long long)first_step + n_steps - 1, UNET_VOL_GEODESIC_MAX_STEP);
-  const gd_dims d = gd_make(X, Y, Z);
+  const vol_bits d = vol_bits_make(X, Y, Z);
   if (d.N == 0) return UNET_OK;
-  if (!arrival || !counts || !ws || !lm_aligned(arrival, 2) || !lm_aligned(counts, 8)) UNET_FAIL(ctx, UNET_E_ARG, "vol_geodesic_steps: null or misaligned buffer");
-  if (ws_bytes < unet_vol_geodesic_ws_bytes(X, Y, Z) || !lm_aligned(ws, 16)) UNET_FAIL(ctx, UNET_E_ARG, "vol_geodesic_steps: workspace too small or not 16-byte aligned");
-  const gd_layout L = gd_layout_of(d);
-  if (lm_overlap(arrival, (size_t)d.N * 2, ws, L.total)) UNET_FAIL(ctx, UNET_E_ARG, "vol_geodesic_steps: arrival must not overlap the workspace");
+  if (!arrival || !counts || !ws || !vol_aligned(arrival, 2) || !vol_aligned(counts, 8)) UNET_FAIL(ctx, UNET_E_ARG, "vol_geodesic_steps: null or misaligned buffer");
+  if (ws_bytes < unet_vol_geodesic_ws_bytes(X, Y, Z) || !vol_aligned(ws, 16)) UNET_FAIL(ctx, UNET_E_ARG, "vol_geodesic_steps: workspace too small or not 16-byte aligned");
+  const vol_bits_layout L = vol_bits_layout_of(d, 4);
+  if (vol_overlap(arrival, (size_t)d.N * 2, ws, L.total)) UNET_FAIL(ctx, UNET_E_ARG, "vol_geodesic_steps: arrival must not overlap the workspace");
   hipStream_t s = as_stream(stream);
   uint8_t* base = static_cast<uint8_t*>(ws);
   u64 *C = reinterpret_cast<u64*>(base), *R = reinterpret_cast<u64*>(base + L.plane);
   u64* F[2] = {reinterpret_cast<u64*>(base + 2 * L.plane), reinterpret_cast<u64*>(base + 3 * L.plane)};
   UNET_HIP(ctx, hipMemsetAsync(counts + first_step, 0, (size_t)n_steps * sizeof(int64_t), s));
-  const unsigned blocks = lm_blocks(d.words);
+  const unsigned blocks = vol_blocks(d.words, GRID_CAP, TPB);
   for (int st = first_step; st < first_step + n_steps; ++st)
     hipLaunchKernelGGL(gd_step_kernel, dim3(blocks), dim3(TPB), 0, s, C, R, F[(st - 1) & 1], F[st & 1], d, connectivity, planar, (unsigned)st, arrival,
                        reinterpret_cast<u64*>(counts) + st);

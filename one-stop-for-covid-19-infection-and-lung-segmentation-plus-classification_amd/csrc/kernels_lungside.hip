@@ -2,7 +2,7 @@
 //   sides[v] = 0 off the mask, else the side of the seed with the smaller squared distance (a tie: the seed whose side is 1), + voxels per side value     unet_vol_side_assign
 //   voxels per side value, infected voxels per side value, voxels of every lesion per side value, the same per slice                                    unet_vol_side_table
 // Volumes are [X, Y, Z] in Fortran order (f = x + X (y + Y z)), X Y Z < 2^31, as in kernels_components.hip.
-// Integer arithmetic only.  The distances are compared as order-preserving 64-bit keys of their bit patterns (kernels_intensity.hip's iv_d2ord): for the non-negative
+// Integer arithmetic only.  The distances are compared as order-preserving 64-bit keys of their bit patterns (vol_common.h's vol_d2ord on the bits): for the non-negative
 // values and +inf that unet_vol_edt_sq writes, key order is value order, and no floating-point instruction runs.  Sums are integers per lane, per wave (ballots /
 // butterflies), per workgroup in LDS, and leave as 64-bit atomics: the same bits on every run.
 // Assign: a lane holds four consecutive voxels -- one 4-byte load of the mask, two 16-byte loads of each distance stream, one 4-byte store -- when the buffers are
@@ -10,6 +10,7 @@
 // Table: kernels_intensity.hip's layout -- chunk c = ST_CHUNK voxels of one slice, a workgroup walks a contiguous range of chunks, the per-slice counters leave LDS when
 // its slice changes -- and its ballot-per-key loop for the (lesion, side) table: one add per distinct key of a wave.
 #include "common.h"
+#include "vol_common.h"
 
 namespace {
 constexpr int TPB = 256;
@@ -18,21 +19,12 @@ constexpr int ST_TABLE = 4096;                                       // (lesion,
 constexpr int ST_CHUNK = TPB * 16;                                   // voxels of a slice a workgroup takes at a time
 constexpr int ST_GRID = 256 * 4;                                     // workgroups of the table launch
 
-inline bool ls_dims_ok(int X, int Y, int Z) { return X >= 0 && Y >= 0 && Z >= 0 && (long long)X * Y * Z < 0x80000000LL && (X == 0 || Y == 0 || (long long)X * Y < 0x80000000LL); }
-inline bool ls_aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
-
 __device__ __forceinline__ unsigned long long ls_key(unsigned long long u) { return (u >> 63) ? ~u : (u | 0x8000000000000000ull); }
 // the side of a mask voxel: `first` (the seed whose side is 1) wins a tie
 __device__ __forceinline__ int ls_side(unsigned long long a, unsigned long long b, int side_a, int side_b) {
   const unsigned long long ka = ls_key(a), kb = ls_key(b);
   return side_a == 1 ? (ka <= kb ? side_a : side_b) : (kb <= ka ? side_b : side_a);
 }
-__device__ __forceinline__ int ls_wave_sum(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // VEC = 4: item g = voxels [4 g, 4 g + 4) (the last item may be short: it goes voxel by voxel); VEC = 1: item g = voxel g.  Trip counts are wave-uniform.
 template <int VEC>
 __global__ __launch_bounds__(TPB) void side_assign_kernel(const uint8_t* __restrict__ mask, const unsigned long long* __restrict__ d2a, const unsigned long long* __restrict__ d2b,
@@ -82,7 +74,7 @@ __global__ __launch_bounds__(TPB) void side_assign_kernel(const uint8_t* __restr
     }
   }
   c0 -= c1 + c2;                                                      // c0 counted every voxel written
-  c0 = ls_wave_sum(c0); c1 = ls_wave_sum(c1); c2 = ls_wave_sum(c2);
+  c0 = vol_wave_sum(c0); c1 = vol_wave_sum(c1); c2 = vol_wave_sum(c2);
   if (lane == 0) { s_cnt[wave][0] = c0; s_cnt[wave][1] = c1; s_cnt[wave][2] = c2; }
   __syncthreads();
   if (tid < 3) {
@@ -171,11 +163,11 @@ extern "C" {
 int32_t unet_vol_side_assign(unet_ctx* ctx, const uint8_t* mask, const double* d2_a, const double* d2_b, int32_t X, int32_t Y, int32_t Z, int32_t side_a, int32_t side_b,
                              uint8_t* sides, int64_t* counts, void* stream) {
   if (!ctx) return UNET_E_ARG;
-  if (!ls_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_side_assign: a dimension is negative or the volume has 2^31 voxels or more");
+  if (!vol_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_side_assign: a dimension is negative or the volume has 2^31 voxels or more");
   if (!((side_a == 1 && side_b == 2) || (side_a == 2 && side_b == 1))) UNET_FAIL(ctx, UNET_E_ARG, "vol_side_assign: side_a, side_b are 1 and 2 in either order, not %d, %d", side_a, side_b);
   const long long N = (long long)X * Y * Z;
   if (N == 0) return UNET_OK;
-  if (!mask || !d2_a || !d2_b || !sides || !counts || !ls_aligned(d2_a, 8) || !ls_aligned(d2_b, 8) || !ls_aligned(counts, 8))
+  if (!mask || !d2_a || !d2_b || !sides || !counts || !vol_aligned(d2_a, 8) || !vol_aligned(d2_b, 8) || !vol_aligned(counts, 8))
     UNET_FAIL(ctx, UNET_E_ARG, "vol_side_assign: null or misaligned buffer");
   if (sides == mask) UNET_FAIL(ctx, UNET_E_ARG, "vol_side_assign: sides must not be the mask's own buffer");
   hipStream_t s = as_stream(stream);
@@ -183,7 +175,7 @@ int32_t unet_vol_side_assign(unet_ctx* ctx, const uint8_t* mask, const double* d
   const unsigned long long* a = reinterpret_cast<const unsigned long long*>(d2_a);
   const unsigned long long* b = reinterpret_cast<const unsigned long long*>(d2_b);
   unsigned long long* cn = reinterpret_cast<unsigned long long*>(counts);
-  const bool vec = ls_aligned(mask, 4) && ls_aligned(sides, 4) && ls_aligned(d2_a, 16) && ls_aligned(d2_b, 16);
+  const bool vec = vol_aligned(mask, 4) && vol_aligned(sides, 4) && vol_aligned(d2_a, 16) && vol_aligned(d2_b, 16);
   const long long items = vec ? (N + 3) / 4 : N;
   long long blocks = (items + TPB - 1) / TPB;
   if (blocks > GRID_CAP) blocks = GRID_CAP;
@@ -195,11 +187,11 @@ int32_t unet_vol_side_assign(unet_ctx* ctx, const uint8_t* mask, const double* d
 int32_t unet_vol_side_table(unet_ctx* ctx, const uint8_t* sides, const uint8_t* infection, const int32_t* labels, int32_t n, int32_t X, int32_t Y, int32_t Z, int64_t* totals,
                             int64_t* lesion_side, int64_t* per_slice, void* stream) {
   if (!ctx) return UNET_E_ARG;
-  if (!ls_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_side_table: a dimension is negative or the volume has 2^31 voxels or more");
+  if (!vol_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_side_table: a dimension is negative or the volume has 2^31 voxels or more");
   if (n < 0) UNET_FAIL(ctx, UNET_E_ARG, "vol_side_table: n is negative");
   const long long XY = (long long)X * Y, N = XY * Z;
   if (N == 0) return UNET_OK;
-  if (!sides || !totals || (n > 0 && !lesion_side) || !ls_aligned(totals, 8) || !ls_aligned(lesion_side, 8) || !ls_aligned(per_slice, 8) || !ls_aligned(labels, 4))
+  if (!sides || !totals || (n > 0 && !lesion_side) || !vol_aligned(totals, 8) || !vol_aligned(lesion_side, 8) || !vol_aligned(per_slice, 8) || !vol_aligned(labels, 4))
     UNET_FAIL(ctx, UNET_E_ARG, "vol_side_table: null or misaligned buffer");
   hipStream_t s = as_stream(stream);
   UNET_HIP(ctx, hipMemsetAsync(totals, 0, 6 * sizeof(int64_t), s));

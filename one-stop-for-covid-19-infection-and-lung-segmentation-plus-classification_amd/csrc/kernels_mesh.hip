@@ -24,7 +24,7 @@ constexpr int CHUNK = TPB * PER;                                     // lattice 
 
 // the lattice: the volume [X, Y, Z] with `pad` layers of outside samples around it; lattice point (i, j, k) is voxel (i - pad, j - pad, k - pad)
 struct ms_lat { int X, Y, Z, pad, PX, PY, PZ; long long PXY, NP, NPpad; };
-struct ms_in { rs_src src; int kind, select; double iso, pad_value; };          // kind 0: uint8 mask, 1: int32 labels, 2: scalar volume
+struct ms_in { vol_voxels src; int kind, select; double iso, pad_value; };          // kind 0: uint8 mask, 1: int32 labels, 2: scalar volume
 
 // tetrahedron n: corners v0 = 0, v1, v2, v3 = 7 as cube corners c = dx + 2 dy + 4 dz (axis orders xyz, xzy, yxz, yzx, zxy, zyx)
 __constant__ uint8_t MS_V1[6] = {1, 1, 2, 2, 4, 4};
@@ -56,11 +56,11 @@ __device__ __forceinline__ unsigned ms_inside(const ms_in& in, const ms_lat& L, 
   if (!ms_voxel(L, i, j, k, &f)) return 0u;                           // pad_value <= iso: a virtual sample is outside
   if (in.kind == 0) return static_cast<const uint8_t*>(in.src.p)[f] != 0 ? 1u : 0u;
   if (in.kind == 1) { const int l = static_cast<const int32_t*>(in.src.p)[f]; return (in.select ? l == in.select : l != 0) ? 1u : 0u; }
-  return rs_dec(in.src, f) > in.iso ? 1u : 0u;                        // (a NaN is outside)
+  return vol_dec(in.src, f) > in.iso ? 1u : 0u;                        // (a NaN is outside)
 }
 __device__ __forceinline__ double ms_value(const ms_in& in, const ms_lat& L, int i, int j, int k) {
   long long f;
-  return ms_voxel(L, i, j, k, &f) ? rs_dec(in.src, f) : in.pad_value;
+  return ms_voxel(L, i, j, k, &f) ? vol_dec(in.src, f) : in.pad_value;
 }
 __device__ __forceinline__ void ms_ijk(const ms_lat& L, long long q, int* i, int* j, int* k) {          // q < NP < 2^31: 32-bit divisions
   const unsigned uq = (unsigned)q, pxy = (unsigned)L.PXY, px = (unsigned)L.PX;
@@ -371,14 +371,14 @@ int ms_check(unet_ctx* ctx, const char* what, const void* src, int kind, int dty
   if (kind < 0 || kind > 2) bad = "kind is 0 (uint8 mask), 1 (int32 labels) or 2 (scalar volume)";
   else if (kind == 0 && dtype != 2) bad = "a mask is uint8 (datatype code 2)";
   else if (kind == 1 && dtype != 8) bad = "a label volume is int32 (datatype code 8)";
-  else if (rs_itemsize(dtype) == 0) bad = "unknown datatype code";
+  else if (vol_itemsize(dtype) == 0) bad = "unknown datatype code";
   else if (!std::isfinite(iso) || !std::isfinite(pad_value)) bad = "iso and pad_value are finite";
   else if (pad_value > iso) bad = "pad_value > iso: the virtual layer must be outside";
   else if (select < 0) bad = "select < 0";
   else if (scaled && (std::isnan(slope) || std::isnan(inter))) bad = "slope and inter are numbers";
   if (bad) { if (ctx) { char b[256]; snprintf(b, sizeof(b), "%s: %s", what, bad); ctx->err = b; } return 0; }
   if (!ms_has_cells(a->L)) return 2;
-  if (!src || (reinterpret_cast<uintptr_t>(src) % (uintptr_t)rs_itemsize(dtype)) != 0 || !ws || (reinterpret_cast<uintptr_t>(ws) % 16) != 0 || ws_bytes < ms_ws_bytes(a->L)) {
+  if (!src || (reinterpret_cast<uintptr_t>(src) % (uintptr_t)vol_itemsize(dtype)) != 0 || !ws || (reinterpret_cast<uintptr_t>(ws) % 16) != 0 || ws_bytes < ms_ws_bytes(a->L)) {
     if (ctx) { char b[256]; snprintf(b, sizeof(b), "%s: null or misaligned buffer (the volume to its element size, the workspace to 16 bytes), or a workspace below unet_vol_mesh_ws_bytes", what); ctx->err = b; }
     return 0;
   }

@@ -15,35 +15,13 @@
 //   fh_final_kernel        out = mask | !touches[label of the background component], and the slice counts
 // Everything is integer / boolean: the result is the same on every run.
 #include "common.h"
+#include "vol_common.h"
 
 namespace {
 constexpr int TPB = 256;
 constexpr long long GRID_CAP = 256 * 32;                             // grid-stride launches: 32 workgroups per CU
 typedef unsigned long long u64;
 
-struct mp_dims { int X, Y, Z, WX; long long XY, N, words; };          // WX words per row, words = WX Y Z
-inline mp_dims mp_make(int X, int Y, int Z) { const int WX = (X + 63) / 64; return {X, Y, Z, WX, (long long)X * Y, (long long)X * Y * Z, (long long)WX * Y * Z}; }
-inline bool mp_dims_ok(int X, int Y, int Z) { return X >= 0 && Y >= 0 && Z >= 0 && (long long)X * Y * Z < 0x80000000LL && (X == 0 || Y == 0 || (long long)X * Y < 0x80000000LL); }
-inline unsigned mp_blocks(long long items) { long long b = (items + TPB - 1) / TPB; return (unsigned)(b < 1 ? 1 : (b > GRID_CAP ? GRID_CAP : b)); }
-inline size_t pad16(size_t b) { return (b + 15) / 16 * 16; }
-
-__device__ __forceinline__ int block_sum_int(int v, int* s_w) {      // -> the sum in every lane; s_w: TPB / 64 words
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
-  __syncthreads();
-  int t = 0;
-#pragma unroll
-  for (int w = 0; w < TPB / 64; ++w) t += s_w[w];
-  return t;
-}
-__device__ __forceinline__ unsigned bytes_to_bits(uint4 w) {          // 16 bytes -> 16 bits (byte != 0)
-  const unsigned ws[4] = {w.x, w.y, w.z, w.w};
-  unsigned bits = 0;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) bits |= ((ws[i >> 2] >> (8 * (i & 3))) & 0xFFu) ? (1u << i) : 0u;
-  return bits;
-}
 __device__ __forceinline__ unsigned nibble_to_bytes(unsigned n) { return (n & 1u) | ((n & 2u) << 7) | ((n & 4u) << 14) | ((n & 8u) << 21); }
 __device__ __forceinline__ uint4 bits_to_bytes(unsigned bits) {
   return make_uint4(nibble_to_bytes(bits & 15u), nibble_to_bytes((bits >> 4) & 15u), nibble_to_bytes((bits >> 8) & 15u), nibble_to_bytes((bits >> 12) & 15u));
@@ -51,7 +29,7 @@ __device__ __forceinline__ uint4 bits_to_bytes(unsigned bits) {
 
 // ---- pack: one 16-voxel segment per lane (VEC: one 16-byte load; X % 16 == 0, so a segment is inside or outside as a whole); the four lanes of a word join by shuffles
 template <bool VEC>
-__global__ __launch_bounds__(TPB) void morph_pack_kernel(const uint8_t* __restrict__ mask, mp_dims d, u64* __restrict__ P) {
+__global__ __launch_bounds__(TPB) void morph_pack_kernel(const uint8_t* __restrict__ mask, vol_bits d, u64* __restrict__ P) {
   const long long segs = d.words * 4;                                 // a multiple of 4: the four lanes of a word are all inside or all outside
   const int lane = threadIdx.x & 63;
   for (long long t0 = (long long)blockIdx.x * TPB + (threadIdx.x - lane); t0 < segs; t0 += (long long)gridDim.x * TPB) {          // wave-uniform trip count
@@ -62,7 +40,7 @@ __global__ __launch_bounds__(TPB) void morph_pack_kernel(const uint8_t* __restri
       const int x0 = (int)(w - row * d.WX) * 64 + (int)(t & 3) * 16;
       const uint8_t* p = mask + row * d.X + x0;
       if (VEC) {
-        if (x0 < d.X) bits = bytes_to_bits(*reinterpret_cast<const uint4*>(p));
+        if (x0 < d.X) bits = vol_bytes_to_bits(*reinterpret_cast<const uint4*>(p));
       } else {
 #pragma unroll
         for (int i = 0; i < 16; ++i) bits |= (x0 + i < d.X && p[i]) ? (1u << i) : 0u;
@@ -75,17 +53,11 @@ __global__ __launch_bounds__(TPB) void morph_pack_kernel(const uint8_t* __restri
   }
 }
 
-// ---- one step.  A word is read as the structuring element sees it: the bits beyond X, and every word outside the volume, hold the border value (fill = 0 or ~0)
-__device__ __forceinline__ u64 mp_valid(const mp_dims& d, int wi) { const int left = d.X - wi * 64; return left >= 64 ? ~0ull : ((1ull << left) - 1ull); }          // 0 <= wi < WX: left >= 1
-__device__ __forceinline__ u64 mp_load(const u64* __restrict__ P, const mp_dims& d, int wi, int y, int z, u64 fill) {
-  if (wi < 0 || wi >= d.WX || y < 0 || y >= d.Y || z < 0 || z >= d.Z) return fill;
-  const u64 v = mp_valid(d, wi);
-  return (P[wi + (long long)d.WX * (y + (long long)d.Y * z)] & v) | (fill & ~v);
-}
+// ---- one step.  A word is read as the structuring element sees it (vol_bits_load with a border value, fill = 0 or ~0)
 // generate_binary_structure(3, conn) holds (dx, dy, dz) when it moves along at most conn axes: a row (dy, dz) with n = (dy != 0) + (dz != 0) <= conn takes part, with its
 // x neighbours when n < conn.  planar: only dz = 0.
 template <bool DILATE>
-__global__ __launch_bounds__(TPB) void morph_step_kernel(const u64* __restrict__ src, mp_dims d, int conn, int planar, u64 fill, u64* __restrict__ dst) {
+__global__ __launch_bounds__(TPB) void morph_step_kernel(const u64* __restrict__ src, vol_bits d, int conn, int planar, u64 fill, u64* __restrict__ dst) {
   const int zr = planar ? 0 : 1;
   for (long long w = (long long)blockIdx.x * TPB + threadIdx.x; w < d.words; w += (long long)gridDim.x * TPB) {
     const long long row = w / d.WX;
@@ -95,22 +67,22 @@ __global__ __launch_bounds__(TPB) void morph_step_kernel(const u64* __restrict__
       for (int dy = -1; dy <= 1; ++dy) {
         const int n = (dy != 0) + (dz != 0);
         if (n > conn) continue;
-        const u64 c = mp_load(src, d, wi, y + dy, z + dz, fill);
+        const u64 c = vol_bits_load(src, d, wi, y + dy, z + dz, fill);
         u64 t = c;
         if (n < conn) {
-          const u64 lo = mp_load(src, d, wi - 1, y + dy, z + dz, fill), hi = mp_load(src, d, wi + 1, y + dy, z + dz, fill);
+          const u64 lo = vol_bits_load(src, d, wi - 1, y + dy, z + dz, fill), hi = vol_bits_load(src, d, wi + 1, y + dy, z + dz, fill);
           const u64 a = (c << 1) | (lo >> 63), b = (c >> 1) | (hi << 63);          // bit x takes voxel x - 1 / voxel x + 1
           t = DILATE ? (c | a | b) : (c & a & b);
         }
         acc = DILATE ? (acc | t) : (acc & t);
       }
-    dst[w] = acc & mp_valid(d, wi);
+    dst[w] = acc & vol_bits_valid(d, wi);
   }
 }
 
 // ---- unpack + counts: a workgroup stays inside one slice (bps workgroups per slice); one 16-voxel segment per lane and trip
 template <bool VEC>
-__global__ __launch_bounds__(TPB) void morph_unpack_kernel(const u64* __restrict__ P, mp_dims d, int bps, uint8_t* __restrict__ out, u64* __restrict__ counts) {
+__global__ __launch_bounds__(TPB) void morph_unpack_kernel(const u64* __restrict__ P, vol_bits d, int bps, uint8_t* __restrict__ out, u64* __restrict__ counts) {
   __shared__ int s_w[TPB / 64];
   const int z = blockIdx.x / bps, part = blockIdx.x - z * bps;
   const long long sps = (long long)d.Y * d.WX * 4;                    // segments per slice
@@ -132,7 +104,7 @@ __global__ __launch_bounds__(TPB) void morph_unpack_kernel(const u64* __restrict
         if (x0 + k < d.X) o[k] = (uint8_t)((bits >> k) & 1u);
     }
   }
-  const int t = block_sum_int(cnt, s_w);
+  const int t = vol_block_sum<int, TPB>(cnt, s_w);
   if (counts && threadIdx.x == 0 && t) atomicAdd(counts + z, (u64)t);          // integer sums: exact in any order
 }
 
@@ -159,14 +131,14 @@ __global__ __launch_bounds__(TPB) void morph_ball_kernel(const double* __restric
     if constexpr (V == 4) *reinterpret_cast<unsigned*>(out + base + i) = word;
     else out[base + i] = (uint8_t)word;
   }
-  const int t = block_sum_int(cnt, s_w);
+  const int t = vol_block_sum<int, TPB>(cnt, s_w);
   if (counts && threadIdx.x == 0 && t) atomicAdd(counts + z, (u64)t);
 }
 
 // ---- fill holes -------------------------------------------------------------------------------------------------------------------------------
 // labels: the components of the mask's zero voxels.  One lane per face voxel: faces x = 0, x = X - 1 (Y Z voxels each), y = 0, y = Y - 1 (X Z each) and, unless planar,
 // z = 0, z = Z - 1 (X Y each).  Every writer stores the same value 1: the order does not matter.
-__global__ __launch_bounds__(TPB) void fh_faces_kernel(const int32_t* __restrict__ labels, mp_dims d, long long FX, long long FY, long long FZ, long long tsize,
+__global__ __launch_bounds__(TPB) void fh_faces_kernel(const int32_t* __restrict__ labels, vol_bits d, long long FX, long long FY, long long FZ, long long tsize,
                                                       uint8_t* __restrict__ touches) {
   const long long total = 2 * (FX + FY + FZ);
   for (long long i = (long long)blockIdx.x * TPB + threadIdx.x; i < total; i += (long long)gridDim.x * TPB) {
@@ -204,7 +176,7 @@ __global__ __launch_bounds__(TPB) void fh_final_kernel(const int32_t* __restrict
       *reinterpret_cast<uint4*>(out + base + i) = make_uint4(w[0], w[1], w[2], w[3]);
     } else out[base + i] = (uint8_t)b[0];
   }
-  const int t = block_sum_int(cnt, s_w);
+  const int t = vol_block_sum<int, TPB>(cnt, s_w);
   if (counts && threadIdx.x == 0 && t) atomicAdd(counts + z, (u64)t);
 }
 
@@ -212,18 +184,13 @@ inline int slice_blocks(long long items_per_slice, long long per_block) {
   long long bps = (items_per_slice + per_block - 1) / per_block;
   return (int)(bps < 1 ? 1 : (bps > 64 ? 64 : bps));
 }
-inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
-inline bool overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t p = reinterpret_cast<uintptr_t>(a), q = reinterpret_cast<uintptr_t>(b);
-  return p < q + nb && q < p + na;
-}
 // the fill-holes workspace: labels [N] int32 | n (16 bytes) | touches [N + 1] bytes | the label workspace
 struct fh_layout { size_t labels, n, touches, label_ws, total; };
 inline fh_layout fh_make(int X, int Y, int Z) {
   const size_t N = (size_t)X * Y * Z;
   fh_layout L;
-  L.labels = 0; L.n = pad16(N * sizeof(int32_t)); L.touches = L.n + 16; L.label_ws = L.touches + pad16(N + 1);
-  L.total = L.label_ws + pad16(unet_vol_label_ws_bytes(X, Y, Z));
+  L.labels = 0; L.n = vol_pad16(N * sizeof(int32_t)); L.touches = L.n + 16; L.label_ws = L.touches + vol_pad16(N + 1);
+  L.total = L.label_ws + vol_pad16(unet_vol_label_ws_bytes(X, Y, Z));
   return L;
 }
 }  // namespace
@@ -231,9 +198,9 @@ inline fh_layout fh_make(int X, int Y, int Z) {
 extern "C" {
 
 size_t unet_vol_morph_ws_bytes(int32_t X, int32_t Y, int32_t Z) {
-  if (!mp_dims_ok(X, Y, Z)) return 0;
-  const mp_dims d = mp_make(X, Y, Z);
-  return d.N == 0 ? 0 : 2 * pad16((size_t)d.words * sizeof(u64));
+  if (!vol_dims_ok(X, Y, Z)) return 0;
+  const vol_bits d = vol_bits_make(X, Y, Z);
+  return d.N == 0 ? 0 : vol_bits_layout_of(d, 2).total;          // two packed volumes, ping and pong
 }
 
 int32_t unet_vol_morph(unet_ctx* ctx, const uint8_t* mask, int32_t X, int32_t Y, int32_t Z, int32_t op, int32_t connectivity, int32_t planar, int32_t iterations,
@@ -244,19 +211,19 @@ int32_t unet_vol_morph(unet_ctx* ctx, const uint8_t* mask, int32_t X, int32_t Y,
     UNET_FAIL(ctx, UNET_E_ARG, "vol_morph: connectivity %d is not 1, 2%s", connectivity, planar ? " (a planar structure has no third axis)" : " or 3");
   if (iterations < 1 || iterations > UNET_VOL_MORPH_MAX_ITERATIONS) UNET_FAIL(ctx, UNET_E_ARG, "vol_morph: %d iterations are outside 1..%d", iterations, UNET_VOL_MORPH_MAX_ITERATIONS);
   if (border_value != 0 && border_value != 1) UNET_FAIL(ctx, UNET_E_ARG, "vol_morph: border_value %d is not 0 or 1", border_value);
-  if (!mp_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_morph: %d x %d x %d is negative or has 2^31 voxels or more", X, Y, Z);
-  const mp_dims d = mp_make(X, Y, Z);
+  if (!vol_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_morph: %d x %d x %d is negative or has 2^31 voxels or more", X, Y, Z);
+  const vol_bits d = vol_bits_make(X, Y, Z);
   if (d.N == 0) return UNET_OK;
   if (!mask || !out || !ws) UNET_FAIL(ctx, UNET_E_ARG, "vol_morph: bad args");
-  if (overlap(mask, (size_t)d.N, out, (size_t)d.N)) UNET_FAIL(ctx, UNET_E_ARG, "vol_morph: out must not be (or overlap) the mask's buffer");
-  if (ws_bytes < unet_vol_morph_ws_bytes(X, Y, Z) || !aligned(ws, 16)) UNET_FAIL(ctx, UNET_E_ARG, "vol_morph: workspace too small or not 16-byte aligned");
-  if (counts && !aligned(counts, 8)) UNET_FAIL(ctx, UNET_E_ARG, "vol_morph: counts is not 8-byte aligned");
+  if (vol_overlap(mask, (size_t)d.N, out, (size_t)d.N)) UNET_FAIL(ctx, UNET_E_ARG, "vol_morph: out must not be (or overlap) the mask's buffer");
+  if (ws_bytes < unet_vol_morph_ws_bytes(X, Y, Z) || !vol_aligned(ws, 16)) UNET_FAIL(ctx, UNET_E_ARG, "vol_morph: workspace too small or not 16-byte aligned");
+  if (counts && !vol_aligned(counts, 8)) UNET_FAIL(ctx, UNET_E_ARG, "vol_morph: counts is not 8-byte aligned");
   hipStream_t s = as_stream(stream);
   u64* cur = static_cast<u64*>(ws);
-  u64* nxt = reinterpret_cast<u64*>(static_cast<uint8_t*>(ws) + pad16((size_t)d.words * sizeof(u64)));
+  u64* nxt = reinterpret_cast<u64*>(static_cast<uint8_t*>(ws) + vol_bits_layout_of(d, 2).plane);
   if (counts) UNET_HIP(ctx, hipMemsetAsync(counts, 0, (size_t)Z * sizeof(int64_t), s));
-  const unsigned pack_blocks = mp_blocks(d.words * 4);
-  if ((X % 16) == 0 && aligned(mask, 16)) hipLaunchKernelGGL(morph_pack_kernel<true>, dim3(pack_blocks), dim3(TPB), 0, s, mask, d, cur);
+  const unsigned pack_blocks = vol_blocks(d.words * 4, GRID_CAP, TPB);
+  if ((X % 16) == 0 && vol_aligned(mask, 16)) hipLaunchKernelGGL(morph_pack_kernel<true>, dim3(pack_blocks), dim3(TPB), 0, s, mask, d, cur);
   else hipLaunchKernelGGL(morph_pack_kernel<false>, dim3(pack_blocks), dim3(TPB), 0, s, mask, d, cur);
   const u64 fill = border_value ? ~0ull : 0ull;
   const bool first_dilates = op == UNET_MORPH_DILATE || op == UNET_MORPH_CLOSE;
@@ -264,38 +231,39 @@ int32_t unet_vol_morph(unet_ctx* ctx, const uint8_t* mask, int32_t X, int32_t Y,
   for (int ph = 0; ph < phases; ++ph) {
     const bool dilate = (ph == 0) == first_dilates;
     for (int it = 0; it < iterations; ++it) {
-      if (dilate) hipLaunchKernelGGL(morph_step_kernel<true>, dim3(mp_blocks(d.words)), dim3(TPB), 0, s, cur, d, connectivity, planar ? 1 : 0, fill, nxt);
-      else hipLaunchKernelGGL(morph_step_kernel<false>, dim3(mp_blocks(d.words)), dim3(TPB), 0, s, cur, d, connectivity, planar ? 1 : 0, fill, nxt);
+      if (dilate) hipLaunchKernelGGL(morph_step_kernel<true>, dim3(vol_blocks(d.words, GRID_CAP, TPB)), dim3(TPB), 0, s, cur, d, connectivity, planar ? 1 : 0, fill, nxt);
+      else hipLaunchKernelGGL(morph_step_kernel<false>, dim3(vol_blocks(d.words, GRID_CAP, TPB)), dim3(TPB), 0, s, cur, d, connectivity, planar ? 1 : 0, fill, nxt);
       u64* t = cur; cur = nxt; nxt = t;
     }
   }
   const int bps = slice_blocks((long long)Y * d.WX * 4, TPB);
   u64* cnt = reinterpret_cast<u64*>(counts);
-  if ((X % 16) == 0 && aligned(out, 16)) hipLaunchKernelGGL(morph_unpack_kernel<true>, dim3((unsigned)bps * Z), dim3(TPB), 0, s, cur, d, bps, out, cnt);
+  if ((X % 16) == 0 && vol_aligned(out, 16)) hipLaunchKernelGGL(morph_unpack_kernel<true>, dim3((unsigned)bps * Z), dim3(TPB), 0, s, cur, d, bps, out, cnt);
   else hipLaunchKernelGGL(morph_unpack_kernel<false>, dim3((unsigned)bps * Z), dim3(TPB), 0, s, cur, d, bps, out, cnt);
   UNET_CHECK_LAUNCH(ctx, "vol_morph"); return UNET_OK;
 }
 
 int32_t unet_vol_ball(unet_ctx* ctx, const double* d2, int32_t X, int32_t Y, int32_t Z, double r2, int32_t keep_le, uint8_t* out, int64_t* counts, void* stream) {
   if (!ctx) UNET_FAIL(ctx, UNET_E_ARG, "vol_ball: bad args");
-  if (!mp_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_ball: %d x %d x %d is negative or has 2^31 voxels or more", X, Y, Z);
+  if (!vol_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_ball: %d x %d x %d is negative or has 2^31 voxels or more", X, Y, Z);
   if (!(r2 >= 0.0) || r2 > 1.7976931348623157e308) UNET_FAIL(ctx, UNET_E_ARG, "vol_ball: r2 must be finite and not negative");
-  const mp_dims d = mp_make(X, Y, Z);
+  const vol_bits d = vol_bits_make(X, Y, Z);
   if (d.N == 0) return UNET_OK;
-  if (!d2 || !out || !aligned(d2, 8) || (counts && !aligned(counts, 8))) UNET_FAIL(ctx, UNET_E_ARG, "vol_ball: null or misaligned buffer (d2 and counts 8 bytes)");
-  if (overlap(d2, (size_t)d.N * sizeof(double), out, (size_t)d.N)) UNET_FAIL(ctx, UNET_E_ARG, "vol_ball: out must not overlap d2");
+  if (!d2 || !out || !vol_aligned(d2, 8) || (counts && !vol_aligned(counts, 8))) UNET_FAIL(ctx, UNET_E_ARG, "vol_ball: null or misaligned buffer (d2 and counts 8 bytes)");
+  if (vol_overlap(d2, (size_t)d.N * sizeof(double), out, (size_t)d.N)) UNET_FAIL(ctx, UNET_E_ARG, "vol_ball: out must not overlap d2");
   hipStream_t s = as_stream(stream);
   if (counts) UNET_HIP(ctx, hipMemsetAsync(counts, 0, (size_t)Z * sizeof(int64_t), s));
   u64* cnt = reinterpret_cast<u64*>(counts);
-  const bool vec = (d.XY % 4) == 0 && aligned(d2, 16) && aligned(out, 4);
-  const int bps = slice_blocks(d.XY, vec ? (long long)TPB * 4 : TPB);
-  if (vec) hipLaunchKernelGGL(morph_ball_kernel<4>, dim3((unsigned)bps * Z), dim3(TPB), 0, s, d2, d.XY, bps, r2, keep_le ? 1 : 0, out, cnt);
-  else hipLaunchKernelGGL(morph_ball_kernel<1>, dim3((unsigned)bps * Z), dim3(TPB), 0, s, d2, d.XY, bps, r2, keep_le ? 1 : 0, out, cnt);
+  const long long XY = (long long)X * Y;
+  const bool vec = (XY % 4) == 0 && vol_aligned(d2, 16) && vol_aligned(out, 4);
+  const int bps = slice_blocks(XY, vec ? (long long)TPB * 4 : TPB);
+  if (vec) hipLaunchKernelGGL(morph_ball_kernel<4>, dim3((unsigned)bps * Z), dim3(TPB), 0, s, d2, XY, bps, r2, keep_le ? 1 : 0, out, cnt);
+  else hipLaunchKernelGGL(morph_ball_kernel<1>, dim3((unsigned)bps * Z), dim3(TPB), 0, s, d2, XY, bps, r2, keep_le ? 1 : 0, out, cnt);
   UNET_CHECK_LAUNCH(ctx, "vol_ball"); return UNET_OK;
 }
 
 size_t unet_vol_fill_holes_ws_bytes(int32_t X, int32_t Y, int32_t Z) {
-  if (!mp_dims_ok(X, Y, Z) || (long long)X * Y * Z == 0) return 0;
+  if (!vol_dims_ok(X, Y, Z) || (long long)X * Y * Z == 0) return 0;
   return fh_make(X, Y, Z).total;
 }
 
@@ -304,13 +272,13 @@ int32_t unet_vol_fill_holes(unet_ctx* ctx, const uint8_t* mask, int32_t X, int32
   if (!ctx) UNET_FAIL(ctx, UNET_E_ARG, "vol_fill_holes: bad args");
   if (connectivity < 1 || connectivity > (planar ? 2 : 3))
     UNET_FAIL(ctx, UNET_E_ARG, "vol_fill_holes: connectivity %d is not 1, 2%s", connectivity, planar ? " (a planar structure has no third axis)" : " or 3");
-  if (!mp_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_fill_holes: %d x %d x %d is negative or has 2^31 voxels or more", X, Y, Z);
-  const mp_dims d = mp_make(X, Y, Z);
+  if (!vol_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_fill_holes: %d x %d x %d is negative or has 2^31 voxels or more", X, Y, Z);
+  const vol_bits d = vol_bits_make(X, Y, Z);
   if (d.N == 0) return UNET_OK;
   if (!mask || !out || !ws) UNET_FAIL(ctx, UNET_E_ARG, "vol_fill_holes: bad args");
-  if (overlap(mask, (size_t)d.N, out, (size_t)d.N)) UNET_FAIL(ctx, UNET_E_ARG, "vol_fill_holes: out must not be (or overlap) the mask's buffer");
-  if (ws_bytes < unet_vol_fill_holes_ws_bytes(X, Y, Z) || !aligned(ws, 16)) UNET_FAIL(ctx, UNET_E_ARG, "vol_fill_holes: workspace too small or not 16-byte aligned");
-  if (counts && !aligned(counts, 8)) UNET_FAIL(ctx, UNET_E_ARG, "vol_fill_holes: counts is not 8-byte aligned");
+  if (vol_overlap(mask, (size_t)d.N, out, (size_t)d.N)) UNET_FAIL(ctx, UNET_E_ARG, "vol_fill_holes: out must not be (or overlap) the mask's buffer");
+  if (ws_bytes < unet_vol_fill_holes_ws_bytes(X, Y, Z) || !vol_aligned(ws, 16)) UNET_FAIL(ctx, UNET_E_ARG, "vol_fill_holes: workspace too small or not 16-byte aligned");
+  if (counts && !vol_aligned(counts, 8)) UNET_FAIL(ctx, UNET_E_ARG, "vol_fill_holes: counts is not 8-byte aligned");
   hipStream_t s = as_stream(stream);
   const fh_layout L = fh_make(X, Y, Z);
   uint8_t* base = static_cast<uint8_t*>(ws);
@@ -322,13 +290,13 @@ int32_t unet_vol_fill_holes(unet_ctx* ctx, const uint8_t* mask, int32_t X, int32
   if (rc != UNET_OK) return rc;
   UNET_HIP(ctx, hipMemsetAsync(touches, 0, (size_t)tsize, s));
   if (counts) UNET_HIP(ctx, hipMemsetAsync(counts, 0, (size_t)Z * sizeof(int64_t), s));
-  const long long FX = (long long)Y * Z, FY = (long long)X * Z, FZ = planar ? 0 : d.XY;
-  hipLaunchKernelGGL(fh_faces_kernel, dim3(mp_blocks(2 * (FX + FY + FZ))), dim3(TPB), 0, s, labels, d, FX, FY, FZ, tsize, touches);
+  const long long XY = (long long)X * Y, FX = (long long)Y * Z, FY = (long long)X * Z, FZ = planar ? 0 : XY;
+  hipLaunchKernelGGL(fh_faces_kernel, dim3(vol_blocks(2 * (FX + FY + FZ), GRID_CAP, TPB)), dim3(TPB), 0, s, labels, d, FX, FY, FZ, tsize, touches);
   u64* cnt = reinterpret_cast<u64*>(counts);
-  const bool vec = (d.XY % 16) == 0 && aligned(out, 16);
-  const int bps = slice_blocks(d.XY, vec ? (long long)TPB * 16 : TPB);
-  if (vec) hipLaunchKernelGGL(fh_final_kernel<16>, dim3((unsigned)bps * Z), dim3(TPB), 0, s, labels, touches, tsize, d.XY, bps, out, cnt);
-  else hipLaunchKernelGGL(fh_final_kernel<1>, dim3((unsigned)bps * Z), dim3(TPB), 0, s, labels, touches, tsize, d.XY, bps, out, cnt);
+  const bool vec = (XY % 16) == 0 && vol_aligned(out, 16);
+  const int bps = slice_blocks(XY, vec ? (long long)TPB * 16 : TPB);
+  if (vec) hipLaunchKernelGGL(fh_final_kernel<16>, dim3((unsigned)bps * Z), dim3(TPB), 0, s, labels, touches, tsize, XY, bps, out, cnt);
+  else hipLaunchKernelGGL(fh_final_kernel<1>, dim3((unsigned)bps * Z), dim3(TPB), 0, s, labels, touches, tsize, XY, bps, out, cnt);
   UNET_CHECK_LAUNCH(ctx, "vol_fill_holes"); return UNET_OK;
 }
 

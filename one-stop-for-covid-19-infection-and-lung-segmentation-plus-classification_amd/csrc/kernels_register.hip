@@ -30,7 +30,7 @@ __device__ __forceinline__ int jh_bin(double v, const jh_window& w, int B) {
   return !(q >= 0.0) ? 0 : (q >= (double)B ? B - 1 : (int)floor(q));
 }
 
-__global__ __launch_bounds__(TPB) void jh_kernel(rs_src fix, const uint8_t* __restrict__ mask, int X, int Y, int Z, rs_src mov, int Xm, int Ym, int Zm, jh_mats mats, int B,
+__global__ __launch_bounds__(TPB) void jh_kernel(vol_voxels fix, const uint8_t* __restrict__ mask, int X, int Y, int Z, vol_voxels mov, int Xm, int Ym, int Zm, jh_mats mats, int B,
                                                  jh_window wf, jh_window wm, uint32_t* __restrict__ counts) {
   __shared__ uint32_t hist[MAX_BINS * MAX_BINS];
   const int cells = B * B, lane = threadIdx.x & 63;
@@ -44,7 +44,7 @@ __global__ __launch_bounds__(TPB) void jh_kernel(rs_src fix, const uint8_t* __re
     bool ok = o < N && (!mask || mask[o] != 0);
     int cell = 0;
     if (ok) {
-      const double fv = rs_dec(fix, o);
+      const double fv = vol_dec(fix, o);
       const long long c = o / X;
       const int i = (int)(o - c * X), k = (int)(c / Y), j = (int)(c - (long long)k * Y);
       double s[3];
@@ -86,7 +86,7 @@ int32_t unet_vol_joint_hist(unet_ctx* ctx, const void* fixed, int32_t f_dtype, i
   if (K < 1 || K > MAX_K) UNET_FAIL(ctx, UNET_E_ARG, "vol_joint_hist: %d candidates, not 1 to %d", K, MAX_K);
   if (bins < 2 || bins > MAX_BINS) UNET_FAIL(ctx, UNET_E_ARG, "vol_joint_hist: %d bins, not 2 to %d", bins, MAX_BINS);
   if (!jh_vol_ok(X, Y, Z) || !jh_vol_ok(Xm, Ym, Zm)) UNET_FAIL(ctx, UNET_E_ARG, "vol_joint_hist: a volume of %d x %d x %d and one of %d x %d x %d (every extent is at least 1, fewer than 2^31 voxels)", X, Y, Z, Xm, Ym, Zm);
-  if (rs_itemsize(f_dtype) == 0 || rs_itemsize(m_dtype) == 0) UNET_FAIL(ctx, UNET_E_ARG, "vol_joint_hist: a NIfTI datatype code is not one of 2, 256, 4, 512, 8, 768, 16, 64");
+  if (vol_itemsize(f_dtype) == 0 || vol_itemsize(m_dtype) == 0) UNET_FAIL(ctx, UNET_E_ARG, "vol_joint_hist: a NIfTI datatype code is not one of 2, 256, 4, 512, 8, 768, 16, 64");
   if (!std::isfinite(f_lo) || !std::isfinite(f_hi) || !std::isfinite(m_lo) || !std::isfinite(m_hi) || !(f_hi > f_lo) || !(m_hi > m_lo))
     UNET_FAIL(ctx, UNET_E_ARG, "vol_joint_hist: a window is two finite numbers lo < hi");
   const jh_window wf{f_lo, (double)bins / (f_hi - f_lo)}, wm{m_lo, (double)bins / (m_hi - m_lo)};
@@ -98,13 +98,13 @@ int32_t unet_vol_joint_hist(unet_ctx* ctx, const void* fixed, int32_t f_dtype, i
       if (!std::isfinite(M[12 * c + i])) UNET_FAIL(ctx, UNET_E_ARG, "vol_joint_hist: entry %d of matrix %d is not finite", i, c);
       mats.M[c].m[i] = M[12 * c + i];
     }
-  if (!fixed || (reinterpret_cast<uintptr_t>(fixed) % rs_itemsize(f_dtype)) != 0 || !moving || (reinterpret_cast<uintptr_t>(moving) % rs_itemsize(m_dtype)) != 0 || !counts ||
+  if (!fixed || (reinterpret_cast<uintptr_t>(fixed) % vol_itemsize(f_dtype)) != 0 || !moving || (reinterpret_cast<uintptr_t>(moving) % vol_itemsize(m_dtype)) != 0 || !counts ||
       (reinterpret_cast<uintptr_t>(counts) % sizeof(uint32_t)) != 0)
     UNET_FAIL(ctx, UNET_E_ARG, "vol_joint_hist: a null buffer, or one not aligned to its element size");
   hipStream_t s = as_stream(stream);
   UNET_HIP(ctx, hipMemsetAsync(counts, 0, (size_t)K * bins * bins * sizeof(uint32_t), s));
   const long long N = (long long)X * Y * Z, blocks = (N + TPB - 1) / TPB;
-  const rs_src fs{fixed, f_dtype, f_scaled ? 1 : 0, f_slope, f_inter}, ms{moving, m_dtype, m_scaled ? 1 : 0, m_slope, m_inter};
+  const vol_voxels fs{fixed, f_dtype, f_scaled ? 1 : 0, f_slope, f_inter}, ms{moving, m_dtype, m_scaled ? 1 : 0, m_slope, m_inter};
   hipLaunchKernelGGL(jh_kernel, dim3((unsigned)(blocks > GRID_CAP ? GRID_CAP : blocks), (unsigned)K), dim3(TPB), 0, s, fs, mask, X, Y, Z, ms, Xm, Ym, Zm, mats, bins, wf, wm, counts);
   UNET_CHECK_LAUNCH(ctx, "vol_joint_hist"); return UNET_OK;
 }

@@ -1,8 +1,8 @@
 // A picture of a segmented CT volume: the raw NIfTI voxels already on the device, decoded as get_fdata() decodes them, and up to four label volumes.
 //   the maximum / minimum of the CT and the largest label of every column of a slab along one axis                                 unet_vol_project
 //   one RGB canvas of up to 64 tiles: a windowed, colour-mapped plane per tile with the label layers blended and outlined on top     unet_vol_render
-// Volumes are [X, Y, Z] in Fortran order (f = x + X (y + Y z)), X Y Z < 2^31, as in kernels_intensity.hip, whose decode (iv_dec) is restated here.
-// Projection: max / min travel as the order-preserving 64-bit keys of kernels_intensity.hip (-0.0 below +0.0, a NaN never enters), so the result does not depend on the
+// Volumes are [X, Y, Z] in Fortran order (f = x + X (y + Y z)), X Y Z < 2^31, decoded by vol_common.h's vol_dec.
+// Projection: max / min travel as the order-preserving 64-bit keys of vol_common.h (-0.0 below +0.0, a NaN never enters), so the result does not depend on the
 // order of the walk.  Along y or z a lane owns one x and walks the slab: every load of a wave is one run of consecutive voxels.  Along x a wave owns one (y, z) column, its
 // lanes stride x (consecutive voxels again), the 64 partial results meet in a butterfly of __shfl_xor and lane 0 stores.
 // Canvas: a lane owns one canvas pixel, a workgroup 256 consecutive pixels of one canvas row; the tile list sits in the kernel arguments (no copy, nothing to synchronise)
@@ -11,6 +11,7 @@
 // nearest; a lane whose label is <= 0 in every layer reads no neighbour and blends nothing.  Stores: the four lanes of a group hold 12 bytes; where the canvas row starts on
 // a 4-byte boundary and all four write, three of them store one assembled dword each, otherwise every writing lane stores its three bytes.  Nothing is written past a row.
 #include "common.h"
+#include "vol_common.h"
 
 #include <cmath>
 
@@ -20,47 +21,18 @@ constexpr int MAX_TILES = UNET_RENDER_MAX_TILES;
 constexpr int MAX_LAYERS = UNET_RENDER_MAX_LAYERS;
 constexpr long long GRID_CAP = 256 * 32;
 
-inline bool rd_dims_ok(int X, int Y, int Z) { return X >= 0 && Y >= 0 && Z >= 0 && (long long)X * Y * Z < 0x80000000LL && (X == 0 || Y == 0 || (long long)X * Y < 0x80000000LL); }
-inline int rd_itemsize(int dt) {
-  switch (dt) { case 2: case 256: return 1; case 4: case 512: return 2; case 8: case 768: case 16: return 4; case 64: return 8; default: return 0; }
-}
-inline unsigned rd_blocks(long long items) { long long b = (items + TPB - 1) / TPB; return (unsigned)(b < 1 ? 1 : (b > GRID_CAP ? GRID_CAP : b)); }
-
-// ---- typed voxel access: kernels_intensity.hip's iv_dec (NIfTI-1 datatype codes; (float64(v) * slope) + inter, two rounded operations) ------------------------
-struct rd_src { const void* p; int dt; int scaled; double slope, inter; };
-__device__ __forceinline__ double rd_dec(const rd_src& s, long long i) {
-  double v;
-  switch (s.dt) {                                                     // (wave-uniform: one datatype per launch)
-    case 2: v = (double)static_cast<const uint8_t*>(s.p)[i]; break;
-    case 256: v = (double)static_cast<const int8_t*>(s.p)[i]; break;
-    case 4: v = (double)static_cast<const int16_t*>(s.p)[i]; break;
-    case 512: v = (double)static_cast<const uint16_t*>(s.p)[i]; break;
-    case 8: v = (double)static_cast<const int32_t*>(s.p)[i]; break;
-    case 768: v = (double)static_cast<const uint32_t*>(s.p)[i]; break;
-    case 16: v = (double)static_cast<const float*>(s.p)[i]; break;
-    default: v = static_cast<const double*>(s.p)[i]; break;           // 64
-  }
-  return s.scaled ? __dadd_rn(__dmul_rn(v, s.slope), s.inter) : v;
-}
 __device__ __forceinline__ int rd_label(const void* p, int i32, long long i) { return i32 ? static_cast<const int32_t*>(p)[i] : (int)static_cast<const uint8_t*>(p)[i]; }
-
-// order-preserving keys of the doubles (-0.0 below +0.0); no non-NaN value maps to 0 or to ~0, the two "nothing seen" marks
-__device__ __forceinline__ unsigned long long rd_d2ord(double d) {
-  const unsigned long long u = (unsigned long long)__double_as_longlong(d);
-  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double rd_ord2d(unsigned long long o) { return __longlong_as_double((long long)((o >> 63) ? (o & 0x7FFFFFFFFFFFFFFFull) : ~o)); }
 
 // ---- (a) projection -------------------------------------------------------------------------------------------------------------------------------------
 struct pj_args {
-  rd_src src;
+  vol_voxels src;
   const void* lab[MAX_LAYERS]; void* lab_out[MAX_LAYERS]; int lab_i32[MAX_LAYERS]; int n_lab;
   double* out;
   int X, Y, Z, axis, a, b, mode;
 };
 __device__ __forceinline__ unsigned long long pj_none(int mode) { return mode ? ~0ull : 0ull; }
 __device__ __forceinline__ unsigned long long pj_pick(unsigned long long acc, unsigned long long k, int mode) { return mode ? min(acc, k) : max(acc, k); }
-__device__ __forceinline__ double pj_value(unsigned long long key, int mode) { return key == pj_none(mode) ? __longlong_as_double(0x7FF8000000000000ll) : rd_ord2d(key); }
+__device__ __forceinline__ double pj_value(unsigned long long key, int mode) { return key == pj_none(mode) ? __longlong_as_double(0x7FF8000000000000ll) : vol_ord2d(key); }
 __device__ __forceinline__ void pj_store_label(void* out, int i32, long long o, int m) {
   if (i32) static_cast<int32_t*>(out)[o] = m; else static_cast<uint8_t*>(out)[o] = (uint8_t)m;
 }
@@ -74,8 +46,8 @@ __global__ __launch_bounds__(TPB) void pj_walk_kernel(pj_args A) {
     const long long q = o / A.X, base = (o - q * A.X) + qstride * q;
     unsigned long long key = pj_none(A.mode);
     for (int k = A.a; k < A.b; ++k) {
-      const double v = rd_dec(A.src, base + step * k);
-      if (v == v) key = pj_pick(key, rd_d2ord(v), A.mode);
+      const double v = vol_dec(A.src, base + step * k);
+      if (v == v) key = pj_pick(key, vol_d2ord(v), A.mode);
     }
     A.out[o] = pj_value(key, A.mode);
     for (int l = 0; l < A.n_lab; ++l) {
@@ -95,8 +67,8 @@ __global__ __launch_bounds__(TPB) void pj_wave_kernel(pj_args A) {
     const long long base = c * A.X;
     unsigned long long key = pj_none(A.mode);
     for (int x = A.a + lane; x < A.b; x += 64) {
-      const double v = rd_dec(A.src, base + x);
-      if (v == v) key = pj_pick(key, rd_d2ord(v), A.mode);
+      const double v = vol_dec(A.src, base + x);
+      if (v == v) key = pj_pick(key, vol_d2ord(v), A.mode);
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) key = pj_pick(key, __shfl_xor(key, o, 64), A.mode);
@@ -115,7 +87,7 @@ __global__ __launch_bounds__(TPB) void pj_wave_kernel(pj_args A) {
 // ---- (b) canvas ---------------------------------------------------------------------------------------------------------------------------------------
 struct rd_layer { const void* labels; const uint8_t* palette; int i32, P, fill, outline; };
 struct rd_args {
-  rd_src src;
+  vol_voxels src;
   int X, Y;
   int lo[3], n[3];                                                    // the region and its extents
   double wlo, whi;
@@ -158,14 +130,14 @@ __global__ __launch_bounds__(TPB) void rd_canvas_kernel(rd_args A) {
     const int c = rd_near(j, nu, T.w), r = rd_near(i, nv, T.h);
     double val;
     if (A.interp == 0) {
-      val = rd_dec(A.src, org + c * su - r * sv);
+      val = vol_dec(A.src, org + c * su - r * sv);
     } else {
       const double u = rd_pos(j, nu, T.w), v = rd_pos(i, nv, T.h);
       const double fu = floor(u), fv = floor(v), fx = __dsub_rn(u, fu), fy = __dsub_rn(v, fv);
       const int xi = (int)fu, yi = (int)fv;
       const int c0 = max(0, min(xi, nu - 1)), c1 = max(0, min(xi + 1, nu - 1)), r0 = max(0, min(yi, nv - 1)), r1 = max(0, min(yi + 1, nv - 1));
-      const double p00 = rd_dec(A.src, org + c0 * su - r0 * sv), p01 = rd_dec(A.src, org + c1 * su - r0 * sv);
-      const double p10 = rd_dec(A.src, org + c0 * su - r1 * sv), p11 = rd_dec(A.src, org + c1 * su - r1 * sv);
+      const double p00 = vol_dec(A.src, org + c0 * su - r0 * sv), p01 = vol_dec(A.src, org + c1 * su - r0 * sv);
+      const double p10 = vol_dec(A.src, org + c0 * su - r1 * sv), p11 = vol_dec(A.src, org + c1 * su - r1 * sv);
       const double top = __dadd_rn(p00, __dmul_rn(__dsub_rn(p01, p00), fx)), bot = __dadd_rn(p10, __dmul_rn(__dsub_rn(p11, p10), fx));
       val = __dadd_rn(top, __dmul_rn(__dsub_rn(bot, top), fy));
     }
@@ -216,8 +188,8 @@ int32_t unet_vol_project(unet_ctx* ctx, const void* vox, int32_t dtype, int32_t 
                          int32_t b, int32_t mode, const void* const* labels, const int32_t* label_dtypes, void* const* label_planes, int32_t n_labels, double* plane,
                          void* stream) {
   if (!ctx) return UNET_E_ARG;
-  if (!rd_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_project: a dimension is negative or the volume has 2^31 voxels or more");
-  if (rd_itemsize(dtype) == 0) UNET_FAIL(ctx, UNET_E_ARG, "vol_project: the NIfTI datatype code is not one of 2, 256, 4, 512, 8, 768, 16, 64");
+  if (!vol_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_project: a dimension is negative or the volume has 2^31 voxels or more");
+  if (vol_itemsize(dtype) == 0) UNET_FAIL(ctx, UNET_E_ARG, "vol_project: the NIfTI datatype code is not one of 2, 256, 4, 512, 8, 768, 16, 64");
   if (axis < 0 || axis > 2) UNET_FAIL(ctx, UNET_E_ARG, "vol_project: axis %d is not 0, 1 or 2", axis);
   if (mode < 0 || mode > 1) UNET_FAIL(ctx, UNET_E_ARG, "vol_project: mode %d is not 0 (max) or 1 (min)", mode);
   const int len = axis == 0 ? X : (axis == 1 ? Y : Z);
@@ -225,10 +197,10 @@ int32_t unet_vol_project(unet_ctx* ctx, const void* vox, int32_t dtype, int32_t 
   if (n_labels < 0 || n_labels > MAX_LAYERS || (n_labels > 0 && (!labels || !label_dtypes || !label_planes)))
     UNET_FAIL(ctx, UNET_E_ARG, "vol_project: 0 to %d label volumes are taken, not %d (or a null list)", MAX_LAYERS, n_labels);
   if ((long long)X * Y * Z == 0) UNET_FAIL(ctx, UNET_E_ARG, "vol_project: the volume has no voxels");
-  if (!vox || (reinterpret_cast<uintptr_t>(vox) % rd_itemsize(dtype)) != 0 || !plane || (reinterpret_cast<uintptr_t>(plane) % 8) != 0)
+  if (!vox || (reinterpret_cast<uintptr_t>(vox) % vol_itemsize(dtype)) != 0 || !plane || (reinterpret_cast<uintptr_t>(plane) % 8) != 0)
     UNET_FAIL(ctx, UNET_E_ARG, "vol_project: null voxel buffer or plane, or a buffer not aligned to its item size");
   pj_args A{};
-  A.src = rd_src{vox, dtype, scaled ? 1 : 0, slope, inter};
+  A.src = vol_voxels{vox, dtype, scaled ? 1 : 0, slope, inter};
   A.n_lab = n_labels;
   for (int l = 0; l < n_labels; ++l) {
     if (!labels[l]) continue;                                         // a null volume: nothing is read or written for it
@@ -241,8 +213,8 @@ int32_t unet_vol_project(unet_ctx* ctx, const void* vox, int32_t dtype, int32_t 
   A.out = plane;
   A.X = X; A.Y = Y; A.Z = Z; A.axis = axis; A.a = a; A.b = b; A.mode = mode;
   hipStream_t s = as_stream(stream);
-  if (axis == 0) hipLaunchKernelGGL(pj_wave_kernel, dim3(rd_blocks((long long)Y * Z * 64)), dim3(TPB), 0, s, A);
-  else hipLaunchKernelGGL(pj_walk_kernel, dim3(rd_blocks((long long)X * (axis == 1 ? Z : Y))), dim3(TPB), 0, s, A);
+  if (axis == 0) hipLaunchKernelGGL(pj_wave_kernel, dim3(vol_blocks((long long)Y * Z * 64, GRID_CAP, TPB)), dim3(TPB), 0, s, A);
+  else hipLaunchKernelGGL(pj_walk_kernel, dim3(vol_blocks((long long)X * (axis == 1 ? Z : Y), GRID_CAP, TPB)), dim3(TPB), 0, s, A);
   UNET_CHECK_LAUNCH(ctx, "vol_project"); return UNET_OK;
 }
 
@@ -250,8 +222,8 @@ int32_t unet_vol_render(unet_ctx* ctx, const void* vox, int32_t dtype, int32_t X
                         double lo, double hi, const uint8_t* table, int32_t interp, int32_t background, int32_t fill_background, const unet_render_layer* layers,
                         int32_t n_layers, const unet_render_tile* tiles, int32_t n_tiles, uint8_t* canvas, int32_t H, int32_t W, void* stream) {
   if (!ctx) return UNET_E_ARG;
-  if (!rd_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_render: a dimension is negative or the volume has 2^31 voxels or more");
-  if (rd_itemsize(dtype) == 0) UNET_FAIL(ctx, UNET_E_ARG, "vol_render: the NIfTI datatype code is not one of 2, 256, 4, 512, 8, 768, 16, 64");
+  if (!vol_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_render: a dimension is negative or the volume has 2^31 voxels or more");
+  if (vol_itemsize(dtype) == 0) UNET_FAIL(ctx, UNET_E_ARG, "vol_render: the NIfTI datatype code is not one of 2, 256, 4, 512, 8, 768, 16, 64");
   if (n_tiles < 0 || n_tiles > MAX_TILES || (n_tiles > 0 && !tiles)) UNET_FAIL(ctx, UNET_E_ARG, "vol_render: 0 to %d tiles are taken, not %d (or a null list)", MAX_TILES, n_tiles);
   if (n_layers < 0 || n_layers > MAX_LAYERS || (n_layers > 0 && !layers)) UNET_FAIL(ctx, UNET_E_ARG, "vol_render: 0 to %d layers are taken, not %d (or a null list)", MAX_LAYERS, n_layers);
   if (!roi) UNET_FAIL(ctx, UNET_E_ARG, "vol_render: no region");
@@ -263,9 +235,9 @@ int32_t unet_vol_render(unet_ctx* ctx, const void* vox, int32_t dtype, int32_t X
   if (interp < 0 || interp > 1) UNET_FAIL(ctx, UNET_E_ARG, "vol_render: interp %d is not 0 (nearest) or 1 (linear)", interp);
   if (background < 0 || background > 0xFFFFFF) UNET_FAIL(ctx, UNET_E_ARG, "vol_render: the background is 0xRRGGBB");
   if (H < 0 || W < 0 || (long long)H * W * 3 >= 0x80000000LL) UNET_FAIL(ctx, UNET_E_ARG, "vol_render: a canvas of %d x %d", H, W);
-  if (!vox || (reinterpret_cast<uintptr_t>(vox) % rd_itemsize(dtype)) != 0 || !table) UNET_FAIL(ctx, UNET_E_ARG, "vol_render: null voxel buffer or colour table, or voxels not aligned to their item size");
+  if (!vox || (reinterpret_cast<uintptr_t>(vox) % vol_itemsize(dtype)) != 0 || !table) UNET_FAIL(ctx, UNET_E_ARG, "vol_render: null voxel buffer or colour table, or voxels not aligned to their item size");
   rd_args A{};
-  A.src = rd_src{vox, dtype, scaled ? 1 : 0, slope, inter};
+  A.src = vol_voxels{vox, dtype, scaled ? 1 : 0, slope, inter};
   A.X = X; A.Y = Y;
   for (int d = 0; d < 3; ++d) { A.lo[d] = roi[2 * d]; A.n[d] = roi[2 * d + 1] - roi[2 * d]; }
   A.wlo = lo; A.whi = hi; A.table = table; A.interp = interp; A.fill_bg = fill_background ? 1 : 0;

@@ -1,6 +1,6 @@
 // A volume put onto another grid: spacing, shape, an oblique affine, a signed axis permutation.
 //   elements of 1, 2, 4 or 8 bytes moved untouched from the nearest source voxel                                       unet_vol_resample_nearest
-//   the decoded voxels (kernels_intensity.hip's iv_dec, restated here) blended trilinearly -> float64 / float32 / a uint8 mask      unet_vol_resample_linear
+//   the decoded voxels (vol_common.h's vol_dec) blended trilinearly -> float64 / float32 / a uint8 mask      unet_vol_resample_linear
 // Volumes are [X, Y, Z] in Fortran order (f = x + X (y + Y z)), X Y Z < 2^31 on both sides.  M (12 doubles, row-major 3 x 4, in the kernel arguments) maps an output
 // voxel index to a source voxel coordinate: s_r = ((M[r][0] i + M[r][1] j) + M[r][2] k) + M[r][3], every operation a rounded float64 one (-ffp-contract=off and the
 // __d*_rn forms: numpy restates them bit for bit).  A coordinate becomes an integer only after it was found inside [-1, n] as a double: |s| = 1e300 or a NaN (inf - inf
@@ -23,11 +23,9 @@ constexpr int TPB = 256;
 constexpr int TILE = 64;
 constexpr long long GRID_CAP = 256 * 32;
 
-inline unsigned rs_blocks(long long items) { long long b = (items + TPB - 1) / TPB; return (unsigned)(b < 1 ? 1 : (b > GRID_CAP ? GRID_CAP : b)); }
-
 struct rs_geom { rs_mat M; int X, Y, Z, mode; };
 
-// ---- nearest and linear: the coordinate, the decode and both samplers are vol_trilinear.h's (shared with kernels_register.hip and kernels_deform.hip) ----------------------
+// ---- nearest and linear: the coordinate and both samplers are vol_trilinear.h's, the decode vol_common.h's (shared with kernels_register.hip and kernels_deform.hip) --------
 template <typename T>
 struct rs_near {
   rs_geom g; const T* src; T cval;
@@ -39,7 +37,7 @@ struct rs_near {
 
 template <typename D>
 struct rs_lin {
-  rs_geom g; rs_src src; double cval;
+  rs_geom g; vol_voxels src; double cval;
   __device__ __forceinline__ D operator()(int i, int j, int k) const {
     const double s[3] = {rs_coord(g.M, 0, i, j, k), rs_coord(g.M, 1, i, j, k), rs_coord(g.M, 2, i, j, k)};
     return rs_store<D>(rs_linear_at(src, g.X, g.Y, g.Z, g.mode, cval, s));
@@ -99,7 +97,7 @@ inline int rs_lane_axis(const double* M, int Y2, int Z2) {
 template <typename T, typename Op>
 void rs_launch(const Op& op, void* dst, int X2, int Y2, int Z2, int a, hipStream_t s) {
   if (a == 0) {
-    hipLaunchKernelGGL((rs_direct_kernel<T, Op>), dim3(rs_blocks((long long)X2 * Y2 * Z2)), dim3(TPB), 0, s, op, static_cast<T*>(dst), X2, Y2, Z2);
+    hipLaunchKernelGGL((rs_direct_kernel<T, Op>), dim3(vol_blocks((long long)X2 * Y2 * Z2, GRID_CAP, TPB)), dim3(TPB), 0, s, op, static_cast<T*>(dst), X2, Y2, Z2);
     return;
   }
   const int tx = (X2 + TILE - 1) / TILE, ta = ((a == 1 ? Y2 : Z2) + TILE - 1) / TILE;
@@ -118,7 +116,7 @@ extern "C" {
 int32_t unet_vol_resample_nearest(unet_ctx* ctx, const void* src, int32_t elem_bytes, int32_t X, int32_t Y, int32_t Z, const double* M, int32_t mode, uint64_t cval_bits,
                                   void* dst, int32_t X2, int32_t Y2, int32_t Z2, void* stream) {
   if (!ctx) return UNET_E_ARG;
-  if (!rs_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_resample_nearest: a source dimension is negative or the source has 2^31 voxels or more");
+  if (!vol_dims_ok_or_empty(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_resample_nearest: a source dimension is negative or the source has 2^31 voxels or more");
   if (!rs_out_ok(X2, Y2, Z2)) UNET_FAIL(ctx, UNET_E_ARG, "vol_resample_nearest: an output of %d x %d x %d (every extent is at least 1, fewer than 2^31 voxels)", X2, Y2, Z2);
   if (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4 && elem_bytes != 8) UNET_FAIL(ctx, UNET_E_ARG, "vol_resample_nearest: elements of %d bytes, not 1, 2, 4 or 8", elem_bytes);
   if (mode < 0 || mode > 1) UNET_FAIL(ctx, UNET_E_ARG, "vol_resample_nearest: mode %d is not 0 (nearest edge) or 1 (constant)", mode);
@@ -142,18 +140,18 @@ int32_t unet_vol_resample_nearest(unet_ctx* ctx, const void* src, int32_t elem_b
 int32_t unet_vol_resample_linear(unet_ctx* ctx, const void* vox, int32_t dtype, int32_t X, int32_t Y, int32_t Z, int32_t scaled, double slope, double inter, const double* M,
                                  int32_t mode, double cval, void* dst, int32_t dst_dtype, int32_t X2, int32_t Y2, int32_t Z2, void* stream) {
   if (!ctx) return UNET_E_ARG;
-  if (!rs_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_resample_linear: a source dimension is negative or the source has 2^31 voxels or more");
+  if (!vol_dims_ok_or_empty(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_resample_linear: a source dimension is negative or the source has 2^31 voxels or more");
   if (!rs_out_ok(X2, Y2, Z2)) UNET_FAIL(ctx, UNET_E_ARG, "vol_resample_linear: an output of %d x %d x %d (every extent is at least 1, fewer than 2^31 voxels)", X2, Y2, Z2);
-  if (rs_itemsize(dtype) == 0) UNET_FAIL(ctx, UNET_E_ARG, "vol_resample_linear: the NIfTI datatype code is not one of 2, 256, 4, 512, 8, 768, 16, 64");
+  if (vol_itemsize(dtype) == 0) UNET_FAIL(ctx, UNET_E_ARG, "vol_resample_linear: the NIfTI datatype code is not one of 2, 256, 4, 512, 8, 768, 16, 64");
   if (dst_dtype != 64 && dst_dtype != 16 && dst_dtype != 2) UNET_FAIL(ctx, UNET_E_ARG, "vol_resample_linear: dst_dtype %d is not 64 (float64), 16 (float32) or 2 (uint8 mask)", dst_dtype);
   if (mode < 0 || mode > 1) UNET_FAIL(ctx, UNET_E_ARG, "vol_resample_linear: mode %d is not 0 (nearest edge) or 1 (constant)", mode);
   const bool empty = (long long)X * Y * Z == 0;
   if (empty && mode == 0) UNET_FAIL(ctx, UNET_E_ARG, "vol_resample_linear: the source has no voxels and mode 0 has no edge to repeat");
   rs_geom g{};
   if (!M || !rs_fill_geom(g, M, X, Y, Z, mode)) UNET_FAIL(ctx, UNET_E_ARG, "vol_resample_linear: M is 12 finite doubles");
-  if ((!empty && (!vox || (reinterpret_cast<uintptr_t>(vox) % rs_itemsize(dtype)) != 0)) || !dst || (reinterpret_cast<uintptr_t>(dst) % rs_itemsize(dst_dtype)) != 0)
+  if ((!empty && (!vox || (reinterpret_cast<uintptr_t>(vox) % vol_itemsize(dtype)) != 0)) || !dst || (reinterpret_cast<uintptr_t>(dst) % vol_itemsize(dst_dtype)) != 0)
     UNET_FAIL(ctx, UNET_E_ARG, "vol_resample_linear: a null buffer, or one not aligned to its element size");
-  const rs_src sv{vox, dtype, scaled ? 1 : 0, slope, inter};
+  const vol_voxels sv{vox, dtype, scaled ? 1 : 0, slope, inter};
   hipStream_t s = as_stream(stream);
   const int a = rs_lane_axis(M, Y2, Z2);
   switch (dst_dtype) {

@@ -10,7 +10,7 @@
 // one register over the 27-bit cube (the centre as bit 13, always clear): a 26-dilation inside the cube is three shifts pairs -- x by 1, y by 3, z by 9, the x and y shifts
 // masked so that no bit leaves its row or plane -- applied one after the other, a 6-dilation the union of the three; the fill repeats until it stops growing.  Those six
 // masks take the place of a table of 26 adjacency constants: they are the same adjacency, and no lane reads memory for them.
-// Thinning: kernels_morph.hip's packed layout -- word wi of row (y, z) holds the voxels x = 64 wi .. 64 wi + 63, bit b voxel 64 wi + b, rows padded to words, no bit at or
+// Thinning: vol_common.h's packed layout (vol_bits) -- word wi of row (y, z) holds the voxels x = 64 wi .. 64 wi + 63, bit b voxel 64 wi + b, rows padded to words, no bit at or
 // beyond X.  The workspace holds the image P and the candidates Q.  One lane per word; the rows (y +- 1, z +- 1) and the edge bits of the x-adjacent words are gathered as
 // gd_step_kernel gathers them.  A word with no set bit reads no neighbour; a word with no border bit in the pass's direction (no candidate of the sub-pass) does no
 // predicate work.
@@ -29,6 +29,7 @@
 // Label spread: a launch of step s writes only labels of voxels with arrival == s and reads only labels of voxels with arrival == s - 1; the two sets are disjoint, so the
 // result does not depend on the order the lanes run in.
 #include "common.h"
+#include "vol_common.h"
 
 namespace {
 typedef unsigned long long u64;
@@ -72,27 +73,7 @@ __host__ __device__ inline bool sk_simple(uint32_t n26) {
   return (c6 & ~f) == 0;
 }
 
-// ---- the packed image ---------------------------------------------------------------------------------------------------------------------------
-struct sk_dims { int X, Y, Z, WX; long long N, words; };              // WX words per row, words = WX Y Z
-inline sk_dims sk_make(int X, int Y, int Z) { const int WX = (X + 63) / 64; return {X, Y, Z, WX, (long long)X * Y * Z, (long long)WX * Y * Z}; }
-inline bool sk_dims_ok(int X, int Y, int Z) {                        // X Y < 2^31 first: with it X Y Z fits 64 bits
-  if (X < 0 || Y < 0 || Z < 0) return false;
-  const long long XY = (long long)X * Y;
-  return XY < 0x80000000LL && XY * Z < 0x80000000LL;
-}
-inline bool sk_aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
-inline bool sk_overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t p = reinterpret_cast<uintptr_t>(a), q = reinterpret_cast<uintptr_t>(b);
-  return p < q + nb && q < p + na;
-}
-inline size_t sk_pad16(size_t b) { return (b + 15) / 16 * 16; }
-struct sk_layout { size_t plane, total; };                            // the workspace: P | Q
-inline sk_layout sk_layout_of(const sk_dims& d) { const size_t p = sk_pad16((size_t)d.words * sizeof(u64)); return {p, 2 * p}; }
-
-__host__ __device__ __forceinline__ u64 sk_load(const u64* P, const sk_dims& d, int wi, int y, int z) {          // every word outside the volume reads as 0
-  if (wi < 0 || wi >= d.WX || y < 0 || y >= d.Y || z < 0 || z >= d.Z) return 0ull;
-  return P[wi + (long long)d.WX * (y + (long long)d.Y * z)];
-}
+// ---- the packed image (vol_common.h's vol_bits; the workspace is P | Q) ----------------------------------------------------------------------------------------------------
 __host__ __device__ __forceinline__ int sk_popc64(u64 v) {
 #if defined(__HIP_DEVICE_COMPILE__)
   return __popcll(v);
@@ -117,11 +98,11 @@ __host__ __device__ __forceinline__ int sk_ctz64(u64 v) {             // v != 0
 
 // the nine rows around a word: c = the word, l / r = the same row seen from x - 1 / x + 1 (bit b = voxel 64 wi + b -+ 1, across the word's edges)
 struct sk_rows { u64 c[9], l[9], r[9]; };
-__host__ __device__ __forceinline__ void sk_gather(const u64* P, const sk_dims& d, int wi, int y, int z, sk_rows& R) {
+__host__ __device__ __forceinline__ void sk_gather(const u64* P, const vol_bits& d, int wi, int y, int z, sk_rows& R) {
 #pragma unroll
   for (int q = 0; q < 9; ++q) {
     const int yy = y + (q % 3) - 1, zz = z + (q / 3) - 1;
-    const u64 c = sk_load(P, d, wi, yy, zz), lo = sk_load(P, d, wi - 1, yy, zz), hi = sk_load(P, d, wi + 1, yy, zz);
+    const u64 c = vol_bits_load(P, d, wi, yy, zz), lo = vol_bits_load(P, d, wi - 1, yy, zz), hi = vol_bits_load(P, d, wi + 1, yy, zz);
     R.c[q] = c;
     R.l[q] = (c << 1) | (lo >> 63);
     R.r[q] = (c >> 1) | (hi << 63);
@@ -135,18 +116,18 @@ __host__ __device__ __forceinline__ uint32_t sk_code(const sk_rows& R, int b) { 
   return sk_compress(c27);
 }
 // the set voxels of word w whose neighbour in direction dir is clear or outside; dir: 0 +z, 1 -z, 2 +y, 3 -y, 4 +x, 5 -x (the order of the passes)
-__host__ __device__ __forceinline__ u64 sk_border(const u64* P, const sk_dims& d, u64 w, int wi, int y, int z, int dir) {
+__host__ __device__ __forceinline__ u64 sk_border(const u64* P, const vol_bits& d, u64 w, int wi, int y, int z, int dir) {
   switch (dir) {
-    case 0: return w & ~sk_load(P, d, wi, y, z + 1);
-    case 1: return w & ~sk_load(P, d, wi, y, z - 1);
-    case 2: return w & ~sk_load(P, d, wi, y + 1, z);
-    case 3: return w & ~sk_load(P, d, wi, y - 1, z);
-    case 4: return w & ~((w >> 1) | (sk_load(P, d, wi + 1, y, z) << 63));
-    default: return w & ~((w << 1) | (sk_load(P, d, wi - 1, y, z) >> 63));
+    case 0: return w & ~vol_bits_load(P, d, wi, y, z + 1);
+    case 1: return w & ~vol_bits_load(P, d, wi, y, z - 1);
+    case 2: return w & ~vol_bits_load(P, d, wi, y + 1, z);
+    case 3: return w & ~vol_bits_load(P, d, wi, y - 1, z);
+    case 4: return w & ~((w >> 1) | (vol_bits_load(P, d, wi + 1, y, z) << 63));
+    default: return w & ~((w << 1) | (vol_bits_load(P, d, wi - 1, y, z) >> 63));
   }
 }
 // the candidates of a direction pass in word `word` of P
-__host__ __device__ inline u64 sk_candidates_word(const u64* P, const sk_dims& d, long long word, int dir, int min_n26) {
+__host__ __device__ inline u64 sk_candidates_word(const u64* P, const vol_bits& d, long long word, int dir, int min_n26) {
   const u64 w = P[word];
   if (!w) return 0ull;
   const long long row = word / d.WX;
@@ -164,7 +145,7 @@ __host__ __device__ inline u64 sk_candidates_word(const u64* P, const sk_dims& d
   return cand;
 }
 // the candidates `cand` (of one subfield) of word `word` that are still simple in P
-__host__ __device__ inline u64 sk_recheck_word(const u64* P, const sk_dims& d, long long word, u64 cand) {
+__host__ __device__ inline u64 sk_recheck_word(const u64* P, const vol_bits& d, long long word, u64 cand) {
   const long long row = word / d.WX;
   const int wi = (int)(word - row * d.WX), z = (int)(row / d.Y), y = (int)(row - (long long)z * d.Y);
   sk_rows R;
@@ -184,7 +165,7 @@ __host__ __device__ __forceinline__ u64 sk_subfield_bits(int k, int y, int z) {
 
 // ---- thinning kernels ---------------------------------------------------------------------------------------------------------------------------
 // a wave per word: lane l holds voxel 64 wi + l, the ballot is the word
-__global__ __launch_bounds__(SK_TPB) void sk_pack_kernel(const uint8_t* __restrict__ vol, sk_dims d, u64* __restrict__ P, u64* __restrict__ Q) {
+__global__ __launch_bounds__(SK_TPB) void sk_pack_kernel(const uint8_t* __restrict__ vol, vol_bits d, u64* __restrict__ P, u64* __restrict__ Q) {
   const long long word = ((long long)blockIdx.x * SK_TPB + threadIdx.x) >> 6;          // wave-uniform
   if (word >= d.words) return;
   const int lane = threadIdx.x & 63;
@@ -194,7 +175,7 @@ __global__ __launch_bounds__(SK_TPB) void sk_pack_kernel(const uint8_t* __restri
   const u64 bits = __ballot(set);
   if (lane == 0) { P[word] = bits; Q[word] = 0ull; }
 }
-__global__ __launch_bounds__(SK_TPB) void sk_unpack_kernel(const u64* __restrict__ P, sk_dims d, uint8_t* __restrict__ vol) {
+__global__ __launch_bounds__(SK_TPB) void sk_unpack_kernel(const u64* __restrict__ P, vol_bits d, uint8_t* __restrict__ vol) {
   const long long word = ((long long)blockIdx.x * SK_TPB + threadIdx.x) >> 6;
   if (word >= d.words) return;
   const int lane = threadIdx.x & 63;
@@ -202,12 +183,12 @@ __global__ __launch_bounds__(SK_TPB) void sk_unpack_kernel(const u64* __restrict
   const int x = (int)(word - row * d.WX) * 64 + lane;
   if (x < d.X) vol[row * d.X + x] = (uint8_t)((P[word] >> lane) & 1ull);
 }
-__global__ __launch_bounds__(SK_TPB) void sk_candidates_kernel(const u64* __restrict__ P, u64* __restrict__ Q, sk_dims d, int dir, int min_n26) {
+__global__ __launch_bounds__(SK_TPB) void sk_candidates_kernel(const u64* __restrict__ P, u64* __restrict__ Q, vol_bits d, int dir, int min_n26) {
   const long long word = (long long)blockIdx.x * SK_TPB + threadIdx.x;
   if (word >= d.words) return;
   Q[word] = sk_candidates_word(P, d, word, dir, min_n26);
 }
-__global__ __launch_bounds__(SK_TPB) void sk_recheck_kernel(u64* __restrict__ P, const u64* __restrict__ Q, sk_dims d, int k, u64* __restrict__ removed) {
+__global__ __launch_bounds__(SK_TPB) void sk_recheck_kernel(u64* __restrict__ P, const u64* __restrict__ Q, vol_bits d, int k, u64* __restrict__ removed) {
   __shared__ int s_w[SK_TPB / 64];
   const long long word = (long long)blockIdx.x * SK_TPB + threadIdx.x;
   int cnt = 0;
@@ -237,7 +218,7 @@ __global__ __launch_bounds__(SK_TPB) void sk_recheck_kernel(u64* __restrict__ P,
 }
 
 // ---- the table ----------------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ u64 sk_word_of_bytes(const uint8_t* __restrict__ vol, const sk_dims& d, long long word, int lane) {
+__device__ __forceinline__ u64 sk_word_of_bytes(const uint8_t* __restrict__ vol, const vol_bits& d, long long word, int lane) {
   bool set = false;
   if (word < d.words) {
     const long long row = word / d.WX;
@@ -246,7 +227,7 @@ __device__ __forceinline__ u64 sk_word_of_bytes(const uint8_t* __restrict__ vol,
   }
   return __ballot(set);
 }
-__global__ __launch_bounds__(SK_TPB) void sk_count_kernel(const uint8_t* __restrict__ vol, sk_dims d, uint32_t* __restrict__ chunk_sums) {
+__global__ __launch_bounds__(SK_TPB) void sk_count_kernel(const uint8_t* __restrict__ vol, vol_bits d, uint32_t* __restrict__ chunk_sums) {
   __shared__ int s_w[SK_TPB / 64];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const long long base = (long long)blockIdx.x * SK_CHUNK + wv * 64;
@@ -286,7 +267,7 @@ __global__ __launch_bounds__(SK_TPB) void sk_scan_kernel(uint32_t* __restrict__ 
   }
   if (threadIdx.x == 0) *total = (long long)s_carry;
 }
-__global__ __launch_bounds__(SK_TPB) void sk_emit_kernel(const uint8_t* __restrict__ vol, sk_dims d, const uint32_t* __restrict__ chunk_off, const double* __restrict__ d2,
+__global__ __launch_bounds__(SK_TPB) void sk_emit_kernel(const uint8_t* __restrict__ vol, vol_bits d, const uint32_t* __restrict__ chunk_off, const double* __restrict__ d2,
                                                         long long capacity, int32_t* __restrict__ index, uint32_t* __restrict__ nbr, double* __restrict__ vals) {
   __shared__ unsigned s_cnt[SK_CHUNK], s_wt[SK_TPB / 64];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -335,7 +316,7 @@ __global__ __launch_bounds__(SK_TPB) void sk_emit_kernel(const uint8_t* __restri
 
 // ---- the label spread -----------------------------------------------------------------------------------------------------------------------------
 // generate_binary_structure(3, conn): (dx, dy, dz) moves along at most conn axes
-__global__ __launch_bounds__(SK_TPB) void sk_spread_kernel(const uint16_t* __restrict__ arrival, int32_t* __restrict__ labels, sk_dims d, int conn, unsigned step) {
+__global__ __launch_bounds__(SK_TPB) void sk_spread_kernel(const uint16_t* __restrict__ arrival, int32_t* __restrict__ labels, vol_bits d, int conn, unsigned step) {
   const long long f = (long long)blockIdx.x * SK_TPB + threadIdx.x;
   if (f >= d.N || arrival[f] != step) return;
   const long long row = f / d.X;
@@ -358,19 +339,19 @@ __global__ __launch_bounds__(SK_TPB) void sk_spread_kernel(const uint16_t* __res
 extern "C" {
 
 size_t unet_vol_thin_ws_bytes(int32_t X, int32_t Y, int32_t Z) {
-  if (!sk_dims_ok(X, Y, Z) || (long long)X * Y * Z == 0) return 0;
-  return sk_layout_of(sk_make(X, Y, Z)).total;
+  if (!vol_dims_ok(X, Y, Z) || (long long)X * Y * Z == 0) return 0;
+  return vol_bits_layout_of(vol_bits_make(X, Y, Z), 2).total;
 }
 
 int32_t unet_vol_thin_begin(unet_ctx* ctx, const uint8_t* mask, int32_t X, int32_t Y, int32_t Z, void* ws, size_t ws_bytes, void* stream) {
   if (!ctx) return UNET_E_ARG;
-  if (!sk_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_thin_begin: a dimension is negative or the volume has 2^31 voxels or more");
-  const sk_dims d = sk_make(X, Y, Z);
+  if (!vol_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_thin_begin: a dimension is negative or the volume has 2^31 voxels or more");
+  const vol_bits d = vol_bits_make(X, Y, Z);
   if (d.N == 0) return UNET_OK;
   if (!mask || !ws) UNET_FAIL(ctx, UNET_E_ARG, "vol_thin_begin: null buffer");
-  if (ws_bytes < unet_vol_thin_ws_bytes(X, Y, Z) || !sk_aligned(ws, 16)) UNET_FAIL(ctx, UNET_E_ARG, "vol_thin_begin: workspace too small or not 16-byte aligned");
-  const sk_layout L = sk_layout_of(d);
-  if (sk_overlap(mask, (size_t)d.N, ws, L.total)) UNET_FAIL(ctx, UNET_E_ARG, "vol_thin_begin: the mask must not overlap the workspace");
+  if (ws_bytes < unet_vol_thin_ws_bytes(X, Y, Z) || !vol_aligned(ws, 16)) UNET_FAIL(ctx, UNET_E_ARG, "vol_thin_begin: workspace too small or not 16-byte aligned");
+  const vol_bits_layout L = vol_bits_layout_of(d, 2);
+  if (vol_overlap(mask, (size_t)d.N, ws, L.total)) UNET_FAIL(ctx, UNET_E_ARG, "vol_thin_begin: the mask must not overlap the workspace");
   uint8_t* base = static_cast<uint8_t*>(ws);
   hipLaunchKernelGGL(sk_pack_kernel, dim3((unsigned)((d.words * 64 + SK_TPB - 1) / SK_TPB)), dim3(SK_TPB), 0, as_stream(stream), mask, d, reinterpret_cast<u64*>(base),
                      reinterpret_cast<u64*>(base + L.plane));
@@ -380,15 +361,15 @@ int32_t unet_vol_thin_begin(unet_ctx* ctx, const uint8_t* mask, int32_t X, int32
 int32_t unet_vol_thin_iterations(unet_ctx* ctx, int32_t X, int32_t Y, int32_t Z, int32_t first, int32_t n, int32_t endpoints, int64_t* removed, void* ws, size_t ws_bytes,
                                  void* stream) {
   if (!ctx) return UNET_E_ARG;
-  if (!sk_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_thin_iterations: a dimension is negative or the volume has 2^31 voxels or more");
+  if (!vol_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_thin_iterations: a dimension is negative or the volume has 2^31 voxels or more");
   if (first < 0 || n < 0 || (long long)first + n > 0x7FFFFFFFLL) UNET_FAIL(ctx, UNET_E_ARG, "vol_thin_iterations: first %d or n %d is negative (or their sum overflows)", first, n);
   if (endpoints != 0 && endpoints != 1) UNET_FAIL(ctx, UNET_E_ARG, "vol_thin_iterations: endpoints %d is not 0 or 1", endpoints);
-  const sk_dims d = sk_make(X, Y, Z);
+  const vol_bits d = vol_bits_make(X, Y, Z);
   if (d.N == 0 || n == 0) return UNET_OK;
-  if (!removed || !ws || !sk_aligned(removed, 8)) UNET_FAIL(ctx, UNET_E_ARG, "vol_thin_iterations: null or misaligned buffer");
-  if (ws_bytes < unet_vol_thin_ws_bytes(X, Y, Z) || !sk_aligned(ws, 16)) UNET_FAIL(ctx, UNET_E_ARG, "vol_thin_iterations: workspace too small or not 16-byte aligned");
-  const sk_layout L = sk_layout_of(d);
-  if (sk_overlap(removed + first, (size_t)n * 8, ws, L.total)) UNET_FAIL(ctx, UNET_E_ARG, "vol_thin_iterations: removed must not overlap the workspace");
+  if (!removed || !ws || !vol_aligned(removed, 8)) UNET_FAIL(ctx, UNET_E_ARG, "vol_thin_iterations: null or misaligned buffer");
+  if (ws_bytes < unet_vol_thin_ws_bytes(X, Y, Z) || !vol_aligned(ws, 16)) UNET_FAIL(ctx, UNET_E_ARG, "vol_thin_iterations: workspace too small or not 16-byte aligned");
+  const vol_bits_layout L = vol_bits_layout_of(d, 2);
+  if (vol_overlap(removed + first, (size_t)n * 8, ws, L.total)) UNET_FAIL(ctx, UNET_E_ARG, "vol_thin_iterations: removed must not overlap the workspace");
   hipStream_t s = as_stream(stream);
   uint8_t* base = static_cast<uint8_t*>(ws);
   u64 *P = reinterpret_cast<u64*>(base), *Q = reinterpret_cast<u64*>(base + L.plane);
@@ -404,33 +385,33 @@ int32_t unet_vol_thin_iterations(unet_ctx* ctx, int32_t X, int32_t Y, int32_t Z,
 
 int32_t unet_vol_thin_end(unet_ctx* ctx, int32_t X, int32_t Y, int32_t Z, uint8_t* out, const void* ws, size_t ws_bytes, void* stream) {
   if (!ctx) return UNET_E_ARG;
-  if (!sk_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_thin_end: a dimension is negative or the volume has 2^31 voxels or more");
-  const sk_dims d = sk_make(X, Y, Z);
+  if (!vol_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_thin_end: a dimension is negative or the volume has 2^31 voxels or more");
+  const vol_bits d = vol_bits_make(X, Y, Z);
   if (d.N == 0) return UNET_OK;
   if (!out || !ws) UNET_FAIL(ctx, UNET_E_ARG, "vol_thin_end: null buffer");
-  if (ws_bytes < unet_vol_thin_ws_bytes(X, Y, Z) || !sk_aligned(ws, 16)) UNET_FAIL(ctx, UNET_E_ARG, "vol_thin_end: workspace too small or not 16-byte aligned");
-  if (sk_overlap(out, (size_t)d.N, ws, sk_layout_of(d).total)) UNET_FAIL(ctx, UNET_E_ARG, "vol_thin_end: the output must not overlap the workspace");
+  if (ws_bytes < unet_vol_thin_ws_bytes(X, Y, Z) || !vol_aligned(ws, 16)) UNET_FAIL(ctx, UNET_E_ARG, "vol_thin_end: workspace too small or not 16-byte aligned");
+  if (vol_overlap(out, (size_t)d.N, ws, vol_bits_layout_of(d, 2).total)) UNET_FAIL(ctx, UNET_E_ARG, "vol_thin_end: the output must not overlap the workspace");
   hipLaunchKernelGGL(sk_unpack_kernel, dim3((unsigned)((d.words * 64 + SK_TPB - 1) / SK_TPB)), dim3(SK_TPB), 0, as_stream(stream), static_cast<const u64*>(ws), d, out);
   UNET_CHECK_LAUNCH(ctx, "vol_thin_end"); return UNET_OK;
 }
 
 size_t unet_vol_skeleton_ws_bytes(int32_t X, int32_t Y, int32_t Z) {
-  if (!sk_dims_ok(X, Y, Z) || (long long)X * Y * Z == 0) return 0;
-  const sk_dims d = sk_make(X, Y, Z);
-  return sk_pad16((size_t)((d.words + SK_CHUNK - 1) / SK_CHUNK) * sizeof(uint32_t));
+  if (!vol_dims_ok(X, Y, Z) || (long long)X * Y * Z == 0) return 0;
+  const vol_bits d = vol_bits_make(X, Y, Z);
+  return vol_pad16((size_t)((d.words + SK_CHUNK - 1) / SK_CHUNK) * sizeof(uint32_t));
 }
 
 int32_t unet_vol_skeleton_count(unet_ctx* ctx, const uint8_t* mask, int32_t X, int32_t Y, int32_t Z, int64_t* total, void* ws, size_t ws_bytes, void* stream) {
   if (!ctx) return UNET_E_ARG;
-  if (!sk_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_skeleton_count: a dimension is negative or the volume has 2^31 voxels or more");
-  if (!total || !sk_aligned(total, 8)) UNET_FAIL(ctx, UNET_E_ARG, "vol_skeleton_count: total is null or misaligned");
-  const sk_dims d = sk_make(X, Y, Z);
+  if (!vol_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_skeleton_count: a dimension is negative or the volume has 2^31 voxels or more");
+  if (!total || !vol_aligned(total, 8)) UNET_FAIL(ctx, UNET_E_ARG, "vol_skeleton_count: total is null or misaligned");
+  const vol_bits d = vol_bits_make(X, Y, Z);
   hipStream_t s = as_stream(stream);
   if (d.N == 0) { UNET_HIP(ctx, hipMemsetAsync(total, 0, sizeof(int64_t), s)); return UNET_OK; }
   if (!mask || !ws) UNET_FAIL(ctx, UNET_E_ARG, "vol_skeleton_count: null buffer");
-  if (ws_bytes < unet_vol_skeleton_ws_bytes(X, Y, Z) || !sk_aligned(ws, 16)) UNET_FAIL(ctx, UNET_E_ARG, "vol_skeleton_count: workspace too small or not 16-byte aligned");
+  if (ws_bytes < unet_vol_skeleton_ws_bytes(X, Y, Z) || !vol_aligned(ws, 16)) UNET_FAIL(ctx, UNET_E_ARG, "vol_skeleton_count: workspace too small or not 16-byte aligned");
   const long long chunks = (d.words + SK_CHUNK - 1) / SK_CHUNK;
-  if (sk_overlap(total, 8, ws, (size_t)chunks * 4) || sk_overlap(mask, (size_t)d.N, ws, (size_t)chunks * 4) || sk_overlap(mask, (size_t)d.N, total, 8))
+  if (vol_overlap(total, 8, ws, (size_t)chunks * 4) || vol_overlap(mask, (size_t)d.N, ws, (size_t)chunks * 4) || vol_overlap(mask, (size_t)d.N, total, 8))
     UNET_FAIL(ctx, UNET_E_ARG, "vol_skeleton_count: the mask, the total and the workspace must not overlap");
   uint32_t* cs = static_cast<uint32_t*>(ws);
   hipLaunchKernelGGL(sk_count_kernel, dim3((unsigned)chunks), dim3(SK_TPB), 0, s, mask, d, cs);
@@ -441,15 +422,15 @@ int32_t unet_vol_skeleton_count(unet_ctx* ctx, const uint8_t* mask, int32_t X, i
 int32_t unet_vol_skeleton_emit(unet_ctx* ctx, const uint8_t* mask, int32_t X, int32_t Y, int32_t Z, const double* d2, int64_t total, int64_t capacity, int32_t* index,
                                uint32_t* nbr, double* vals, const void* ws, size_t ws_bytes, void* stream) {
   if (!ctx) return UNET_E_ARG;
-  if (!sk_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_skeleton_emit: a dimension is negative or the volume has 2^31 voxels or more");
-  const sk_dims d = sk_make(X, Y, Z);
+  if (!vol_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_skeleton_emit: a dimension is negative or the volume has 2^31 voxels or more");
+  const vol_bits d = vol_bits_make(X, Y, Z);
   if (total < 0 || total > d.N || capacity < 0 || capacity >= 0x80000000LL) UNET_FAIL(ctx, UNET_E_ARG, "vol_skeleton_emit: total or capacity out of range");
   if (capacity < total) UNET_FAIL(ctx, UNET_E_ARG, "vol_skeleton_emit: capacity %lld is below the total %lld", (long long)capacity, (long long)total);
   if ((d2 == nullptr) != (vals == nullptr)) UNET_FAIL(ctx, UNET_E_ARG, "vol_skeleton_emit: d2 and vals are given together or not at all");
   if (d.N == 0 || total == 0) return UNET_OK;
-  if (!mask || !ws || !index || !nbr || !sk_aligned(index, 4) || !sk_aligned(nbr, 4) || !sk_aligned(d2, 8) || !sk_aligned(vals, 8))
+  if (!mask || !ws || !index || !nbr || !vol_aligned(index, 4) || !vol_aligned(nbr, 4) || !vol_aligned(d2, 8) || !vol_aligned(vals, 8))
     UNET_FAIL(ctx, UNET_E_ARG, "vol_skeleton_emit: null or misaligned buffer");
-  if (ws_bytes < unet_vol_skeleton_ws_bytes(X, Y, Z) || !sk_aligned(ws, 16)) UNET_FAIL(ctx, UNET_E_ARG, "vol_skeleton_emit: workspace too small or not 16-byte aligned");
+  if (ws_bytes < unet_vol_skeleton_ws_bytes(X, Y, Z) || !vol_aligned(ws, 16)) UNET_FAIL(ctx, UNET_E_ARG, "vol_skeleton_emit: workspace too small or not 16-byte aligned");
   const long long chunks = (d.words + SK_CHUNK - 1) / SK_CHUNK;
   const size_t cap = (size_t)capacity;
   const void* ins[3] = {mask, ws, d2};
@@ -459,9 +440,9 @@ int32_t unet_vol_skeleton_emit(unet_ctx* ctx, const uint8_t* mask, int32_t X, in
   for (int o = 0; o < 3; ++o) {
     if (!outs[o]) continue;
     for (int i = 0; i < 3; ++i)
-      if (ins[i] && sk_overlap(outs[o], out_bytes[o], ins[i], in_bytes[i])) UNET_FAIL(ctx, UNET_E_ARG, "vol_skeleton_emit: an output overlaps an input");
+      if (ins[i] && vol_overlap(outs[o], out_bytes[o], ins[i], in_bytes[i])) UNET_FAIL(ctx, UNET_E_ARG, "vol_skeleton_emit: an output overlaps an input");
     for (int p = o + 1; p < 3; ++p)
-      if (outs[p] && sk_overlap(outs[o], out_bytes[o], outs[p], out_bytes[p])) UNET_FAIL(ctx, UNET_E_ARG, "vol_skeleton_emit: two outputs overlap");
+      if (outs[p] && vol_overlap(outs[o], out_bytes[o], outs[p], out_bytes[p])) UNET_FAIL(ctx, UNET_E_ARG, "vol_skeleton_emit: two outputs overlap");
   }
   hipLaunchKernelGGL(sk_emit_kernel, dim3((unsigned)chunks), dim3(SK_TPB), 0, as_stream(stream), mask, d, static_cast<const uint32_t*>(ws), d2, (long long)capacity, index, nbr,
                      vals);
@@ -471,14 +452,14 @@ int32_t unet_vol_skeleton_emit(unet_ctx* ctx, const uint8_t* mask, int32_t X, in
 int32_t unet_vol_label_spread(unet_ctx* ctx, const uint16_t* arrival, int32_t* labels, int32_t X, int32_t Y, int32_t Z, int32_t first, int32_t n, int32_t connectivity,
                               void* stream) {
   if (!ctx) return UNET_E_ARG;
-  if (!sk_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_label_spread: a dimension is negative or the volume has 2^31 voxels or more");
+  if (!vol_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_label_spread: a dimension is negative or the volume has 2^31 voxels or more");
   if (connectivity < 1 || connectivity > 3) UNET_FAIL(ctx, UNET_E_ARG, "vol_label_spread: connectivity %d is not 1, 2 or 3", connectivity);
   if (first < 1 || n < 0 || (long long)first + n - 1 > UNET_VOL_GEODESIC_MAX_STEP)
     UNET_FAIL(ctx, UNET_E_ARG, "vol_label_spread: steps %d .. %lld are not inside 1 .. %d", first, (long long)first + n - 1, UNET_VOL_GEODESIC_MAX_STEP);
-  const sk_dims d = sk_make(X, Y, Z);
+  const vol_bits d = vol_bits_make(X, Y, Z);
   if (d.N == 0 || n == 0) return UNET_OK;
-  if (!arrival || !labels || !sk_aligned(arrival, 2) || !sk_aligned(labels, 4)) UNET_FAIL(ctx, UNET_E_ARG, "vol_label_spread: null or misaligned buffer");
-  if (sk_overlap(arrival, (size_t)d.N * 2, labels, (size_t)d.N * 4)) UNET_FAIL(ctx, UNET_E_ARG, "vol_label_spread: the labels must not overlap the arrival volume");
+  if (!arrival || !labels || !vol_aligned(arrival, 2) || !vol_aligned(labels, 4)) UNET_FAIL(ctx, UNET_E_ARG, "vol_label_spread: null or misaligned buffer");
+  if (vol_overlap(arrival, (size_t)d.N * 2, labels, (size_t)d.N * 4)) UNET_FAIL(ctx, UNET_E_ARG, "vol_label_spread: the labels must not overlap the arrival volume");
   hipStream_t s = as_stream(stream);
   const unsigned blocks = (unsigned)((d.N + SK_TPB - 1) / SK_TPB);
   for (int st = first; st < first + n; ++st) hipLaunchKernelGGL(sk_spread_kernel, dim3(blocks), dim3(SK_TPB), 0, s, arrival, labels, d, connectivity, (unsigned)st);

@@ -3,7 +3,7 @@
 //   the decoded CT -> grey levels 1..Ng (0 = takes no part) + their first-order histogram per group          unet_vol_texture_quantize
 //   C[g][k][a][b] += 1 for every voxel p and q = p + distance dir_k with levels a, b > 0 in one group g      unet_vol_texture_glcm
 //   R[g][k][a][min(len, max_run)] += 1 for every maximal run of one level and one group along dir_k          unet_vol_texture_runs
-// Volumes are [X, Y, Z] in Fortran order (f = x + X (y + Y z)), X Y Z < 2^31, decoded as kernels_intensity.hip decodes them.  The level of a non-NaN value is
+// Volumes are [X, Y, Z] in Fortran order (f = x + X (y + Y z)), X Y Z < 2^31, decoded by vol_common.h's vol_dec.  The level of a non-NaN value is
 // floor(fl(fl(v - lo) / width)), every operation rounded on its own (compiled with -ffp-contract=off like the other files that restate a float64 formula).
 // GLCM: persistent workgroups of 256 lanes walk bricks of 32 x 8 x 8 voxels, x fastest.  A brick is staged in LDS with a halo of `distance` on +x, +-y and +-z (the 13
 // directions all have dx >= 0), level and group per voxel, so the 13 neighbour reads of a voxel are LDS reads and a global byte is read about once.  A brick whose core
@@ -12,6 +12,7 @@
 // beyond that every add is a 64-bit global atomic.  Integer atomics only, no workgroup waits for another: the same bits on every run.
 // TEXTURE_GLCM_LDS=0 (make texture_loads, a measurement build that is never the product library) reads the neighbours straight from global memory instead.
 #include "common.h"
+#include "vol_common.h"
 
 #include <cmath>
 
@@ -36,34 +37,6 @@ constexpr int TQ_TABLE = 4096;                                       // (group, 
 constexpr long long GRID_CAP = 256 * 32;
 constexpr int8_t DIRS[NDIR][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}, {1, 1, 0}, {1, -1, 0}, {1, 0, 1}, {1, 0, -1}, {0, 1, 1}, {0, 1, -1}, {1, 1, 1}, {1, 1, -1}, {1, -1, 1}, {1, -1, -1}};
 
-inline bool tx_dims_ok(int X, int Y, int Z) { return X >= 0 && Y >= 0 && Z >= 0 && (long long)X * Y * Z < 0x80000000LL && (X == 0 || Y == 0 || (long long)X * Y < 0x80000000LL); }
-inline unsigned tx_blocks(long long items, long long cap) { long long b = (items + TPB - 1) / TPB; return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b)); }
-inline int tx_itemsize(int dt) {
-  switch (dt) { case 2: case 256: return 1; case 4: case 512: return 2; case 8: case 768: case 16: return 4; case 64: return 8; default: return 0; }
-}
-
-// ---- typed voxel access and groups: kernels_intensity.hip's iv_dec / iv_group ---------------------------------------------------------------------------
-struct tx_src { const void* p; int dt; int scaled; double slope, inter; };
-__device__ __forceinline__ double tx_dec(const tx_src& s, long long i) {
-  double v;
-  switch (s.dt) {                                                     // (wave-uniform: one datatype per launch)
-    case 2: v = (double)static_cast<const uint8_t*>(s.p)[i]; break;
-    case 256: v = (double)static_cast<const int8_t*>(s.p)[i]; break;
-    case 4: v = (double)static_cast<const int16_t*>(s.p)[i]; break;
-    case 512: v = (double)static_cast<const uint16_t*>(s.p)[i]; break;
-    case 8: v = (double)static_cast<const int32_t*>(s.p)[i]; break;
-    case 768: v = (double)static_cast<const uint32_t*>(s.p)[i]; break;
-    case 16: v = (double)static_cast<const float*>(s.p)[i]; break;
-    default: v = static_cast<const double*>(s.p)[i]; break;           // 64
-  }
-  return s.scaled ? __dadd_rn(__dmul_rn(v, s.slope), s.inter) : v;
-}
-struct tx_groups { const int32_t* labels; const uint8_t* mask; const uint8_t* region; int n; };
-__device__ __forceinline__ int tx_group(const tx_groups& g, long long i) {
-  if (g.region && g.region[i] == 0) return 0;
-  const int l = g.labels ? g.labels[i] : (g.mask[i] ? 1 : 0);
-  return (unsigned)(l - 1) < (unsigned)g.n ? l : 0;
-}
 // the two counting kernels: `levels` says whether a voxel takes part, `labels` (null: one group) which group it is in.  (level, group) of voxel f, (0, 0) when it takes
 // no part; a level above Ng or a label outside 1..n takes no part and is never an address.
 __device__ __forceinline__ void tx_voxel(const uint8_t* __restrict__ levels, const int32_t* __restrict__ labels, int n, int Ng, long long f, int& a, int& g) {
@@ -82,7 +55,7 @@ struct tx_dirlist { int count; int dx[NDIR], dy[NDIR], dz[NDIR]; };
 // A lane holds one voxel.  The lanes of a wave that share a (group, level) key are counted with one ballot (kernels_intensity.hip's ib_bands_kernel).  The loop bound and
 // the barriers are uniform over the workgroup.
 template <bool LDS_TABLE>
-__global__ __launch_bounds__(TPB) void tq_quantize_kernel(tx_src src, tx_groups grp, long long N, double lo, double width, int Ng, int drop, uint8_t* __restrict__ levels,
+__global__ __launch_bounds__(TPB) void tq_quantize_kernel(vol_voxels src, vol_groups grp, long long N, double lo, double width, int Ng, int drop, uint8_t* __restrict__ levels,
                                                          unsigned long long* __restrict__ level_counts) {
   __shared__ int s_tab[LDS_TABLE ? TQ_TABLE : 1];
   const int tid = threadIdx.x, lane = tid & 63, n = grp.n;
@@ -92,11 +65,11 @@ __global__ __launch_bounds__(TPB) void tq_quantize_kernel(tx_src src, tx_groups 
   }
   for (long long base = (long long)blockIdx.x * TPB; base < N; base += (long long)gridDim.x * TPB) {
     const long long i = base + tid;
-    const int g = i < N ? tx_group(grp, i) : 0;
+    const int g = i < N ? vol_group(grp, i) : 0;
     int lvl = 0;
     if (__ballot(g != 0)) {                                           // wave-uniform: most waves of a CT lie outside every lesion and never read a voxel
       if (g) {
-        const double v = tx_dec(src, i);
+        const double v = vol_dec(src, i);
         if (v == v) {
           const double q = floor(__ddiv_rn(__dsub_rn(v, lo), width));          // +-inf for an infinite v (lo is finite): clipped or dropped like any other q
           if (drop) { if (q >= 0.0 && q < (double)Ng) lvl = (int)q + 1; }
@@ -277,7 +250,7 @@ __global__ __launch_bounds__(TPB) void tr_runs_kernel(const uint8_t* __restrict_
 
 // the checks the two counting entry points share -> 0, or the message of the refusal
 const char* tx_count_refusal(int X, int Y, int Z, int n, int Ng, int directions) {
-  if (!tx_dims_ok(X, Y, Z)) return "a dimension is negative or the volume has 2^31 voxels or more";
+  if (!vol_dims_ok(X, Y, Z)) return "a dimension is negative or the volume has 2^31 voxels or more";
   if (n < 0) return "n is negative";
   if (Ng < 1 || Ng > MAX_LEVELS) return "Ng lies in 1 .. UNET_VOL_TEXTURE_MAX_LEVELS";
   if (directions <= 0 || (directions >> NDIR) != 0) return "directions is a non-empty set of the bits 0 .. 12";
@@ -303,8 +276,8 @@ int32_t unet_vol_texture_quantize(unet_ctx* ctx, const void* vox, int32_t dtype,
                                   const int32_t* labels, const uint8_t* mask, int32_t n, const uint8_t* region, double lo, double width, int32_t Ng, int32_t outside,
                                   uint8_t* levels, int64_t* level_counts, void* stream) {
   if (!ctx) return UNET_E_ARG;
-  if (!tx_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_texture_quantize: a dimension is negative or the volume has 2^31 voxels or more");
-  if (tx_itemsize(dtype) == 0) UNET_FAIL(ctx, UNET_E_ARG, "vol_texture_quantize: the NIfTI datatype code is not one of 2, 256, 4, 512, 8, 768, 16, 64");
+  if (!vol_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_texture_quantize: a dimension is negative or the volume has 2^31 voxels or more");
+  if (vol_itemsize(dtype) == 0) UNET_FAIL(ctx, UNET_E_ARG, "vol_texture_quantize: the NIfTI datatype code is not one of 2, 256, 4, 512, 8, 768, 16, 64");
   if ((labels != nullptr) == (mask != nullptr)) UNET_FAIL(ctx, UNET_E_ARG, "vol_texture_quantize: exactly one of labels and mask is given");
   if (n < 0) UNET_FAIL(ctx, UNET_E_ARG, "vol_texture_quantize: n is negative");
   if (Ng < 1 || Ng > MAX_LEVELS) UNET_FAIL(ctx, UNET_E_ARG, "vol_texture_quantize: 1 to %d levels are taken, not %d", MAX_LEVELS, Ng);
@@ -313,16 +286,16 @@ int32_t unet_vol_texture_quantize(unet_ctx* ctx, const void* vox, int32_t dtype,
   const long long N = (long long)X * Y * Z;
   if ((n > 0 && !level_counts) || (reinterpret_cast<uintptr_t>(level_counts) % 8) != 0 || (N > 0 && !levels))
     UNET_FAIL(ctx, UNET_E_ARG, "vol_texture_quantize: null or misaligned output");
-  if (N > 0 && (!vox || (reinterpret_cast<uintptr_t>(vox) % tx_itemsize(dtype)) != 0 || (labels && (reinterpret_cast<uintptr_t>(labels) % 4) != 0)))
+  if (N > 0 && (!vox || (reinterpret_cast<uintptr_t>(vox) % vol_itemsize(dtype)) != 0 || (labels && (reinterpret_cast<uintptr_t>(labels) % 4) != 0)))
     UNET_FAIL(ctx, UNET_E_ARG, "vol_texture_quantize: null voxel buffer, or a buffer not aligned to its item size");
   hipStream_t s = as_stream(stream);
   if (n > 0) UNET_HIP(ctx, hipMemsetAsync(level_counts, 0, (size_t)n * Ng * sizeof(int64_t), s));
   if (N == 0) return UNET_OK;
-  const tx_src src{vox, dtype, scaled ? 1 : 0, slope, inter};
-  const tx_groups grp{labels, mask, region, n};
+  const vol_voxels src{vox, dtype, scaled ? 1 : 0, slope, inter};
+  const vol_groups grp{labels, mask, region, n};
   unsigned long long* lc = reinterpret_cast<unsigned long long*>(level_counts);
-  if ((long long)n * Ng <= TQ_TABLE) hipLaunchKernelGGL(tq_quantize_kernel<true>, dim3(tx_blocks(N, GRID_CAP)), dim3(TPB), 0, s, src, grp, N, lo, width, Ng, outside, levels, lc);
-  else hipLaunchKernelGGL(tq_quantize_kernel<false>, dim3(tx_blocks(N, GRID_CAP)), dim3(TPB), 0, s, src, grp, N, lo, width, Ng, outside, levels, lc);
+  if ((long long)n * Ng <= TQ_TABLE) hipLaunchKernelGGL(tq_quantize_kernel<true>, dim3(vol_blocks(N, GRID_CAP, TPB)), dim3(TPB), 0, s, src, grp, N, lo, width, Ng, outside, levels, lc);
+  else hipLaunchKernelGGL(tq_quantize_kernel<false>, dim3(vol_blocks(N, GRID_CAP, TPB)), dim3(TPB), 0, s, src, grp, N, lo, width, Ng, outside, levels, lc);
   UNET_CHECK_LAUNCH(ctx, "vol_texture_quantize"); return UNET_OK;
 }
 
@@ -372,7 +345,7 @@ int32_t unet_vol_texture_runs(unet_ctx* ctx, const uint8_t* levels, const int32_
     UNET_HIP(ctx, hipMemsetAsync(clamped, 0, (size_t)rows * sizeof(int64_t), s));
   }
   if (N == 0 || n == 0) return UNET_OK;
-  hipLaunchKernelGGL(tr_runs_kernel, dim3(tx_blocks(N, GRID_CAP)), dim3(TPB), 0, s, levels, labels, n, X, Y, Z, Ng, dl, max_run, N, reinterpret_cast<unsigned long long*>(counts),
+  hipLaunchKernelGGL(tr_runs_kernel, dim3(vol_blocks(N, GRID_CAP, TPB)), dim3(TPB), 0, s, levels, labels, n, X, Y, Z, Ng, dl, max_run, N, reinterpret_cast<unsigned long long*>(counts),
                      reinterpret_cast<unsigned long long*>(clamped));
   UNET_CHECK_LAUNCH(ctx, "vol_texture_runs"); return UNET_OK;
 }

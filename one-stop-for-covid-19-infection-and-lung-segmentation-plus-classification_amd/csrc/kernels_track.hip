@@ -12,6 +12,7 @@
 // rest go per lane.  A workgroup walks a contiguous range of chunks of UNET_VOL_PAIRS_CHUNK voxels and counts in an LDS table of UNET_VOL_PAIRS_LDS_SLOTS slots first (at
 // most PAIRS_LDS_PROBES probes; a pair that finds no slot there goes straight to the global table); the LDS table is flushed when the range ends.
 #include "common.h"
+#include "vol_common.h"
 
 #include <vector>
 
@@ -24,9 +25,6 @@ constexpr int PAIRS_LDS_PROBES = 16;
 constexpr int TRACK_GRID = 256 * 4;                                  // workgroups of either launch
 constexpr unsigned long long HASH_MUL = 0x9E3779B97F4A7C15ull;       // 2^64 / the golden ratio: the top bits of key * HASH_MUL spread consecutive keys
 static_assert((1 << PAIRS_SLOTS_LOG) == PAIRS_SLOTS && PAIRS_SLOTS < PAIRS_CHUNK && PAIRS_CHUNK % (TPB * 4) == 0, "the LDS stage is a power of two below a chunk");
-
-inline bool tk_dims_ok(int X, int Y, int Z) { return X >= 0 && Y >= 0 && Z >= 0 && (long long)X * Y * Z < 0x80000000LL && (X == 0 || Y == 0 || (long long)X * Y < 0x80000000LL); }
-inline bool tk_aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
 
 __device__ __forceinline__ int tk_clamp(int l, int n) { return (unsigned)l <= (unsigned)n ? l : 0; }          // n >= 0: a negative label is above it as unsigned
 __device__ __forceinline__ unsigned long long tk_key(int a, int b) { return ((unsigned long long)(unsigned)a << 32) | (unsigned)b; }
@@ -227,12 +225,12 @@ int32_t unet_vol_label_pairs(unet_ctx* ctx, const int32_t* labels_a, int32_t n_a
                              int64_t* counts, int64_t capacity, int64_t* info, void* stream) {
   if (!ctx) return UNET_E_ARG;
   if (n_a < 0 || n_b < 0) UNET_FAIL(ctx, UNET_E_ARG, "vol_label_pairs: n_a, n_b are not negative");
-  if (!tk_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_label_pairs: %d x %d x %d is negative or has 2^31 voxels or more", X, Y, Z);
+  if (!vol_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_label_pairs: %d x %d x %d is negative or has 2^31 voxels or more", X, Y, Z);
   if (capacity < 16 || capacity > (1LL << 30) || (capacity & (capacity - 1)) != 0)
     UNET_FAIL(ctx, UNET_E_ARG, "vol_label_pairs: capacity %lld is not a power of two in 16 .. 2^30", (long long)capacity);
-  if (!keys || !counts || !info || !tk_aligned(keys, 8) || !tk_aligned(counts, 8) || !tk_aligned(info, 8)) UNET_FAIL(ctx, UNET_E_ARG, "vol_label_pairs: null or misaligned table");
+  if (!keys || !counts || !info || !vol_aligned(keys, 8) || !vol_aligned(counts, 8) || !vol_aligned(info, 8)) UNET_FAIL(ctx, UNET_E_ARG, "vol_label_pairs: null or misaligned table");
   const long long N = (long long)X * Y * Z;
-  if (N > 0 && (!labels_a || !labels_b || !tk_aligned(labels_a, 4) || !tk_aligned(labels_b, 4))) UNET_FAIL(ctx, UNET_E_ARG, "vol_label_pairs: null or misaligned label volume");
+  if (N > 0 && (!labels_a || !labels_b || !vol_aligned(labels_a, 4) || !vol_aligned(labels_b, 4))) UNET_FAIL(ctx, UNET_E_ARG, "vol_label_pairs: null or misaligned label volume");
   hipStream_t s = as_stream(stream);
   UNET_HIP(ctx, hipMemsetAsync(keys, 0, (size_t)capacity * sizeof(uint64_t), s));
   UNET_HIP(ctx, hipMemsetAsync(counts, 0, (size_t)capacity * sizeof(int64_t), s));
@@ -243,7 +241,7 @@ int32_t unet_vol_label_pairs(unet_ctx* ctx, const int32_t* labels_a, int32_t n_a
   const long long chunks = (N + PAIRS_CHUNK - 1) / PAIRS_CHUNK;
   const long long per = (chunks + TRACK_GRID - 1) / TRACK_GRID;
   const unsigned grid = (unsigned)((chunks + per - 1) / per);
-  const int vec = tk_aligned(labels_a, 16) && tk_aligned(labels_b, 16);
+  const int vec = vol_aligned(labels_a, 16) && vol_aligned(labels_b, 16);
   hipLaunchKernelGGL(pairs_kernel, dim3(grid), dim3(TPB), 0, s, labels_a, labels_b, N, n_a, n_b, vec, per, reinterpret_cast<unsigned long long*>(keys),
                      reinterpret_cast<unsigned long long*>(counts), (long long)capacity, cap_log, reinterpret_cast<unsigned long long*>(info));
   UNET_CHECK_LAUNCH(ctx, "vol_label_pairs"); return UNET_OK;
@@ -253,15 +251,15 @@ int32_t unet_vol_track_map(unet_ctx* ctx, const int32_t* labels_a, int32_t n_a, 
                            const int32_t* lut_b, const uint8_t* cls_a, const uint8_t* cls_b, uint8_t* cls, int32_t* track_a, int32_t* track_b, int64_t* per_slice, void* stream) {
   if (!ctx) return UNET_E_ARG;
   if (n_a < 0 || n_b < 0) UNET_FAIL(ctx, UNET_E_ARG, "vol_track_map: n_a, n_b are not negative");
-  if (!tk_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_track_map: %d x %d x %d is negative or has 2^31 voxels or more", X, Y, Z);
+  if (!vol_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_track_map: %d x %d x %d is negative or has 2^31 voxels or more", X, Y, Z);
   if (!cls && !track_a && !track_b && !per_slice) UNET_FAIL(ctx, UNET_E_ARG, "vol_track_map: no output");
-  if (!tk_aligned(track_a, 4) || !tk_aligned(track_b, 4) || !tk_aligned(per_slice, 8) || !tk_aligned(lut_a, 4) || !tk_aligned(lut_b, 4))
+  if (!vol_aligned(track_a, 4) || !vol_aligned(track_b, 4) || !vol_aligned(per_slice, 8) || !vol_aligned(lut_a, 4) || !vol_aligned(lut_b, 4))
     UNET_FAIL(ctx, UNET_E_ARG, "vol_track_map: misaligned buffer");
   const bool want_cls = cls || per_slice;
   if ((track_a && n_a > 0 && !lut_a) || (track_b && n_b > 0 && !lut_b) || (want_cls && ((n_a > 0 && !cls_a) || (n_b > 0 && !cls_b))))
     UNET_FAIL(ctx, UNET_E_ARG, "vol_track_map: an output is asked for without the table it is read from");
   const long long XY = (long long)X * Y, N = XY * Z;
-  if (N > 0 && (!labels_a || !labels_b || !tk_aligned(labels_a, 4) || !tk_aligned(labels_b, 4))) UNET_FAIL(ctx, UNET_E_ARG, "vol_track_map: null or misaligned label volume");
+  if (N > 0 && (!labels_a || !labels_b || !vol_aligned(labels_a, 4) || !vol_aligned(labels_b, 4))) UNET_FAIL(ctx, UNET_E_ARG, "vol_track_map: null or misaligned label volume");
   if (cls && ((const void*)cls == (const void*)labels_a || (const void*)cls == (const void*)labels_b)) UNET_FAIL(ctx, UNET_E_ARG, "vol_track_map: cls must not be a label volume's own buffer");
   hipStream_t s = as_stream(stream);
   if (want_cls) {                                                     // the class tables are small (n + 1 bytes): the host reads them before anything is written
@@ -282,8 +280,8 @@ int32_t unet_vol_track_map(unet_ctx* ctx, const int32_t* labels_a, int32_t n_a, 
   const long long chunks = (N + TM_CHUNK - 1) / TM_CHUNK;
   const long long per = (chunks + TRACK_GRID - 1) / TRACK_GRID;
   const unsigned grid = (unsigned)((chunks + per - 1) / per);
-  const int vec = ((tk_aligned(labels_a, 16) && tk_aligned(labels_b, 16)) ? TM_VEC_IN : 0) | (tk_aligned(cls, 4) ? TM_VEC_CLS : 0) | (tk_aligned(track_a, 16) ? TM_VEC_TA : 0) |
-                  (tk_aligned(track_b, 16) ? TM_VEC_TB : 0);
+  const int vec = ((vol_aligned(labels_a, 16) && vol_aligned(labels_b, 16)) ? TM_VEC_IN : 0) | (vol_aligned(cls, 4) ? TM_VEC_CLS : 0) | (vol_aligned(track_a, 16) ? TM_VEC_TA : 0) |
+                  (vol_aligned(track_b, 16) ? TM_VEC_TB : 0);
   hipLaunchKernelGGL(track_map_kernel, dim3(grid), dim3(TPB), 0, s, labels_a, labels_b, N, (unsigned)XY, n_a, n_b, lut_a, lut_b, cls_a, cls_b, vec, per, cls, track_a, track_b,
                      reinterpret_cast<unsigned long long*>(per_slice));
   UNET_CHECK_LAUNCH(ctx, "vol_track_map"); return UNET_OK;

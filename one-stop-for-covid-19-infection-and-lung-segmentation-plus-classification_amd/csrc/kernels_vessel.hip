@@ -10,6 +10,7 @@
 // barrier, so a lane ends them as soon as its three off-diagonals are exactly 0 (skipping a rotation whose pivot is 0 gives the same bits as running to the fifth sweep).
 // One launch per scale, no atomics, no workgroup waits for another, every output element written by one lane: the same bits on every run.
 #include "common.h"
+#include "vol_common.h"
 
 namespace {
 constexpr int TPB = 256;
@@ -171,15 +172,11 @@ __global__ __launch_bounds__(TPB) void vs_kernel(const float* __restrict__ L, co
 }
 
 bool vs_factor_ok(double v) { return v > 0.0 && v < __builtin_inf(); }          // (a NaN fails the first comparison)
-bool vs_overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-  return pa < pb + nb && pb < pa + na;
-}
 
 // the checks both entries share -> UNET_OK and N, or the refusal
 int32_t vs_check(unet_ctx* ctx, const char* what, const float* L, int X, int Y, int Z, const double* k, long long* N) {
   if (!ctx) return UNET_E_ARG;
-  if (X <= 0 || Y <= 0 || Z <= 0 || (long long)X * Y >= 0x80000000LL || (long long)X * Y * Z >= 0x80000000LL)
+  if (X <= 0 || Y <= 0 || Z <= 0 || !vol_dims_ok(X, Y, Z))
     UNET_FAIL(ctx, UNET_E_ARG, "%s: an extent is <= 0 or the volume has 2^31 voxels or more", what);
   if (!L || !k || reinterpret_cast<uintptr_t>(L) % 4 != 0) UNET_FAIL(ctx, UNET_E_ARG, "%s: null volume or factors, or a volume not aligned to its element", what);
   for (int i = 0; i < 6; ++i)
@@ -204,7 +201,7 @@ int32_t unet_vol_hessian_eig(unet_ctx* ctx, const float* L, int32_t X, int32_t Y
   const int32_t rc = vs_check(ctx, "vol_hessian_eig", L, X, Y, Z, k, &N);
   if (rc != UNET_OK) return rc;
   if (!eig || reinterpret_cast<uintptr_t>(eig) % 4 != 0) UNET_FAIL(ctx, UNET_E_ARG, "vol_hessian_eig: null output, or one not aligned to its element");
-  if (vs_overlap(eig, (size_t)N * 12, L, (size_t)N * 4) || (region && vs_overlap(eig, (size_t)N * 12, region, (size_t)N)))
+  if (vol_overlap(eig, (size_t)N * 12, L, (size_t)N * 4) || (region && vol_overlap(eig, (size_t)N * 12, region, (size_t)N)))
     UNET_FAIL(ctx, UNET_E_ARG, "vol_hessian_eig: the output overlaps the volume or the region (a voxel's neighbours must be read as they were)");
   vs_params P{k[0], k[1], k[2], k[3], k[4], k[5], 1.0, 1.0, 1.0, 1, 0};
   vs_launch<true>(as_stream(stream), L, region, X, Y, Z, P, eig, nullptr, nullptr);
@@ -221,8 +218,8 @@ int32_t unet_vol_vesselness(unet_ctx* ctx, const float* L, int32_t X, int32_t Y,
   if (bright != 0 && bright != 1) UNET_FAIL(ctx, UNET_E_ARG, "vol_vesselness: bright is 0 or 1, not %d", bright);
   if (index < 0 || index > UNET_VOL_VESSEL_MAX_SCALES - 1) UNET_FAIL(ctx, UNET_E_ARG, "vol_vesselness: the scale's index lies in 0 .. %d, not %d", UNET_VOL_VESSEL_MAX_SCALES - 1, index);
   if (!best || !scale || reinterpret_cast<uintptr_t>(best) % 4 != 0) UNET_FAIL(ctx, UNET_E_ARG, "vol_vesselness: null best or scale, or best not aligned to its element");
-  if (vs_overlap(best, (size_t)N * 4, L, (size_t)N * 4) || vs_overlap(scale, (size_t)N, L, (size_t)N * 4) || vs_overlap(best, (size_t)N * 4, scale, (size_t)N) ||
-      (region && (vs_overlap(best, (size_t)N * 4, region, (size_t)N) || vs_overlap(scale, (size_t)N, region, (size_t)N))))
+  if (vol_overlap(best, (size_t)N * 4, L, (size_t)N * 4) || vol_overlap(scale, (size_t)N, L, (size_t)N * 4) || vol_overlap(best, (size_t)N * 4, scale, (size_t)N) ||
+      (region && (vol_overlap(best, (size_t)N * 4, region, (size_t)N) || vol_overlap(scale, (size_t)N, region, (size_t)N))))
     UNET_FAIL(ctx, UNET_E_ARG, "vol_vesselness: best or scale overlaps the volume, the region or each other");
   vs_params P{k[0], k[1], k[2], k[3], k[4], k[5], den_a, den_b, den_c, bright, index};
   vs_launch<false>(as_stream(stream), L, region, X, Y, Z, P, nullptr, best, scale);

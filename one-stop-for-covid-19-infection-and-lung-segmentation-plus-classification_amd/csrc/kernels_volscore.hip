@@ -13,6 +13,7 @@
 // with -ffp-contract=off: a fused multiply-add would round w d^2 + g once instead of twice.
 // Phase boundaries are kernel boundaries; no workgroup waits for another one inside a launch; the sums are integers or fixed-shape trees: the same bits on every run.
 #include "common.h"
+#include "vol_common.h"
 
 #include <cmath>
 
@@ -24,10 +25,9 @@ constexpr int EDT_TILE = 4096;                                       // doubles 
 constexpr int XCH = EDT_MAX / 1024;                                  // a lane of the x pass holds 16 voxels of each 1024-voxel chunk of its line
 constexpr int SD_GROUPS_CAP = UNET_VOL_SURFDIST_WS_BYTES / 8;        // workgroups (= partial sums) of the surface-distance reduction
 
-inline bool vs_dims_ok(int X, int Y, int Z) { return X >= 0 && Y >= 0 && Z >= 0 && (long long)X * Y * Z < 0x80000000LL && (X == 0 || Y == 0 || (long long)X * Y < 0x80000000LL); }
-inline unsigned vs_blocks(long long items, long long cap) { long long b = (items + TPB - 1) / TPB; return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b)); }
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) % 16) == 0; }
+inline bool al16(const void* p) { return vol_aligned(p, 16); }
 
+// vol_common.h's vol_block_sum with a barrier in front, so that it can be called back to back on one s_w (kept here: the shared form has no such barrier)
 __device__ __forceinline__ long long block_sum_ll(long long v, long long* s_w) {          // -> the sum in every lane; s_w: TPB / 64 words; integer: exact in any order
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -247,6 +247,7 @@ __global__ __launch_bounds__(TPB) void vs_sqrt_kernel(double* __restrict__ x, lo
 // SD_GROUPS_CAP) workgroups of 256 lanes.  A lane adds its groups k = 0, 1, .. (group index (k G + workgroup) 256 + lane) voxel by voxel into one double: a chain
 // of at most 16 ceil(items / (256 G)) additions; then a 6-level butterfly over the 64 lanes of its wave, then the four wave sums left to right (3 additions).  The second
 // launch is ONE workgroup: lane t adds the partial sums t, t + 256, .. (a chain of ceil(G / 256)), the same butterfly, the same three additions.
+// (kept here and not vol_common.h's vol_block_sum: the wave sums are added from s_w[0], not from 0.0, and that order is the documented one)
 __device__ __forceinline__ double block_sum_f64(double v, double* s_w) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);        // both partners compute a + b: the same bits in every lane
@@ -360,7 +361,7 @@ __global__ __launch_bounds__(TPB) void vs_overlap_kernel(const int32_t* __restri
 extern "C" {
 
 int32_t unet_vol_confusion(unet_ctx* ctx, const uint8_t* pred, const uint8_t* truth, int32_t X, int32_t Y, int32_t Z, int64_t* counts, void* stream) {
-  if (!ctx || !vs_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_confusion: %d x %d x %d is negative or has 2^31 voxels or more", X, Y, Z);
+  if (!ctx || !vol_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_confusion: %d x %d x %d is negative or has 2^31 voxels or more", X, Y, Z);
   const long long XY = (long long)X * Y, N = XY * Z;
   if (Z == 0) return UNET_OK;
   if (!counts) UNET_FAIL(ctx, UNET_E_ARG, "vol_confusion: bad args");
@@ -381,7 +382,7 @@ int32_t unet_vol_confusion(unet_ctx* ctx, const uint8_t* pred, const uint8_t* tr
 int32_t unet_vol_surface(unet_ctx* ctx, const uint8_t* mask, int32_t X, int32_t Y, int32_t Z, int32_t connectivity, uint8_t* surface, int64_t* count, void* stream) {
   if (!ctx || !count) UNET_FAIL(ctx, UNET_E_ARG, "vol_surface: bad args");
   if (connectivity < 1 || connectivity > 3) UNET_FAIL(ctx, UNET_E_ARG, "vol_surface: connectivity %d is not 1 (6 neighbours), 2 (18) or 3 (26)", connectivity);
-  if (!vs_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_surface: %d x %d x %d is negative or has 2^31 voxels or more", X, Y, Z);
+  if (!vol_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_surface: %d x %d x %d is negative or has 2^31 voxels or more", X, Y, Z);
   hipStream_t s = as_stream(stream);
   const long long N = (long long)X * Y * Z;
   if (N == 0) { UNET_HIP(ctx, hipMemsetAsync(count, 0, sizeof(int64_t), s)); return UNET_OK; }
@@ -389,7 +390,7 @@ int32_t unet_vol_surface(unet_ctx* ctx, const uint8_t* mask, int32_t X, int32_t 
   UNET_HIP(ctx, hipMemsetAsync(count, 0, sizeof(int64_t), s));
   const int vec = (X % 16) == 0 && al16(mask) && al16(surface);
   const long long items = (long long)((X + 15) / 16) * Y * Z;
-  hipLaunchKernelGGL(vs_surface_kernel, dim3(vs_blocks(items, GRID_CAP)), dim3(TPB), 0, s, mask, X, Y, Z, connectivity, vec, surface,
+  hipLaunchKernelGGL(vs_surface_kernel, dim3(vol_blocks(items, GRID_CAP, TPB)), dim3(TPB), 0, s, mask, X, Y, Z, connectivity, vec, surface,
                      reinterpret_cast<unsigned long long*>(count));
   UNET_CHECK_LAUNCH(ctx, "vol_surface"); return UNET_OK;
 }
@@ -403,7 +404,7 @@ int32_t unet_vol_edt_sq(unet_ctx* ctx, const uint8_t* vol, int32_t X, int32_t Y,
                         void* stream) {
   (void)ws;
   if (!ctx || !w) UNET_FAIL(ctx, UNET_E_ARG, "vol_edt_sq: bad args");
-  if (!vs_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_edt_sq: %d x %d x %d is negative or has 2^31 voxels or more", X, Y, Z);
+  if (!vol_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_edt_sq: %d x %d x %d is negative or has 2^31 voxels or more", X, Y, Z);
   if (X > EDT_MAX || Y > EDT_MAX || Z > EDT_MAX) UNET_FAIL(ctx, UNET_E_ARG, "vol_edt_sq: %d x %d x %d has a dimension above %d", X, Y, Z, EDT_MAX);
   for (int k = 0; k < 3; ++k)
     if (!(w[k] > 0.0) || !std::isfinite(w[k])) UNET_FAIL(ctx, UNET_E_ARG, "vol_edt_sq: weight %d (a squared spacing) is not positive and finite", k);
@@ -430,14 +431,14 @@ int32_t unet_vol_edt_sq(unet_ctx* ctx, const uint8_t* vol, int32_t X, int32_t Y,
 int32_t unet_vol_sqrt_f64(unet_ctx* ctx, double* x, int64_t n, void* stream) {
   if (!ctx || n < 0 || (n > 0 && !x)) UNET_FAIL(ctx, UNET_E_ARG, "vol_sqrt_f64: bad args");
   if (n == 0) return UNET_OK;
-  hipLaunchKernelGGL(vs_sqrt_kernel, dim3(vs_blocks(n, GRID_CAP)), dim3(TPB), 0, as_stream(stream), x, (long long)n);
+  hipLaunchKernelGGL(vs_sqrt_kernel, dim3(vol_blocks(n, GRID_CAP, TPB)), dim3(TPB), 0, as_stream(stream), x, (long long)n);
   UNET_CHECK_LAUNCH(ctx, "vol_sqrt_f64"); return UNET_OK;
 }
 
 int32_t unet_vol_surface_distances(unet_ctx* ctx, const uint8_t* surface, const double* d2, int32_t X, int32_t Y, int32_t Z, void* result, double* gathered, int64_t capacity,
                                    void* ws, size_t ws_bytes, void* stream) {
   if (!ctx || !result || capacity < 0 || (capacity > 0 && !gathered) || (reinterpret_cast<uintptr_t>(result) % 8) != 0) UNET_FAIL(ctx, UNET_E_ARG, "vol_surface_distances: bad args");
-  if (!vs_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_surface_distances: %d x %d x %d is negative or has 2^31 voxels or more", X, Y, Z);
+  if (!vol_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_surface_distances: %d x %d x %d is negative or has 2^31 voxels or more", X, Y, Z);
   hipStream_t s = as_stream(stream);
   const long long N = (long long)X * Y * Z;
   if (N == 0) { UNET_HIP(ctx, hipMemsetAsync(result, 0, 24, s)); return UNET_OK; }
@@ -445,7 +446,7 @@ int32_t unet_vol_surface_distances(unet_ctx* ctx, const uint8_t* surface, const 
     UNET_FAIL(ctx, UNET_E_ARG, "vol_surface_distances: null buffer, or a workspace below UNET_VOL_SURFDIST_WS_BYTES");
   UNET_HIP(ctx, hipMemsetAsync(result, 0, 24, s));
   const long long items = (N + 15) / 16;
-  const int G = (int)vs_blocks(items, SD_GROUPS_CAP);
+  const int G = (int)vol_blocks(items, SD_GROUPS_CAP, TPB);
   unsigned long long* res = static_cast<unsigned long long*>(result);
   double* partial = static_cast<double*>(ws);
   hipLaunchKernelGGL(vs_surfdist_kernel, dim3((unsigned)G), dim3(TPB), 0, s, surface, d2, N, al16(surface) ? 1 : 0, (long long)capacity, res, gathered, partial);
@@ -455,7 +456,7 @@ int32_t unet_vol_surface_distances(unet_ctx* ctx, const uint8_t* surface, const 
 
 int32_t unet_vol_lesion_overlap(unet_ctx* ctx, const int32_t* labels_t, int32_t n_t, const int32_t* labels_p, int32_t n_p, int32_t X, int32_t Y, int32_t Z, int64_t* cover_t,
                                 int64_t* cover_p, void* stream) {
-  if (!ctx || n_t < 0 || n_p < 0 || !vs_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_lesion_overlap: bad args");
+  if (!ctx || n_t < 0 || n_p < 0 || !vol_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_lesion_overlap: bad args");
   if ((n_t > 0 && !cover_t) || (n_p > 0 && !cover_p)) UNET_FAIL(ctx, UNET_E_ARG, "vol_lesion_overlap: bad args");
   hipStream_t s = as_stream(stream);
   const long long N = (long long)X * Y * Z;
@@ -464,7 +465,7 @@ int32_t unet_vol_lesion_overlap(unet_ctx* ctx, const int32_t* labels_t, int32_t 
   if (n_p > 0) UNET_HIP(ctx, hipMemsetAsync(cover_p, 0, (size_t)n_p * sizeof(int64_t), s));
   if (N == 0 || n_t == 0 || n_p == 0) return UNET_OK;                  // nothing can overlap
   const int vec = al16(labels_t) && al16(labels_p);
-  hipLaunchKernelGGL(vs_overlap_kernel, dim3(vs_blocks((N + 3) / 4, GRID_CAP)), dim3(TPB), 0, s, labels_t, labels_p, N, n_t, n_p, vec,
+  hipLaunchKernelGGL(vs_overlap_kernel, dim3(vol_blocks((N + 3) / 4, GRID_CAP, TPB)), dim3(TPB), 0, s, labels_t, labels_p, N, n_t, n_p, vec,
                      reinterpret_cast<unsigned long long*>(cover_t), reinterpret_cast<unsigned long long*>(cover_p));
   UNET_CHECK_LAUNCH(ctx, "vol_lesion_overlap"); return UNET_OK;
 }

@@ -6,38 +6,17 @@
 // Bit-exact against tests/volume_oracle.py, which restates OpenCV's resize.cpp for 64-bit float images (cv2 is not in this image: parity unpinned, like CLAHE).
 // Compiled with -ffp-contract=off (csrc/Makefile): every product and sum below is rounded on its own, as the C++ / numpy expressions it restates are.
 #include "common.h"
+#include "vol_common.h"
 #include "vol_sample.h"
 
 namespace {
 constexpr int TPB = 256;
 
 // ---- typed voxel access: NIfTI-1 datatype codes, Fortran order [X, Y, Z] -------------------------------------------------------------------
-struct vol_src { const void* p; int dt, X, Y; int scaled; double slope, inter; };
-__device__ __forceinline__ double vol_raw(const void* p, long long i, int dt) {
-  switch (dt) {                                                       // (wave-uniform: one datatype per launch)
-    case 2: return (double)static_cast<const uint8_t*>(p)[i];
-    case 256: return (double)static_cast<const int8_t*>(p)[i];
-    case 4: return (double)static_cast<const int16_t*>(p)[i];
-    case 512: return (double)static_cast<const uint16_t*>(p)[i];
-    case 8: return (double)static_cast<const int32_t*>(p)[i];
-    case 768: return (double)static_cast<const uint32_t*>(p)[i];
-    case 16: return (double)static_cast<const float*>(p)[i];
-    default: return static_cast<const double*>(p)[i];                 // 64
-  }
-}
-// get_fdata: (float64(v) * slope) + inter, two rounded operations
-__device__ __forceinline__ double vol_dec(const vol_src& s, long long i) {
-  const double v = vol_raw(s.p, i, s.dt);
-  return s.scaled ? __dadd_rn(__dmul_rn(v, s.slope), s.inter) : v;
-}
+struct vol_src { const void* p; int dt, X, Y; int scaled; double slope, inter; };          // vol_common.h's vol_voxels and the slice extents, in the order the kernels take them
+__device__ __forceinline__ double vol_dec(const vol_src& s, long long i) { return vol_dec(vol_voxels{s.p, s.dt, s.scaled, s.slope, s.inter}, i); }
 // pixel (row i, column j) of slice z after np.rot90: vol[x = j, y = Y - 1 - i, z]; a row of the image is contiguous in x
 __device__ __forceinline__ double vol_px(const vol_src& s, long long zoff, int i, int j) { return vol_dec(s, zoff + (long long)(s.Y - 1 - i) * s.X + j); }
-
-__device__ __forceinline__ unsigned long long d2ord(double d) {
-  const unsigned long long u = (unsigned long long)__double_as_longlong(d);
-  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double ord2d(unsigned long long o) { return __longlong_as_double((long long)((o >> 63) ? (o & 0x7FFFFFFFFFFFFFFFull) : ~o)); }
 
 // computeResizeAreaTab for one destination index (the same table kernels_pre.hip rebuilds for uint8 images)
 struct vspan { int s1, s2; float a_left, a_mid, a_right; bool left, right; };
@@ -145,7 +124,7 @@ __global__ __launch_bounds__(TPB) void vol_resize_kernel(vol_src s, int z0, int 
   if (tid == 0) {
     for (int w = 1; w < TPB / 64; ++w) { mn = fmin(mn, s_mn[w]); mx = fmax(mx, s_mx[w]); }
     unsigned long long* q = st + (long long)VOL_STATE * li;
-    if (mn <= mx) { atomicMin(q, d2ord(mn)); atomicMax(q + 1, d2ord(mx)); }
+    if (mn <= mx) { atomicMin(q, vol_d2ord(mn)); atomicMax(q + 1, vol_d2ord(mx)); }
     if (s_flag[0]) atomicOr(q + 2, 1ull);
     if (s_flag[1]) atomicOr(q + 3, 1ull);
   }
@@ -156,7 +135,7 @@ __global__ __launch_bounds__(TPB) void vol_resize_kernel(vol_src s, int z0, int 
 struct vol_mm { double mn, mx, d; };
 __device__ __forceinline__ vol_mm vol_minmax(const unsigned long long* st, int li) {
   const unsigned long long* q = st + (long long)VOL_STATE * li;
-  double mn = ord2d(q[0]), mx = ord2d(q[1]);
+  double mn = vol_ord2d(q[0]), mx = vol_ord2d(q[1]);
   if (q[2]) mn = mx = __longlong_as_double(0x7FF8000000000000ll);                              // numpy's min / max propagate a NaN
   return {mn, mx, mx - mn};
 }
@@ -250,10 +229,6 @@ __global__ __launch_bounds__(TPB) void vol_unslice_kernel(const float* __restric
   if (threadIdx.x == 0 && s_cnt) atomicAdd(counts + li, (unsigned long long)s_cnt);            // integer sums: exact in any order
 }
 
-inline unsigned vol_blocks(long long items, int cap) { long long b = (items + TPB - 1) / TPB; return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b)); }
-inline int vol_itemsize(int dt) {
-  switch (dt) { case 2: case 256: return 1; case 4: case 512: return 2; case 8: case 768: case 16: return 4; case 64: return 8; default: return 0; }
-}
 }  // namespace
 
 extern "C" {
@@ -276,11 +251,11 @@ int32_t unet_vol_slices_f64(unet_ctx* ctx, const void* vox, int32_t dtype, int32
   unsigned long long* st = reinterpret_cast<unsigned long long*>(img + (size_t)n * P);
   const vol_src src{vox, dtype, X, Y, scaled ? 1 : 0, slope, inter};
   hipLaunchKernelGGL(vol_state_init_kernel, dim3((n + 63) / 64), dim3(64), 0, s, st, n);
-  hipLaunchKernelGGL(vol_resize_kernel, dim3(vol_blocks(P, 1024), n), dim3(TPB), 0, s, src, z0, S, img, st);
+  hipLaunchKernelGGL(vol_resize_kernel, dim3(vol_blocks(P, 1024, TPB), n), dim3(TPB), 0, s, src, z0, S, img, st);
   const bool vec = (P % 4) == 0 && (!img_f32 || reinterpret_cast<uintptr_t>(img_f32) % 16 == 0) && (!img_u8 || reinterpret_cast<uintptr_t>(img_u8) % 4 == 0) &&
                    (!lung_u8 || reinterpret_cast<uintptr_t>(lung_u8) % 4 == 0);
-  if (vec) hipLaunchKernelGGL(vol_outputs_kernel<4>, dim3(vol_blocks(P / 4, 256), n), dim3(TPB), 0, s, img, st, P, img_f32, img_u8, lung_u8, uniform, minmax);
-  else hipLaunchKernelGGL(vol_outputs_kernel<1>, dim3(vol_blocks(P, 1024), n), dim3(TPB), 0, s, img, st, P, img_f32, img_u8, lung_u8, uniform, minmax);
+  if (vec) hipLaunchKernelGGL(vol_outputs_kernel<4>, dim3(vol_blocks(P / 4, 256, TPB), n), dim3(TPB), 0, s, img, st, P, img_f32, img_u8, lung_u8, uniform, minmax);
+  else hipLaunchKernelGGL(vol_outputs_kernel<1>, dim3(vol_blocks(P, 1024, TPB), n), dim3(TPB), 0, s, img, st, P, img_f32, img_u8, lung_u8, uniform, minmax);
   UNET_CHECK_LAUNCH(ctx, "vol_slices_f64"); return UNET_OK;
 }
 
@@ -318,9 +293,9 @@ int32_t unet_vol_unslice(unet_ctx* ctx, const float* canvas, int32_t S, float th
   UNET_HIP(ctx, hipMemsetAsync(counts, 0, (size_t)n * sizeof(int64_t), s));
   unsigned long long* cnt = reinterpret_cast<unsigned long long*>(counts);
   if ((X % 4) == 0 && reinterpret_cast<uintptr_t>(mask) % 4 == 0)
-    hipLaunchKernelGGL(vol_unslice_kernel<4>, dim3(vol_blocks((long long)(X / 4) * Y, 256), n), dim3(TPB), 0, s, canvas, S, threshold, X, Y, z0, mask, cnt);
+    hipLaunchKernelGGL(vol_unslice_kernel<4>, dim3(vol_blocks((long long)(X / 4) * Y, 256, TPB), n), dim3(TPB), 0, s, canvas, S, threshold, X, Y, z0, mask, cnt);
   else
-    hipLaunchKernelGGL(vol_unslice_kernel<1>, dim3(vol_blocks((long long)X * Y, 1024), n), dim3(TPB), 0, s, canvas, S, threshold, X, Y, z0, mask, cnt);
+    hipLaunchKernelGGL(vol_unslice_kernel<1>, dim3(vol_blocks((long long)X * Y, 1024, TPB), n), dim3(TPB), 0, s, canvas, S, threshold, X, Y, z0, mask, cnt);
   UNET_CHECK_LAUNCH(ctx, "vol_unslice"); return UNET_OK;
 }
 

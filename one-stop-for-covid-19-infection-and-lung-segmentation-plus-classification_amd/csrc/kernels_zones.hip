@@ -14,6 +14,7 @@
 // (side, axis, k) and the kernel keeps them in LDS.  The flip mirrors the coordinate, not the quotient: parts - 1 - floor((c - lo) parts / extent) cuts a range that is no
 // multiple of `parts` at other voxels than the same range stored the other way round, and the numbering is anatomical whatever the storage.
 #include "common.h"
+#include "vol_common.h"
 
 #include <cmath>
 #include <cstring>
@@ -26,8 +27,6 @@ constexpr int ZT_TABLE = 4096;                                       // per-lesi
 constexpr int ZT_LESIONS = ZT_TABLE / 3;                             // lesions of that table at the most (2 P + S >= 3): their smallest distances sit beside it
 constexpr unsigned long long ZT_NONE = ~0ull;
 
-inline bool zt_dims_ok(int X, int Y, int Z) { return X >= 0 && Y >= 0 && Z >= 0 && (long long)X * Y * Z < 0x80000000LL && (X == 0 || Y == 0 || (long long)X * Y < 0x80000000LL); }
-inline bool zt_aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
 inline unsigned long long zt_host_key(double v) { unsigned long long u; memcpy(&u, &v, 8); return (u >> 63) ? ~u : (u | 0x8000000000000000ull); }
 
 // what the table kernel needs of a unet_zone_spec, passed by value
@@ -44,11 +43,6 @@ __device__ __forceinline__ unsigned zt_sides4(unsigned m) {            // a side
 #pragma unroll
   for (int k = 0; k < 4; ++k) { const unsigned b = (m >> (8 * k)) & 0xFFu; r |= (b <= 2u ? b : 0u) << (8 * k); }
   return r;
-}
-__device__ __forceinline__ int zt_wave_sum(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 __device__ __forceinline__ int zt_wave_min(int v) {
 #pragma unroll
@@ -322,7 +316,7 @@ __global__ __launch_bounds__(TPB) void zone_table_kernel(const uint8_t* __restri
       }
     }
   }
-  n_out = zt_wave_sum(n_out);
+  n_out = vol_wave_sum(n_out);
   if (lane == 0 && n_out) atomicAdd(&s_out, n_out);
   __syncthreads();
   for (int i = tid; i < 2 * B; i += TPB) { const int v = s_bin[i]; if (v) atomicAdd(table + i, (unsigned long long)v); }
@@ -344,15 +338,15 @@ extern "C" {
 
 int32_t unet_vol_side_extents(unet_ctx* ctx, const uint8_t* sides, const double* d2, int32_t X, int32_t Y, int32_t Z, int32_t* box, uint64_t* dmax_key, void* stream) {
   if (!ctx) return UNET_E_ARG;
-  if (!zt_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_side_extents: a dimension is negative or the volume has 2^31 voxels or more");
+  if (!vol_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_side_extents: a dimension is negative or the volume has 2^31 voxels or more");
   const long long N = (long long)X * Y * Z;
   if (N == 0) return UNET_OK;
-  if (!sides || !box || !dmax_key || !zt_aligned(d2, 8) || !zt_aligned(box, 4) || !zt_aligned(dmax_key, 8)) UNET_FAIL(ctx, UNET_E_ARG, "vol_side_extents: null or misaligned buffer");
+  if (!sides || !box || !dmax_key || !vol_aligned(d2, 8) || !vol_aligned(box, 4) || !vol_aligned(dmax_key, 8)) UNET_FAIL(ctx, UNET_E_ARG, "vol_side_extents: null or misaligned buffer");
   hipStream_t s = as_stream(stream);
   unsigned long long* dm = reinterpret_cast<unsigned long long*>(dmax_key);
   const unsigned long long* d = reinterpret_cast<const unsigned long long*>(d2);
   hipLaunchKernelGGL(extents_init_kernel, dim3(1), dim3(64), 0, s, box, dm);
-  const bool vec = zt_aligned(sides, 4) && zt_aligned(d2, 16);
+  const bool vec = vol_aligned(sides, 4) && vol_aligned(d2, 16);
   if (vec) hipLaunchKernelGGL(side_extents_kernel<4>, dim3(zt_grid((N + 3) / 4)), dim3(TPB), 0, s, sides, d, N, X, Y, box, dm);
   else hipLaunchKernelGGL(side_extents_kernel<1>, dim3(zt_grid(N)), dim3(TPB), 0, s, sides, d, N, X, Y, box, dm);
   UNET_CHECK_LAUNCH(ctx, "vol_side_extents"); return UNET_OK;
@@ -362,7 +356,7 @@ int32_t unet_vol_zone_table(unet_ctx* ctx, const uint8_t* sides, const uint8_t* 
                             const unet_zone_spec* spec, int64_t* table, int64_t* outside, int64_t* lesion_zone, int64_t* lesion_shell, uint64_t* lesion_dmin_key,
                             uint8_t* zone_map, void* stream) {
   if (!ctx) return UNET_E_ARG;
-  if (!zt_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_zone_table: a dimension is negative or the volume has 2^31 voxels or more");
+  if (!vol_dims_ok(X, Y, Z)) UNET_FAIL(ctx, UNET_E_ARG, "vol_zone_table: a dimension is negative or the volume has 2^31 voxels or more");
   if (n < 0) UNET_FAIL(ctx, UNET_E_ARG, "vol_zone_table: n is negative");
   if (!spec) UNET_FAIL(ctx, UNET_E_ARG, "vol_zone_table: spec is null");
   ZtParams prm;
@@ -397,8 +391,8 @@ int32_t unet_vol_zone_table(unet_ctx* ctx, const uint8_t* sides, const uint8_t* 
   prm.P = (int)P; prm.S = S;
   const long long N = (long long)X * Y * Z;
   if (N == 0) return UNET_OK;
-  if (!sides || !table || !outside || (n > 0 && (!lesion_zone || !lesion_shell || !lesion_dmin_key)) || !zt_aligned(table, 8) || !zt_aligned(outside, 8) ||
-      !zt_aligned(lesion_zone, 8) || !zt_aligned(lesion_shell, 8) || !zt_aligned(lesion_dmin_key, 8) || !zt_aligned(labels, 4) || !zt_aligned(d2, 8))
+  if (!sides || !table || !outside || (n > 0 && (!lesion_zone || !lesion_shell || !lesion_dmin_key)) || !vol_aligned(table, 8) || !vol_aligned(outside, 8) ||
+      !vol_aligned(lesion_zone, 8) || !vol_aligned(lesion_shell, 8) || !vol_aligned(lesion_dmin_key, 8) || !vol_aligned(labels, 4) || !vol_aligned(d2, 8))
     UNET_FAIL(ctx, UNET_E_ARG, "vol_zone_table: null or misaligned buffer");
   hipStream_t st = as_stream(stream);
   const int B = (int)(2 * P * S);
@@ -415,7 +409,7 @@ int32_t unet_vol_zone_table(unet_ctx* ctx, const uint8_t* sides, const uint8_t* 
   unsigned long long* lz = reinterpret_cast<unsigned long long*>(lesion_zone);
   unsigned long long* lh = reinterpret_cast<unsigned long long*>(lesion_shell);
   unsigned long long* ld = reinterpret_cast<unsigned long long*>(lesion_dmin_key);
-  const bool vec = zt_aligned(sides, 4) && zt_aligned(infection, 4) && zt_aligned(zone_map, 4) && zt_aligned(d2, 16) && zt_aligned(labels, 16);
+  const bool vec = vol_aligned(sides, 4) && vol_aligned(infection, 4) && vol_aligned(zone_map, 4) && vol_aligned(d2, 16) && vol_aligned(labels, 16);
   const bool lds = (long long)n * (2 * P + S) <= ZT_TABLE;
   const dim3 grid(zt_grid(vec ? (N + 3) / 4 : N));
 #define ZT_LAUNCH(V, L) hipLaunchKernelGGL((zone_table_kernel<V, L>), grid, dim3(TPB), 0, st, sides, infection, labels, n, d, N, X, Y, prm, tb, ou, lz, lh, ld, zone_map)

@@ -25,8 +25,8 @@ int main(int argc, char** argv) {
   if (argc != 9 || strcmp(argv[1], "thin")) { fprintf(stderr, "usage: %s count | thin X Y Z in.bin endpoints max_iterations out.bin\n", argv[0]); return 2; }
   const int X = atoi(argv[2]), Y = atoi(argv[3]), Z = atoi(argv[4]), endpoints = atoi(argv[6]) != 0;
   const long long max_it = atoll(argv[7]);
-  if (X <= 0 || Y <= 0 || Z <= 0 || !sk_dims_ok(X, Y, Z)) { fprintf(stderr, "bad extents\n"); return 2; }
-  const sk_dims d = sk_make(X, Y, Z);
+  if (X <= 0 || Y <= 0 || Z <= 0 || !vol_dims_ok(X, Y, Z)) { fprintf(stderr, "bad extents\n"); return 2; }
+  const vol_bits d = vol_bits_make(X, Y, Z);
   std::vector<uint8_t> vol(d.N);
   FILE* f = fopen(argv[5], "rb");
   if (!f || fread(vol.data(), 1, d.N, f) != (size_t)d.N) { fprintf(stderr, "cannot read %s\n", argv[5]); return 2; }
