@@ -1230,6 +1230,49 @@ int32_t unet_vol_skeleton_emit(unet_ctx*, const uint8_t* mask, int32_t X, int32_
 int32_t unet_vol_label_spread(unet_ctx*, const uint16_t* arrival, int32_t* labels, int32_t X, int32_t Y, int32_t Z, int32_t first, int32_t n, int32_t connectivity,
                               void* stream);
 
+/* ---- marker-controlled watershed and cost-weighted geodesic distance on a volume, the depth cost (csrc/kernels_watershed.hip; exact against
+ * tests/watershed_oracle.py; watershed.py) ----
+ * Volumes are [X, Y, Z] in Fortran order, X Y Z < 2^31; outside the volume there is nothing; extents of 1 are legal.
+ * cost uint32 per voxel.  markers int32 per voxel: 1 .. 2^24 - 1 a marker, 0 none, anything else is invalid -- counted, treated as none, never an address.  mask: bytes,
+ * or null for "everywhere"; a voxel where it is zero takes no part, a marker there is ignored.  Neighbours: generate_binary_structure(3, connectivity), 1, 2 or 3.
+ * Each phase is the greatest fixed point, below "unreached", of a monotone operator, so the result is unique and independent of the order of updates:
+ *   HEIGHT  the pass height H: H[v] = cost[v] on a marker, elsewhere min over neighbours n of max(H[n], cost[v]); 0xFFFFFFFF where no marker is connected in the mask.
+ *   LABEL   on the finished H: an edge n -> v is tight when max(H[n], cost[v]) == H[v]; key = steps << 32 | label; a marker holds (0, its label), every other voxel the
+ *           minimum over its tight neighbours of key[n] + (1 << 32).  A voxel goes to the marker nearest in steps along pass-height-realising paths, among equally near
+ *           markers to the lowest label; a plateau is divided by step distance.  Every voxel with a finite H receives a label.
+ *   SUM     key = dist << 24 | label, dist 40 bits; a marker holds (0, label), elsewhere the minimum over neighbours of (dist[n] + cost[v], label[n]); a candidate whose
+ *           distance would exceed 2^40 - 2 is no candidate.  A mask voxel that ends unreached beside a reached neighbour is counted as overflowed.
+ * The watershed (rule "max") is HEIGHT to its fixed point, then LABEL to its fixed point; the label is not carried in the height key because height << k | label is not
+ * monotone ((3, 2) < (4, 1), but through a voxel of cost 5: (5, 2) > (5, 1)).
+ *   _ws_bytes   two buffers of a 64-bit key per voxel, the heights, per-brick bytes and partial counts; 0 for a bad or zero dimension.
+ *   _begin      seeds both key buffers for `phase` and notes the invalid markers.  LABEL: first keeps the heights of the HEIGHT phase, `done` = the HEIGHT sweeps that were
+ *               run (it says which buffer holds them); other phases ignore done (>= 0).
+ *   _sweeps     runs the sweeps first .. first + n - 1 of `phase` (one launch each: sweep s reads key buffer s & 1 and writes the other) and overwrites changed[s] (int64,
+ *               8-byte aligned, at least first + n entries) with the voxels whose key sweep s lowered.  The host reads changed only between calls and stops after the first
+ *               sweep with changed == 0: the state is then the fixed point.  skip = 1: a 32 x 8 x 8 brick whose own and 26 neighbour bricks' keys the previous sweep left
+ *               alone is not visited; skip = 0 visits every brick with a mask voxel; the results, changed included, are the same.
+ *   _end        `done` = the sweeps of `phase` that were run.  HEIGHT: height.  LABEL: labels (int32, 0 unreached), steps (uint32, 0xFFFFFFFF unreached) and, when not
+ *               null, height.  SUM: labels and distance (uint64, 2^40 - 1 unreached).  Outputs the phase does not write must be null.  counts (int64 [4], 8-byte
+ *               aligned): voxels reached, mask voxels unreached, overflowed (SUM; else 0), invalid markers.  A zero dimension: counts = 0.
+ *   UNET_E_ARG, nothing launched, nothing written: a bad dimension, connectivity or phase, first < 0, n < 0, done < 0, skip outside 0 / 1, a null or misaligned buffer
+ *   (cost, markers, labels, height, steps 4, changed, distance, counts 8, ws 16 bytes), a workspace below _ws_bytes, an input or output overlapping the workspace, an
+ *   output overlapping the mask or another output.  A zero dimension, or n == 0, launches nothing.
+ * Every sweep, every changed[s] and the sweep count are the same on every run: a launch reads what earlier launches wrote and every element is written by one lane.  Integer
+ * arithmetic, no atomics but changed[s], no workgroup waits for another; a sweep's grid is bounded (at most 2048 workgroups walk the bricks).
+ * unet_vol_depth_cost: cost[v] = uint32(floor((d2max - d2[v]) / quantum)) in float64, every operation rounded on its own, clipped to 0 .. 2^32 - 2; 0 where mask (bytes, or
+ *   null) is zero.  UNET_E_ARG: a bad dimension, quantum not positive and finite, d2max negative or not finite, a null or misaligned buffer, cost overlapping an input. */
+#define UNET_VOL_WATERSHED_HEIGHT 0
+#define UNET_VOL_WATERSHED_LABEL 1
+#define UNET_VOL_WATERSHED_SUM 2
+size_t unet_vol_watershed_ws_bytes(int32_t X, int32_t Y, int32_t Z);
+int32_t unet_vol_watershed_begin(unet_ctx*, const uint32_t* cost, const int32_t* markers, const uint8_t* mask, int32_t X, int32_t Y, int32_t Z, int32_t phase, int32_t done,
+                                 void* ws, size_t ws_bytes, void* stream);
+int32_t unet_vol_watershed_sweeps(unet_ctx*, const uint32_t* cost, const int32_t* markers, const uint8_t* mask, int32_t X, int32_t Y, int32_t Z, int32_t first, int32_t n,
+                                  int32_t phase, int32_t connectivity, int32_t skip, int64_t* changed, void* ws, size_t ws_bytes, void* stream);
+int32_t unet_vol_watershed_end(unet_ctx*, const uint8_t* mask, int32_t X, int32_t Y, int32_t Z, int32_t phase, int32_t done, int32_t connectivity, int32_t* labels,
+                               uint32_t* height, uint32_t* steps, uint64_t* distance, int64_t* counts, const void* ws, size_t ws_bytes, void* stream);
+int32_t unet_vol_depth_cost(unet_ctx*, const double* d2, const uint8_t* mask, int32_t X, int32_t Y, int32_t Z, double d2max, double quantum, uint32_t* cost, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Model level. Replaces the Keras Model built at T1:853-916 and driven by
  * compile/fit/evaluate/predict (T1:1053-1061, 1101, 1137).  A model is a fixed-shape plan:

@@ -29,6 +29,9 @@ Public surface:
   thin_volume / skeleton_table / skeleton_graph / prune / root_tree / branch_territories / airway_tree / vessel_tree (Skeleton, SkeletonGraph, RootedTree,
                             BranchTerritories, CenterlineTree) -- skeleton's centerlines of the airway and vessel masks: topology-preserving thinning on the device, the
                             branch graph with lengths and calibres, generations from a root and the mask voxels of every branch; also reachable from the package itself
+  watershed / watershed_device / depth_cost_device / split_lesions (WatershedResult, SplitLesions, WatershedError) -- watershed's marker-controlled watershed over an
+                            integer cost volume (pass height, then labels along the edges that realise it; or the summed cost) and the split of touching lesions
+                            into parts grown from the cores of the distance transform; also reachable from the package itself
   engine.HipUNet         -- the HIP backend (libunet_hip.so through the C ABI of include/unet_hip.h)
 Importing this package has no side effects and does not need a GPU; constructing the
 backend does (there is no CPU fallback).
@@ -42,7 +45,8 @@ __all__ = ["runners", "keras_like", "engine", "weights", "data", "volume", "nift
            "lungs", "lung_mask", "threshold_volume", "geodesic_distance", "reconstruct", "body_mask", "find_trachea", "grow_airways", "LungMask", "AirwayGrowth", "TracheaSeed",
            "LungMaskError", "vessels", "hessian_eigenvalues", "vesselness", "vessel_mask", "Vesselness", "VesselMask",
            "skeleton", "thin_volume", "skeleton_table", "skeleton_graph", "prune", "root_tree", "branch_territories", "airway_tree", "vessel_tree", "Skeleton", "SkeletonGraph",
-           "RootedTree", "BranchTerritories", "CenterlineTree"]
+           "RootedTree", "BranchTerritories", "CenterlineTree",
+           "watershed", "watershed_device", "depth_cost_device", "split_lesions", "split_lesions_device", "WatershedResult", "SplitLesions", "WatershedError"]
 _FROM_VOLUME = ("split_lungs", "lung_burden", "LungSides", "LungBurden", "LungSplitError", "render_planes", "project_volume", "key_slices", "Layer", "RenderedSheet",
                 "resample_volume", "resample_mask", "resample_labels", "reorient_volume", "change_between", "Grid", "ResampledVolume", "VolumeChange",
                 "extract_surface", "lesion_shapes", "SurfaceMesh")
@@ -55,6 +59,7 @@ _FROM_LUNGS = ("lung_mask", "threshold_volume", "geodesic_distance", "reconstruc
 _FROM_VESSELS = ("hessian_eigenvalues", "vesselness", "vessel_mask", "Vesselness", "VesselMask")
 _FROM_SKELETON = ("thin_volume", "skeleton_table", "skeleton_graph", "prune", "root_tree", "branch_territories", "airway_tree", "vessel_tree", "Skeleton", "SkeletonGraph",
                   "RootedTree", "BranchTerritories", "CenterlineTree")
+_FROM_WATERSHED = ("watershed_device", "depth_cost_device", "split_lesions", "split_lesions_device", "WatershedResult", "SplitLesions", "WatershedError")
 _FROM_TEXTURE = ("texture_stats", "lesion_texture", "glcm", "run_lengths", "quantize_volume", "glcm_features", "run_features", "TextureStats")
 
 
@@ -83,4 +88,7 @@ def __getattr__(name):                                              # resolved o
     if name in _FROM_SKELETON:
         import importlib
         return getattr(importlib.import_module(__name__ + ".skeleton"), name)
+    if name in _FROM_WATERSHED:
+        import importlib
+        return getattr(importlib.import_module(__name__ + ".watershed"), name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

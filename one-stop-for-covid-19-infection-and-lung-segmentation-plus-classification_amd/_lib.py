@@ -292,6 +292,12 @@ _PROTOS = {
     "unet_vol_skeleton_count": (i32, [vp, vp, i32, i32, i32, vp, vp, sz, vp]),
     "unet_vol_skeleton_emit": (i32, [vp, vp, i32, i32, i32, vp, i64, i64, vp, vp, vp, vp, sz, vp]),
     "unet_vol_label_spread": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+    # marker-controlled watershed / cost-weighted geodesic distance and the depth cost (csrc/kernels_watershed.hip, watershed.py)
+    "unet_vol_watershed_ws_bytes": (sz, [i32, i32, i32]),
+    "unet_vol_watershed_begin": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, sz, vp]),
+    "unet_vol_watershed_sweeps": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, sz, vp]),
+    "unet_vol_watershed_end": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "unet_vol_depth_cost": (i32, [vp, vp, vp, i32, i32, i32, f64, f64, vp, vp]),
     "unet_model_create": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(vp)]),
     "unet_model_dtype": (i32, [vp]),
     "unet_model_tap_elem_bytes": (i32, [vp, C.c_char_p, i32]),

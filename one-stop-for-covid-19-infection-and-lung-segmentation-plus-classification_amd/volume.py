@@ -315,7 +315,8 @@ class VolumeSegmentation:
     distribution / distribution_error: the zones.LungDistribution of the final mask -- where in the lungs it sits -- (None unless segment_volume was given distribution=)
     and, when the lungs could not be split, why;
     sheet: the RenderedSheet of the final mask over the CT (None unless segment_volume was given render=);
-    mesh / lung_mesh: the SurfaceMesh of the final mask and of the lung mask (None unless segment_volume was given mesh=)."""
+    mesh / lung_mesh: the SurfaceMesh of the final mask and of the lung mask (None unless segment_volume was given mesh=);
+    lesion_parts: the watershed.SplitLesions of the final mask with its own table (the field exists only when segment_volume was given split_lesions=)."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -1090,6 +1091,30 @@ def _segmentation_airway_tree(kw, lm, ct, lungs):
     return dict(airway_tree=SK.airway_tree(lm, **kw), airway_tree_error=None)
 
 
+def _check_split_lesions(split_lesions):
+    """segment_volume's split_lesions= -> None (off) or the checked keyword arguments of watershed.split_lesions_device"""
+    if split_lesions is None or split_lesions is False:
+        return None
+    if split_lesions is not True and not isinstance(split_lesions, dict):
+        raise ValueError(f"split_lesions is True or a dict of watershed.split_lesions keyword arguments, not {split_lesions!r}")
+    from . import watershed as W
+    kw = {} if split_lesions is True else dict(split_lesions)
+    unknown = sorted(set(kw) - {"seed_depth_mm", "connectivity", "min_seed_voxels", "quantum_mm2"})
+    if unknown:
+        raise ValueError(f"split_lesions takes seed_depth_mm, connectivity, min_seed_voxels and quantum_mm2, not {unknown}")
+    W._check_split_args((1.0, 1.0, 1.0), kw.get("seed_depth_mm", W.SEED_DEPTH_MM), kw.get("connectivity", 1), kw.get("min_seed_voxels", 1), kw.get("quantum_mm2"))
+    return kw
+
+
+def _segmentation_lesion_parts(kw, mask_dev, shape, pixdim):
+    """the parts of the final mask and their table -> the extra result field"""
+    from . import watershed as W
+    parts = W.split_lesions_device(mask_dev, shape, pixdim, **kw)
+    parts.table = table_from_stats(component_stats_device(parts.labels, shape, parts.n), pixdim)
+    parts.labels = _host_of(parts.labels, np.int32, shape)
+    return dict(lesion_parts=parts)
+
+
 def _segmentation_vessels(vessels, vol, lv, mask_dev, shape, density):
     """the vessel mask inside the lung mask, the infection's volume on it and, with density=, the infection's density without it -> the extra result fields"""
     from . import lungs as L
@@ -1163,7 +1188,8 @@ def _prepare_segmentation(ct, lung_mask, truth, img_size, trim, input_size):
 
 
 def segment_volume(ct, model, lung_mask=None, threshold=0.547, batch_size=32, out_path=None, img_size=512, trim=(0.2, 0.8), min_lesion_ml=None, connectivity=1,
-                   lesions=False, truth=None, postprocess=None, density=None, per_lung=None, render=None, mesh=None, distribution=None, lungs=None, vessels=None, airway_tree=None):
+                   lesions=False, truth=None, postprocess=None, density=None, per_lung=None, render=None, mesh=None, distribution=None, lungs=None, vessels=None, airway_tree=None,
+                   split_lesions=None):
     """CT file (or array) -> VolumeSegmentation.  `model`: a UNetModel or a routed.ClusterRoutedModel (only `predict` is used); lung_mask=None: whole-frame
     boxes (the two halves of the frame); boxes are keyed by slice number (box_indexing="slice"); out_path: the mask as .nii / .nii.gz with the CT's geometry.
     min_lesion_ml: connected components (`connectivity` 1, 2, 3 = 6, 18, 26 neighbours) smaller than that are removed on the device before the mask comes to the
@@ -1211,10 +1237,15 @@ def segment_volume(ct, model, lung_mask=None, threshold=0.547, batch_size=32, ou
     lung mask: res.airway_tree = the CenterlineTree of the airway lungs.lung_mask grew -- centerline, branch graph, generations from the superior end, the airway voxels
     of every branch; a cycle marks a leak.  The superior end comes from the keyword's own orientation / affine, else from lungs=' orientation, else from the CT file's
     axis codes; it is never guessed.  When the airway step did not run res.airway_tree is None and res.airway_tree_error says why.  seconds["airway_tree"]: its time.
-    None: nothing runs and no field is added."""
+    None: nothing runs and no field is added.
+    split_lesions: True, or a dict of watershed.split_lesions keyword arguments (seed_depth_mm, connectivity, min_seed_voxels, quantum_mm2; the pixdim is the CT's).  On
+    the final mask, after the component filter: res.lesion_parts = the SplitLesions of the mask -- lesions that touch over a narrow bridge come apart -- with its labels on
+    the host and its own component_table in res.lesion_parts.table.  res.lesions and every other field stay what they are without it.  seconds["split_lesions"]: its
+    time.  None: nothing runs and no field is added."""
     _check_connectivity(connectivity)
     lungs = _check_lungs(lungs, lung_mask)
     airway_tree = _check_airway_tree(airway_tree, lungs)
+    split_lesions = _check_split_lesions(split_lesions)
     lung_mask = True if lungs is not None else lung_mask          # (the checks below ask only whether there is one)
     vessels = _check_vessels(vessels, lung_mask)
     density = _check_density(density)
@@ -1238,11 +1269,12 @@ def segment_volume(ct, model, lung_mask=None, threshold=0.547, batch_size=32, ou
     canvas = paste_back(prob, R1, R2, S)
     mask_dev, counts_dev = unslice(canvas, threshold, (X, Y, Z), z0, z1)
     return _finish_segmentation(vol, lv, truth_mask, mask_dev, counts_dev, z0, z1, has, info, threshold, sec, t0, postprocess, min_lesion_ml, lesions, connectivity, out_path,
-                                density=density, per_lung=per_lung, render=render, mesh=mesh, distribution=distribution, vessels=vessels, **found[0])
+                                density=density, per_lung=per_lung, render=render, mesh=mesh, distribution=distribution, vessels=vessels, split_lesions=split_lesions,
+                                **found[0])
 
 
 def _finish_segmentation(vol, lv, truth_mask, mask_dev, counts_dev, z0, z1, has, info, threshold, sec, t0, postprocess, min_lesion_ml, lesions, connectivity, out_path,
-                         density=None, per_lung=None, render=None, mesh=None, distribution=None, vessels=None, **extra):
+                         density=None, per_lung=None, render=None, mesh=None, distribution=None, vessels=None, split_lesions=None, **extra):
     """What segment_volume and segment_volume_ensemble do with the mask volume once it is formed (mask_dev, counts_dev [z1 - z0], both on the device): postprocess,
     min_lesion_ml / lesions, density (the checked keyword arguments of intensity_stats, or None), per_lung (those of split_lungs, or None), render (those of the sheet, or None), mesh (the checked dict of _check_mesh, or None), distribution (the checked pair of _check_distribution, or None), truth, the download, the lung share and out_path -> VolumeSegmentation (+ `extra` fields).  t0: when the paste-back began."""
     torch = _torch()
@@ -1275,6 +1307,10 @@ def _finish_segmentation(vol, lv, truth_mask, mask_dev, counts_dev, z0, z1, has,
         if density is None and per_lung is None:                      # (distribution= needs per_lung=)
             labels_dev = None
         torch.cuda.synchronize(); sec["components"] = time.perf_counter() - tc
+    if split_lesions is not None:                                   # (the fields exist only when it is asked for)
+        torch.cuda.synchronize(); tw = time.perf_counter()
+        extra.update(_segmentation_lesion_parts(split_lesions, mask_dev, (X, Y, Z), vol.pixdim))
+        torch.cuda.synchronize(); sec["split_lesions"] = time.perf_counter() - tw
     dens, lung_dens = None, None
     if density is not None:
         torch.cuda.synchronize(); td = time.perf_counter()
